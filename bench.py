@@ -18,8 +18,9 @@ pass after the timed region (every kernel alone on the chip).
   python bench.py --gpus N --steps K --warmup W
 N > 1: one rank per GPU, every rank works on its own stream (weak scaling, no data-path collective); RCCL only takes the MAX of
 the timing and gathers the counters.  Run as a plain command it spawns its N ranks itself; under torch.distributed.run it uses
-the ranks it is given.  The timed region is `repeats` x K steps, with `repeats` chosen so that it lasts at least
-`--min-seconds` (default 6 s, so that a 5 s device sampler must land inside it; 0 = exactly K steps).  Prints ONE JSON line on rank 0.
+the ranks it is given.  The timed region of the `--config` run is exactly K steps; `--min-seconds S` instead repeats the K-step
+block until the region lasts at least S seconds (6 s lets a 5 s device sampler land inside it).  Prints ONE JSON line on rank 0.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_frontend / dump_match).
 
 After the timed region (never inside it) every rank compares the LAST timed step's outputs with the CPU oracle — EVERY frame of
 the step (`--parity all`, the default: one oracle instance per host thread; `--parity sample` = lane and step borders + interior
@@ -141,6 +142,53 @@ def _percentiles_ms(per):
     a = np.sort(np.asarray(per)) * 1e3
     return {"median_ms": round(float(np.median(a)), 4), "p10_ms": round(float(a[int(0.1 * (len(a) - 1))]), 4),
             "p90_ms": round(float(a[int(0.9 * (len(a) - 1))]), 4), "iterations": len(a)}
+
+
+DUMP_BUDGET = 48 << 20      # --dump-outputs: bytes of array data per run (the .npy files stay under 64 MB)
+
+
+def save_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
+
+
+def dump_frontend(d, pipe):
+    """--dump-outputs of an extraction configuration: what LanePipeline returns to its caller after the last timed step.  Per frame
+    the key point count and status, the key points (x, y, size, angle, response, octave, class_id: orbx_keypoint's fields as float32
+    values) and descriptors (32 bytes each, one float32 per byte); with the match leg the top-2 match against the previous frame
+    (train index, best and second distance).  Slots past
+    a frame's count are zeroed: the library leaves them unspecified.  When the whole step exceeds DUMP_BUDGET, a fixed seeded sample
+    of its frames is written; `frame` holds their indices in the step."""
+    import numpy as np
+    import torch
+    counts = pipe.counts()
+    n = counts.cpu().numpy()
+    B, cap = len(n), pipe.cap
+    per_frame = 3 * 8 + cap * 4 * (7 + 32) + (cap * 3 * 8 if pipe.do_match else 0)
+    nf = min(B, DUMP_BUDGET // per_frame)
+    fr = np.arange(B) if nf == B else np.sort(np.random.default_rng(0).choice(B, nf, replace=False))
+    sel = torch.from_numpy(fr).to(counts.device)
+    live = np.arange(cap)[None, :] < n[fr][:, None]
+    kp = pipe.keypoints().index_select(0, sel).cpu().numpy()               # orbx_keypoint as 7 float32 words; octave, class_id are int32
+    kp = np.concatenate([kp[..., :5], kp.view(np.int32)[..., 5:].astype(np.float32)], axis=-1)
+    out = {"frame": fr.astype(np.float64), "count": n[fr].astype(np.float64),
+           "status": pipe.status().cpu().numpy()[fr].astype(np.float64),
+           "keypoints": np.where(live[:, :, None], kp, 0).astype(np.float32),
+           "descriptors": np.where(live[:, :, None], pipe.descriptors().index_select(0, sel).cpu().numpy(), 0).astype(np.float32)}
+    if pipe.do_match:
+        m = pipe.matches().index_select(1, sel).cpu().numpy()
+        for k, name in enumerate(("match_index", "match_best", "match_second")):
+            out[name] = np.where(live, m[k], 0).astype(np.float64)
+    save_outputs(d, out)
+
+
+def dump_match(d, out3, nq):
+    """--dump-outputs of match100k: the last timed call's top-2 per query (train index, best and second distance)"""
+    import numpy as np
+    m = out3[:, :nq].cpu().numpy().astype(np.float64)
+    save_outputs(d, {"match_index": m[0], "match_best": m[1], "match_second": m[2]})
 
 
 def cpu_baseline(w, h, nfeat, do_match, seconds, kind="port"):
@@ -399,6 +447,8 @@ def run_frontend(a, cfg, world, rank, local_rank, dist, torch):
     dist_util.barrier(dist, a.backend, local_rank)
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_frontend(a.dump_outputs, pipe)
 
     # parity leg (outside the timed region): the outputs the LAST timed step left on the device against the CPU oracle
     parity = {"frames": 0, "mismatches": 0, "detail": []}
@@ -696,6 +746,8 @@ def run_match(a, cfg, world, rank, local_rank, dist, torch):
     dist_util.barrier(dist, a.backend, local_rank)
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_match(a.dump_outputs, out3, nq)
     region_ms = e0.elapsed_time(e1) / nsteps            # split + merge kernels of one call, averaged over the timed region (calls back to back)
     # steady-state duration of ONE call: 30 further calls, each between its own pair of HIP events on the launch stream
     # (the r02 rocprof summary held 7 cold calls and disagreed with the region average; min / median / max are reported,
@@ -883,8 +935,8 @@ def main():
                     help="a step's frames go through this many concurrent lanes (own extractor handle + HIP stream each); 1 = one stream")
     ap.add_argument("--region-timing", action="store_true",
                     help="also time every kernel inside the timed region (HIP events between the kernels of every lane: costs a few percent)")
-    ap.add_argument("--min-seconds", type=float, default=6.0,
-                    help="repeat the --steps block until the timed region lasts at least this long (0: exactly --steps steps)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the --steps block until the timed region lasts at least this long (default 0: exactly --steps steps)")
     ap.add_argument("--parity", default=None, choices=["all", "sample", "none"],
                     help="oracle comparison of the LAST timed step's outputs: every frame (default at one rank), lane / step borders + interior "
                          "frames (default at N > 1: the ranks of a node share its host cores), or none")
@@ -898,6 +950,9 @@ def main():
     ap.add_argument("--also-min-seconds", type=float, default=6.0,
                     help="timed region of each other frame configuration (as long as the headline's: sustained clocks)")
     ap.add_argument("--also-match-min-seconds", type=float, default=2.0, help="timed region of the 100k x 100k configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write the last timed step's outputs of the --config run as DIR/<name>.npy "
+                         "(float32 / float64, under 64 MB; rank 0's)")
     ap.add_argument("--live-traffic", default="auto", choices=["auto", "on", "off"],
                     help="measure roofline.traffic in this run (two rocprofv3 --pmc child runs, ~40 s); auto = only in the full default command "
                          "(one rank, --config vga with its `also` entries)")
@@ -966,7 +1021,7 @@ def main():
             a2.match_path = {"match100k_popcount": 0, "match100k_int8": 1}.get(key, -1)
             a2.config, a2.cpu_seconds, a2.cpu_allcores_seconds, a2.cpu_reference_seconds = name, a.also_cpu_seconds, 0.0, 0.0
             a2.min_seconds = a.also_match_min_seconds if name == "match100k" else a.also_min_seconds
-            a2.batch = a2.ring = a2.width = a2.height = a2.nfeatures = None
+            a2.batch = a2.ring = a2.width = a2.height = a2.nfeatures = a2.dump_outputs = None
             a2.region_timing = False
             a2.family = family
             a2.no_cpu_baseline = a.no_cpu_baseline or not cpu

@@ -306,7 +306,7 @@ void retainBest(std::vector<KeyPoint>& v, int n) {
 
 // reference src/ORBextractor.cc:79-120 (HarrisResponses), `img` = the cell view inside the level.
 // fp_contract: the reference's own build (CMakeLists.txt:12-13: -O3 -march=native, GCC's default -ffp-contract=fast) fuses two
-// multiply-adds of the last expression (read off its object code: oracle/Makefile _ref_native):
+// multiply-adds of the last expression (read off its object code: oracle/Makefile _ref/native):
 //   t = fma(a, b, -(c*c));  response = fma(-(a+b), k*(a+b), t) * scale^4
 void HarrisResponses(const uint8_t* ptr00, int step, std::vector<KeyPoint>& pts, int blockSize, float harris_k, bool fp_contract = false) {
     int r = blockSize / 2;

@@ -291,7 +291,7 @@ def ref_available():
 _REF = {}
 
 
-NATIVE_DIR = os.path.join(os.path.dirname(REF_DIR), "_ref_native")
+NATIVE_DIR = os.path.join(REF_DIR, "native")
 
 
 def native_available():
@@ -299,7 +299,7 @@ def native_available():
 
 
 def ref_lib(name, native=False):
-    """the reference's own sources compiled against oracle/cvstub (oracle/Makefile → oracle/_ref/; native: → oracle/_ref_native/, the
+    """the reference's own sources compiled against oracle/cvstub (oracle/Makefile → oracle/_ref/; native: → oracle/_ref/native/, the
     extractor built with the reference's own optimisation flags, i.e. with GCC's default FMA contraction)"""
     key = ("native:" if native else "") + name
     if key in _REF:

@@ -96,3 +96,54 @@ def test_bare_multi_gpu_command_refuses_missing_devices():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(max(n, 2))], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 2 and "device(s)" in r.stderr and r.stdout.strip() == "", (r.returncode, r.stderr[-300:])
+
+
+def test_dump_outputs_sample_and_fields(tmp_path):
+    """--dump-outputs at the headline's shape (1024 frames x 1000 key points, more than the budget): the same seeded sample of frames
+    every run, the key point record's int32 fields as their values, slots past a frame's count zeroed, float arrays under 64 MB"""
+    import numpy as np
+    import torch
+    from orb_slam_amd import capi
+    B, cap = 1024, 1000
+    rng = np.random.default_rng(3)
+    rec = np.zeros((B, cap), dtype=capi.KP_DTYPE)
+    rec["x"], rec["octave"], rec["class_id"] = rng.random((B, cap)) * 640, rng.integers(0, 8, (B, cap)), -1
+    n = rng.integers(500, cap + 1, B).astype(np.int32)
+    desc = rng.integers(0, 256, (B, cap, 32), dtype=np.uint8)
+    match = rng.integers(-1, 2**31 - 1, (3, B, cap), dtype=np.int32)
+
+    class Pipe:                 # LanePipeline's accessors for the results of its last step, on host tensors
+        do_match = True
+
+        def __init__(self):
+            self.cap = cap
+
+        def counts(self):
+            return torch.from_numpy(n)
+
+        def status(self):
+            return torch.zeros(B, dtype=torch.int32)
+
+        def keypoints(self):
+            return torch.from_numpy(rec.view(np.float32).reshape(B, cap, 7))
+
+        def descriptors(self):
+            return torch.from_numpy(desc)
+
+        def matches(self):
+            return torch.from_numpy(match)
+
+    for d in ("a", "b"):
+        bench.dump_frontend(str(tmp_path / d), Pipe())
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) < 64e6
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert np.array_equal(a["frame"], np.load(tmp_path / "b" / "frame.npy"))
+    fr = a["frame"].astype(np.int64)
+    assert 100 < len(fr) < B and np.all(np.diff(fr) > 0) and np.array_equal(a["count"], n[fr])
+    for i, j in ((0, fr[0]), (len(fr) - 1, fr[-1])):
+        k = n[j]
+        assert np.array_equal(a["keypoints"][i, :k], np.stack([rec[j, :k][f].astype(np.float32) for f in capi.KP_DTYPE.names], -1))
+        assert np.array_equal(a["descriptors"][i, :k], desc[j, :k]) and np.array_equal(a["match_best"][i, :k], match[1, j, :k])
+        assert not a["keypoints"][i, k:].any() and not a["descriptors"][i, k:].any() and not a["match_index"][i, k:].any()

@@ -147,6 +147,39 @@ def test_single_rank_configs_and_min_duration():
     assert m["unit"] == "pairs/s" and m["roofline"]["bound"] == "mfma" and m["value"] > 5e11
 
 
+def test_steps_and_dump_outputs(tmp_path):
+    """--steps K times exactly K steps; --dump-outputs writes what the last of them returned: float arrays under 64 MB, the same from
+    two runs with the same arguments, and equal to the oracle's key points, descriptors and top-2 match"""
+    import numpy as np
+    import oracle_lib as orc
+    from orb_slam_amd import capi, synth
+    args = ("--steps", "3", "--warmup", "1", "--batch", "64", "--ring", "128", "--no-also", "--no-cpu-baseline")
+    d = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert d["steps"] == 3 and d["repeats"] == 1 and d["timed_steps"] == 3 and d["config"]["parity_mismatches"] == 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == sorted(
+        n + ".npy" for n in ("frame", "count", "status", "keypoints", "descriptors", "match_index", "match_best", "match_second"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64e6
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert a[n[:-4]].dtype in (np.float32, np.float64) and np.array_equal(a[n[:-4]], np.load(tmp_path / "b" / n)), n
+    assert np.array_equal(a["frame"], np.arange(64)) and not a["status"].any()
+    # the last timed step is step warmup + 2 + steps - 1 (two untimed submit-cost steps follow the warm-up); its frame j is stream frame
+    # (step * batch + j) % ring
+    last = 1 + 2 + 3 - 1
+    o = orc.OracleExtractor(nfeatures=1000)
+    want = [o(synth.frame(640, 480, synth.BLOCKS, (last * 64 + j) % 128)) for j in (62, 63)]
+    for (ok, od), j in zip(want, (62, 63)):
+        n = len(ok)
+        assert a["count"][j] == n
+        assert np.array_equal(a["keypoints"][j, :n], np.stack([ok[f].astype(np.float32) for f in capi.KP_DTYPE.names], -1))
+        assert np.array_equal(a["descriptors"][j, :n], od.astype(np.float32)) and not a["descriptors"][j, n:].any()
+    ri, rb, rs = orc.match_top2(want[1][1], want[0][1])
+    n = len(want[1][0])
+    assert np.array_equal(a["match_index"][63, :n], ri) and np.array_equal(a["match_best"][63, :n], rb) and np.array_equal(a["match_second"][63, :n], rs)
+
+
 def test_rccl_path_at_world_size_one():
     """the `nccl` (= RCCL) backend had never executed — at world size 1 bench.py returned before any collective.
     --force-dist builds the process group anyway: lazy communicator at the first collective, barrier(device_ids), the float64

@@ -625,7 +625,7 @@ def test_fallback_hint_is_per_frame_slot_of_the_launch_group(gpu_extractor_facto
 
 
 # ---- round 6: the FMA caveat.  orbx_params::fp_contract = ORBX_FP_GCC_CONTRACT evaluates the descriptor rotation and the Harris response as
-# the reference's OWN build flags fuse them (oracle/_ref_native = src/ORBextractor.cc with -O3 and GCC's default contraction; the oracle's
+# the reference's OWN build flags fuse them (oracle/_ref/native = src/ORBextractor.cc with -O3 and GCC's default contraction; the oracle's
 # fp_contract mode is pinned to it byte for byte by tests/test_ref_pin_native.py)
 @pytest.mark.parametrize("cfg", [
     dict(w=640, h=480, nfeatures=1000),

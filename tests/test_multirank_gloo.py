@@ -31,7 +31,8 @@ def _worker(rank, world, port, q):
     k, d = orc.OracleExtractor(nfeatures=100, nlevels=3)(frames[0])    # stands in for the GPU step on CPU
     elapsed = 1.0 + rank                                                # rank 1 is the slow one
     tmax, total, rows = dist_util.reduce_run(dist, elapsed, [ring, len(k), int(frames[0].sum()) % 1000003], torch.device("cpu"))
-    dist.barrier()
+    # gloo's own CPU barrier: dist.barrier() probes for an accelerator first, which opens the GPU in every rank of this CPU-only test
+    dist.monitored_barrier()
     q.put((rank, first, tmax, total, rows))
     dist.destroy_process_group()
 

@@ -1,7 +1,7 @@
 """The FMA caveat, pinned.  The reference's own build (CMakeLists.txt:12-13: -O3 -march=native, GCC's default -ffp-contract=fast) fuses the
 multiply-adds of two float expressions of src/ORBextractor.cc — `x*b + y*a` / `x*a - y*b` in computeOrbDescriptor (:165-166) and the Harris
 response (:118-119); everything else in this repository (oracle, oracle/_ref, golden fixtures, the device's default mode) evaluates them
-unfused.  oracle/_ref_native/libref_orbextractor.so is the same translation unit with the reference's flags.  Here:
+unfused.  oracle/_ref/native/libref_orbextractor.so is the same translation unit with the reference's flags.  Here:
   * how much the two builds of the REFERENCE differ (>= 500 frames): a handful of descriptor bits per 10^5 key points, a third of the Harris
     responses in their last bits;
   * the oracle's fp_contract mode reproduces the native build byte for byte (the 7 x 4 configurations of tests/test_ref_pin.py + strided +
@@ -20,7 +20,7 @@ from test_ref_pin import EXTRACT_CASES
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if not ol.native_available() and os.path.exists("/root/reference/src/ORBextractor.cc"):
     subprocess.call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-pytestmark = pytest.mark.skipif(not (ol.native_available() and ol.ref_available()), reason="oracle/_ref_native not built and /root/reference absent")
+pytestmark = pytest.mark.skipif(not (ol.native_available() and ol.ref_available()), reason="oracle/_ref/native not built and /root/reference absent")
 
 
 def test_the_two_builds_really_differ_in_their_object_code():
