@@ -146,6 +146,33 @@ int orbx_extract_batch_device_phases(orbx_extractor* h, const uint8_t* d_imgs, i
                                      orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap,
                                      int32_t* d_status, void* stream, int phases);
 
+/* Gather form of orbx_extract_batch_device: frames from a pointer array, in device or in host memory (a multi-camera rig with one
+ * buffer per camera, frames handed over by a decoder, ROIs / views of larger images, host frames as Frame.cc has them).
+ * imgs: HOST array of nframes pointers; frame f is w x hgt bytes, rows row_strides[f] bytes apart (row_strides == NULL: every row
+ * stride is w).  All frames share one geometry (w, hgt).  Outputs, stream and d_status are as in orbx_extract_batch_device: frame f's
+ * results are at d_kps + f*cap, d_desc + f*cap*32, d_n + f, and are bit-identical to what orbx_extract_batch_device gives for the same
+ * pixels.  Frames may repeat, overlap or come in any order.  Frame f0 + f of a launch group uses fallback-hint slot f, as there.
+ *   ORBX_FRAMES_ON_DEVICE  imgs[f] are DEVICE pointers, read in place by the kernels (the level-0 readers take base and row stride per
+ *                          frame from a table the library uploads per launch group).  Asynchronous on `stream`; the pointer array may be
+ *                          reused as soon as the call returns.  (The per-group tables rotate through four slots: with more than four
+ *                          launch groups queued and not yet run — in one call or over consecutive calls — the calling thread waits for
+ *                          the kernels of the group four back before it queues the next.)  Each row must be readable up to min(row_strides[f], w rounded up to 16)
+ *                          bytes (the pitched-row rule of orbx_extract_batch_device, per frame).  Fastest when every pointer and row
+ *                          stride is a multiple of 16.
+ *   ORBX_FRAMES_ON_HOST    imgs[f] are HOST pointers, pageable or pinned.  Each launch group is uploaded into a device buffer of the
+ *                          handle on an internal copy stream (pinned frames straight from the caller's memory, pageable ones through a
+ *                          pinned staging buffer filled by the calling thread) while the previous group computes.  The call returns once
+ *                          every frame has been read, so the caller may overwrite its buffers at once; outputs are ready when `stream`
+ *                          reaches them.  Exactly w bytes of each row are read.
+ * Host-checkable arguments only: a NULL array or entry, row_strides[f] < w or >= 2^24, or a bad `where` give ORBX_ERR_ARG (as does a
+ * device pointer in the host form); nframes <= 0, w <= 0 or hgt <= 0 give ORBX_EMPTY; cap < orbx_max_keypoints() ORBX_ERR_CAPACITY.
+ * There is no phased variant of this call. */
+#define ORBX_FRAMES_ON_DEVICE 0
+#define ORBX_FRAMES_ON_HOST   1
+int orbx_extract_batch(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt,
+                       int where, orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap,
+                       int32_t* d_status, void* stream);
+
 /* ---- matcher ---------------------------------------------------------------------------------- */
 /* Hamming distance of two 256-bit descriptors (pure, re-entrant, host). */
 int orbm_hamming256(const uint8_t* a, const uint8_t* b);

@@ -24,7 +24,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 # every symbol include/orbx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "orbx_default_params", "orbx_create", "orbx_destroy", "orbx_get_levels", "orbx_get_scale_factor",
-    "orbx_max_keypoints", "orbx_last_error", "orbx_build_id", "orbx_extract", "orbx_extract_batch_device", "orbx_extract_batch_device_phases",
+    "orbx_max_keypoints", "orbx_last_error", "orbx_build_id", "orbx_extract", "orbx_extract_batch_device", "orbx_extract_batch_device_phases", "orbx_extract_batch",
     "orbm_hamming256", "orbm_match_top2", "orbm_match_top2_device", "orbm_match_top2_batch_device", "orbm_match_top2_masked", "orbm_match_top2_masked_device",
     "orbm_count_accepted", "orbm_match_top2_segments", "orbm_match_top2_segments_device", "orbm_distinctive", "orbm_distinctive_device",
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_download",
@@ -131,6 +131,7 @@ def lib():
         L.orbx_extract.argtypes = [vp, vp, ci, ci, pd, vp, vp, ci, ctypes.POINTER(ci)]
         L.orbx_extract_batch_device.argtypes = [vp, vp, ci, ci, ci, pd, pd, vp, vp, vp, ci, vp, vp]
         L.orbx_extract_batch_device_phases.argtypes = [vp, vp, ci, ci, ci, pd, pd, vp, vp, vp, ci, vp, vp, ci]
+        L.orbx_extract_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp]
         L.orbm_hamming256.argtypes = [vp, vp]
         L.orbm_match_top2.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci]
         L.orbm_match_top2_device.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp]
@@ -194,6 +195,49 @@ def lib():
     return _LIB
 
 
+FRAMES_ON_DEVICE, FRAMES_ON_HOST = 0, 1     # orbx_extract_batch's `where`
+
+
+def frame_table(frames):
+    """The arguments orbx_extract_batch takes for a list of 2-D uint8 frames of one size: (where, pointers, row strides, w, h, keep).
+    CUDA tensors give the device form (row stride = stride(0), stride(1) must be 1); numpy arrays and CPU tensors the host form (host
+    frames whose rows are not contiguous are copied first; `keep` holds what must stay alive during the call).  Needs no GPU."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("no frames")
+    on_dev = [bool(getattr(f, "is_cuda", False)) for f in frames]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("frames mix device and host memory")
+    ptrs, strides, keep, shape = [], [], [], None
+    for f in frames:
+        if hasattr(f, "data_ptr"):                 # torch tensor (device or host)
+            import torch
+            if f.dtype != torch.uint8 or f.dim() != 2:
+                raise ValueError("frames must be 2-D uint8")
+            if f.stride(1) != 1 or f.stride(0) < f.shape[1]:
+                if f.is_cuda:
+                    raise ValueError("device frame rows must be contiguous (stride(1) == 1)")
+                f = f.contiguous()
+            hw, p, rs = tuple(f.shape), f.data_ptr(), f.stride(0)
+        else:
+            a = np.asarray(f)
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise ValueError("frames must be 2-D uint8")
+            if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+                a = np.ascontiguousarray(a)
+            hw, p, rs = a.shape, a.ctypes.data, a.strides[0]
+            f = a
+        if shape is None:
+            shape = hw
+        elif hw != shape:
+            raise ValueError("frames differ in size: %s vs %s" % (hw, shape))
+        keep.append(f)
+        ptrs.append(p)
+        strides.append(rs)
+    return (FRAMES_ON_DEVICE if on_dev[0] else FRAMES_ON_HOST, np.array(ptrs, dtype=np.uint64), np.array(strides, dtype=np.int64),
+            shape[1], shape[0], keep)
+
+
 class ORBextractor:
     """Same constructor arguments as the reference ORBextractor(nfeatures, scaleFactor, nlevels, scoreType, fastTh)
     (include/ORBextractor.h:38) plus device placement; __call__(image) is operator()."""
@@ -255,6 +299,17 @@ class ORBextractor:
         phases: PHASE_* bit mask (orbx_extract_batch_device_phases); the parts of one batch go to one stream, in order."""
         rc = self.L.orbx_extract_batch_device_phases(self.h, d_imgs, nframes, w, h, row_stride, frame_stride, d_kps, d_desc, d_n, cap,
                                                      d_status or None, stream or None, phases)
+        if rc != ORBX_OK:
+            raise self._err(rc)
+
+    def extract_batch(self, frames, d_kps, d_desc, d_n, cap, d_status=0, stream=0):
+        """orbx_extract_batch: frames is a list of 2-D uint8 frames of one size (see frame_table: CUDA tensors = device form, numpy arrays
+        or CPU tensors = host form); outputs are integer device addresses, frame f's results at slot f.  Asynchronous on `stream` (the
+        host form returns once the frames have been read)."""
+        where, ptrs, strides, w, h, keep = frame_table(frames)
+        rc = self.L.orbx_extract_batch(self.h, ptrs.ctypes.data, strides.ctypes.data, len(ptrs), w, h, where, d_kps, d_desc, d_n, cap,
+                                       d_status or None, stream or None)
+        del keep
         if rc != ORBX_OK:
             raise self._err(rc)
 

@@ -20,18 +20,23 @@ class ORBextractor {
 public:
     enum { HARRIS_SCORE = 0, FAST_SCORE = 1 };
 
+    // maxBatch: frames per launch group of ExtractBatch (operator() is unaffected)
     ORBextractor(int nfeatures = 1000, float scaleFactor = 1.2f, int nlevels = 8, int scoreType = FAST_SCORE, int fastTh = 20,
-                 int device = 0)
-        : h_(nullptr), nlevels_(nlevels), scaleFactor_(scaleFactor) {
+                 int device = 0, int maxBatch = 1)
+        : h_(nullptr), nlevels_(nlevels), scaleFactor_(scaleFactor), device_(device) {
         orbx_params p;
         orbx_default_params(&p);
         p.nfeatures = nfeatures; p.scale_factor = scaleFactor; p.nlevels = nlevels; p.score_type = scoreType; p.fast_th = fastTh;
         p.device = device;
+        p.max_batch = maxBatch;
         const int rc = orbx_create(&p, &h_);
         if (rc != ORBX_OK) throw std::runtime_error("orbx_create failed (" + std::to_string(rc) + "): no usable MI355X / HIP runtime");
         cap_ = orbx_max_keypoints(h_);
     }
-    ~ORBextractor() { orbx_destroy(h_); }
+    ~ORBextractor() {
+        freeBatch();
+        orbx_destroy(h_);
+    }
     ORBextractor(const ORBextractor&) = delete;
     ORBextractor& operator=(const ORBextractor&) = delete;
 
@@ -58,14 +63,73 @@ public:
         _keypoints.assign(kps_.begin(), kps_.begin() + n);            // reference :746-747,:777
     }
 
+    // Several host images of one size, any step each, in one call (orbx_extract_batch, host form: launch groups of maxBatch frames, the
+    // upload of one overlapping the kernels of the previous one).  keypoints[i] / descriptors[i] are exactly what operator() gives for
+    // images[i], descriptors[i] released when it has no features.
+    void ExtractBatch(const std::vector<cv::Mat>& images, std::vector<std::vector<cv::KeyPoint> >& keypoints, std::vector<cv::Mat>& descriptors) {
+        const int F = (int)images.size();
+        keypoints.assign(F, std::vector<cv::KeyPoint>());
+        descriptors.resize(F);
+        if (F == 0) return;
+        const int w = images[0].cols, hgt = images[0].rows;
+        std::vector<const uint8_t*> ptrs(F);
+        std::vector<ptrdiff_t> steps(F);
+        for (int i = 0; i < F; i++) {
+            if (images[i].cols != w || images[i].rows != hgt) throw std::invalid_argument("ExtractBatch: images differ in size");
+            ptrs[i] = images[i].data;
+            steps[i] = (ptrdiff_t)images[i].step;
+        }
+        if (w <= 0 || hgt <= 0) return;                               // reference :721-722: outputs untouched
+        if (F > batchCap_) {
+            freeBatch();
+            if (orbx_device_alloc(device_, (size_t)F * cap_ * sizeof(orbx_keypoint), &dKps_) != ORBX_OK ||
+                orbx_device_alloc(device_, (size_t)F * cap_ * 32, &dDesc_) != ORBX_OK || orbx_device_alloc(device_, (size_t)F * 8, &dN_) != ORBX_OK)
+                throw std::runtime_error("ExtractBatch: device allocation failed");
+            batchCap_ = F;
+        }
+        int32_t* dn = static_cast<int32_t*>(dN_);
+        const int rc = orbx_extract_batch(h_, ptrs.data(), steps.data(), F, w, hgt, ORBX_FRAMES_ON_HOST, static_cast<orbx_keypoint*>(dKps_),
+                                          static_cast<uint8_t*>(dDesc_), dn, cap_, dn + F, nullptr);
+        if (rc == ORBX_EMPTY) return;
+        if (rc != ORBX_OK) throw std::runtime_error(std::string("orbx_extract_batch: ") + orbx_last_error(h_));
+        std::vector<int32_t> ns((size_t)2 * F);
+        kps_.resize((size_t)F * cap_);
+        desc_.resize((size_t)F * cap_ * 32);
+        if (orbx_device_download(device_, ns.data(), dN_, ns.size() * 4) != ORBX_OK ||
+            orbx_device_download(device_, kps_.data(), dKps_, kps_.size() * sizeof(orbx_keypoint)) != ORBX_OK ||
+            orbx_device_download(device_, desc_.data(), dDesc_, desc_.size()) != ORBX_OK)
+            throw std::runtime_error("ExtractBatch: device download failed");
+        for (int i = 0; i < F; i++) {
+            if (ns[F + i] != ORBX_OK) throw std::runtime_error("ExtractBatch: internal list capacity exceeded");
+            const int n = ns[i];
+            if (n == 0) descriptors[i].release();                     // reference :738-739
+            else {
+                descriptors[i].create(n, 32, CV_8U);
+                for (int k = 0; k < n; k++) std::memcpy(descriptors[i].ptr(k), desc_.data() + ((size_t)i * cap_ + k) * 32, 32);
+            }
+            keypoints[i].assign(kps_.begin() + (size_t)i * cap_, kps_.begin() + (size_t)i * cap_ + n);
+        }
+    }
+
     int inline GetLevels() { return nlevels_; }
     float inline GetScaleFactor() { return (float)scaleFactor_; }
 
 private:
+    void freeBatch() {
+        orbx_device_free(device_, dKps_);
+        orbx_device_free(device_, dDesc_);
+        orbx_device_free(device_, dN_);
+        dKps_ = dDesc_ = dN_ = nullptr;
+        batchCap_ = 0;
+    }
+
     orbx_extractor* h_;
     int nlevels_;
     double scaleFactor_;   // the reference keeps a double member initialised from the float argument
+    int device_;
     int cap_;
+    void *dKps_ = nullptr, *dDesc_ = nullptr, *dN_ = nullptr;     // ExtractBatch outputs on the device: batchCap_ frames (dN_: n, then status)
+    int batchCap_ = 0;
     std::vector<cv::KeyPoint> kps_;
     std::vector<unsigned char> desc_;
 };

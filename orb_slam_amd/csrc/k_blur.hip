@@ -10,15 +10,19 @@
 
 namespace orbx {
 
-template <bool ALIGNED, int ROWS>
-__global__ __launch_bounds__(BLUR_WAVES * 64) void k_blur(Batch b) {
+template <bool ALIGNED, int ROWS, bool GATHER>
+__device__ __forceinline__ void k_blur_body(const Batch& b) {
     const DevGeom& g = b.g;
     const int ntiles = ROWS != BLUR_ROWS ? g.nbtiles_total_s : g.nbtiles_total;
     int frame, wgi;
     if (!frame_item(b, blockIdx.x, (ntiles + BLUR_WAVES - 1) / BLUR_WAVES, frame, wgi)) return;
     const int t = wgi * BLUR_WAVES + wave_id();
-    if (t < ntiles) blur_strip<ALIGNED, ROWS>(b, frame, t);
+    if (t < ntiles) blur_strip<ALIGNED, ROWS, GATHER>(b, frame, t);
 }
+template <bool ALIGNED, int ROWS>
+__global__ __launch_bounds__(BLUR_WAVES * 64) void k_blur(Batch b) { k_blur_body<ALIGNED, ROWS, false>(b); }
+template <bool ALIGNED, int ROWS>
+__global__ __launch_bounds__(BLUR_WAVES * 64) void k_blur_gather(Batch b) { k_blur_body<ALIGNED, ROWS, true>(b); }
 
 // ------------------------------------------------------------------------------------ blur on the matrix cores (round 4)
 // The same filter as exact int8 matrix products per 32 x 32 tile (v_mfma_i32_32x32x32_i8, i32 accumulate).  k_blur spends 19.7
@@ -338,12 +342,13 @@ __global__ __launch_bounds__(MB_WAVES * 64) void k_blur_mfma(Batch b) {      // 
 int launch_blur(const Batch& b, const HostGeom& hg, hipStream_t st) {
     const DevGeom& g = hg.g;
     const int F = b.nframes;
-    const bool aligned = (((uintptr_t)b.img | (uintptr_t)b.img_row_stride | (uintptr_t)b.img_frame_stride) & 3) == 0;
+    const bool aligned = (level0_bits(b) & 3) == 0;
     if (F < PYR_FUSED_MAX_FRAMES) {   // short strips: 4x the waves, a quarter of the serial row chain each
         const int nblk = frame_item_blocks(b, (g.nbtiles_total_s + BLUR_WAVES - 1) / BLUR_WAVES);
-        if (aligned) hipLaunchKernelGGL((k_blur<true, BLUR_ROWS_SMALL>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
-        else hipLaunchKernelGGL((k_blur<false, BLUR_ROWS_SMALL>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
-    } else if (ORBX_BLUR_MFMA && aligned && ((b.img_row_stride | b.img_frame_stride) & 15) == 0 && (g.lv[0].w <= MB_MAX_WIDTH || ORBX_BLUR_MFMA > 1)) {
+        if (aligned) hipLaunchKernelGGL((b.img_tab ? k_blur_gather<true, BLUR_ROWS_SMALL> : k_blur<true, BLUR_ROWS_SMALL>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
+        else hipLaunchKernelGGL((b.img_tab ? k_blur_gather<false, BLUR_ROWS_SMALL> : k_blur<false, BLUR_ROWS_SMALL>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
+    } else if (ORBX_BLUR_MFMA && !b.img_tab && aligned && ((b.img_row_stride | b.img_frame_stride) & 15) == 0 && (g.lv[0].w <= MB_MAX_WIDTH || ORBX_BLUR_MFMA > 1)) {
+        // (gather launch groups take k_blur_gather: same outputs; full groups blur per keypoint window in k_describe_od anyway)
         // full launch groups whose frames can be staged in whole 16-byte chunks: the filter as int8 matrix products.  Measured
         // (NOTES.md 9.2): 0.50 against 0.55 ms per 1024 VGA frames and half the VALU instructions, which the lanes next to it pick
         // up (+1.5 % frames/s); on 1920-byte rows its 96-byte row pieces lose to k_blur's 256-byte ones (0.88 against 0.78 ms per
@@ -351,8 +356,8 @@ int launch_blur(const Batch& b, const HostGeom& hg, hipStream_t st) {
         hipLaunchKernelGGL(k_blur_mfma, dim3(frame_item_blocks(b, (g.nmb_total + MB_WAVES - 1) / MB_WAVES)), dim3(MB_WAVES * 64), 0, st, b);
     } else {
         const int nblk = frame_item_blocks(b, (g.nbtiles_total + BLUR_WAVES - 1) / BLUR_WAVES);
-        if (aligned) hipLaunchKernelGGL((k_blur<true, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
-        else hipLaunchKernelGGL((k_blur<false, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
+        if (aligned) hipLaunchKernelGGL((b.img_tab ? k_blur_gather<true, BLUR_ROWS> : k_blur<true, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
+        else hipLaunchKernelGGL((b.img_tab ? k_blur_gather<false, BLUR_ROWS> : k_blur<false, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
     }
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;

@@ -24,7 +24,7 @@ __device__ __forceinline__ uint32_t load_px4_reflect(const uint8_t* row, int x, 
     return v;
 }
 
-template <bool ALIGNED, int ROWS>
+template <bool ALIGNED, int ROWS, bool GATHER = false>
 __device__ __forceinline__ void blur_strip(const Batch& b, int frame, int t) {   // t = strip index within the frame (wave-uniform)
     const DevGeom& g = b.g;
     constexpr bool SHORT = ROWS != BLUR_ROWS;       // the tiling with short strips (launch_extract picks it for small launch groups)
@@ -37,7 +37,7 @@ __device__ __forceinline__ void blur_strip(const Batch& b, int frame, int t) {  
     const int y0 = band * ROWS;
     const int w = L.w, h = L.h;
     long long stride;
-    const uint8_t* src = plain_plane(b, L, level, frame, stride);
+    const uint8_t* src = plain_plane<GATHER>(b, L, level, frame, stride);
     uint8_t* dst = b.blur + (long long)frame * g.frame_plane_bytes + L.plane_off;
     const bool fetch = x >= -4 && x < w + 4;                   // halo lanes beyond that are never consumed
     const int xq = (w - 1) & ~3;                               // first pixel of the last (possibly partial) dword of a row

@@ -29,8 +29,8 @@ constexpr int DESC_WIN_PITCH = 40, DESC_WIN_ROWS = 37, DESC_WIN_BYTES = DESC_WIN
 
 // FMA: the two rotation expressions of computeOrbDescriptor as the reference's own build flags contract them (orbx_params::fp_contract):
 // `x*b + y*a` -> fma(x, b, y*a), `x*a - y*b` -> fma(x, a, -(y*b)); false: unfused (ISO evaluation, the default).
-template <bool FMA>
-__global__ __launch_bounds__(DESC_WAVES * 64) void k_describe(Batch b) {
+template <bool FMA, bool GATHER>
+__device__ __forceinline__ void k_describe_body(const Batch& b) {
 #if ORBX_DESC_PACKED_PATTERN
     __shared__ uint32_t s_pat[256];                                    // test t: x0, y0, x1, y1 as the four int8 of c_pattern[t] (1 KB: six workgroups per CU; as floats, 4 KB: five)
 #else
@@ -158,7 +158,13 @@ __global__ __launch_bounds__(DESC_WAVES * 64) void k_describe(Batch b) {
     const int x = kp.pos & 0xFFFF, y = kp.pos >> 16;
     const uint8_t* plain;
     unsigned pstride;                                        // rows < 2^24 bytes, planes < 2^31 bytes (host-checked)
-    if (level == 0) { pstride = (unsigned)b.img_row_stride; plain = b.img + (long long)frame * b.img_frame_stride; }
+    if (level == 0) {
+        if constexpr (GATHER) {
+            long long s0;
+            plain = level0_src(b, frame, s0);
+            pstride = (unsigned)s0;
+        } else { pstride = (unsigned)b.img_row_stride; plain = b.img + (long long)frame * b.img_frame_stride; }
+    }
     else { pstride = (unsigned)L.stride; plain = b.pyr + (long long)frame * g.frame_plane_bytes + L.plane_off; }
     const uint8_t* blur = b.blur + (long long)frame * g.frame_plane_bytes + L.plane_off;
     // rounded pattern offsets never exceed 18 px (|(-13,-13)| = 18.4): keypoints at least 19 px from every edge — all but the
@@ -321,13 +327,17 @@ __global__ __launch_bounds__(DESC_WAVES * 64) void k_describe(Batch b) {
         b.out_kps[(long long)frame * b.cap + out_idx] = o;
     }
 }
+template <bool FMA>
+__global__ __launch_bounds__(DESC_WAVES * 64) void k_describe(Batch b) { k_describe_body<FMA, false>(b); }
+template <bool FMA>
+__global__ __launch_bounds__(DESC_WAVES * 64) void k_describe_gather(Batch b) { k_describe_body<FMA, true>(b); }
 
 
 int launch_describe(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const DevGeom& g = hg.g;
     const dim3 grid(frame_item_blocks(b, (g.nquads + DESC_WAVES - 1) / DESC_WAVES)), block(DESC_WAVES * 64);
-    if (g.fp_contract) hipLaunchKernelGGL(k_describe<true>, grid, block, 0, stream, b);
-    else hipLaunchKernelGGL(k_describe<false>, grid, block, 0, stream, b);
+    if (g.fp_contract) hipLaunchKernelGGL(b.img_tab ? k_describe_gather<true> : k_describe<true>, grid, block, 0, stream, b);
+    else hipLaunchKernelGGL(b.img_tab ? k_describe_gather<false> : k_describe<false>, grid, block, 0, stream, b);
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }

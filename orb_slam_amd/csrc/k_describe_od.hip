@@ -91,8 +91,8 @@ constexpr OdTables make_od_tables() {
 }
 static __device__ __constant__ OdTables c_od = make_od_tables();
 
-template <bool FMA>
-__global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od(Batch b) {
+template <bool FMA, bool GATHER>
+__device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     __shared__ __attribute__((aligned(16))) float s_pat[256 * 4];       // test t: x0, y0, x1, y1 as floats (one ds_read_b128 = the two points as register pairs)
     __shared__ __attribute__((aligned(16))) uint32_t s_mask[256];       // circle byte masks of the 31 x 8 patch dwords (slots 248.. = 0)
     __shared__ __attribute__((aligned(16))) uint8_t s_win[OD_WAVES * OD_KPW * OD_WIN_BYTES + OD_TAIL];
@@ -168,7 +168,11 @@ __global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od(Batch b) {
     unsigned pstride;                                        // rows < 2^24 bytes, planes < 2^31 bytes (host-checked)
     int wlim;                                                // bytes of a row that may be read (>= w and >= 64: host-checked)
     if (level == 0) {
-        pstride = (unsigned)b.img_row_stride; plain = b.img + (long long)frame * b.img_frame_stride;
+        if constexpr (GATHER) {
+            long long s0;
+            plain = level0_src(b, frame, s0);
+            pstride = (unsigned)s0;
+        } else { pstride = (unsigned)b.img_row_stride; plain = b.img + (long long)frame * b.img_frame_stride; }
         wlim = (int)min((long long)pstride, (long long)((L.w + 15) & ~15));               // include/orbx.h: what a pitched caller buffer promises (any value: the 16-byte DMA takes byte-aligned sources)
     } else { pstride = (unsigned)L.stride; plain = b.pyr + (long long)frame * g.frame_plane_bytes + L.plane_off; wlim = L.stride; }
     uint8_t* const win0 = s_win + wave_id() * OD_KPW * OD_WIN_BYTES;
@@ -464,21 +468,25 @@ __global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od(Batch b) {
         b.out_kps[(long long)frame * b.cap + out_idx] = o;
     }
 }
+template <bool FMA>
+__global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od(Batch b) { k_describe_od_body<FMA, false>(b); }
+template <bool FMA>
+__global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od_gather(Batch b) { k_describe_od_body<FMA, true>(b); }
 
 // every level must offer 48 readable bytes per row and be at least 64 px wide (the border fix-up's case analysis), rows single-reflect
 bool describe_od_supported(const Batch& b, const HostGeom& hg) {
     const DevGeom& g = hg.g;
     for (int l = 0; l < g.nlevels; l++)
         if (g.lv[l].w < 64 || g.lv[l].h < 44) return false;
-    const long long wlim0 = std::min<long long>(b.img_row_stride, (g.lv[0].w + 15) & ~15);
+    const long long wlim0 = std::min<long long>(level0_min_stride(b), (g.lv[0].w + 15) & ~15);     // (gather form: the narrowest frame)
     return wlim0 >= 64 && wlim0 >= g.lv[0].w;
 }
 
 int launch_describe_od(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const DevGeom& g = hg.g;
     const dim3 grid(frame_item_blocks(b, (g.nquads + OD_WAVES - 1) / OD_WAVES)), block(OD_WAVES * 64);
-    if (g.fp_contract) hipLaunchKernelGGL(k_describe_od<true>, grid, block, 0, stream, b);
-    else hipLaunchKernelGGL(k_describe_od<false>, grid, block, 0, stream, b);
+    if (g.fp_contract) hipLaunchKernelGGL(b.img_tab ? k_describe_od_gather<true> : k_describe_od<true>, grid, block, 0, stream, b);
+    else hipLaunchKernelGGL(b.img_tab ? k_describe_od_gather<false> : k_describe_od<false>, grid, block, 0, stream, b);
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 

@@ -79,7 +79,7 @@ static_assert(sizeof(FastHdr) == 64, "LDS carve");
 __device__ __forceinline__ int lane_rank(unsigned long long m) {   // number of set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
-template <bool ALIGNED, int NT, int PPT>
+template <bool ALIGNED, int NT, int PPT, bool GATHER = false>
 __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int item, uint8_t* smem) {
     constexpr int NW = NT / 64;
     static_assert((NW & (NW - 1)) == 0, "wave roles rotate modulo NW");
@@ -126,7 +126,7 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
     const int q_own_lo = (3 + own_lo) * S, q_own_hi = (3 + own_hi + 1) * S;      // byte offsets of the band's own rows
     const int nchunks = (q_own_hi - q_own_lo + 63) >> 6;
     long long stride64;
-    const uint8_t* src = plain_plane(b, L, level, frame, stride64);
+    const uint8_t* src = plain_plane<GATHER>(b, L, level, frame, stride64);
     auto clear_lds = [&]() {
         for (int i = tid; i < ((nrows * S + 15) >> 4); i += NT) reinterpret_cast<uint4*>(s_sc)[i] = make_uint4(0, 0, 0, 0);
         if (tid < (int)(sizeof(FastHdr) / 4)) reinterpret_cast<int*>(hdr)[tid] = 0;
@@ -420,20 +420,24 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
 // (round 5: workgroups walking 2 / 4 / 16 bands grid-stride — one launch of long-lived workgroups instead of 729 k short ones — took
 //  1.02 / 1.02 / 1.05 ms against 0.845 per 1024 VGA frames: the dispatcher's interleaving of fresh workgroups is what hides a band's
 //  serial phases, a resident workgroup exposes them)
-template <bool ALIGNED, int NT, int PPT>
-__global__ __launch_bounds__(NT) void k_fast_cells(Batch b) {
+template <bool ALIGNED, int NT, int PPT, bool GATHER>
+__device__ __forceinline__ void k_fast_cells_body(const Batch& b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int frame, item;
     if (!frame_item_magic(b, blockIdx.x, (unsigned)b.g.nbands_total, b.g.nbands_magic, frame, item)) return;
-    fast_band_task<ALIGNED, NT, PPT>(b, frame, item, smem);
+    fast_band_task<ALIGNED, NT, PPT, GATHER>(b, frame, item, smem);
 }
+template <bool ALIGNED, int NT, int PPT>
+__global__ __launch_bounds__(NT) void k_fast_cells(Batch b) { k_fast_cells_body<ALIGNED, NT, PPT, false>(b); }
+template <bool ALIGNED, int NT, int PPT>
+__global__ __launch_bounds__(NT) void k_fast_cells_gather(Batch b) { k_fast_cells_body<ALIGNED, NT, PPT, true>(b); }
 
 // FAST and the blur both depend on the pyramid only.  A launch group that cannot fill the chip (the one-frame drop-in call) runs
 // them side by side in ONE launch: the first blocks of a frame blur short strips (4 waves = 4 strips), the rest are cell bands.
 // (Two streams would do the same for a full batch - launch_extract forks there - but a fork / join across hardware queues costs
 // ~8 us each way, as much as either kernel takes on one frame.)
-template <bool ALIGNED, bool SMALL>
-__global__ __launch_bounds__(SMALL ? FAST_SMALL.threads : FAST_LARGE.threads) void k_fast_blur(Batch b) {
+template <bool ALIGNED, bool SMALL, bool GATHER>
+__device__ __forceinline__ void k_fast_blur_body(const Batch& b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr FastShape A = SMALL ? FAST_SMALL : FAST_LARGE;
     constexpr int NW = A.threads / 64;
@@ -443,16 +447,20 @@ __global__ __launch_bounds__(SMALL ? FAST_SMALL.threads : FAST_LARGE.threads) vo
     const int frame = blockIdx.x / per_frame, item = blockIdx.x - frame * per_frame;
     if (item < nblur) {
         const int t = item * NW + wave_id();
-        if (t < g.nbtiles_total_s) blur_strip<ALIGNED, BLUR_ROWS_SMALL>(b, frame, t);
-    } else fast_band_task<ALIGNED, A.threads, A.ppt>(b, frame, item - nblur, smem);
+        if (t < g.nbtiles_total_s) blur_strip<ALIGNED, BLUR_ROWS_SMALL, GATHER>(b, frame, t);
+    } else fast_band_task<ALIGNED, A.threads, A.ppt, GATHER>(b, frame, item - nblur, smem);
 }
+template <bool ALIGNED, bool SMALL>
+__global__ __launch_bounds__(SMALL ? FAST_SMALL.threads : FAST_LARGE.threads) void k_fast_blur(Batch b) { k_fast_blur_body<ALIGNED, SMALL, false>(b); }
+template <bool ALIGNED, bool SMALL>
+__global__ __launch_bounds__(SMALL ? FAST_SMALL.threads : FAST_LARGE.threads) void k_fast_blur_gather(Batch b) { k_fast_blur_body<ALIGNED, SMALL, true>(b); }
 
 
 // (launch_extract's FAST stage.  fuse_blur: the blur's short strips ride in the same launch)
 int launch_fast(const Batch& b, const HostGeom& hg, hipStream_t stream, bool fuse_blur) {
     const DevGeom& g = hg.g;
     const int F = b.nframes;
-    const bool aligned = (((uintptr_t)b.img | (uintptr_t)b.img_row_stride | (uintptr_t)b.img_frame_stride) & 3) == 0;
+    const bool aligned = (level0_bits(b) & 3) == 0;
     const size_t lds = (size_t)g.fast_lds_bytes;
     auto launch = [&](auto kern, int threads) -> bool {
         if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
@@ -469,8 +477,14 @@ int launch_fast(const Batch& b, const HostGeom& hg, hipStream_t stream, bool fus
             hipLaunchKernelGGL(kern, dim3(F * per_frame), dim3(threads), lds, stream, b);
             return true;
         };
-        if (g.fast_small) ok = aligned ? launch2(k_fast_blur<true, true>) : launch2(k_fast_blur<false, true>);
+        if (b.img_tab) {
+            if (g.fast_small) ok = aligned ? launch2(k_fast_blur_gather<true, true>) : launch2(k_fast_blur_gather<false, true>);
+            else ok = aligned ? launch2(k_fast_blur_gather<true, false>) : launch2(k_fast_blur_gather<false, false>);
+        } else if (g.fast_small) ok = aligned ? launch2(k_fast_blur<true, true>) : launch2(k_fast_blur<false, true>);
         else ok = aligned ? launch2(k_fast_blur<true, false>) : launch2(k_fast_blur<false, false>);
+    } else if (b.img_tab) {
+        if (g.fast_small) ok = aligned ? launch(k_fast_cells_gather<true, A.threads, A.ppt>, A.threads) : launch(k_fast_cells_gather<false, A.threads, A.ppt>, A.threads);
+        else ok = aligned ? launch(k_fast_cells_gather<true, B.threads, B.ppt>, B.threads) : launch(k_fast_cells_gather<false, B.threads, B.ppt>, B.threads);
     } else if (g.fast_small) ok = aligned ? launch(k_fast_cells<true, A.threads, A.ppt>, A.threads) : launch(k_fast_cells<false, A.threads, A.ppt>, A.threads);
     else ok = aligned ? launch(k_fast_cells<true, B.threads, B.ppt>, B.threads) : launch(k_fast_cells<false, B.threads, B.ppt>, B.threads);
     if (!ok) return ORBX_ERR_DEVICE;

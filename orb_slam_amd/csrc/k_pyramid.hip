@@ -16,8 +16,8 @@ namespace orbx {
 // LDS source tile: L.rz_rows x L.rz_pitch bytes, the exact maximum over the level's tiles (a fixed worst-case array for scale
 // 2.5 capped the kernel's occupancy)
 
-template <bool ALIGNED, bool WINDOW>
-__global__ __launch_bounds__(256) void k_resize(Batch b, int level) {
+template <bool ALIGNED, bool WINDOW, bool GATHER>
+__device__ __forceinline__ void k_resize_body(Batch b, int level) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_src[];
     const DevGeom& g = b.g;
     const LevelGeom& L = g.lv[level];
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_resize(Batch b, int level) {
     const int bx0 = tile_x * 256, by0 = tile_y * RZ_ROWS;
     const int bx1 = min(bx0 + 255, L.w - 1), by1 = min(by0 + RZ_ROWS - 1, L.h - 1);
     long long sstride;
-    const uint8_t* src = plain_plane(b, P, level - 1, frame, sstride);
+    const uint8_t* src = plain_plane<GATHER>(b, P, level - 1, frame, sstride);
     const ResizeX* tx = b.tabx + L.tabx_off;
     const ResizeY* ty = b.taby + L.taby_off;
     // this lane's 4 output columns (independent of the staging below: issued first)
@@ -168,6 +168,10 @@ __global__ __launch_bounds__(256) void k_resize(Batch b, int level) {
         *reinterpret_cast<uint32_t*>(dplane + (long long)dy * L.stride + dx0) = packed;
     }
 }
+template <bool ALIGNED, bool WINDOW>
+__global__ __launch_bounds__(256) void k_resize(Batch b, int level) { k_resize_body<ALIGNED, WINDOW, false>(b, level); }
+template <bool ALIGNED, bool WINDOW>
+__global__ __launch_bounds__(256) void k_resize_gather(Batch b, int level) { k_resize_body<ALIGNED, WINDOW, true>(b, level); }
 
 // Fused pyramid: one launch produces the levels l0+1 .. l0+depth of a PyrGroup (round 2: 2 launches for 8 levels instead of 7
 // dependent ones — on one frame each k_resize launch cost ~9 us of latency, 65 of the ~150 us of a frame's kernel chain).
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(256) void k_resize(Batch b, int level) {
 // tables as k_resize), kept in LDS for the next one and written to HBM where the tile OWNS it (regions of neighbouring tiles
 // overlap by the bilinear footprint; ownership — region start to the next tile's region start — partitions each level).
 // Threads: 32 dword columns x 8 row phases; a thread keeps its four resize-table entries across its rows.
-template <bool ALIGNED>
+template <bool ALIGNED, bool GATHER>
 __global__ __launch_bounds__(256) void k_pyramid(Batch b, int group) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_lv[];
     const DevGeom& g = b.g;
@@ -195,7 +199,7 @@ __global__ __launch_bounds__(256) void k_pyramid(Batch b, int group) {
         const int xs = xr(0, ix, 0), xe = xr(0, ix, 1), ys = yr(0, iy, 0), ye = yr(0, iy, 1);
         const int nd = ((xe - xs) >> 2) + 1, nr = ye - ys + 1;
         long long sstride;
-        const uint8_t* src = plain_plane(b, P, l0, frame, sstride);
+        const uint8_t* src = plain_plane<GATHER>(b, P, l0, frame, sstride);
         const uint8_t* base = src + (long long)ys * sstride + xs;
         const int xm = P.w - 1 - xs;
         const int total = nr * nd;
@@ -274,7 +278,7 @@ int launch_pyramid(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const DevGeom& g = hg.g;
     const int F = b.nframes;
     const bool fused_pyramid = g.npyr_groups > 0 && F < PYR_FUSED_MAX_FRAMES;
-    const bool al0 = (((uintptr_t)b.img | (uintptr_t)b.img_row_stride | (uintptr_t)b.img_frame_stride) & 3) == 0;
+    const bool al0 = (level0_bits(b) & 3) == 0;
     // Fused launches when the batch is too small to fill the chip (the drop-in call: one frame): there the chain of dependent
     // launches is the cost (189 vs 236 us per VGA frame); a full batch prefers the leaner per-level kernels (0.72 vs 0.81 ms per 1024
     // frames: the cones recompute their overlap and synchronise per level).
@@ -283,8 +287,11 @@ int launch_pyramid(const Batch& b, const HostGeom& hg, hipStream_t stream) {
             const PyrGroup& pg = g.pyr[gi];
             const bool al = pg.l0 > 0 || al0;
             dim3 grid(pg.ntx, pg.nty, F);
-            if (al) hipLaunchKernelGGL(k_pyramid<true>, grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
-            else hipLaunchKernelGGL(k_pyramid<false>, grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
+            if (b.img_tab && pg.l0 == 0) {     // (gather form: only the cone that starts at level 0 reads the caller's frames)
+                if (al) hipLaunchKernelGGL((k_pyramid<true, true>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
+                else hipLaunchKernelGGL((k_pyramid<false, true>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
+            } else if (al) hipLaunchKernelGGL((k_pyramid<true, false>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
+            else hipLaunchKernelGGL((k_pyramid<false, false>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
             ORBX_LAUNCH_CHECK();
         }
     } else {
@@ -293,7 +300,15 @@ int launch_pyramid(const Batch& b, const HostGeom& hg, hipStream_t stream) {
             dim3 grid(frame_item_blocks(b, ((L.w + 255) / 256) * ((L.h + RZ_ROWS - 1) / RZ_ROWS)));
             const bool al = l > 1 || al0;
             const size_t lds = (size_t)L.rz_pitch * L.rz_rows;
-            if (L.rz_window) {
+            if (b.img_tab && l == 1) {        // (gather form: level 1 is the one resized from the caller's frames)
+                if (L.rz_window) {
+                    if (al) hipLaunchKernelGGL((k_resize_gather<true, true>), grid, dim3(256), lds, stream, b, l);
+                    else hipLaunchKernelGGL((k_resize_gather<false, true>), grid, dim3(256), lds, stream, b, l);
+                } else {
+                    if (al) hipLaunchKernelGGL((k_resize_gather<true, false>), grid, dim3(256), lds, stream, b, l);
+                    else hipLaunchKernelGGL((k_resize_gather<false, false>), grid, dim3(256), lds, stream, b, l);
+                }
+            } else if (L.rz_window) {
                 if (al) hipLaunchKernelGGL((k_resize<true, true>), grid, dim3(256), lds, stream, b, l);
                 else hipLaunchKernelGGL((k_resize<false, true>), grid, dim3(256), lds, stream, b, l);
             } else {

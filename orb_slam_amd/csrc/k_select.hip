@@ -307,6 +307,7 @@ __device__ float harris_response(const uint8_t* img, long long step, int x, int 
 constexpr int SEL_SMALL = 384;
 __host__ __device__ constexpr int sel_wave_bytes(int entries) { return (entries * ((int)sizeof(Cand) + 4) + 16 + 15) & ~15; }
 // one wave; returns false when the cell's list belongs to the other length class (it did nothing)
+template <bool GATHER>
 __device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int cell, int level, uint8_t* smem, int lds_entries, int min_entries, int lane) {
     const DevGeom& g = b.g;
     const LevelGeom& L = g.lv[level];
@@ -324,7 +325,7 @@ __device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int 
     Cand* out = b.sel + (long long)frame * g.frame_sel + L.sel_base + s.out_off;
     const float thr = (float)s.thr;
     long long stride;
-    const uint8_t* img = plain_plane(b, L, level, frame, stride);
+    const uint8_t* img = plain_plane<GATHER>(b, L, level, frame, stride);
     if (n_all > lds_entries) {
         // rare: list longer than the LDS staging area -> the plain sequential algorithm in global memory
         // (filtered entries are compacted to the front of the cell's area; the write index never passes the read index)
@@ -381,17 +382,20 @@ __device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int 
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_cell_select(Batch b, int lds_entries) {
+template <bool GATHER>
+__device__ __forceinline__ void k_cell_select_body(const Batch& b, int lds_entries) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DevGeom& g = b.g;
     const int wave = wave_id(), lane = (int)threadIdx.x & 63;
     const int id = (int)blockIdx.x * 4 + wave;
     if (id >= b.nframes * g.ncells_total) return;
     const int frame = id / g.ncells_total, cell = id - frame * g.ncells_total;
-    const bool done = cell_select_body(b, frame, cell, find_level(g.cell_bases, cell), smem + wave * sel_wave_bytes(lds_entries), lds_entries, 0, lane);
+    const bool done = cell_select_body<GATHER>(b, frame, cell, find_level(g.cell_bases, cell), smem + wave * sel_wave_bytes(lds_entries), lds_entries, 0, lane);
     if (lane == 0) b.long_cells[id] = done ? 0 : 1;          // a flag per cell: no list, no atomics (one counter for ~150 k long cells of a
-}                                                            // noise-like batch serialised for 1.3 ms, 64 sharded ones still for 0.5)
-
+                                                            // noise-like batch serialised for 1.3 ms, 64 sharded ones still for 0.5)
+}
+__global__ __launch_bounds__(256) void k_cell_select(Batch b, int lds_entries) { k_cell_select_body<false>(b, lds_entries); }
+__global__ __launch_bounds__(256) void k_cell_select_gather(Batch b, int lds_entries) { k_cell_select_body<true>(b, lds_entries); }
 // The cells k_cell_select left over (lists beyond its staging area).  A workgroup of four waves looks at the flags of SEL_LONG_CHUNK
 // consecutive cells and shares ONE full staging area (sel_lds_entries entries) by list length: lists that fit a quarter of it are taken
 // four at a time (one wave each), lists that fit a third three at a time, half two at a time, the rest one at a time with all of it.  A wave's selection
@@ -410,7 +414,8 @@ __host__ __device__ constexpr int sel_long_bytes(int entries) {      // the shar
     for (int share = 1; share <= 4; share++) { const int v = share * sel_wave_bytes((entries + share - 1) / share); m = v > m ? v : m; }
     return m;
 }
-__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long(Batch b) {
+template <bool GATHER>
+__device__ __forceinline__ void k_cell_select_long_body(const Batch& b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DevGeom& g = b.g;
     const int lane = (int)threadIdx.x & 63, wave = wave_id(), total = b.nframes * g.ncells_total;
@@ -444,13 +449,15 @@ __global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long(Batch 
                 m &= m - 1;
                 if (r % share != wave) continue;
                 const int frame = id / g.ncells_total, cell = id - frame * g.ncells_total;
-                (void)cell_select_body(b, frame, cell, find_level(g.cell_bases, cell), area, entries, 0, lane);
+                (void)cell_select_body<GATHER>(b, frame, cell, find_level(g.cell_bases, cell), area, entries, 0, lane);
                 wave_lds_fence();
             }
         }
         __syncthreads();                                       // the parts change owners
     }
 }
+__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long(Batch b) { k_cell_select_long_body<false>(b); }
+__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long_gather(Batch b) { k_cell_select_long_body<true>(b); }
 
 // reference :697-701 (per-level cap), same scheme; one wave
 __device__ __forceinline__ void level_select_body(const Batch& b, int frame, int level, uint8_t* smem, int lane) {
@@ -529,13 +536,15 @@ int launch_cell_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     // more than the occupancy gains); otherwise short lists first, then the (usually empty) list of long cells
     const int small = F < PYR_FUSED_MAX_FRAMES ? g.sel_lds_entries : std::min(SEL_SMALL, g.sel_lds_entries);
     const size_t lds = (size_t)4 * sel_wave_bytes(small);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cell_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
-    hipLaunchKernelGGL(k_cell_select, dim3((F * g.ncells_total + 3) / 4), dim3(256), lds, stream, b, small);
+    auto* const ksel = b.img_tab ? k_cell_select_gather : k_cell_select;      // (gather form: Harris reads the caller's frames)
+    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ksel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
+    hipLaunchKernelGGL(ksel, dim3((F * g.ncells_total + 3) / 4), dim3(256), lds, stream, b, small);
     ORBX_LAUNCH_CHECK();
     if (small < g.sel_lds_entries) {
         const size_t ldsl = (size_t)sel_long_bytes(g.sel_lds_entries);
-        if (ldsl > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cell_select_long), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl) != hipSuccess) return ORBX_ERR_DEVICE;
-        hipLaunchKernelGGL(k_cell_select_long, dim3((F * g.ncells_total + SEL_LONG_CHUNK - 1) / SEL_LONG_CHUNK), dim3(SEL_LONG_WAVES * 64), ldsl, stream, b);
+        auto* const klong = b.img_tab ? k_cell_select_long_gather : k_cell_select_long;
+        if (ldsl > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(klong), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl) != hipSuccess) return ORBX_ERR_DEVICE;
+        hipLaunchKernelGGL(klong, dim3((F * g.ncells_total + SEL_LONG_CHUNK - 1) / SEL_LONG_CHUNK), dim3(SEL_LONG_WAVES * 64), ldsl, stream, b);
         ORBX_LAUNCH_CHECK();
     }
     return ORBX_OK;

@@ -1,5 +1,6 @@
 // C ABI of the extractor (include/orbx.h): handle, device memory, launch orchestration.
 // All pixel work happens in the k_*.hip kernels (strung together by orbx_launch.hip); there is no host fallback.
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,6 +66,23 @@ struct orbx_extractor {
                    cap == o.cap && row_stride == o.row_stride && frame_stride == o.frame_stride;
         }
     } ph_key = {};
+    // gather form (orbx_extract_batch): the per-frame level-0 table of each launch group, staged in a pinned ring and copied in stream
+    // order into the matching device slot; tab_ev[i] is recorded after the kernels of the group that used slot i, so a slot is rewritten
+    // only once both its copy and the kernels reading the device copy are done
+    static constexpr int TAB_RING = 4;
+    ImgSrc* d_tab = nullptr;
+    ImgSrc* h_tab = nullptr;
+    hipEvent_t tab_ev[TAB_RING] = {};
+    int tab_next = 0;
+    std::vector<ImgSrc> last_tab;     // the last gather group's table (orbx_debug_fetch of level 0)
+    // host form: two device frame buffers of one launch group each (pitch w rounded up to 16), two pinned staging buffers for pageable
+    // frames, and the copy stream.  up_ev[i]: the upload into buffer i is done; kern_ev[i]: the kernels that read buffer i are done.
+    hipStream_t up = nullptr;
+    uint8_t* d_hbuf[2] = {};
+    uint8_t* h_stage[2] = {};
+    size_t hbuf_bytes = 0;
+    hipEvent_t up_ev[2] = {}, kern_ev[2] = {};
+    int hnext = 0;
 };
 
 #define HIPCHK(h, call)                                                                      \
@@ -140,6 +158,168 @@ static void fill_batch(orbx_extractor* h, Batch& b) {
     b.level_total = h->d_level_total; b.level_count = h->d_level_count; b.status = h->d_status; b.long_cells = h->d_long_cells;
 }
 
+// the parts of a launch group's Batch that do not depend on where its frames are
+static void group_batch(orbx_extractor* h, Batch& b, int f0, int n, orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status) {
+    memset(&b, 0, sizeof(b));
+    fill_batch(h, b);
+    b.fallback_hint = h->fallback_hint ? 1 : 0;
+    b.nframes = n;
+    b.xcd_affinity = (b.nframes >= XCD_AFFINITY_MIN_FRAMES && !h->no_xcd_affinity) ? 1 : 0;
+    b.blur_on_demand = h->blur_on_demand;
+    b.od_min_frames = h->od_min_frames;
+    b.out_kps = d_kps + (size_t)f0 * cap;
+    b.out_desc = d_desc + (size_t)f0 * cap * 32;
+    b.out_n = d_n + f0;
+    b.out_status = d_status ? d_status + f0 : nullptr;
+    b.cap = cap;
+}
+
+// pinned (page-locked, registered) host memory: the copy engine reads it in place.  Pageable memory makes hipPointerGetAttributes fail
+// or report hipMemoryTypeUnregistered.
+static hipMemoryType host_memory_type(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return hipMemoryTypeUnregistered;
+    }
+    return a.type;
+}
+
+static int ensure_tab(orbx_extractor* h) {
+    if (h->d_tab) return ORBX_OK;
+    const size_t bytes = (size_t)orbx_extractor::TAB_RING * h->p.max_batch * sizeof(ImgSrc);
+    HIPCHK(h, hipMalloc(&h->d_tab, bytes));
+    HIPCHK(h, hipHostMalloc(&h->h_tab, bytes, hipHostMallocDefault));
+    for (hipEvent_t& e : h->tab_ev) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return ORBX_OK;
+}
+
+// device form of orbx_extract_batch: one table per launch group, the kernels read the caller's frames through it
+static int extract_gather(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, orbx_keypoint* d_kps,
+                          uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
+    int rc = ensure_tab(h);
+    if (rc != ORBX_OK) return rc;
+    const int mb = h->p.max_batch;
+    for (int f0 = 0; f0 < nframes; f0 += mb) {
+        const int n = std::min(mb, nframes - f0);
+        const int slot = h->tab_next;
+        h->tab_next = (slot + 1) % orbx_extractor::TAB_RING;
+        HIPCHK(h, hipEventSynchronize(h->tab_ev[slot]));      // the slot's last copy and the kernels that read its device copy are done
+        ImgSrc* ht = h->h_tab + (size_t)slot * mb;
+        ImgSrc* dt = h->d_tab + (size_t)slot * mb;
+        unsigned long long bits = 0;
+        long long min_stride = LLONG_MAX;
+        for (int i = 0; i < n; i++) {
+            const long long s = row_strides ? (long long)row_strides[f0 + i] : (long long)w;
+            ht[i].data = imgs[f0 + i];
+            ht[i].row_stride = s;
+            bits |= (uintptr_t)imgs[f0 + i] | (unsigned long long)s;
+            min_stride = std::min(min_stride, s);
+        }
+        HIPCHK(h, hipMemcpyAsync(dt, ht, (size_t)n * sizeof(ImgSrc), hipMemcpyHostToDevice, stream));
+        Batch b;
+        group_batch(h, b, f0, n, d_kps, d_desc, d_n, cap, d_status);
+        b.img_row_stride = min_stride;
+        b.img_tab = dt;
+        b.img_tab_bits = bits;
+        b.img_tab_min_stride = min_stride;
+        rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side);
+        if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
+        HIPCHK(h, hipEventRecord(h->tab_ev[slot], stream));
+        h->last = b;
+        h->have_last = true;
+        h->last_tab.assign(ht, ht + n);
+    }
+    return ORBX_OK;
+}
+
+// host form of orbx_extract_batch: each launch group is uploaded into one of two device buffers on the copy stream (pinned frames straight
+// from the caller's memory, pageable ones through a pinned staging buffer filled by this thread) while the previous group computes, and then
+// runs the contiguous path on that buffer
+static int extract_host(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt, orbx_keypoint* d_kps,
+                        uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
+    const int mb = h->p.max_batch;
+    const size_t P = ((size_t)w + 15) & ~(size_t)15, fb = P * hgt;
+    if (!h->up) {
+        HIPCHK(h, hipStreamCreateWithFlags(&h->up, hipStreamNonBlocking));
+        for (int i = 0; i < 2; i++) {
+            HIPCHK(h, hipEventCreateWithFlags(&h->up_ev[i], hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&h->kern_ev[i], hipEventDisableTiming));
+        }
+    }
+    std::vector<char> pinned(nframes);
+    bool any_pageable = false;
+    for (int f = 0; f < nframes; f++) {
+        const hipMemoryType t = host_memory_type(imgs[f]);
+        if (t == hipMemoryTypeDevice || t == hipMemoryTypeArray) { h->err = "ORBX_FRAMES_ON_HOST with a device pointer"; return ORBX_ERR_ARG; }
+        pinned[f] = t == hipMemoryTypeHost;
+        any_pageable |= !pinned[f];
+    }
+    if (h->hbuf_bytes < fb * mb || (any_pageable && !h->h_stage[0])) {
+        // grown with the geometry (nothing queued may still use the old buffers); the pinned staging buffers only once a pageable frame comes
+        HIPCHK(h, hipDeviceSynchronize());
+        const bool stage = any_pageable || h->h_stage[0];
+        h->hbuf_bytes = 0;
+        for (int i = 0; i < 2; i++) {
+            dev_free(h->d_hbuf[i]);
+            if (h->h_stage[i]) (void)hipHostFree(h->h_stage[i]);
+            h->h_stage[i] = nullptr;
+        }
+        for (int i = 0; i < 2; i++) {
+            HIPCHK(h, hipMalloc(&h->d_hbuf[i], fb * mb));
+            if (stage) HIPCHK(h, hipHostMalloc(&h->h_stage[i], fb * mb, hipHostMallocDefault));
+        }
+        h->hbuf_bytes = fb * mb;
+    }
+    for (int f0 = 0; f0 < nframes; f0 += mb) {
+        const int n = std::min(mb, nframes - f0);
+        const int i = h->hnext;
+        h->hnext ^= 1;
+        uint8_t* dbuf = h->d_hbuf[i];
+        uint8_t* stage = h->h_stage[i];
+        HIPCHK(h, hipStreamWaitEvent(h->up, h->kern_ev[i], 0));   // the kernels of the group that last read buffer i
+        bool stage_free = false;
+        for (int j = 0; j < n;) {
+            const uint8_t* src = imgs[f0 + j];
+            const ptrdiff_t s = row_strides ? row_strides[f0 + j] : (ptrdiff_t)w;
+            if (pinned[f0 + j]) {
+                HIPCHK(h, hipMemcpy2DAsync(dbuf + j * fb, P, src, (size_t)s, (size_t)w, (size_t)hgt, hipMemcpyHostToDevice, h->up));
+                j++;
+                continue;
+            }
+            if (!stage_free) {                                    // its last upload (two groups back) has been read out
+                HIPCHK(h, hipEventSynchronize(h->up_ev[i]));
+                stage_free = true;
+            }
+            int j1 = j;                                           // a run of pageable frames: one copy
+            for (; j1 < n && !pinned[f0 + j1]; j1++) {
+                const uint8_t* fs = imgs[f0 + j1];
+                const ptrdiff_t fst = row_strides ? row_strides[f0 + j1] : (ptrdiff_t)w;
+                uint8_t* d = stage + j1 * fb;
+                if (fst == (ptrdiff_t)P) memcpy(d, fs, fb - (P - (size_t)w));      // (the last row: w bytes, not P)
+                else for (int y = 0; y < hgt; y++) memcpy(d + y * P, fs + (ptrdiff_t)y * fst, (size_t)w);
+            }
+            HIPCHK(h, hipMemcpyAsync(dbuf + j * fb, stage + j * fb, (size_t)(j1 - j) * fb, hipMemcpyHostToDevice, h->up));
+            j = j1;
+        }
+        HIPCHK(h, hipEventRecord(h->up_ev[i], h->up));
+        HIPCHK(h, hipStreamWaitEvent(stream, h->up_ev[i], 0));
+        Batch b;
+        group_batch(h, b, f0, n, d_kps, d_desc, d_n, cap, d_status);
+        b.img = dbuf;
+        b.img_row_stride = (long long)P;
+        b.img_frame_stride = (long long)fb;
+        const int rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side);
+        if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
+        HIPCHK(h, hipEventRecord(h->kern_ev[i], stream));
+        h->last = b;
+        h->have_last = true;
+    }
+    // every caller frame has been read once both uploads are done (pinned frames are DMA'd from the caller's memory)
+    for (int i = 0; i < 2; i++) HIPCHK(h, hipEventSynchronize(h->up_ev[i]));
+    return ORBX_OK;
+}
+
 extern "C" {
 
 void orbx_default_params(orbx_params* p) {
@@ -196,6 +376,16 @@ void orbx_destroy(orbx_extractor* h) {
     if (h->h_img1) (void)hipHostFree(h->h_img1);
     if (h->h_out1) (void)hipHostFree(h->h_out1);
     if (h->s1) (void)hipStreamDestroy(h->s1);
+    dev_free(h->d_tab);
+    if (h->h_tab) (void)hipHostFree(h->h_tab);
+    for (hipEvent_t e : h->tab_ev) if (e) (void)hipEventDestroy(e);
+    for (int i = 0; i < 2; i++) {
+        dev_free(h->d_hbuf[i]);
+        if (h->h_stage[i]) (void)hipHostFree(h->h_stage[i]);
+        if (h->up_ev[i]) (void)hipEventDestroy(h->up_ev[i]);
+        if (h->kern_ev[i]) (void)hipEventDestroy(h->kern_ev[i]);
+    }
+    if (h->up) (void)hipStreamDestroy(h->up);
     delete h;
 }
 
@@ -254,21 +444,10 @@ int orbx_extract_batch_device_phases(orbx_extractor* h, const uint8_t* d_imgs, i
     hipStream_t stream = (hipStream_t)stream_;
     for (int f0 = 0; f0 < nframes; f0 += h->p.max_batch) {
         Batch b;
-        memset(&b, 0, sizeof(b));
-        fill_batch(h, b);
-        b.fallback_hint = h->fallback_hint ? 1 : 0;
-        b.nframes = std::min(h->p.max_batch, nframes - f0);
-        b.xcd_affinity = (b.nframes >= XCD_AFFINITY_MIN_FRAMES && !h->no_xcd_affinity) ? 1 : 0;
-        b.blur_on_demand = h->blur_on_demand;
-        b.od_min_frames = h->od_min_frames;
+        group_batch(h, b, f0, std::min(h->p.max_batch, nframes - f0), d_kps, d_desc, d_n, cap, d_status);
         b.img = d_imgs + (ptrdiff_t)f0 * frame_stride;
         b.img_row_stride = row_stride;
         b.img_frame_stride = frame_stride;
-        b.out_kps = d_kps + (size_t)f0 * cap;
-        b.out_desc = d_desc + (size_t)f0 * cap * 32;
-        b.out_n = d_n + f0;
-        b.out_status = d_status ? d_status + f0 : nullptr;
-        b.cap = cap;
         rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side, phases);
         if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
         h->last = b;
@@ -277,6 +456,28 @@ int orbx_extract_batch_device_phases(orbx_extractor* h, const uint8_t* d_imgs, i
     if (phases & ORBX_PHASE_PYRAMID) h->ph_key = key;
     h->ph_done |= phases;
     return ORBX_OK;
+}
+
+int orbx_extract_batch(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt, int where,
+                       orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, void* stream_) {
+    if (!h) return ORBX_ERR_ARG;
+    if (nframes <= 0 || w <= 0 || hgt <= 0) return ORBX_EMPTY;
+    if (!imgs || (where != ORBX_FRAMES_ON_DEVICE && where != ORBX_FRAMES_ON_HOST) || !d_kps || !d_desc || !d_n || cap < 1) {
+        h->err = "bad argument";
+        return ORBX_ERR_ARG;
+    }
+    for (int f = 0; f < nframes; f++) {
+        const ptrdiff_t s = row_strides ? row_strides[f] : (ptrdiff_t)w;
+        if (!imgs[f] || s < w || s >= ((ptrdiff_t)1 << 24)) { h->err = "bad frame pointer or row stride"; return ORBX_ERR_ARG; }
+    }
+    HIPCHK(h, hipSetDevice(h->p.device));
+    int rc = ensure_geometry(h, w, hgt);
+    if (rc != ORBX_OK) return rc;
+    if (cap < h->hg.g.nslots) { h->err = "cap < orbx_max_keypoints()"; return ORBX_ERR_CAPACITY; }
+    h->ph_done = 0;                                              // the handle's scratch now holds this call's groups: no phased call may continue
+    hipStream_t stream = (hipStream_t)stream_;
+    if (where == ORBX_FRAMES_ON_HOST) return extract_host(h, imgs, row_strides, nframes, w, hgt, d_kps, d_desc, d_n, cap, d_status, stream);
+    return extract_gather(h, imgs, row_strides, nframes, w, d_kps, d_desc, d_n, cap, d_status, stream);
 }
 
 int orbx_extract(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_t stride, orbx_keypoint* kps, uint8_t* desc, int cap,
@@ -434,8 +635,13 @@ long orbx_debug_fetch(orbx_extractor* h, int what, int frame, int level, void* h
         const uint8_t* src;
         size_t spitch;
         if (what == ORBX_DBG_PLANE && level == 0) {
-            src = b.img + (ptrdiff_t)frame * b.img_frame_stride;
-            spitch = (size_t)b.img_row_stride;
+            if (b.img_tab) {
+                src = h->last_tab[frame].data;
+                spitch = (size_t)h->last_tab[frame].row_stride;
+            } else {
+                src = b.img + (ptrdiff_t)frame * b.img_frame_stride;
+                spitch = (size_t)b.img_row_stride;
+            }
         } else {
             const uint8_t* base = what == ORBX_DBG_PLANE ? b.pyr : b.blur;
             src = base + (size_t)frame * g.frame_plane_bytes + L.plane_off;

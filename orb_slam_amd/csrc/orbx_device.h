@@ -12,8 +12,21 @@ static __device__ __constant__ uint32_t c_pattern[256] = {
 #include "orb_pattern_packed.inc"
 };
 
+// Level 0 of `frame` in a gather launch group (b.img_tab set).  `frame` is wave-uniform and the table is read through the constant
+// address space, so the entry arrives with one s_load_dwordx4 per wave (a generic pointer is not provably unclobbered: per-lane loads).
+__device__ __forceinline__ const uint8_t* level0_src(const Batch& b, int frame, long long& stride) {
+    typedef const ImgSrc __attribute__((address_space(4)))* ctab_t;
+    const ctab_t e = (ctab_t)(uintptr_t)b.img_tab + frame;
+    stride = e->row_stride;
+    return e->data;
+}
+
+// GATHER: the launch group's level 0 comes from b.img_tab (the *_gather kernels); a template argument rather than a test of img_tab, so
+// that the contiguous kernels keep their exact code, registers and occupancy.
+template <bool GATHER = false>
 __device__ __forceinline__ const uint8_t* plain_plane(const Batch& b, const LevelGeom& L, int level, int frame, long long& stride) {
     if (level == 0) {
+        if constexpr (GATHER) return level0_src(b, frame, stride);
         stride = b.img_row_stride;
         return b.img + (long long)frame * b.img_frame_stride;
     }

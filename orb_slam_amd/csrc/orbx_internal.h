@@ -209,6 +209,14 @@ struct DevGeom {
     LevelGeom lv[MAX_LEVELS];
 };
 
+// One frame of a gather launch group (orbx_extract_batch): where its level 0 lies and how far apart its rows are.  16 bytes, so that a
+// wave fetches its frame's entry with one s_load_dwordx4 (level0_src).
+struct ImgSrc {
+    const uint8_t* data;
+    long long row_stride;
+};
+static_assert(sizeof(ImgSrc) == 16, "one scalar dwordx4 per table entry");
+
 // Arguments of one batch launch group; passed to kernels BY VALUE so that the geometry lives in the kernarg
 // segment: every LevelGeom field is then fetched with scalar loads (wave-uniform, no vector-memory round trip).
 // (A pointer to the same struct in global memory makes the compiler issue per-lane global loads for each field.)
@@ -242,7 +250,19 @@ struct Batch {
     int xcd_affinity;         // 1: launches renumber their blocks so that a frame's work items share one XCD (its L2)
     int od_min_frames;        // ... from this many frames per launch group on
     int blur_on_demand;       // 1: no blurred plane — k_describe_od blurs each keypoint's window itself (full launch groups of supported geometries)
+    // gather form (orbx_extract_batch): level 0 of frame f is img_tab[f] (a DEVICE table, one entry per frame of the launch group) and
+    // img / img_frame_stride are unused; NULL: the contiguous form above.  The two host-side summaries pick the launch variants.
+    const ImgSrc* img_tab;
+    unsigned long long img_tab_bits;   // host: OR of every data pointer and row stride in the table (alignment choice)
+    long long img_tab_min_stride;      // host: smallest row stride in the table (describe_od_supported)
 };
+
+// Level-0 alignment bits of a launch group: the OR of every frame base and row stride (the frame-stride term is 0 in the gather form).
+static inline unsigned long long level0_bits(const Batch& b) {
+    return b.img_tab ? b.img_tab_bits : ((uintptr_t)b.img | (unsigned long long)b.img_row_stride | (unsigned long long)b.img_frame_stride);
+}
+// Smallest level-0 row stride of a launch group.
+static inline long long level0_min_stride(const Batch& b) { return b.img_tab ? b.img_tab_min_stride : b.img_row_stride; }
 
 // Host-side geometry builder result.
 struct HostGeom {
