@@ -17,6 +17,7 @@
 #include "orbf.h"
 #include "orbf_math.h"
 #include "orbx.h"
+#include "orbx_host.h"
 
 namespace orbf {
 
@@ -174,24 +175,20 @@ int orbf_undistort_grid_batch_device(const orbf_camera* cam, const orbf_bounds* 
 int orbf_undistort_grid(const orbf_camera* cam, const orbf_bounds* b, const orbx_keypoint* kps, int n, orbx_keypoint* kps_un,
                         int32_t* cell_off, int32_t* cell_feat, int device) {
     if (!cam || !b || n < 0 || n > ORBF_MAX_FEATURES || !cell_off || (n > 0 && (!kps || !kps_un || !cell_feat))) return ORBX_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    const size_t N = (size_t)std::max(n, 1);
-    const size_t o_un = N * 28, o_off = ((2 * N * 28 + 15) & ~(size_t)15), o_feat = o_off + (ORBF_GRID_CELLS + 1) * 4, o_n = o_feat + N * 4,
-                 total = o_n + 4;
-    uint8_t* d = nullptr;
-    int rc = ORBX_ERR_DEVICE;
+    HIPTRY(hipSetDevice(device));
     const int32_t count = n;
-    if (hipMalloc(&d, total) == hipSuccess && (n == 0 || hipMemcpy(d, kps, (size_t)n * 28, hipMemcpyHostToDevice) == hipSuccess) &&
-        hipMemcpy(d + o_n, &count, 4, hipMemcpyHostToDevice) == hipSuccess) {
-        rc = orbf_undistort_grid_batch_device(cam, b, (const orbx_keypoint*)d, (const int32_t*)(d + o_n), 1, (int)N, (orbx_keypoint*)(d + o_un),
-                                              (int32_t*)(d + o_off), (int32_t*)(d + o_feat), nullptr);
-        if (rc == ORBX_OK && (hipMemcpy(cell_off, d + o_off, (ORBF_GRID_CELLS + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              (n > 0 && (hipMemcpy(kps_un, d + o_un, (size_t)n * 28, hipMemcpyDeviceToHost) != hipSuccess ||
-                                         hipMemcpy(cell_feat, d + o_feat, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))))
-            rc = ORBX_ERR_DEVICE;
-    }
-    if (d) (void)hipFree(d);
-    return rc;
+    orbx::Staging s;
+    const auto k = s.in(kps, n);
+    const auto c = s.in(&count, 1);
+    const auto un = s.out<orbx_keypoint>(n);
+    const auto off = s.out<int32_t>(ORBF_GRID_CELLS + 1), feat = s.out<int32_t>(n);
+    HIPTRY(s.alloc());
+    const int rc = orbf_undistort_grid_batch_device(cam, b, s[k], s[c], 1, std::max(n, 1), s[un], s[off], s[feat], nullptr);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(cell_off, off, ORBF_GRID_CELLS + 1));
+    HIPTRY(s.get(kps_un, un, n));
+    HIPTRY(s.get(cell_feat, feat, n));
+    return ORBX_OK;
 }
 
 int orbf_features_in_area_device(const orbf_bounds* b, const orbx_keypoint* d_kps_un, int n, const int32_t* d_cell_off, const int32_t* d_cell_feat,
@@ -215,32 +212,21 @@ int orbf_features_in_area(const orbf_bounds* b, const orbx_keypoint* kps_un, int
                           const float* qxyr, const int32_t* qlev, int nq, int32_t* seg_off, int32_t* cand, int cand_cap, int device) {
     if (!b || n < 0 || nq < 0 || cand_cap < 0 || !seg_off || !cell_off) return ORBX_ERR_ARG;
     if (nq > 0 && (!qxyr || !qlev)) return ORBX_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    const size_t N = (size_t)std::max(n, 1), Q = (size_t)std::max(nq, 1), C = (size_t)std::max(cand_cap, 1);
-    const size_t o_off = (N * 28 + 15) & ~(size_t)15, o_feat = o_off + (ORBF_GRID_CELLS + 1) * 4, o_q = o_feat + N * 4, o_l = o_q + Q * 12,
-                 o_seg = o_l + Q * 8, o_cand = o_seg + (Q + 1) * 4, o_st = o_cand + C * 4, total = o_st + 4;
-    uint8_t* d = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&d, total) == hipSuccess && (n == 0 || (hipMemcpy(d, kps_un, (size_t)n * 28, hipMemcpyHostToDevice) == hipSuccess &&
-                                                            hipMemcpy(d + o_feat, cell_feat, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess)) &&
-        hipMemcpy(d + o_off, cell_off, (ORBF_GRID_CELLS + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-        (nq == 0 || (hipMemcpy(d + o_q, qxyr, (size_t)nq * 12, hipMemcpyHostToDevice) == hipSuccess &&
-                     hipMemcpy(d + o_l, qlev, (size_t)nq * 8, hipMemcpyHostToDevice) == hipSuccess))) {
-        rc = orbf_features_in_area_device(b, (const orbx_keypoint*)d, n, (const int32_t*)(d + o_off), (const int32_t*)(d + o_feat), (const float*)(d + o_q),
-                                          (const int32_t*)(d + o_l), nq, (int32_t*)(d + o_seg), (int32_t*)(d + o_cand), cand_cap, (int32_t*)(d + o_st), nullptr);
-        int32_t st = 0;
-        if (rc == ORBX_OK && (hipMemcpy(&st, d + o_st, 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(seg_off, d + o_seg, ((size_t)nq + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ORBX_ERR_DEVICE;
-        if (rc == ORBX_OK) {
-            const int total_c = seg_off[nq];
-            const int ncopy = std::min(total_c, cand_cap);
-            if (ncopy > 0 && hipMemcpy(cand, d + o_cand, (size_t)ncopy * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = ORBX_ERR_DEVICE;
-            else if (st != ORBX_OK) rc = st;
-        }
-    }
-    if (d) (void)hipFree(d);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    orbx::Staging s;
+    const auto k = s.in(kps_un, n);
+    const auto off = s.in(cell_off, ORBF_GRID_CELLS + 1), feat = s.in(cell_feat, n);
+    const auto q = s.in(qxyr, (size_t)nq * 3);
+    const auto l = s.in(qlev, (size_t)nq * 2);
+    const auto seg = s.out<int32_t>((size_t)std::max(nq, 1) + 1), c = s.out<int32_t>(cand_cap), st = s.out<int32_t>(1);
+    HIPTRY(s.alloc());
+    int rc = orbf_features_in_area_device(b, s[k], n, s[off], s[feat], s[q], s[l], nq, s[seg], s[c], cand_cap, s[st], nullptr);
+    if (rc != ORBX_OK) return rc;
+    int32_t status = 0;
+    HIPTRY(s.get(&status, st, 1));
+    HIPTRY(s.get(seg_off, seg, (size_t)nq + 1));
+    HIPTRY(s.get(cand, c, (size_t)std::max(std::min(seg_off[nq], cand_cap), 0)));
+    return status;
 }
 
 }  // extern "C"

@@ -1023,28 +1023,18 @@ int orbm_match_top2_segments(const uint8_t* Q, int nq, const uint8_t* T, int nt,
     if (ncand < 0) return ORBX_ERR_ARG;
     for (int q = 0; q < nq; q++)      // monotone offsets; the key keeps the position inside ONE segment in 22 bits
         if (seg_off[q] > seg_off[q + 1] || seg_off[q] < 0 || seg_off[q + 1] - seg_off[q] >= (1 << KEY_SHIFT)) return ORBX_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    uint8_t *dQ = nullptr, *dT = nullptr;
-    int32_t *dseg = nullptr, *dcand = nullptr, *dout = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&dQ, (size_t)nq * 32) == hipSuccess && hipMalloc(&dT, (size_t)std::max(nt, 1) * 32) == hipSuccess &&
-        hipMalloc(&dseg, (size_t)(nq + 1) * 4) == hipSuccess && hipMalloc(&dcand, (size_t)std::max(ncand, 1) * 4) == hipSuccess &&
-        hipMalloc(&dout, (size_t)nq * 12) == hipSuccess && hipMemcpy(dQ, Q, (size_t)nq * 32, hipMemcpyHostToDevice) == hipSuccess &&
-        (nt == 0 || hipMemcpy(dT, T, (size_t)nt * 32, hipMemcpyHostToDevice) == hipSuccess) &&
-        hipMemcpy(dseg, seg_off, (size_t)(nq + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-        (ncand == 0 || hipMemcpy(dcand, cand, (size_t)ncand * 4, hipMemcpyHostToDevice) == hipSuccess)) {
-        rc = orbm_match_top2_segments_device(dQ, nq, dT, nt, dseg, dcand, dout, dout + nq, dout + 2 * (size_t)nq, nullptr);
-        if (rc == ORBX_OK && (hipMemcpy(best_idx, dout, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(best, dout + nq, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(second, dout + 2 * (size_t)nq, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ORBX_ERR_DEVICE;
-    }
-    if (dQ) (void)hipFree(dQ);
-    if (dT) (void)hipFree(dT);
-    if (dseg) (void)hipFree(dseg);
-    if (dcand) (void)hipFree(dcand);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto q = s.in(Q, (size_t)nq * 32), t = s.in(T, (size_t)nt * 32);
+    const auto sg = s.in(seg_off, (size_t)nq + 1), c = s.in(cand, (size_t)ncand);
+    const auto bi = s.out<int32_t>(nq), bd = s.out<int32_t>(nq), sd = s.out<int32_t>(nq);
+    HIPTRY(s.alloc());
+    const int rc = orbm_match_top2_segments_device(s[q], nq, s[t], nt, s[sg], s[c], s[bi], s[bd], s[sd], nullptr);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(best_idx, bi, nq));
+    HIPTRY(s.get(best, bd, nq));
+    HIPTRY(s.get(second, sd, nq));
+    return ORBX_OK;
 }
 
 // ---- dense top-2 over a SUBSET of the train descriptors (the optional t_valid mask) ------------------------------------
@@ -1133,50 +1123,34 @@ int orbm_match_top2_masked(const uint8_t* Q, int nq, const uint8_t* T, int nt, c
     if (!t_valid) return orbm_match_top2(Q, nq, T, nt, best_idx, best, second, device);
     if (nq < 0 || nt < 0) return ORBX_ERR_ARG;
     if (nq == 0) return ORBX_OK;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    uint8_t *dQ = nullptr, *dT = nullptr, *dV = nullptr;
-    int32_t* dout = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&dQ, (size_t)nq * 32) == hipSuccess && hipMalloc(&dT, (size_t)std::max(nt, 1) * 32) == hipSuccess &&
-        hipMalloc(&dV, (size_t)std::max(nt, 1)) == hipSuccess && hipMalloc(&dout, (size_t)nq * 3 * sizeof(int32_t)) == hipSuccess &&
-        hipMemcpy(dQ, Q, (size_t)nq * 32, hipMemcpyHostToDevice) == hipSuccess &&
-        (nt == 0 || (hipMemcpy(dT, T, (size_t)nt * 32, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dV, t_valid, (size_t)nt, hipMemcpyHostToDevice) == hipSuccess))) {
-        rc = orbm_match_top2_masked_device(dQ, nq, dT, nt, dV, dout, dout + nq, dout + 2 * (size_t)nq, nullptr);
-        if (rc == ORBX_OK && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(best_idx, dout, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(best, dout + nq, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(second, dout + 2 * (size_t)nq, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ORBX_ERR_DEVICE;
-    }
-    if (dQ) (void)hipFree(dQ);
-    if (dT) (void)hipFree(dT);
-    if (dV) (void)hipFree(dV);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto q = s.in(Q, (size_t)nq * 32), t = s.in(T, (size_t)nt * 32), v = s.in(t_valid, (size_t)nt);
+    const auto bi = s.out<int32_t>(nq), bd = s.out<int32_t>(nq), sd = s.out<int32_t>(nq);
+    HIPTRY(s.alloc());
+    const int rc = orbm_match_top2_masked_device(s[q], nq, s[t], nt, s[v], s[bi], s[bd], s[sd], nullptr);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(hipStreamSynchronize(nullptr));
+    HIPTRY(s.get(best_idx, bi, nq));
+    HIPTRY(s.get(best, bd, nq));
+    HIPTRY(s.get(second, sd, nq));
+    return ORBX_OK;
 }
 
 int orbm_match_top2(const uint8_t* Q, int nq, const uint8_t* T, int nt, int32_t* best_idx, int32_t* best, int32_t* second, int device) {
     if (nq < 0 || nt < 0) return ORBX_ERR_ARG;
     if (nq == 0) return ORBX_OK;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    uint8_t *dQ = nullptr, *dT = nullptr;
-    int32_t* dout = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&dQ, (size_t)nq * 32) == hipSuccess && hipMalloc(&dT, (size_t)std::max(nt, 1) * 32) == hipSuccess &&
-        hipMalloc(&dout, (size_t)nq * 3 * sizeof(int32_t)) == hipSuccess &&
-        hipMemcpy(dQ, Q, (size_t)nq * 32, hipMemcpyHostToDevice) == hipSuccess &&
-        (nt == 0 || hipMemcpy(dT, T, (size_t)nt * 32, hipMemcpyHostToDevice) == hipSuccess)) {
-        rc = orbm_match_top2_device(dQ, nq, dT, nt, dout, dout + nq, dout + 2 * (size_t)nq, nullptr);
-        if (rc == ORBX_OK) {
-            if (hipMemcpy(best_idx, dout, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(best, dout + nq, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(second, dout + 2 * (size_t)nq, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = ORBX_ERR_DEVICE;
-        }
-    }
-    if (dQ) (void)hipFree(dQ);
-    if (dT) (void)hipFree(dT);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto q = s.in(Q, (size_t)nq * 32), t = s.in(T, (size_t)nt * 32);
+    const auto bi = s.out<int32_t>(nq), bd = s.out<int32_t>(nq), sd = s.out<int32_t>(nq);
+    HIPTRY(s.alloc());
+    const int rc = orbm_match_top2_device(s[q], nq, s[t], nt, s[bi], s[bd], s[sd], nullptr);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(best_idx, bi, nq));
+    HIPTRY(s.get(best, bd, nq));
+    HIPTRY(s.get(second, sd, nq));
+    return ORBX_OK;
 }
 
 
@@ -1196,20 +1170,17 @@ int orbm_distinctive(const uint8_t* desc, const int32_t* seg_off, int npoints, i
     const int total = seg_off[npoints];
     if (total < 0 || total >= 65536 * 64 || (total > 0 && !desc)) return ORBX_ERR_ARG;
     for (int p = 0; p < npoints; p++) if (seg_off[p + 1] < seg_off[p] || seg_off[p + 1] - seg_off[p] > 65535) return ORBX_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    uint8_t* d = nullptr;
-    const size_t o_seg = (size_t)std::max(total, 1) * 32, o_out = o_seg + ((size_t)npoints + 1) * 4, bytes = o_out + (size_t)npoints * 8;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&d, bytes) == hipSuccess && (total == 0 || hipMemcpy(d, desc, (size_t)total * 32, hipMemcpyHostToDevice) == hipSuccess) &&
-        hipMemcpy(d + o_seg, seg_off, ((size_t)npoints + 1) * 4, hipMemcpyHostToDevice) == hipSuccess) {
-        int32_t* out = (int32_t*)(d + o_out);
-        rc = orbm_distinctive_device(d, (const int32_t*)(d + o_seg), npoints, out, out + npoints, nullptr);
-        if (rc == ORBX_OK && (hipMemcpy(best_idx, out, (size_t)npoints * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(best_median, out + npoints, (size_t)npoints * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ORBX_ERR_DEVICE;
-    }
-    if (d) (void)hipFree(d);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto d = s.in(desc, (size_t)total * 32);
+    const auto sg = s.in(seg_off, (size_t)npoints + 1);
+    const auto bi = s.out<int32_t>(npoints), bm = s.out<int32_t>(npoints);
+    HIPTRY(s.alloc());
+    const int rc = orbm_distinctive_device(s[d], s[sg], npoints, s[bi], s[bm], nullptr);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(best_idx, bi, npoints));
+    HIPTRY(s.get(best_median, bm, npoints));
+    return ORBX_OK;
 }
 
 }  // extern "C"

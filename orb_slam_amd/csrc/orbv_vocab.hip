@@ -33,6 +33,7 @@
 
 #include "orbv.h"
 #include "orbx.h"
+#include "orbx_host.h"
 
 namespace orbv {
 
@@ -216,15 +217,13 @@ __global__ __launch_bounds__(ASM_BLOCK) void k_assemble(const int32_t* __restric
 }  // namespace orbv
 
 // ------------------------------------------------------------------------------------------------ host side
-struct orbv_vocabulary {
+// (hidden: the C ABI hands out a pointer only)
+struct __attribute__((visibility("hidden"))) orbv_vocabulary {
     int k = 0, L = 0, scoring = 0, weighting = 0, n_words = 0, n_nodes = 0, max_children = 0, device = 0;
     orbv::VocDev dev{};
-    void* d_block = nullptr;              // one allocation holding the five tables
+    orbx::DevBuf block;                   // one allocation holding the five tables
     // scratch of the per-feature descent results (transform paths)
-    uint32_t* s_word = nullptr;
-    double* s_weight = nullptr;
-    uint32_t* s_node = nullptr;
-    size_t s_cap = 0;
+    orbx::DevBuf s_word, s_weight, s_node;
 };
 
 namespace {
@@ -281,30 +280,23 @@ int build(int k, int L, int scoring, int weighting, const std::vector<HostNode>&
         word[i] = word_of[t];
         weight[i] = nodes[t].weight;
     }
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_desc = 0, o_fc = al((size_t)n * 32), o_orig = o_fc + al((size_t)(n + 1) * 4), o_word = o_orig + al((size_t)n * 4),
-                 o_wt = o_word + al((size_t)n * 4), total = o_wt + al((size_t)n * 8);
+    HIPTRY(hipSetDevice(device));
+    orbx::Staging s;
+    const auto o_desc = s.in(desc.data(), (size_t)n * 32);
+    const auto o_fc = s.in(first_child.data(), (size_t)n + 1);
+    const auto o_orig = s.in(orig.data(), n), o_word = s.in(word.data(), n);
+    const auto o_wt = s.in(weight.data(), n);
+    HIPTRY(s.alloc());
     orbv_vocabulary* v = new orbv_vocabulary();
-    if (hipMalloc(&v->d_block, total) != hipSuccess) { delete v; return ORBX_ERR_DEVICE; }
-    char* b = (char*)v->d_block;
-    if (hipMemcpy(b + o_desc, desc.data(), (size_t)n * 32, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b + o_fc, first_child.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b + o_orig, orig.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b + o_word, word.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b + o_wt, weight.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(v->d_block);
-        delete v;
-        return ORBX_ERR_DEVICE;
-    }
     v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting; v->n_words = n_words; v->n_nodes = n;
     v->max_children = max_children; v->device = device;
-    v->dev.desc = (const uint4*)(b + o_desc);
-    v->dev.first_child = (const int32_t*)(b + o_fc);
-    v->dev.orig_id = (const uint32_t*)(b + o_orig);
-    v->dev.word = (const uint32_t*)(b + o_word);
-    v->dev.weight = (const double*)(b + o_wt);
+    v->dev.desc = (const uint4*)s[o_desc];
+    v->dev.first_child = s[o_fc];
+    v->dev.orig_id = s[o_orig];
+    v->dev.word = s[o_word];
+    v->dev.weight = s[o_wt];
     v->dev.L = L;
+    v->block = std::move(s.buf);
     *out = v;
     return ORBX_OK;
 }
@@ -323,12 +315,9 @@ int launch_descend(const orbv_vocabulary* v, const uint8_t* d_desc, const int32_
 }
 
 int ensure_scratch(orbv_vocabulary* v, size_t slots) {
-    if (slots <= v->s_cap) return ORBX_OK;
-    if (v->s_word) { (void)hipFree(v->s_word); (void)hipFree(v->s_weight); (void)hipFree(v->s_node); v->s_word = nullptr; v->s_cap = 0; }
-    if (hipMalloc(&v->s_word, slots * 4) != hipSuccess || hipMalloc(&v->s_weight, slots * 8) != hipSuccess ||
-        hipMalloc(&v->s_node, slots * 4) != hipSuccess)
-        return ORBX_ERR_DEVICE;
-    v->s_cap = slots;
+    HIPTRY(v->s_word.ensure(slots * 4));
+    HIPTRY(v->s_weight.ensure(slots * 8));
+    HIPTRY(v->s_node.ensure(slots * 4));
     return ORBX_OK;
 }
 }  // namespace
@@ -390,12 +379,7 @@ int orbv_load_text(const char* path, int device, orbv_vocabulary** out) {
     return build((int)k, (int)L, (int)sc, (int)wt, nodes, device, out);
 }
 
-void orbv_destroy(orbv_vocabulary* v) {
-    if (!v) return;
-    if (v->d_block) (void)hipFree(v->d_block);
-    if (v->s_word) { (void)hipFree(v->s_word); (void)hipFree(v->s_weight); (void)hipFree(v->s_node); }
-    delete v;
-}
+void orbv_destroy(orbv_vocabulary* v) { delete v; }
 
 int orbv_info(const orbv_vocabulary* v, int* k, int* L, int* scoring, int* weighting, int* n_words, int* n_nodes) {
     if (!v) return ORBX_ERR_ARG;
@@ -419,19 +403,18 @@ int orbv_descend_device(const orbv_vocabulary* v, const uint8_t* d_desc, int n, 
 int orbv_descend(const orbv_vocabulary* v, const uint8_t* desc, int n, int levelsup, uint32_t* word, double* weight, uint32_t* node) {
     if (!v || n < 0 || (n > 0 && (!desc || !word || !weight || !node))) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
-    if (hipSetDevice(v->device) != hipSuccess) return ORBX_ERR_DEVICE;
-    uint8_t* d = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    const size_t o_w = (size_t)n * 32, o_wt = o_w + (((size_t)n * 4 + 7) & ~(size_t)7), o_n = o_wt + (size_t)n * 8;
-    if (hipMalloc(&d, o_n + (size_t)n * 4) == hipSuccess && hipMemcpy(d, desc, (size_t)n * 32, hipMemcpyHostToDevice) == hipSuccess) {
-        rc = launch_descend(v, d, nullptr, n, 1, levelsup, (uint32_t*)(d + o_w), (double*)(d + o_wt), (uint32_t*)(d + o_n), nullptr);
-        if (rc == ORBX_OK && (hipMemcpy(word, d + o_w, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(weight, d + o_wt, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(node, d + o_n, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ORBX_ERR_DEVICE;
-    }
-    if (d) (void)hipFree(d);
-    return rc;
+    HIPTRY(hipSetDevice(v->device));
+    orbx::Staging s;
+    const auto d = s.in(desc, (size_t)n * 32);
+    const auto w = s.out<uint32_t>(n), nd = s.out<uint32_t>(n);
+    const auto wt = s.out<double>(n);
+    HIPTRY(s.alloc());
+    const int rc = launch_descend(v, s[d], nullptr, n, 1, levelsup, s[w], s[wt], s[nd], nullptr);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(word, w, n));
+    HIPTRY(s.get(weight, wt, n));
+    HIPTRY(s.get(node, nd, n));
+    return ORBX_OK;
 }
 
 int orbv_transform_batch_device(orbv_vocabulary* v, const uint8_t* d_desc, const int32_t* d_n, int nframes, int cap, int levelsup,
@@ -444,7 +427,7 @@ int orbv_transform_batch_device(orbv_vocabulary* v, const uint8_t* d_desc, const
     int rc = ensure_scratch(v, (size_t)nframes * cap);
     if (rc != ORBX_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    rc = launch_descend(v, d_desc, d_n, cap, nframes, levelsup, v->s_word, v->s_weight, v->s_node, st);
+    rc = launch_descend(v, d_desc, d_n, cap, nframes, levelsup, v->s_word.as<uint32_t>(), v->s_weight.as<double>(), v->s_node.as<uint32_t>(), st);
     if (rc != ORBX_OK) return rc;
     int P = 1;
     while (P < cap) P <<= 1;
@@ -454,7 +437,7 @@ int orbv_transform_batch_device(orbv_vocabulary* v, const uint8_t* d_desc, const
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)orbv::k_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, ORBV_MAX_FEATURES * 16) != hipSuccess)
         return ORBX_ERR_DEVICE;
     hipLaunchKernelGGL(orbv::k_assemble, dim3(nframes), dim3(orbv::ASM_BLOCK), lds, st, d_n, cap, P, v->weighting, norm_mode,
-                       v->s_word, v->s_weight, v->s_node, d_bow_id, d_bow_val, d_n_bow, d_fv_node, d_fv_off, d_fv_feat, d_n_fv);
+                       v->s_word.as<uint32_t>(), v->s_weight.as<double>(), v->s_node.as<uint32_t>(), d_bow_id, d_bow_val, d_n_bow, d_fv_node, d_fv_off, d_fv_feat, d_n_fv);
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
@@ -463,32 +446,26 @@ int orbv_transform(const orbv_vocabulary* v, const uint8_t* desc, int n, int lev
     if (!v || n < 0 || n > ORBV_MAX_FEATURES || !n_bow || !n_fv || !fv_off) return ORBX_ERR_ARG;
     if (n == 0 || v->n_words == 0) { *n_bow = 0; *n_fv = 0; fv_off[0] = 0; return ORBX_OK; }
     if (!desc || !bow_id || !bow_val || !fv_node || !fv_feat) return ORBX_ERR_ARG;
-    if (hipSetDevice(v->device) != hipSuccess) return ORBX_ERR_DEVICE;
-    // one allocation: desc | bow_val (8-aligned) | bow_id | fv_node | fv_feat | fv_off | counts
-    const size_t N = (size_t)n;
-    const size_t o_val = N * 32, o_id = o_val + N * 8, o_fn = o_id + N * 4, o_ff = o_fn + N * 4, o_fo = o_ff + N * 4,
-                 o_cnt = o_fo + (N + 1) * 4, total = o_cnt + 8;
-    uint8_t* d = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&d, total) == hipSuccess && hipMemcpy(d, desc, N * 32, hipMemcpyHostToDevice) == hipSuccess) {
-        int32_t* cnt = (int32_t*)(d + o_cnt);
-        rc = orbv_transform_batch_device(const_cast<orbv_vocabulary*>(v), d, nullptr, 1, n, levelsup, (uint32_t*)(d + o_id), (double*)(d + o_val),
-                                         cnt, (uint32_t*)(d + o_fn), (int32_t*)(d + o_fo), (uint32_t*)(d + o_ff), cnt + 1, nullptr);
-        int32_t hc[2] = {0, 0};
-        if (rc == ORBX_OK && hipMemcpy(hc, cnt, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = ORBX_ERR_DEVICE;
-        if (rc == ORBX_OK) {
-            *n_bow = hc[0];
-            *n_fv = hc[1];
-            if ((hc[0] && (hipMemcpy(bow_id, d + o_id, (size_t)hc[0] * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                           hipMemcpy(bow_val, d + o_val, (size_t)hc[0] * 8, hipMemcpyDeviceToHost) != hipSuccess)) ||
-                (hc[1] && hipMemcpy(fv_node, d + o_fn, (size_t)hc[1] * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                hipMemcpy(fv_off, d + o_fo, ((size_t)hc[1] + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(fv_feat, d + o_ff, N * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = ORBX_ERR_DEVICE;
-        }
-    }
-    if (d) (void)hipFree(d);
-    return rc;
+    HIPTRY(hipSetDevice(v->device));
+    orbx::Staging s;
+    const auto d = s.in(desc, (size_t)n * 32);
+    const auto val = s.out<double>(n);
+    const auto id = s.out<uint32_t>(n), fn = s.out<uint32_t>(n), ff = s.out<uint32_t>(n);
+    const auto fo = s.out<int32_t>((size_t)n + 1), cnt = s.out<int32_t>(2);
+    HIPTRY(s.alloc());
+    const int rc = orbv_transform_batch_device(const_cast<orbv_vocabulary*>(v), s[d], nullptr, 1, n, levelsup, s[id], s[val], s[cnt], s[fn], s[fo], s[ff],
+                                               s[cnt] + 1, nullptr);
+    if (rc != ORBX_OK) return rc;
+    int32_t hc[2] = {0, 0};
+    HIPTRY(s.get(hc, cnt, 2));
+    *n_bow = hc[0];
+    *n_fv = hc[1];
+    HIPTRY(s.get(bow_id, id, hc[0]));
+    HIPTRY(s.get(bow_val, val, hc[0]));
+    HIPTRY(s.get(fv_node, fn, hc[1]));
+    HIPTRY(s.get(fv_off, fo, (size_t)hc[1] + 1));
+    HIPTRY(s.get(fv_feat, ff, n));
+    return ORBX_OK;
 }
 
 // DBoW2/ScoringObject.cpp: the six merge walks (the reference's lower_bound jumps only skip keys that cannot match)

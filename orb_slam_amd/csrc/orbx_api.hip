@@ -18,34 +18,23 @@ using namespace orbx;
 struct orbx_extractor {
     orbx_params p;
     std::string err;
-    // geometry for the current image size
+    // geometry for the current image size, and the per-batch working set (max_batch frames): replaced together by ensure_geometry
+    // (hidden: the library exports the C ABI, not its internals)
     int gw = 0, gh = 0;
     HostGeom hg;
-    CellGeom* d_cells = nullptr;
-    BandGeom* d_bands = nullptr;
-    ResizeX* d_tabx = nullptr;
-    ResizeY* d_taby = nullptr;
-    int* d_pyr_tab = nullptr;
-    // per-batch working set (max_batch frames)
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr;
-    Cand *d_cand = nullptr, *d_sel = nullptr;
-    CellState* d_cstate = nullptr;
+    struct __attribute__((visibility("hidden"))) Geom {
+        DevBuf cells, bands, tabx, taby, pyr_tab;
+        DevBuf pyr, blur, cand, sel, cstate, csel, level_total, level_count, status, long_cells;
+    } geo;
     bool fallback_hint = true;        // ORBX_FALLBACK_HINT=0 at orbx_create
-    CellSel* d_csel = nullptr;
-    int32_t *d_level_total = nullptr, *d_level_count = nullptr, *d_status = nullptr, *d_long_cells = nullptr;
     // single-frame staging for orbx_extract
-    uint8_t* d_img1 = nullptr;
-    size_t img1_bytes = 0;
-    int img1_stride = 0;
-    uint8_t* d_out1 = nullptr;   // one block: [n, status, pad to 64 B][kps: cap x 28 B, padded to 64][desc: cap x 32 B]
-    uint8_t* h_out1 = nullptr;   // the same block in pinned host memory, mapped into the device: k_describe writes the results there
-    uint8_t* m_out1 = nullptr;   //   (its device address); d_out1 + one D2H copy only with ORBX_ZERO_COPY=0
-    uint8_t* h_img1 = nullptr;   // pinned staging of the input frame, mapped into the device (m_img1): fetched by k_ingest
-    uint8_t* m_img1 = nullptr;
+    DevBuf d_img1;
+    PinnedBuf h_img1;            // pinned staging of the input frame, mapped into the device: fetched by k_ingest
+    DevBuf d_out1;               // one block: [n, status, pad to 64 B][kps: cap x 28 B, padded to 64][desc: cap x 32 B]
+    PinnedBuf h_out1;            // the same block in pinned host memory, mapped into the device: k_describe writes the results there
+                                 //   (its device address); d_out1 + one D2H copy only with ORBX_ZERO_COPY=0
     bool zero_copy = true;       // ORBX_ZERO_COPY=0 at orbx_create: DMA copies both ways instead (A/B measurements)
-    hipStream_t s1 = nullptr;    // stream of the single-frame path
-    size_t out1_bytes = 0, kps1_off = 0, desc1_off = 0;
-    int out1_cap = 0;
+    Stream s1;                   // stream of the single-frame path
     // diagnostics
     int stop_after = -1;
     bool no_xcd_affinity = false;     // ORBX_XCD_AFFINITY=0 at orbx_create (A/B measurements)
@@ -70,81 +59,58 @@ struct orbx_extractor {
     // order into the matching device slot; tab_ev[i] is recorded after the kernels of the group that used slot i, so a slot is rewritten
     // only once both its copy and the kernels reading the device copy are done
     static constexpr int TAB_RING = 4;
-    ImgSrc* d_tab = nullptr;
-    ImgSrc* h_tab = nullptr;
-    hipEvent_t tab_ev[TAB_RING] = {};
+    DevBuf d_tab;
+    PinnedBuf h_tab;
+    Event tab_ev[TAB_RING];
     int tab_next = 0;
     std::vector<ImgSrc> last_tab;     // the last gather group's table (orbx_debug_fetch of level 0)
     // host form: two device frame buffers of one launch group each (pitch w rounded up to 16), two pinned staging buffers for pageable
     // frames, and the copy stream.  up_ev[i]: the upload into buffer i is done; kern_ev[i]: the kernels that read buffer i are done.
-    hipStream_t up = nullptr;
-    uint8_t* d_hbuf[2] = {};
-    uint8_t* h_stage[2] = {};
-    size_t hbuf_bytes = 0;
-    hipEvent_t up_ev[2] = {}, kern_ev[2] = {};
+    Stream up;
+    DevBuf d_hbuf[2];
+    PinnedBuf h_stage[2];
+    Event up_ev[2], kern_ev[2];
     int hnext = 0;
 };
 
-#define HIPCHK(h, call)                                                                      \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return ORBX_ERR_DEVICE;                                                          \
-        }                                                                                    \
-    } while (0)
-
 template <typename T>
-static void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-static void free_geometry(orbx_extractor* h) {
-    dev_free(h->d_cells); dev_free(h->d_bands); dev_free(h->d_tabx); dev_free(h->d_taby); dev_free(h->d_pyr_tab);
-    dev_free(h->d_pyr); dev_free(h->d_blur);
-    dev_free(h->d_cand); dev_free(h->d_sel); dev_free(h->d_cstate); dev_free(h->d_csel);
-    dev_free(h->d_level_total); dev_free(h->d_level_count); dev_free(h->d_status); dev_free(h->d_long_cells);
-    h->gw = h->gh = 0;
-    h->have_last = false;
-}
-
-template <typename T>
-static int upload(orbx_extractor* h, T*& dptr, const std::vector<T>& v) {
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    HIPCHK(h, hipMalloc(&dptr, bytes));
-    if (!v.empty()) HIPCHK(h, hipMemcpy(dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+static int upload(orbx_extractor* h, DevBuf& d, const std::vector<T>& v) {
+    HIPCHK(h, d.ensure(std::max<size_t>(v.size(), 1) * sizeof(T)));
+    if (!v.empty()) HIPCHK(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return ORBX_OK;
 }
 
 static int ensure_geometry(orbx_extractor* h, int w, int hgt) {
     if (h->gw == w && h->gh == hgt) return ORBX_OK;
     HIPCHK(h, hipDeviceSynchronize());
-    free_geometry(h);
+    h->geo = {};
+    h->gw = h->gh = 0;
+    h->have_last = false;
     HostGeom hg;
     int rc = build_geometry(h->p, w, hgt, hg, h->err);
     if (rc != ORBX_OK) return rc;
     h->hg = hg;
     const DevGeom& g = h->hg.g;
     const size_t B = (size_t)h->p.max_batch;
-    if ((rc = upload(h, h->d_cells, h->hg.cells)) != ORBX_OK) return rc;
-    if ((rc = upload(h, h->d_bands, h->hg.bands)) != ORBX_OK) return rc;
-    if ((rc = upload(h, h->d_tabx, h->hg.tabx)) != ORBX_OK) return rc;
-    if ((rc = upload(h, h->d_taby, h->hg.taby)) != ORBX_OK) return rc;
-    if ((rc = upload(h, h->d_pyr_tab, h->hg.pyr_tab)) != ORBX_OK) return rc;
-    HIPCHK(h, hipMalloc(&h->d_pyr, B * g.frame_plane_bytes));
-    HIPCHK(h, hipMalloc(&h->d_blur, B * g.frame_plane_bytes));
-    HIPCHK(h, hipMalloc(&h->d_cand, B * std::max(g.frame_cands, 1) * sizeof(Cand)));
-    HIPCHK(h, hipMalloc(&h->d_sel, (B * std::max(g.frame_sel, 1) + 4) * sizeof(Cand)));      // (+ 4: k_describe reads a wave's four keypoints as one 32-byte scalar load)
-    HIPCHK(h, hipMalloc(&h->d_cstate, B * g.nbands_total * sizeof(CellState)));
-    HIPCHK(h, hipMemset(h->d_cstate, 0, B * g.nbands_total * sizeof(CellState)));      // (the fallback runs start at 0: k_fast_cells reads its slot's state before it writes it)
-    HIPCHK(h, hipMalloc(&h->d_csel, B * g.ncells_total * sizeof(CellSel)));
-    HIPCHK(h, hipMalloc(&h->d_level_total, B * MAX_LEVELS * sizeof(int32_t)));
-    HIPCHK(h, hipMalloc(&h->d_level_count, B * MAX_LEVELS * sizeof(int32_t)));
-    HIPCHK(h, hipMemset(h->d_level_total, 0, B * MAX_LEVELS * sizeof(int32_t)));
-    HIPCHK(h, hipMemset(h->d_level_count, 0, B * MAX_LEVELS * sizeof(int32_t)));
-    HIPCHK(h, hipMalloc(&h->d_status, B * sizeof(int32_t)));
-    HIPCHK(h, hipMalloc(&h->d_long_cells, (B * g.ncells_total + 64) * sizeof(int32_t)));
+    orbx_extractor::Geom& d = h->geo;
+    if ((rc = upload(h, d.cells, h->hg.cells)) != ORBX_OK) return rc;
+    if ((rc = upload(h, d.bands, h->hg.bands)) != ORBX_OK) return rc;
+    if ((rc = upload(h, d.tabx, h->hg.tabx)) != ORBX_OK) return rc;
+    if ((rc = upload(h, d.taby, h->hg.taby)) != ORBX_OK) return rc;
+    if ((rc = upload(h, d.pyr_tab, h->hg.pyr_tab)) != ORBX_OK) return rc;
+    HIPCHK(h, d.pyr.ensure(B * g.frame_plane_bytes));
+    HIPCHK(h, d.blur.ensure(B * g.frame_plane_bytes));
+    HIPCHK(h, d.cand.ensure(B * std::max(g.frame_cands, 1) * sizeof(Cand)));
+    HIPCHK(h, d.sel.ensure((B * std::max(g.frame_sel, 1) + 4) * sizeof(Cand)));      // (+ 4: k_describe reads a wave's four keypoints as one 32-byte scalar load)
+    HIPCHK(h, d.cstate.ensure(B * g.nbands_total * sizeof(CellState)));
+    HIPCHK(h, hipMemset(d.cstate, 0, B * g.nbands_total * sizeof(CellState)));      // (the fallback runs start at 0: k_fast_cells reads its slot's state before it writes it)
+    HIPCHK(h, d.csel.ensure(B * g.ncells_total * sizeof(CellSel)));
+    HIPCHK(h, d.level_total.ensure(B * MAX_LEVELS * sizeof(int32_t)));
+    HIPCHK(h, d.level_count.ensure(B * MAX_LEVELS * sizeof(int32_t)));
+    HIPCHK(h, hipMemset(d.level_total, 0, B * MAX_LEVELS * sizeof(int32_t)));
+    HIPCHK(h, hipMemset(d.level_count, 0, B * MAX_LEVELS * sizeof(int32_t)));
+    HIPCHK(h, d.status.ensure(B * sizeof(int32_t)));
+    HIPCHK(h, d.long_cells.ensure((B * g.ncells_total + 64) * sizeof(int32_t)));
     HIPCHK(h, hipDeviceSynchronize());
     h->gw = w;
     h->gh = hgt;
@@ -152,10 +118,12 @@ static int ensure_geometry(orbx_extractor* h, int w, int hgt) {
 }
 
 static void fill_batch(orbx_extractor* h, Batch& b) {
-    b.g = h->hg.g; b.cells = h->d_cells; b.bands = h->d_bands; b.tabx = h->d_tabx; b.taby = h->d_taby; b.pyr_tab = h->d_pyr_tab;
-    b.pyr = h->d_pyr; b.blur = h->d_blur;
-    b.cand = h->d_cand; b.sel = h->d_sel; b.cstate = h->d_cstate; b.csel = h->d_csel;
-    b.level_total = h->d_level_total; b.level_count = h->d_level_count; b.status = h->d_status; b.long_cells = h->d_long_cells;
+    const orbx_extractor::Geom& d = h->geo;
+    b.g = h->hg.g; b.cells = d.cells.as<CellGeom>(); b.bands = d.bands.as<BandGeom>(); b.tabx = d.tabx.as<ResizeX>(); b.taby = d.taby.as<ResizeY>();
+    b.pyr_tab = d.pyr_tab.as<int>(); b.pyr = d.pyr.as(); b.blur = d.blur.as();
+    b.cand = d.cand.as<Cand>(); b.sel = d.sel.as<Cand>(); b.cstate = d.cstate.as<CellState>(); b.csel = d.csel.as<CellSel>();
+    b.level_total = d.level_total.as<int32_t>(); b.level_count = d.level_count.as<int32_t>(); b.status = d.status.as<int32_t>();
+    b.long_cells = d.long_cells.as<int32_t>();
 }
 
 // the parts of a launch group's Batch that do not depend on where its frames are
@@ -185,28 +153,30 @@ static hipMemoryType host_memory_type(const void* p) {
     return a.type;
 }
 
-static int ensure_tab(orbx_extractor* h) {
-    if (h->d_tab) return ORBX_OK;
-    const size_t bytes = (size_t)orbx_extractor::TAB_RING * h->p.max_batch * sizeof(ImgSrc);
-    HIPCHK(h, hipMalloc(&h->d_tab, bytes));
-    HIPCHK(h, hipHostMalloc(&h->h_tab, bytes, hipHostMallocDefault));
-    for (hipEvent_t& e : h->tab_ev) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+// queues one launch group; it becomes the group the diagnostics read
+static int launch_group(orbx_extractor* h, const Batch& b, hipStream_t stream, int phases = ORBX_PHASE_ALL) {
+    const int rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side, phases);
+    if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
+    h->last = b;
+    h->have_last = true;
     return ORBX_OK;
 }
 
 // device form of orbx_extract_batch: one table per launch group, the kernels read the caller's frames through it
 static int extract_gather(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, orbx_keypoint* d_kps,
                           uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
-    int rc = ensure_tab(h);
-    if (rc != ORBX_OK) return rc;
     const int mb = h->p.max_batch;
+    const size_t tab_bytes = (size_t)orbx_extractor::TAB_RING * mb * sizeof(ImgSrc);
+    HIPCHK(h, h->d_tab.ensure(tab_bytes));
+    HIPCHK(h, h->h_tab.ensure(tab_bytes, hipHostMallocDefault));
+    for (Event& e : h->tab_ev) HIPCHK(h, e.ensure());
     for (int f0 = 0; f0 < nframes; f0 += mb) {
         const int n = std::min(mb, nframes - f0);
         const int slot = h->tab_next;
         h->tab_next = (slot + 1) % orbx_extractor::TAB_RING;
         HIPCHK(h, hipEventSynchronize(h->tab_ev[slot]));      // the slot's last copy and the kernels that read its device copy are done
-        ImgSrc* ht = h->h_tab + (size_t)slot * mb;
-        ImgSrc* dt = h->d_tab + (size_t)slot * mb;
+        ImgSrc* ht = h->h_tab.as<ImgSrc>() + (size_t)slot * mb;
+        ImgSrc* dt = h->d_tab.as<ImgSrc>() + (size_t)slot * mb;
         unsigned long long bits = 0;
         long long min_stride = LLONG_MAX;
         for (int i = 0; i < n; i++) {
@@ -223,11 +193,9 @@ static int extract_gather(orbx_extractor* h, const uint8_t* const* imgs, const p
         b.img_tab = dt;
         b.img_tab_bits = bits;
         b.img_tab_min_stride = min_stride;
-        rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side);
-        if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
+        const int rc = launch_group(h, b, stream);
+        if (rc != ORBX_OK) return rc;
         HIPCHK(h, hipEventRecord(h->tab_ev[slot], stream));
-        h->last = b;
-        h->have_last = true;
         h->last_tab.assign(ht, ht + n);
     }
     return ORBX_OK;
@@ -240,12 +208,10 @@ static int extract_host(orbx_extractor* h, const uint8_t* const* imgs, const ptr
                         uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
     const int mb = h->p.max_batch;
     const size_t P = ((size_t)w + 15) & ~(size_t)15, fb = P * hgt;
-    if (!h->up) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->up, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIPCHK(h, hipEventCreateWithFlags(&h->up_ev[i], hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->kern_ev[i], hipEventDisableTiming));
-        }
+    HIPCHK(h, h->up.ensure());
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(h, h->up_ev[i].ensure());
+        HIPCHK(h, h->kern_ev[i].ensure());
     }
     std::vector<char> pinned(nframes);
     bool any_pageable = false;
@@ -255,28 +221,24 @@ static int extract_host(orbx_extractor* h, const uint8_t* const* imgs, const ptr
         pinned[f] = t == hipMemoryTypeHost;
         any_pageable |= !pinned[f];
     }
-    if (h->hbuf_bytes < fb * mb || (any_pageable && !h->h_stage[0])) {
-        // grown with the geometry (nothing queued may still use the old buffers); the pinned staging buffers only once a pageable frame comes
+    // grown with the geometry (nothing queued may still use the old buffers); the pinned staging buffers only once a pageable frame comes
+    const size_t bytes = fb * mb;
+    const bool stage = any_pageable || h->h_stage[0].size() > 0;
+    bool grow = false;
+    for (int i = 0; i < 2; i++) grow |= h->d_hbuf[i].size() < bytes || (stage && h->h_stage[i].size() < bytes);
+    if (grow) {
         HIPCHK(h, hipDeviceSynchronize());
-        const bool stage = any_pageable || h->h_stage[0];
-        h->hbuf_bytes = 0;
         for (int i = 0; i < 2; i++) {
-            dev_free(h->d_hbuf[i]);
-            if (h->h_stage[i]) (void)hipHostFree(h->h_stage[i]);
-            h->h_stage[i] = nullptr;
+            HIPCHK(h, h->d_hbuf[i].ensure(bytes));
+            if (stage) HIPCHK(h, h->h_stage[i].ensure(bytes, hipHostMallocDefault));
         }
-        for (int i = 0; i < 2; i++) {
-            HIPCHK(h, hipMalloc(&h->d_hbuf[i], fb * mb));
-            if (stage) HIPCHK(h, hipHostMalloc(&h->h_stage[i], fb * mb, hipHostMallocDefault));
-        }
-        h->hbuf_bytes = fb * mb;
     }
     for (int f0 = 0; f0 < nframes; f0 += mb) {
         const int n = std::min(mb, nframes - f0);
         const int i = h->hnext;
         h->hnext ^= 1;
-        uint8_t* dbuf = h->d_hbuf[i];
-        uint8_t* stage = h->h_stage[i];
+        uint8_t* dbuf = h->d_hbuf[i].as();
+        uint8_t* stage = h->h_stage[i].as();
         HIPCHK(h, hipStreamWaitEvent(h->up, h->kern_ev[i], 0));   // the kernels of the group that last read buffer i
         bool stage_free = false;
         for (int j = 0; j < n;) {
@@ -309,11 +271,9 @@ static int extract_host(orbx_extractor* h, const uint8_t* const* imgs, const ptr
         b.img = dbuf;
         b.img_row_stride = (long long)P;
         b.img_frame_stride = (long long)fb;
-        const int rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side);
-        if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
+        const int rc = launch_group(h, b, stream);
+        if (rc != ORBX_OK) return rc;
         HIPCHK(h, hipEventRecord(h->kern_ev[i], stream));
-        h->last = b;
-        h->have_last = true;
     }
     // every caller frame has been read once both uploads are done (pinned frames are DMA'd from the caller's memory)
     for (int i = 0; i < 2; i++) HIPCHK(h, hipEventSynchronize(h->up_ev[i]));
@@ -353,10 +313,7 @@ int orbx_create(const orbx_params* p, orbx_extractor** out) {
     { const char* od = getenv("ORBX_BLUR_ON_DEMAND"); if (od && (od[0] == '0' || od[0] == '1') && od[1] == 0) h->blur_on_demand = od[0] - '0'; }
     { const char* zc = getenv("ORBX_ZERO_COPY"); h->zero_copy = !(zc && zc[0] == '0'); }
     const char* ovl = getenv("ORBX_OVERLAP");
-    if (ovl && ovl[0] == '0') { *out = h; return ORBX_OK; }
-    if (hipStreamCreateWithFlags(&h->side.aux, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->side.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->side.join, hipEventDisableTiming) != hipSuccess) {
+    if (!(ovl && ovl[0] == '0') && (h->side.aux.ensure() != hipSuccess || h->side.fork.ensure() != hipSuccess || h->side.join.ensure() != hipSuccess)) {
         delete h;
         return ORBX_ERR_DEVICE;
     }
@@ -367,25 +324,7 @@ int orbx_create(const orbx_params* p, orbx_extractor** out) {
 void orbx_destroy(orbx_extractor* h) {
     if (!h) return;
     (void)hipSetDevice(h->p.device);
-    (void)hipDeviceSynchronize();
-    free_geometry(h);
-    if (h->side.fork) (void)hipEventDestroy(h->side.fork);
-    if (h->side.join) (void)hipEventDestroy(h->side.join);
-    if (h->side.aux) (void)hipStreamDestroy(h->side.aux);
-    dev_free(h->d_img1); dev_free(h->d_out1);
-    if (h->h_img1) (void)hipHostFree(h->h_img1);
-    if (h->h_out1) (void)hipHostFree(h->h_out1);
-    if (h->s1) (void)hipStreamDestroy(h->s1);
-    dev_free(h->d_tab);
-    if (h->h_tab) (void)hipHostFree(h->h_tab);
-    for (hipEvent_t e : h->tab_ev) if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; i++) {
-        dev_free(h->d_hbuf[i]);
-        if (h->h_stage[i]) (void)hipHostFree(h->h_stage[i]);
-        if (h->up_ev[i]) (void)hipEventDestroy(h->up_ev[i]);
-        if (h->kern_ev[i]) (void)hipEventDestroy(h->kern_ev[i]);
-    }
-    if (h->up) (void)hipStreamDestroy(h->up);
+    (void)hipDeviceSynchronize();      // the owners free nothing that queued work still reads
     delete h;
 }
 
@@ -448,10 +387,7 @@ int orbx_extract_batch_device_phases(orbx_extractor* h, const uint8_t* d_imgs, i
         b.img = d_imgs + (ptrdiff_t)f0 * frame_stride;
         b.img_row_stride = row_stride;
         b.img_frame_stride = frame_stride;
-        rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side, phases);
-        if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
-        h->last = b;
-        h->have_last = true;
+        if ((rc = launch_group(h, b, stream, phases)) != ORBX_OK) return rc;
     }
     if (phases & ORBX_PHASE_PYRAMID) h->ph_key = key;
     h->ph_done |= phases;
@@ -492,55 +428,39 @@ int orbx_extract(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_
     if (cap < need) { h->err = "cap < orbx_max_keypoints()"; return ORBX_ERR_CAPACITY; }
     const int dstride = (w + 63) / 64 * 64;
     const size_t bytes = (size_t)dstride * hgt;
-    if (h->img1_bytes < bytes) {
-        dev_free(h->d_img1);
-        if (h->h_img1) (void)hipHostFree(h->h_img1);
-        h->h_img1 = nullptr;
-        HIPCHK(h, hipMalloc(&h->d_img1, bytes));
-        HIPCHK(h, hipHostMalloc(&h->h_img1, bytes, hipHostMallocMapped));
-        HIPCHK(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->m_img1), h->h_img1, 0));
-        h->img1_bytes = bytes;
-    }
-    if (h->out1_cap < need) {
-        dev_free(h->d_out1);
-        if (h->h_out1) (void)hipHostFree(h->h_out1);
-        h->h_out1 = nullptr;
-        h->kps1_off = 64;
-        h->desc1_off = h->kps1_off + ((size_t)need * sizeof(orbx_keypoint) + 63) / 64 * 64;
-        h->out1_bytes = h->desc1_off + (size_t)need * 32;
-        HIPCHK(h, hipMalloc(&h->d_out1, h->out1_bytes));
-        HIPCHK(h, hipHostMalloc(&h->h_out1, h->out1_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->m_out1), h->h_out1, 0));
-        h->out1_cap = need;
-    }
-    if (!h->s1) HIPCHK(h, hipStreamCreateWithFlags(&h->s1, hipStreamNonBlocking));
+    const size_t kps_off = 64, desc_off = kps_off + ((size_t)need * sizeof(orbx_keypoint) + 63) / 64 * 64, out_bytes = desc_off + (size_t)need * 32;
+    HIPCHK(h, h->d_img1.ensure(bytes));
+    HIPCHK(h, h->h_img1.ensure(bytes, hipHostMallocMapped));
+    HIPCHK(h, h->d_out1.ensure(out_bytes));
+    HIPCHK(h, h->h_out1.ensure(out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(h, h->s1.ensure());
     // In: small frames are staged in pinned memory and fetched from there by a kernel (k_ingest: no copy engine, no queue switch before
     // the first pyramid launch); large ones go through the runtime's pipelined copy.  Out: k_describe, the only writer of the results,
     // stores n / status / keypoints / descriptors straight into the pinned, device-mapped block (posted PCIe writes, visible to the
     // host once the stream has drained) - the D2H copy and the kernel -> copy dependency in front of it (~15 us) are gone.
     if (bytes <= (size_t)512 << 10) {
-        for (int y = 0; y < hgt; y++) memcpy(h->h_img1 + (size_t)y * dstride, img + (ptrdiff_t)y * stride, (size_t)w);
-        if (h->zero_copy) { if ((rc = launch_ingest(h->d_img1, h->m_img1, bytes, h->s1)) != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; } }
+        for (int y = 0; y < hgt; y++) memcpy(h->h_img1.as() + (size_t)y * dstride, img + (ptrdiff_t)y * stride, (size_t)w);
+        if (h->zero_copy) { if ((rc = launch_ingest(h->d_img1.as(), h->h_img1.mapped(), bytes, h->s1)) != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; } }
         else HIPCHK(h, hipMemcpyAsync(h->d_img1, h->h_img1, bytes, hipMemcpyHostToDevice, h->s1));
     } else {
         HIPCHK(h, hipMemcpy2DAsync(h->d_img1, dstride, img, stride, w, hgt, hipMemcpyHostToDevice, h->s1));
     }
-    uint8_t* out = h->zero_copy ? h->m_out1 : h->d_out1;
+    uint8_t* out = h->zero_copy ? h->h_out1.mapped() : h->d_out1.as();
     int32_t* d_n = reinterpret_cast<int32_t*>(out);
     // (Replaying the launch group from a HIP graph was measured and does not help: 188 vs 181 us - the latency is the
     //  chain of dependent small kernels, not the launch calls.)
-    rc = orbx_extract_batch_device(h, h->d_img1, 1, w, hgt, dstride, (ptrdiff_t)bytes, reinterpret_cast<orbx_keypoint*>(out + h->kps1_off),
-                                   out + h->desc1_off, d_n, need, d_n + 1, h->s1);
+    rc = orbx_extract_batch_device(h, h->d_img1.as(), 1, w, hgt, dstride, (ptrdiff_t)bytes, reinterpret_cast<orbx_keypoint*>(out + kps_off),
+                                   out + desc_off, d_n, need, d_n + 1, h->s1);
     if (rc != ORBX_OK) return rc;
-    if (!h->zero_copy) HIPCHK(h, hipMemcpyAsync(h->h_out1, h->d_out1, h->out1_bytes, hipMemcpyDeviceToHost, h->s1));
+    if (!h->zero_copy) HIPCHK(h, hipMemcpyAsync(h->h_out1, h->d_out1, out_bytes, hipMemcpyDeviceToHost, h->s1));
     HIPCHK(h, hipStreamSynchronize(h->s1));
-    const int32_t* res = reinterpret_cast<const int32_t*>(h->h_out1);
+    const int32_t* res = h->h_out1.as<int32_t>();
     if (h->stop_after >= 0) { *n_out = 0; return ORBX_OK; }
     if (res[1] != ORBX_OK) { h->err = "internal list capacity exceeded"; return res[1]; }
     const int n = res[0];
     if (n > 0) {
-        memcpy(kps, h->h_out1 + h->kps1_off, (size_t)n * sizeof(orbx_keypoint));
-        memcpy(desc, h->h_out1 + h->desc1_off, (size_t)n * 32);
+        memcpy(kps, h->h_out1.as() + kps_off, (size_t)n * sizeof(orbx_keypoint));
+        memcpy(desc, h->h_out1.as() + desc_off, (size_t)n * 32);
     }
     *n_out = n;
     return ORBX_OK;
@@ -694,45 +614,38 @@ int orbx_debug_geometry(const orbx_params* p, int w, int hgt, int32_t* out, int 
 
 int orbx_debug_nth_element(const float* resp, int n, int nth, int32_t* out_perm, int device) {
     if (!resp || !out_perm || n < 1 || nth < 0 || nth > n || n > 13000) return ORBX_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    float* d_r = nullptr;
-    int* d_o = nullptr;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMalloc(&d_r, (size_t)n * 4) == hipSuccess && hipMalloc(&d_o, (size_t)n * 4) == hipSuccess &&
-        hipMemcpy(d_r, resp, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess) {
-        rc = launch_debug_nth(d_r, n, nth, d_o);
-        if (rc == ORBX_OK && hipMemcpy(out_perm, d_o, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = ORBX_ERR_DEVICE;
-    }
-    if (d_r) (void)hipFree(d_r);
-    if (d_o) (void)hipFree(d_o);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto r = s.in(resp, n);
+    const auto o = s.out<int>(n);
+    HIPTRY(s.alloc());
+    const int rc = launch_debug_nth(s[r], n, nth, s[o]);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(out_perm, o, n));
+    return ORBX_OK;
 }
 
 int orbx_debug_eval_math(int kind, const float* in0, const float* in1, float* out0, float* out1, int n, int device) {
     if (n <= 0) return ORBX_OK;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    float* d = nullptr;
-    const size_t nb = (size_t)n * sizeof(float);
-    if (hipMalloc(&d, 4 * nb) != hipSuccess) return ORBX_ERR_DEVICE;
-    int rc = ORBX_ERR_DEVICE;
-    if (hipMemcpy(d, in0, nb, hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(d + n, in1 ? in1 : in0, nb, hipMemcpyHostToDevice) == hipSuccess) {
-        rc = launch_eval_math(kind, d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n);
-        if (rc == ORBX_OK && hipMemcpy(out0, d + 2 * (size_t)n, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = ORBX_ERR_DEVICE;
-        if (rc == ORBX_OK && out1 && hipMemcpy(out1, d + 3 * (size_t)n, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = ORBX_ERR_DEVICE;
-    }
-    (void)hipFree(d);
-    return rc;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto i0 = s.in(in0, n), i1 = s.in(in1 ? in1 : in0, n);
+    const auto o0 = s.out<float>(n), o1 = s.out<float>(n);
+    HIPTRY(s.alloc());
+    const int rc = launch_eval_math(kind, s[i0], s[i1], s[o0], s[o1], n);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(out0, o0, n));
+    if (out1) HIPTRY(s.get(out1, o1, n));
+    return ORBX_OK;
 }
-
 
 int orbx_device_alloc(int device, size_t bytes, void** d_ptr) {
     if (!d_ptr || bytes == 0) return ORBX_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ORBX_ERR_DEVICE;
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return ORBX_ERR_DEVICE;
-    if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipFree(p); return ORBX_ERR_DEVICE; }
-    *d_ptr = p;
+    HIPTRY(hipSetDevice(device));
+    DevBuf p;
+    HIPTRY(p.ensure(bytes));
+    HIPTRY(hipMemset(p, 0, bytes));
+    *d_ptr = p.release();
     return ORBX_OK;
 }
 

@@ -1,0 +1,129 @@
+// Host-side owners of the HIP resources behind the C ABI: device and pinned buffers, streams, events, and the one-shot staging of the
+// synchronous host forms.  Each owner releases what it holds when it goes out of scope, so an early return leaks nothing.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "orbx.h"
+
+// on failure: the handle's error text names the call, and the function returns ORBX_ERR_DEVICE
+#define HIPCHK(h, call)                                                                      \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                   \
+            return ORBX_ERR_DEVICE;                                                          \
+        }                                                                                    \
+    } while (0)
+// the same for the entry points without a handle
+#define HIPTRY(call) do { if ((call) != hipSuccess) return ORBX_ERR_DEVICE; } while (0)
+
+// internal to the library: none of these types is exported
+#pragma GCC visibility push(hidden)
+namespace orbx {
+
+// Move-only owner of one HIP resource, released with Release.  bytes_: the size of an allocation (0 for streams and events).
+template <class T, hipError_t (*Release)(T)>
+class Owner {
+  public:
+    Owner() = default;
+    Owner(Owner&& o) noexcept { *this = std::move(o); }
+    Owner& operator=(Owner&& o) noexcept {
+        if (this != &o) { reset(); v_ = std::exchange(o.v_, nullptr); bytes_ = std::exchange(o.bytes_, 0); }
+        return *this;
+    }
+    ~Owner() { reset(); }
+    void reset() { if (v_) (void)Release(v_); v_ = nullptr; bytes_ = 0; }
+    T release() { bytes_ = 0; return std::exchange(v_, nullptr); }      // hands the resource to the caller
+    operator T() const { return v_; }
+    size_t size() const { return bytes_; }
+
+  protected:
+    // ensure(): create the resource unless one is held; it is owned only once `make` has succeeded
+    template <class F> hipError_t take(F make) {
+        T t = nullptr;
+        const hipError_t e = v_ ? hipSuccess : make(&t);
+        if (e == hipSuccess && t) v_ = t;
+        return e;
+    }
+    T v_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+// ensure(bytes) grows the buffer only when it is too small, dropping the old contents.  The size is recorded once the new allocation
+// has succeeded: a failed grow leaves an empty buffer of size 0.
+struct DevBuf : Owner<void*, hipFree> {
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= bytes_) return hipSuccess;
+        reset();
+        const hipError_t e = take([&](void** p) { return hipMalloc(p, bytes); });
+        if (e == hipSuccess) bytes_ = bytes;
+        return e;
+    }
+    template <class T = uint8_t> T* as() const { return static_cast<T*>(v_); }
+};
+
+// pinned host memory (hipHostMalloc flags); with hipHostMallocMapped, mapped() is its device address
+struct PinnedBuf : Owner<void*, hipHostFree> {
+    hipError_t ensure(size_t bytes, unsigned flags) {
+        if (bytes <= bytes_) return hipSuccess;
+        reset();
+        hipError_t e = take([&](void** p) { return hipHostMalloc(p, bytes, flags); });
+        if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer(&mapped_, v_, 0);
+        if (e == hipSuccess) bytes_ = bytes;
+        else reset();
+        return e;
+    }
+    template <class T = uint8_t> T* as() const { return static_cast<T*>(v_); }
+    template <class T = uint8_t> T* mapped() const { return v_ ? static_cast<T*>(mapped_) : nullptr; }
+
+  private:
+    void* mapped_ = nullptr;
+};
+
+// ensure() creates the stream (non-blocking) or event (no timing) unless it exists
+struct Stream : Owner<hipStream_t, hipStreamDestroy> {
+    hipError_t ensure() { return take([](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }); }
+};
+struct Event : Owner<hipEvent_t, hipEventDestroy> {
+    hipError_t ensure() { return take([](hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }); }
+};
+
+// One-shot staging of a synchronous host form: the arrays live in ONE device allocation, each at a multiple of 256 bytes (the alignment
+// separate hipMalloc calls give).  in() / out() reserve an array of max(n, 1) elements; alloc() allocates and uploads the inputs;
+// get() downloads; everything is freed with the object unless `buf` is moved to a longer-lived owner.  Empty copies are skipped.
+class Staging {
+  public:
+    template <class T> struct Slot { size_t off; };
+    template <class T> Slot<T> in(const T* src, size_t n) {
+        ups_.push_back({total_, src, n * sizeof(T)});
+        return out<T>(n);
+    }
+    template <class T> Slot<T> out(size_t n) {
+        const size_t off = total_;
+        total_ = (off + (n > 0 ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
+        return {off};
+    }
+    hipError_t alloc() {
+        hipError_t e = buf.ensure(total_);
+        for (const Up& u : ups_)
+            if (e == hipSuccess && u.bytes) e = hipMemcpy(buf.as() + u.off, u.src, u.bytes, hipMemcpyHostToDevice);
+        return e;
+    }
+    template <class T> T* operator[](Slot<T> s) const { return reinterpret_cast<T*>(buf.as() + s.off); }
+    template <class T> hipError_t get(T* dst, Slot<T> s, size_t n) const {
+        return n ? hipMemcpy(dst, (*this)[s], n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+    }
+    DevBuf buf;
+
+  private:
+    struct Up { size_t off; const void* src; size_t bytes; };
+    std::vector<Up> ups_;
+    size_t total_ = 0;
+};
+
+}  // namespace orbx
+#pragma GCC visibility pop

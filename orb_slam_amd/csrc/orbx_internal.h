@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "orbx.h"
+#include "orbx_host.h"
 
 namespace orbx {
 
@@ -294,8 +295,8 @@ struct StageTimer {
 // Side stream: the blur depends only on the pyramid.  It is forked after the (VALU-bound) FAST kernel so that it
 // runs concurrently with the quota / retainBest kernels, which are latency-bound and leave the chip mostly idle.
 struct SideStream {
-    hipStream_t aux = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
+    Stream aux;
+    Event fork, join;
 };
 // `phases`: ORBX_PHASE_* bits of include/orbx.h (which parts of the sequence to queue; ORBX_PHASE_ALL = everything)
 int launch_extract(const Batch& b, const HostGeom& hg, hipStream_t stream, int stop_after, StageTimer* timer, const SideStream* side,

@@ -1,0 +1,38 @@
+// Host-only stand-in for the part of the HIP runtime that orb_slam_amd/csrc/orbx_host.h uses: allocations come from malloc, copies
+// are memcpy, and `hip_stub_fail` makes the next n-th creating call fail.  `hip_stub_live` counts what is held.
+#pragma once
+#include <cstdlib>
+#include <cstring>
+
+typedef enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 } hipError_t;
+typedef enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 } hipMemcpyKind;
+typedef struct ihipStream_t* hipStream_t;
+typedef struct ihipEvent_t* hipEvent_t;
+enum { hipHostMallocDefault = 0, hipHostMallocMapped = 2, hipHostMallocCoherent = 0x40000000, hipStreamNonBlocking = 1, hipEventDisableTiming = 2 };
+
+inline int hip_stub_fail = 0;      // 1: the next creating call fails, 2: the one after it, ...
+inline int hip_stub_live = 0;
+inline bool hip_stub_failing() { return hip_stub_fail > 0 && --hip_stub_fail == 0; }
+inline hipError_t hip_stub_make(void** p, size_t bytes) {
+    if (hip_stub_failing()) return hipErrorOutOfMemory;
+    *p = std::malloc(bytes ? bytes : 1);
+    hip_stub_live++;
+    return hipSuccess;
+}
+inline hipError_t hip_stub_free(void* p) { std::free(p); hip_stub_live--; return hipSuccess; }
+
+inline hipError_t hipMalloc(void** p, size_t bytes) { return hip_stub_make(p, bytes); }
+inline hipError_t hipFree(void* p) { return hip_stub_free(p); }
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return hip_stub_make(p, bytes); }
+inline hipError_t hipHostFree(void* p) { return hip_stub_free(p); }
+inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) {
+    if (hip_stub_failing()) return hipErrorOutOfMemory;
+    *d = h;
+    return hipSuccess;
+}
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hip_stub_make(reinterpret_cast<void**>(s), 8); }
+inline hipError_t hipStreamDestroy(hipStream_t s) { return hip_stub_free(s); }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hip_stub_make(reinterpret_cast<void**>(e), 8); }
+inline hipError_t hipEventDestroy(hipEvent_t e) { return hip_stub_free(e); }
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) { std::memcpy(dst, src, bytes); return hipSuccess; }
+inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "hipErrorOutOfMemory"; }
