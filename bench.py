@@ -12,8 +12,7 @@ A step = one pass of the hot path over one batch of synthetic input already resi
 
 A step's `batch` consecutive frames go through `--lanes` (default 4) lanes of batch/lanes consecutive frames, each lane with its
 own extractor handle and HIP stream; a lane matches its own frames, and lanes meet only where the frame-to-frame match crosses
-a lane border (event-ordered hand-off of one frame's descriptors).  The per-kernel roofline numbers come from a short serial
-pass after the timed region (every kernel alone on the chip).
+a lane border (event-ordered hand-off of one frame's descriptors).
 
   python bench.py --gpus N --steps K --warmup W
 N > 1: one rank per GPU, every rank works on its own stream (weak scaling, no data-path collective); RCCL only takes the MAX of
@@ -22,13 +21,17 @@ the ranks it is given.  The timed region of the `--config` run is exactly K step
 block until the region lasts at least S seconds (6 s lets a 5 s device sampler land inside it).  Prints ONE JSON line on rank 0.
 `--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_frontend / dump_match).
 
+Without `--full` that is all a run does: set up, warm up, time the K steps, dump, print the line.  Everything below needs `--full`
+(a plain run takes the parity leg only when `--parity all` or `--parity sample` asks for it).
+
 After the timed region (never inside it) every rank compares the LAST timed step's outputs with the CPU oracle — EVERY frame of
 the step (`--parity all`, the default: one oracle instance per host thread; `--parity sample` = lane and step borders + interior
 frames only): keypoints + descriptors byte for byte, top-2 match against the previous frame integer for integer — and the line
-carries `config.parity_checked_frames` / `config.parity_mismatches`; a mismatch makes every rank exit 1.  The default run
-(`--config vga`) then also runs, for >= 1.5 s each with the same parity leg, and embeds under `also` (headline keys unchanged;
-`--no-also` skips them): BASELINE.json's other GPU configurations — `vga_extract` (configs[1]), `hd1080` (configs[2]; at N > 1 this
-is configs[3], one 1080p stream per GPU), `match100k` (configs[4], FP4 MFMA kernels; `match100k_int8` = the same through the int8 MFMA
+carries `config.parity_checked_frames` / `config.parity_mismatches`; a mismatch makes every rank exit 1.  The per-kernel roofline
+numbers come from a short serial pass after the timed region (every kernel alone on the chip); the CPU baselines follow.  The
+default configuration (`--config vga`) then also runs, for >= 1.5 s each with the same parity leg, and embeds under `also`
+(headline keys unchanged; `--no-also` skips them): BASELINE.json's other GPU configurations — `vga_extract` (configs[1]),
+`hd1080` (configs[2]; at N > 1 this is configs[3], one 1080p stream per GPU), `match100k` (configs[4], FP4 MFMA kernels; `match100k_int8` = the same through the int8 MFMA
 kernels of rounds 2-4, `match100k_popcount` = through the xor + popcount kernels the north_star names) — and the headline configuration on the other synthetic
 families, whose corner statistics (and therefore FAST / selection cost) differ: `vga_noise` (SURVEY 8d's worst case), `vga_midtex`
 (textured: several times more corners at threshold 7 than at 20, no fallback cells), `vga_lowtex` (every cell takes the fallback).
@@ -145,6 +148,7 @@ def _percentiles_ms(per):
 
 
 DUMP_BUDGET = 48 << 20      # --dump-outputs: bytes of array data per run (the .npy files stay under 64 MB)
+NO_PARITY_NOTE = "not compared with the CPU oracle in this run (--full compares the last timed step unless --parity none)"
 
 
 def save_outputs(d, arrays):
@@ -468,10 +472,11 @@ def run_frontend(a, cfg, world, rank, local_rank, dist, torch):
 
     stage = pipe.stage_times()
     pipe.stage_timing(0)
-    kp_mean = float(pipe.counts().float().mean().item())
-    bad_status = int((pipe.status() != 0).sum().item())
-    accepted, accepted_rate = -1, None
-    if do_match:
+    kp_mean, bad_status, accepted, accepted_rate = 0.0, 0, -1, None
+    if a.full:
+        kp_mean = float(pipe.counts().float().mean().item())
+        bad_status = int((pipe.status() != 0).sum().item())
+    if a.full and do_match:
         last = pipe.lanes[G - 1]
         best = last.match[1, b - 1, :cap].cpu().numpy()
         sec = last.match[2, b - 1, :cap].cpu().numpy()
@@ -545,8 +550,53 @@ def run_frontend(a, cfg, world, rank, local_rank, dist, torch):
         pipe.close()
         return {"_mismatches": int(counters[5])}
     total_frames = float(counters[0])
-    a_extract, a_match, per_stage = algorithmic_bytes(w, h, nfeat)
+    step_ms = tmax / nsteps * 1e3
+    value = total_frames / tmax
+    out = {
+        "metric": "frames/s ORB %s @%dx%d, %d kp" % ("extract+match" if do_match else "extract", w, h, nfeat),
+        "value": round(value, 1),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "repeats": repeats,
+        "timed_steps": nsteps,
+        "timed_seconds": round(tmax, 3),
+        "ms_per_step": round(step_ms, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": "%s: %dx%d grayscale stream, 8 levels, nFeatures %d, %s frames, extract%s (BASELINE.json configs[%d]%s)" % (
+                       a.config, w, h, nfeat, synth.FAMILY_NAMES.get(a.family, str(a.family)),
+                       " + Hamming top-2 match vs previous frame" if do_match else " only", cfg["baseline_config"],
+                       " + the frame-to-frame match of the metric" if a.config == "vga" else ""),
+                   "frames_per_step_per_gpu": B, "resident_frames_per_gpu": ring,
+                   "parallelism": "one image stream per GPU; a step's %d frames go through %d lanes of %d consecutive frames "
+                                  "(own extractor handle + HIP stream each), frame-to-frame matches across lane borders via event-ordered hand-off" % (B, G, b),
+                   "lanes": G, "lane_placement": placement,
+                   "parity_checked_frames": int(counters[4]), "parity_mismatches": int(counters[5]),
+                   "parity_note": "outputs of the LAST timed step vs the CPU oracle, after the timed region, on every rank: %s; keypoints + descriptors "
+                                  "byte-equal, top-2 match vs the previous frame integer-equal (%.1f s on %d host threads)"
+                                  % ("EVERY frame of the step" if a.parity == "all" else "first + last frame of every lane, the step border, interior frames",
+                                     t_par, host_threads(world)) if a.parity != "none" else NO_PARITY_NOTE,
+                   "parity_detail": parity["detail"],
+                   "host_submit_ms_per_step": round(float(counters[6]) / world, 4),
+                   "library_build_id": capi.build_id()},
+        "per_rank": [{"rank": r, "device": int(row[7]), "frames": int(row[0]), "elapsed_s": round(row[3], 4), "frames_per_s": round(row[0] / row[3], 1),
+                      "host_submit_ms": round(row[6], 4), "parity_checked_frames": int(row[4]),
+                      "pci_bus": int(row[8]), "numa_node": int(row[9]), "host_threads": int(row[10]), "numa_bound": int(row[11])}
+                     for r, row in enumerate(rows)],
+    }
     region_ms = {k: (ms / n if n else 0.0) for k, (ms, n) in stage.items()}      # per LAUNCH: one lane's slice of b frames
+    if a.region_timing:
+        out["stage_ms_per_launch_timed_region"] = {k: round(v, 4) for k, v in region_ms.items()}
+    if not a.full:
+        pipe.close()
+        return out
+
+    a_extract, a_match, per_stage = algorithmic_bytes(w, h, nfeat)
     concurrent = G > 1 or not a.region_timing        # without in-region timing the serial pass is the only per-kernel timing
     stage_ms = serial_pass(10) if concurrent else dict(region_ms)
     dom = max(stage_ms, key=lambda k: stage_ms[k])
@@ -555,9 +605,7 @@ def run_frontend(a, cfg, world, rank, local_rank, dist, torch):
     dom_gbs = dom_bytes / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
     kernel_ms = sum(stage_ms.values())
     pipe_bytes = (a_extract + (a_match if do_match else 0)) * B
-    step_ms = tmax / nsteps * 1e3
     pipe_gbs = pipe_bytes / (step_ms * 1e-3) / 1e9
-    value = total_frames / tmax
 
     # counters replayed from profiles/ (PMC passes cannot run inside this process): only when measured on THIS build
     # the two workloads with committed counter passes: VGA / 1000 (profiles/traffic.json) and 1080p / 2000 (profiles/traffic_hd1080.json)
@@ -612,56 +660,20 @@ def run_frontend(a, cfg, world, rank, local_rank, dist, torch):
             "pricing": "SQ_INSTS_VALU of the kernel (profiles/%s) priced with its static opcode mix (profiles/valu_mix.json): 2 cycles per "
                        "wave64 instruction for mov/add/sub/and/or/xor/bitop3/right shifts/f32 add-mul-fma, 4 for every other measured opcode "
                        "(profiles/r01_valu_issue_rates.txt, r02_valu_issue_rates2.txt)" % traffic_file}
-    out = {
-        "metric": "frames/s ORB %s @%dx%d, %d kp" % ("extract+match" if do_match else "extract", w, h, nfeat),
-        "value": round(value, 1),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "repeats": repeats,
-        "timed_steps": nsteps,
-        "timed_seconds": round(tmax, 3),
-        "ms_per_step": round(step_ms, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": "%s: %dx%d grayscale stream, 8 levels, nFeatures %d, %s frames, extract%s (BASELINE.json configs[%d]%s)" % (
-                       a.config, w, h, nfeat, synth.FAMILY_NAMES.get(a.family, str(a.family)),
-                       " + Hamming top-2 match vs previous frame" if do_match else " only", cfg["baseline_config"],
-                       " + the frame-to-frame match of the metric" if a.config == "vga" else ""),
-                   "frames_per_step_per_gpu": B, "resident_frames_per_gpu": ring,
-                   "parallelism": "one image stream per GPU; a step's %d frames go through %d lanes of %d consecutive frames "
-                                  "(own extractor handle + HIP stream each), frame-to-frame matches across lane borders via event-ordered hand-off" % (B, G, b),
-                   "lanes": G, "lane_placement": placement,
-                   "parity_checked_frames": int(counters[4]), "parity_mismatches": int(counters[5]),
-                   "parity_note": "outputs of the LAST timed step vs the CPU oracle, after the timed region, on every rank: %s; keypoints + descriptors "
-                                  "byte-equal, top-2 match vs the previous frame integer-equal (%.1f s on %d host threads)"
-                                  % ("EVERY frame of the step" if a.parity == "all" else "first + last frame of every lane, the step border, interior frames",
-                                     t_par, host_threads(world)),
-                   "parity_detail": parity["detail"],
-                   "host_submit_ms_per_step": round(float(counters[6]) / world, 4),
-                   "mean_keypoints_per_frame": round(float(counters[1]) / total_frames, 2),
-                   "frames_with_error_status": int(counters[2]), "accepted_matches_last_frame": accepted, "accepted_match_rate_last_step": accepted_rate,
-                   "accepted_note": "best <= 50 && best < 0.6 * second over every frame of the last timed step.  Consecutive S-blocks (noise, lowtex, "
-                                    "midtex) frames are "
-                                    "independent images, so few matches pass; S-warp (--family 5, `also.vga_warp`) is a correlated stream: "
-                                    "consecutive frames show the "
-                                    "same corners a pixel or two apart.  What the match leg computes is checked against the oracle in the parity leg "
-                                    "(integer-equal top-2)",
-                   "library_build_id": capi.build_id()},
-        "per_rank": [{"rank": r, "device": int(row[7]), "frames": int(row[0]), "elapsed_s": round(row[3], 4), "frames_per_s": round(row[0] / row[3], 1),
-                      "host_submit_ms": round(row[6], 4), "parity_checked_frames": int(row[4]),
-                      "pci_bus": int(row[8]), "numa_node": int(row[9]), "host_threads": int(row[10]), "numa_bound": int(row[11])}
-                     for r, row in enumerate(rows)],
+    out["config"].update({
+        "mean_keypoints_per_frame": round(float(counters[1]) / total_frames, 2),
+        "frames_with_error_status": int(counters[2]), "accepted_matches_last_frame": accepted, "accepted_match_rate_last_step": accepted_rate,
+        "accepted_note": "best <= 50 && best < 0.6 * second over every frame of the last timed step.  Consecutive S-blocks (noise, lowtex, "
+                         "midtex) frames are independent images, so few matches pass; S-warp (--family 5, `also.vga_warp`) is a correlated "
+                         "stream: consecutive frames show the same corners a pixel or two apart.  What the match leg computes is checked against "
+                         "the oracle in the parity leg (integer-equal top-2)"})
+    out.update({
         "roofline": roofline,
         "roofline_pipeline": {"bound": "hbm", "achieved": round(pipe_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                               "frac": round(pipe_gbs / HBM_PEAK_GBS, 5), "frac_of_achievable": round(pipe_gbs / HBM_ACHIEVABLE_GBS, 5),
                               "algorithmic_bytes_per_step": pipe_bytes, "ms_per_step": round(step_ms, 4), "kernel_ms_per_step_serial": round(kernel_ms, 4)},
         "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
-    }
+    })
     if valu_insts and mix and all(k in mix for k in valu_insts):
         n_inst = sum(valu_insts.values())
         ach = value / world * n_inst
@@ -681,8 +693,6 @@ def run_frontend(a, cfg, world, rank, local_rank, dist, torch):
     elif rep["note"]:
         out["roofline_valu"] = None
         out["roofline_note"] = rep["note"]
-    if a.region_timing:
-        out["stage_ms_per_launch_timed_region"] = {k: round(v, 4) for k, v in region_ms.items()}
     pipe.close()
     del d_img
     torch.cuda.empty_cache()
@@ -752,15 +762,16 @@ def run_match(a, cfg, world, rank, local_rank, dist, torch):
     # steady-state duration of ONE call: 30 further calls, each between its own pair of HIP events on the launch stream
     # (the r02 rocprof summary held 7 cold calls and disagreed with the region average; min / median / max are reported,
     # the roofline uses the MEDIAN)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(30)]
-    for ea, eb in evs:
-        ea.record(s)
-        step()
-        eb.record(s)
-    torch.cuda.synchronize(dev)
-    per_call = sorted(ea.elapsed_time(eb) for ea, eb in evs)
-    kernel_ms = per_call[len(per_call) // 2]
-    checksum = int(out3[1, :nq].sum().item()) if nq else 0
+    per_call = []
+    if a.full:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(30)]
+        for ea, eb in evs:
+            ea.record(s)
+            step()
+            eb.record(s)
+        torch.cuda.synchronize(dev)
+        per_call = sorted(ea.elapsed_time(eb) for ea, eb in evs)
+    checksum = int(out3[1, :nq].sum().item()) if a.full and nq else 0
     capi.set_match_path(-1)
     # parity leg (outside the timed region): sampled query rows of the last call against the oracle's sequential scan
     checked, mism = 0, 0
@@ -780,10 +791,30 @@ def run_match(a, cfg, world, rank, local_rank, dist, torch):
         return {"_mismatches": int(counters[4])}
     pairs = float(counters[0])
     value = pairs / tmax
+    mfma, fp4 = path != 0, path == 2
+    out = {
+        "metric": "pairs/s Hamming top-2, %d x %d 256-bit descriptors" % (n, n),
+        "value": round(value, 1), "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "repeats": repeats, "timed_steps": nsteps,
+        "timed_seconds": round(tmax, 3), "ms_per_step": round(tmax / nsteps * 1e3, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None,
+        "dtype": ("fp4 e2m1 (+-1 encoded bits, f32 accumulate, exact)" if fp4 else "i8 (+-1 encoded bits, i32 accumulate)") if mfma else "u32 xor + popcount",
+        "data": "synthetic",
+        "config": {"workload": "match100k: batched N-to-M descriptor match, %d x %d random 256-bit descriptors, dense top-2 (BASELINE.json "
+                               "configs[4])" % (n, n),
+                   "queries_per_gpu": nq, "train_descriptors": n, "parallelism": "queries sharded by rank, train set replicated, no exchange",
+                   "parity_checked_rows": int(counters[3]), "parity_mismatches": int(counters[4]),
+                   "parity_note": "64 evenly spaced query rows per rank of the last call vs the oracle's sequential scan (index, best, second)"
+                                  if a.parity != "none" else NO_PARITY_NOTE,
+                   "library_build_id": capi.build_id()},
+        "per_rank": [{"rank": r, "pairs": row[0], "elapsed_s": round(row[2], 4)} for r, row in enumerate(rows)],
+    }
+    if not a.full:
+        return out
+
+    kernel_ms = per_call[len(per_call) // 2]
     a_match = 32 * (nq + n) + 12 * nq
     gbs = a_match / (kernel_ms * 1e-3) / 1e9
     tops = 2.0 * 256.0 * nq * n / (kernel_ms * 1e-3) / 1e12
-    mfma, fp4 = path != 0, path == 2
     if not mfma:
         # the popcount form: 8 x v_xor + 8 x v_bcnt per pair (accumulating form) = 16 lane-operations -> 7.9e13 / 16 = 4.9e12 pairs/s
         pps = float(nq) * n / (kernel_ms * 1e-3)
@@ -817,22 +848,8 @@ def run_match(a, cfg, world, rank, local_rank, dist, torch):
         roofline["measured_issue_ceiling"] = {"peak": round(ceil, 3), "unit": "10^12 pairs/s", "frac": round(tops / ceil, 4),
                                               "note": "8 v_xor (2.61 cycles) + 8 v_bcnt (4.08 cycles) per 64 pairs and SIMD at 2.4 GHz, top-2 "
                               "bookkeeping not counted"}
-    out = {
-        "metric": "pairs/s Hamming top-2, %d x %d 256-bit descriptors" % (n, n),
-        "value": round(value, 1), "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "repeats": repeats, "timed_steps": nsteps,
-        "timed_seconds": round(tmax, 3), "ms_per_step": round(tmax / nsteps * 1e3, 4), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None,
-        "dtype": ("fp4 e2m1 (+-1 encoded bits, f32 accumulate, exact)" if fp4 else "i8 (+-1 encoded bits, i32 accumulate)") if mfma else "u32 xor + popcount",
-        "data": "synthetic",
-        "config": {"workload": "match100k: batched N-to-M descriptor match, %d x %d random 256-bit descriptors, dense top-2 (BASELINE.json "
-                               "configs[4])" % (n, n),
-                   "queries_per_gpu": nq, "train_descriptors": n, "parallelism": "queries sharded by rank, train set replicated, no exchange",
-                   "best_distance_checksum": int(counters[1]), "parity_checked_rows": int(counters[3]), "parity_mismatches": int(counters[4]),
-                   "parity_note": "64 evenly spaced query rows per rank of the last call vs the oracle's sequential scan (index, best, second)",
-                   "library_build_id": capi.build_id()},
-        "per_rank": [{"rank": r, "pairs": row[0], "elapsed_s": round(row[2], 4)} for r, row in enumerate(rows)],
-        "roofline": roofline,
-    }
+    out["config"]["best_distance_checksum"] = int(counters[1])
+    out["roofline"] = roofline
     if world == 1 and not a.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as orc
@@ -857,8 +874,8 @@ def _pick(d, keys):
 
 
 def compact_line(full, also=None):
-    """The LAST stdout line: the contract's headline keys + roofline + cpu_baseline, and one short row per other configuration
-    (`also_summary`).  Everything else (notes, per-call timings, parity detail, the full `also` reports) is printed in front of it as
+    """The LAST stdout line: the contract's headline keys (+ roofline + cpu_baseline in a --full run), and one short row per other
+    configuration (`also_summary`).  Everything else (notes, per-call timings, parity detail, the full `also` reports) is printed in front of it as
     `#detail <name> <json>` lines.  Bounded: <= 4 KB at one rank, <= 6 KB at eight (the 23 KB line of round 4 did not
     parse in the driver's record); tests/test_bench_line.py asserts it on CPU, tests/test_gpu_bench.py on the GPU."""
     out = _pick(full, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "repeats", "timed_steps", "timed_seconds", "ms_per_step",
@@ -870,17 +887,18 @@ def compact_line(full, also=None):
     if isinstance(cfg.get("lane_placement"), dict):
         c["lane_placement"] = cfg["lane_placement"].get("chosen")
     out["config"] = c
-    r = full.get("roofline") or {}
-    ro = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "avg_launch_ms",
-                   "frames_per_launch", "pairs_per_launch", "frac_of_achievable"))
-    ro.setdefault("traffic", None)
-    if "traffic_source" in r:
-        ro["traffic_measured_in_this_run"] = r["traffic_source"] == "measured in this run"
-    if isinstance(r.get("valu_issue"), dict):
-        ro["valu_issue"] = _pick(r["valu_issue"], ("achieved", "peak", "unit", "frac", "clock_ghz", "frac_at_clock"))
-    if isinstance(r.get("hbm"), dict):
-        ro["hbm"] = _pick(r["hbm"], ("bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch"))
-    out["roofline"] = ro
+    r = full.get("roofline")
+    if isinstance(r, dict):              # (--full)
+        ro = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "avg_launch_ms",
+                       "frames_per_launch", "pairs_per_launch", "frac_of_achievable"))
+        ro.setdefault("traffic", None)
+        if "traffic_source" in r:
+            ro["traffic_measured_in_this_run"] = r["traffic_source"] == "measured in this run"
+        if isinstance(r.get("valu_issue"), dict):
+            ro["valu_issue"] = _pick(r["valu_issue"], ("achieved", "peak", "unit", "frac", "clock_ghz", "frac_at_clock"))
+        if isinstance(r.get("hbm"), dict):
+            ro["hbm"] = _pick(r["hbm"], ("bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch"))
+        out["roofline"] = ro
     if isinstance(full.get("roofline_pipeline"), dict):
         out["roofline_pipeline"] = _pick(full["roofline_pipeline"], ("bound", "achieved", "peak", "unit", "frac", "kernel_ms_per_step_serial", "traffic"))
     if isinstance(full.get("roofline_valu"), dict):
@@ -922,6 +940,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run everything else the benchmark measures or checks: the parity leg, the serial "
+                         "per-kernel pass and the rooflines, the CPU baselines, the `also` configurations and the live traffic passes "
+                         "(the module docstring); without it a run sets up, warms up, times --steps steps, dumps and prints the line")
     ap.add_argument("--config", default="vga", choices=sorted(CONFIGS), help="BASELINE.json workload (see the module docstring)")
     ap.add_argument("--batch", type=int, default=None, help="frames per step per GPU (default: the config's)")
     ap.add_argument("--ring", type=int, default=None, help="distinct frames resident per GPU (>= 1024 VGA frames exceeds the 256 MiB Infinity Cache)")
@@ -938,15 +960,16 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat the --steps block until the timed region lasts at least this long (default 0: exactly --steps steps)")
     ap.add_argument("--parity", default=None, choices=["all", "sample", "none"],
-                    help="oracle comparison of the LAST timed step's outputs: every frame (default at one rank), lane / step borders + interior "
-                         "frames (default at N > 1: the ranks of a node share its host cores), or none")
+                    help="oracle comparison of the LAST timed step's outputs: every frame (--full's default at one rank), lane / step borders + "
+                         "interior frames (--full's default at N > 1: the ranks of a node share its host cores), or none (the default without --full)")
     ap.add_argument("--no-parity", action="store_true", help="same as --parity none")
     ap.add_argument("--cpu-reference-seconds", type=float, default=4.0,
                     help="CPU sample of oracle/_ref/libref_orbextractor.so (the reference's own ORBextractor.cc), when that file is present; 0 disables")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed even at world size 1 (the RCCL communicator, barrier and collectives then run as at N > 1)")
     ap.add_argument("--no-also", action="store_true",
-                    help="headline configuration only (the default run also measures vga_extract, hd1080, match100k and the other frame families)")
+                    help="headline configuration only (a --full run of the default configuration also measures vga_extract, hd1080, match100k "
+                         "and the other frame families)")
     ap.add_argument("--also-min-seconds", type=float, default=6.0,
                     help="timed region of each other frame configuration (as long as the headline's: sustained clocks)")
     ap.add_argument("--also-match-min-seconds", type=float, default=2.0, help="timed region of the 100k x 100k configurations")
@@ -954,8 +977,8 @@ def main():
                     help="after the timed region, write the last timed step's outputs of the --config run as DIR/<name>.npy "
                          "(float32 / float64, under 64 MB; rank 0's)")
     ap.add_argument("--live-traffic", default="auto", choices=["auto", "on", "off"],
-                    help="measure roofline.traffic in this run (two rocprofv3 --pmc child runs, ~40 s); auto = only in the full default command "
-                         "(one rank, --config vga with its `also` entries)")
+                    help="--full: measure roofline.traffic in this run (two rocprofv3 --pmc child runs, ~40 s); auto = only in the full default "
+                         "command (one rank, --config vga with its `also` entries)")
     ap.add_argument("--detail-file", default=None, help="also write the full reports (headline + also + the compact line) to this JSON file")
     ap.add_argument("--rank-timeout", type=float, default=1500.0, help="bare --gpus N command: kill the ranks when the run exceeds this many seconds")
     ap.add_argument("--also-cpu-seconds", type=float, default=5.0, help="CPU baseline sample of each embedded configuration")
@@ -969,7 +992,9 @@ def main():
     if a.no_parity:
         a.parity = "none"
     if a.parity is None:
-        a.parity = "all" if max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))) == 1 else "sample"
+        a.parity = ("all" if max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))) == 1 else "sample") if a.full else "none"
+    if a.live_traffic == "on" and not a.full:
+        ap.error("--live-traffic on needs --full (it measures the traffic of the roofline's kernel)")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus, a.share_device, a.rank_timeout))
@@ -1003,7 +1028,7 @@ def main():
     if rank == 0 and numa.get("desc"):
         out["config"]["host_numa_binding"] = numa["desc"]
     also = {}
-    if a.config == "vga" and a.family == synth.BLOCKS and not a.no_also:
+    if a.full and a.config == "vga" and a.family == synth.BLOCKS and not a.no_also:
         # BASELINE.json's other GPU configurations and the headline configuration on the other frame families, in the same run (the
         # driver runs this command once): same definitions, same parity leg, a timed region as long as the headline's for the frame
         # configurations (--also-min-seconds, 6 s: the chip clocks down over the first seconds of a region).  At
@@ -1032,8 +1057,8 @@ def main():
                 bad += int(r["config"].get("parity_mismatches", 0))
                 also[key] = r
     # roofline.traffic measured in THIS run (rank 0 of a one-rank default command; everything timed is behind us)
-    live = a.live_traffic == "on" or (a.live_traffic == "auto" and world == 1 and a.config == "vga" and a.family == synth.BLOCKS and not a.no_also
-                                      and a.batch is None and a.width is None and a.nfeatures is None)
+    live = a.full and (a.live_traffic == "on" or (a.live_traffic == "auto" and world == 1 and a.config == "vga" and a.family == synth.BLOCKS
+                                                  and not a.no_also and a.batch is None and a.width is None and a.nfeatures is None))
     if live and rank == 0 and world == 1 and isinstance(out.get("roofline"), dict) and out["roofline"].get("kernel"):
         lt, lt_note = measure_live_traffic(int(out["config"]["frames_per_step_per_gpu"]))
         rf = out["roofline"]

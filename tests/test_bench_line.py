@@ -147,3 +147,25 @@ def test_dump_outputs_sample_and_fields(tmp_path):
         assert np.array_equal(a["keypoints"][i, :k], np.stack([rec[j, :k][f].astype(np.float32) for f in capi.KP_DTYPE.names], -1))
         assert np.array_equal(a["descriptors"][i, :k], desc[j, :k]) and np.array_equal(a["match_best"][i, :k], match[1, j, :k])
         assert not a["keypoints"][i, k:].any() and not a["descriptors"][i, k:].any() and not a["match_index"][i, k:].any()
+
+
+def test_compact_line_of_a_plain_run():
+    """a run without --full reports the headline figure and its configuration only: the line carries no roofline, CPU baseline or
+    `also_summary` (nor an empty stand-in for them)"""
+    full, _ = _full()
+    plain = {k: v for k, v in full.items() if k not in ("roofline", "roofline_pipeline", "roofline_valu", "roofline_note", "stage_ms_per_step",
+                                                        "cpu_baseline", "cpu_baseline_reference_source", "cpu_baseline_allcores")}
+    line = bench.compact_line(plain)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "timed_steps"):
+        assert line[k] == full[k], k
+    for k in ("roofline", "roofline_pipeline", "roofline_valu", "stage_ms_per_step", "cpu_baseline", "also_summary"):
+        assert k not in line, k
+    assert line["config"]["workload"] == full["config"]["workload"]
+
+
+def test_live_traffic_on_needs_full():
+    """the live traffic passes measure the roofline's kernel, which only a --full run finds: asking for them without it is an argument
+    error, before anything touches a GPU"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--live-traffic", "on"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr and r.stdout == "", (r.returncode, r.stderr[-300:])

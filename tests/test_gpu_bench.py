@@ -1,6 +1,7 @@
 """bench.py as the driver runs it: a bare command (no torchrun) that starts its own ranks for --gpus N > 1 and prints ONE JSON
 line carrying the contract fields.  On the 1-GPU box the two ranks share cuda:0 and talk over gloo: a functional check of the
-N > 1 path (sharding, barrier, MAX / all-gather of the counters), not a scaling number."""
+N > 1 path (sharding, barrier, MAX / all-gather of the counters), not a scaling number.  A plain run carries the headline figure only;
+the tests of the parity leg, the rooflines, the CPU baselines and the other configurations run it with --full."""
 import json
 import os
 import subprocess
@@ -12,7 +13,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args, timeout=600):
+def _run(*args, timeout=600):
+    """one bench.py command in a fresh process: (its JSON line, the "#detail <name> <json>" reports by name)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -22,14 +24,21 @@ def _bench(*args, timeout=600):
     line = json.loads(lines[0])
     # the driver's record keeps a bounded tail of stdout: the line must stay small (23 KB did not parse)
     assert len(lines[0]) <= (4096 if line["n_gpus"] == 1 else 6144), len(lines[0])
-    for k in ("roofline", "config", "timed_steps", "timed_seconds"):
+    for k in ("config", "timed_steps", "timed_seconds"):
         assert k in line, k
-    # the full reports travel in front of it as "#detail <name> <json>" lines; the tests read the headline's and hang the others under `also`
+    # the full reports travel in front of it as "#detail <name> <json>" lines
     detail = {}
     for ln in out:
         if ln.startswith("#detail "):
             _, name, body = ln.split(" ", 2)
             detail[name] = json.loads(body)
+    return line, detail
+
+
+def _bench(*args, timeout=600):
+    """a --full command: the tests read the headline's report and hang the others under `also`"""
+    line, detail = _run("--full", *args, timeout=timeout)
+    assert "roofline" in line
     d = detail["headline"]
     assert d["value"] == line["value"] and d["ms_per_step"] == line["ms_per_step"] and d["config"]["workload"] == line["config"]["workload"]
     assert line["roofline"]["frac"] == d["roofline"]["frac"] and line["roofline"]["bound"] == d["roofline"]["bound"]
@@ -178,6 +187,30 @@ def test_steps_and_dump_outputs(tmp_path):
     ri, rb, rs = orc.match_top2(want[1][1], want[0][1])
     n = len(want[1][0])
     assert np.array_equal(a["match_index"][63, :n], ri) and np.array_equal(a["match_best"][63, :n], rb) and np.array_equal(a["match_second"][63, :n], rs)
+
+
+def test_plain_run_times_and_dumps_only(tmp_path):
+    """without --full a run sets up, warms up, times its steps, dumps and prints the line: no parity leg, serial pass, roofline, CPU
+    baseline or other configuration; it times the same steps and dumps the same outputs as the --full run of the same arguments"""
+    import numpy as np
+    args = ("--steps", "3", "--warmup", "1", "--batch", "64", "--ring", "128")
+    line, detail = _run(*args, "--dump-outputs", str(tmp_path / "plain"))
+    d = _bench(*args, "--no-also", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    assert set(detail) == {"headline"}
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line and (k in ("value", "ms_per_step") or line[k] == d[k]), k
+    assert line["value"] > 0 and line["steps"] == 3 and line["timed_steps"] == 3 and line["config"]["frames_per_step_per_gpu"] == 64
+    for k in ("roofline", "roofline_pipeline", "roofline_valu", "stage_ms_per_step", "cpu_baseline", "also_summary"):
+        assert k not in line and k not in detail["headline"], k
+    assert line["config"]["parity_checked_frames"] == 0 and "mean_keypoints_per_frame" not in line["config"]
+    assert d["config"]["parity_checked_frames"] == 64 and d["config"]["parity_mismatches"] == 0
+    names = sorted(os.listdir(tmp_path / "full"))
+    assert sorted(os.listdir(tmp_path / "plain")) == names and "descriptors.npy" in names
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)), n
+    m, mdetail = _run("--config", "match100k", "--steps", "2", "--warmup", "1")
+    assert m["unit"] == "pairs/s" and m["value"] > 5e11 and "roofline" not in m and "cpu_baseline" not in m
+    assert m["config"]["parity_checked_rows"] == 0 and "best_distance_checksum" not in mdetail["headline"]["config"]
 
 
 def test_rccl_path_at_world_size_one():

@@ -1,9 +1,12 @@
 #!/bin/bash
-# Everything profiles/ is built from, in one go on the GPU box.  usage: tools/collect_round_artifacts.sh <name> [lines]   (-> gpurun_out/<name>, gpurun_out/<name>_pmc)
+# Everything profiles/ is built from, in one go on the GPU box.  usage: tools/collect_round_artifacts.sh <name> [lines | dir]   (-> the output
+# directory of <name> and its _pmc sibling)
 # `lines` skips the counter passes (profiles/traffic.json and valu_mix.json must already carry this build's hash) and only re-runs the bench lines.
+# `dir` prints the output directory of <name> and runs nothing.
 # Order: counter passes first (profiles/traffic.json of THIS build — it carries the library's source hash — is what bench.py replays for the
 # VALU-issue roofline and roofline.hbm.traffic), then the bench lines.
 R=${GRAFT_REPO_ROOT:-/root/repo}; D=$R/gpurun_out/$1; mkdir -p $D; cd /tmp; export TMPDIR=/tmp
+[ "$2" = dir ] && { echo $D; exit 0; }
 B=1024      # bench.py's default frames per step = frames per launch of the serial command
 if [ "$2" != "lines" ]; then
 SER="--steps 10 --warmup 2 --no-cpu-baseline --lanes 1 --region-timing --min-seconds 0 --no-also --no-parity"
@@ -22,15 +25,15 @@ fi
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o stats_overlap -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --min-seconds 0 --no-also --no-parity > $D/stats_overlap.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o stats_match -- python $R/bench.py --config match100k --steps 40 --warmup 5 --no-cpu-baseline --min-seconds 0 --no-parity > $D/stats_match.log 2>&1
 cd $R
-( time timeout 900 python bench.py --detail-file $D/bench.json > $D/bench.line.json 2> $D/bench.err ) 2> $D/bench_wall.txt          # the driver's command: headline + also{hd1080, match100k}, parity legs, CPU baselines
-Q="--no-cpu-baseline --no-also --min-seconds 2"
+( time timeout 900 python bench.py --full --detail-file $D/bench.json > $D/bench.line.json 2> $D/bench.err ) 2> $D/bench_wall.txt          # the full command: headline + also{hd1080, match100k, ...}, parity legs, rooflines, CPU baselines
+Q="--full --no-cpu-baseline --no-also --min-seconds 2"
 timeout 300 python bench.py --lanes 1 $Q --detail-file $D/bench_one_lane.json > $D/bench_one_lane.line.json 2>/dev/null
 timeout 300 python bench.py --region-timing $Q --detail-file $D/bench_region_timing.json > $D/bench_region_timing.line.json 2>/dev/null
 timeout 300 python bench.py --config vga_extract $Q --detail-file $D/bench_extract_only.json > $D/bench_extract_only.line.json 2>/dev/null
 timeout 300 python bench.py --family 0 $Q --detail-file $D/bench_noise.json > $D/bench_noise.line.json 2>/dev/null
-ORBX_MATCH_MFMA=0 timeout 300 python bench.py --config match100k --no-cpu-baseline --min-seconds 2 --detail-file $D/bench_match100k_popcount.json > $D/bench_match100k_popcount.line.json 2>/dev/null
-ORBX_MATCH_MFMA=8 timeout 300 python bench.py --config match100k --no-cpu-baseline --min-seconds 2 --detail-file $D/bench_match100k_int8.json > $D/bench_match100k_int8.line.json 2>/dev/null
-timeout 600 python bench.py --gpus 2 --backend gloo --share-device --no-cpu-baseline --batch 512 --min-seconds 2 --also-min-seconds 1 --detail-file $D/bench_two_ranks_one_gpu_gloo.json > $D/bench_two_ranks_one_gpu_gloo.line.json 2>/dev/null
+ORBX_MATCH_MFMA=0 timeout 300 python bench.py --full --config match100k --no-cpu-baseline --min-seconds 2 --detail-file $D/bench_match100k_popcount.json > $D/bench_match100k_popcount.line.json 2>/dev/null
+ORBX_MATCH_MFMA=8 timeout 300 python bench.py --full --config match100k --no-cpu-baseline --min-seconds 2 --detail-file $D/bench_match100k_int8.json > $D/bench_match100k_int8.line.json 2>/dev/null
+timeout 600 python bench.py --full --gpus 2 --backend gloo --share-device --no-cpu-baseline --batch 512 --min-seconds 2 --also-min-seconds 1 --detail-file $D/bench_two_ranks_one_gpu_gloo.json > $D/bench_two_ranks_one_gpu_gloo.line.json 2>/dev/null
 timeout 200 python tools/corun_probe.py > $D/corun_probe.json 2>/dev/null
 (timeout 100 python tools/bench_single_frame.py; timeout 100 python tools/bench_single_frame.py 1920 1080 2000; timeout 100 orb_slam_amd/cpp/bench_single_frame; timeout 100 orb_slam_amd/cpp/bench_single_frame 1920 1080 2000) > $D/single_frame.txt 2>/dev/null
 timeout 100 tools/microbench/valu_rate2 > $D/valu_issue_rates2.txt 2>&1

@@ -3,7 +3,7 @@
 # a list of (variant, family) pairs.   usage: tools/exp_ab.sh <name> "<variant>:<family>[:config] ..."   (variant "tree" = orb_slam_amd/liborbx.so)
 N=${1:?name}; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}; D=$R/gpurun_out/$N; mkdir -p $D; cd $R
-S="--lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --region-timing --min-seconds 0 --no-also --no-parity"
+S="--full --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --region-timing --min-seconds 0 --no-also --no-parity"
 for item in $*; do
   v=${item%%:*}; rest=${item#*:}; f=${rest%%:*}; c=vga; [ "$rest" != "$f" ] && c=${rest#*:}
   lib=$R/build_variants/$v/liborbx.so; [ "$v" = tree ] && lib=$R/orb_slam_amd/liborbx.so

@@ -3,8 +3,8 @@
 # collect_round_artifacts.sh produce), most important first, so that a call cut short by the GPU budget still leaves the front of the list.
 # usage: tools/side_lines.sh <name>   (-> gpurun_out/<name>/)
 N=${1:?name}; R=${GRAFT_REPO_ROOT:-/root/repo}; D=$R/gpurun_out/$N; mkdir -p $D; cd $R
-Q="--no-cpu-baseline --no-also --min-seconds 2"
-timeout 200 python bench.py --config hd1080 --cpu-allcores-seconds 0 --cpu-seconds 5 --detail-file $D/bench_hd1080.json > $D/bench_hd1080.line.json 2>/dev/null
+Q="--full --no-cpu-baseline --no-also --min-seconds 2"
+timeout 200 python bench.py --full --config hd1080 --cpu-allcores-seconds 0 --cpu-seconds 5 --detail-file $D/bench_hd1080.json > $D/bench_hd1080.line.json 2>/dev/null
 timeout 100 python bench.py --lanes 1 $Q --detail-file $D/bench_one_lane.json > $D/bench_one_lane.line.json 2>/dev/null
 timeout 100 python bench.py --config vga_extract $Q --detail-file $D/bench_extract_only.json > $D/bench_extract_only.line.json 2>/dev/null
 timeout 100 python bench.py --region-timing $Q --detail-file $D/bench_region_timing.json > $D/bench_region_timing.line.json 2>/dev/null
@@ -14,8 +14,8 @@ tools/run_pmc_match.sh ${N}_mfma > /dev/null 2>&1; cp gpurun_out/${N}_mfma/pmc_m
 (cd /tmp; export TMPDIR=/tmp
  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o stats_overlap -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --min-seconds 0 --no-also --no-parity > $D/stats_overlap.log 2>&1
  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o stats_match -- python $R/bench.py --config match100k --steps 40 --warmup 5 --no-cpu-baseline --min-seconds 0 --no-parity > $D/stats_match.log 2>&1)
-timeout 300 python bench.py --gpus 2 --backend gloo --share-device --no-cpu-baseline --batch 512 --min-seconds 2 --also-min-seconds 1 2>/dev/null | grep "^{" > $D/bench_two_ranks_one_gpu_gloo.json
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --backend gloo --share-device --no-cpu-baseline --batch 512 --min-seconds 1 --also-min-seconds 0.5 2>/dev/null | grep "^{" > $D/bench_torchrun_two_ranks.json
+timeout 300 python bench.py --full --gpus 2 --backend gloo --share-device --no-cpu-baseline --batch 512 --min-seconds 2 --also-min-seconds 1 2>/dev/null | grep "^{" > $D/bench_two_ranks_one_gpu_gloo.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --backend gloo --share-device --no-cpu-baseline --batch 512 --min-seconds 1 --also-min-seconds 0.5 2>/dev/null | grep "^{" > $D/bench_torchrun_two_ranks.json
 python - <<PY
 import sys
 sys.path.insert(0, "$R")
@@ -27,7 +27,7 @@ PY
 timeout 100 python tools/bench_pcie.py --steps 30 > $D/pcie_inclusive.json 2>/dev/null
 timeout 200 python tools/bench_frontend.py --window 15 2>/dev/null | tail -1 > $D/frontend_w15.json
 timeout 200 python tools/bench_frontend.py 2>/dev/null | tail -1 > $D/frontend_w100.json
-ORBX_MATCH_MFMA=0 timeout 100 python bench.py --config match100k --no-cpu-baseline --min-seconds 2 --detail-file $D/bench_match100k_popcount.json > $D/bench_match100k_popcount.line.json 2>/dev/null
+ORBX_MATCH_MFMA=0 timeout 100 python bench.py --full --config match100k --no-cpu-baseline --min-seconds 2 --detail-file $D/bench_match100k_popcount.json > $D/bench_match100k_popcount.line.json 2>/dev/null
 timeout 100 python tools/corun_probe.py > $D/corun_probe.json 2>/dev/null
 timeout 100 python tools/bench_kf_search.py 2>/dev/null | tail -1 > $D/kf_search.json
 ls $D | wc -l
