@@ -29,7 +29,8 @@
 //               orb_math.h blur_round, as k_blur / k_blur_mfma.
 //   H4          taps up to 2 px outside the level read the UNBLURRED reflect-101 border in the reference.  Outputs at
 //               out-of-level positions are simply not written: the window keeps the plain reflected pixel there.
-// 27 MFMAs (432 matrix-pipe cycles) and ~250 VALU instructions per keypoint for the blur; a wave owns four keypoints.
+//   tiles       two 16-wide tiles per axis per window; the last 8 columns and 5 rows of two windows share one tile (see the blur below).
+// 20 MFMAs and ~150 VALU instructions per keypoint for the blur; a wave owns four keypoints.
 #include <algorithm>
 #include <type_traits>
 
@@ -47,8 +48,6 @@ constexpr int OD_TAIL = 512;                                     // the operand 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int float_bits(float v) { return __builtin_bit_cast(int, v); }
-__host__ __device__ constexpr int od_col0(int ct) { return ct == 0 ? 0 : ct == 1 ? 16 : 24; }      // first output column c' of column tile ct
-__host__ __device__ constexpr int od_row0(int rt) { return rt == 0 ? 0 : rt == 1 ? 16 : 21; }      // first output row ro of row tile rt
 typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
 
@@ -59,8 +58,10 @@ constexpr uint32_t od_taps4(int t0) { return (uint32_t)od_tap(t0) | (uint32_t)od
 struct OdTables {
     uint32_t mask[256];            // circle byte masks of the 31 x 8 patch dwords (umax[] of reference :495-510; slots 248.. = 0)
     float pat[256][4];             // test t: x0, y0, x1, y1
-    uint32_t trow[3][64][4];       // row pass, column tile ct, lane: K = window column 16 g + 4 v + byte, output column c' = col0(ct) + n
-    uint32_t tcol[3][64][4];       // column pass, row tile rt, lane: K = 16 g + 4 v + byte <-> Mid row 16 v + 4 g + byte, output row ro = row0(rt) + n
+    uint32_t trow[3][64][4];       // row pass, lane: K = 16 g + 4 v + byte; [ct < 2]: window column K, output column c' = 16 ct + n;
+                                   // [2] (PCOL): K block 2 = the first window's columns 32 .. 47 -> c' = 32 + n (n < 8), block 3 = the second's -> c' = 24 + n (n >= 8)
+    uint32_t tcol[3][64][4];       // column pass, lane: K = 16 g + 4 v + byte <-> Mid row 16 v + 4 g + byte; [rt < 2]: output row ro = 16 rt + n;
+                                   // [2] (PROW, CORNER): register 2 -> ro = 32 + n (n < 5), register 3 = the other window's -> ro = 24 + n (8 <= n < 13)
 };
 constexpr uint32_t c_pattern_host[256] = {
 #include "orb_pattern_packed.inc"
@@ -84,8 +85,13 @@ constexpr OdTables make_od_tables() {
         for (int l = 0; l < 64; l++)
             for (int v = 0; v < 4; v++) {
                 const int n = l & 15, g = l >> 4;
-                T.trow[c][l][v] = od_taps4(16 * g + 4 * v - (od_col0(c) + n) - 1);
-                T.tcol[c][l][v] = od_taps4(16 * v + 4 * g - (od_row0(c) + n));
+                if (c < 2) {
+                    T.trow[c][l][v] = od_taps4(16 * g + 4 * v - (16 * c + n) - 1);
+                    T.tcol[c][l][v] = od_taps4(16 * v + 4 * g - (16 * c + n));
+                } else {
+                    T.trow[c][l][v] = g == 2 && n < 8 ? od_taps4(4 * v - n - 1) : g == 3 && n >= 8 ? od_taps4(4 * v - (n - 8) - 1) : 0u;
+                    T.tcol[c][l][v] = v == 2 && n < 5 ? od_taps4(4 * g - n) : v == 3 && n >= 8 && n < 13 ? od_taps4(4 * g - (n - 8)) : 0u;
+                }
             }
     return T;
 }
@@ -221,9 +227,7 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
 
     // ---- lane constants of the two passes (independent of the keypoint)
     const int n16 = li, g4 = grp;                            // the MFMA's view of the lane: row / column lane % 16, K block lane / 16
-    // Tile origins: output columns c' = 0 / 16 / 24 + n, output rows ro = 0 / 16 / 21 + n.  The third tile of either axis OVERLAPS the second instead
-    // of running past what is needed (c' <= 39, ro <= 36): every output of every tile is one the taps can reach or a second, identical copy
-    // of one, every store lands inside the window — no predicate anywhere (round 6: 374 -> 2xx VALU instructions per keypoint).
+    // [0], [1]: the 16-wide column / row tiles of one window; [2]: the paired tiles of the last 8 columns / 5 rows (blur below)
     v4i Trow[3], Tcol[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -314,84 +318,150 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     const float angle = fast_atan2_deg((float)m01, (float)m10);
     wave_lds_fence();                                          // every patch read is done before the windows are overwritten
 
-    // ---- the blur, window after window, the whole wave on each
-    const unsigned a_off = (unsigned)(n16 * OD_PITCH + 16 * g4);                 // the lane's 16 operand bytes in a row tile
-    const unsigned o_off = (unsigned)((n16 + 3) * OD_PITCH + 4 + 4 * g4);        // the lane's output dword in tile (0, 0)
-    auto blur_window = [&](auto EDGE, uint8_t* W, int xs, int yq) {
-        constexpr bool edge = decltype(EDGE)::value;
-        v4i A[3];
-        {
-            const unsigned ra = (unsigned)(uintptr_t)(lptr_t)(W + a_off);
-            asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %3 offset:768\n\tds_read_b128 %2, %3 offset:1536\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]) : "v"(ra) : "memory");
-        }
+    // ---- the blur, two windows (a pair: slots 2 p, 2 p + 1) at a time, the whole wave on each
+    // Output column c' <-> window column c' + 4, output row ro <-> window row ro + 3; the taps read c' <= 39, ro <= 36.  Tiles:
+    //   OWN     c' 16 ct .. +15, ro 16 rt .. +15 (ct, rt < 2) of one window: 4 per window
+    //   PROW    c' 16 ct .. +15, ro 32 .. 36 of BOTH windows of a pair: the column pass's A carries the first window's Mid rows 32 .. 47 in
+    //           register 2 (as always) and the second window's in register 3 (whose K slots are empty in every other tile); N < 8 <-> the
+    //           first window's row 32 + N, N >= 8 <-> the second's row 32 + N - 8 (N = 5 .. 7, 13 .. 15: zero taps, stored to rows 37 .. 39,
+    //           which nothing reads once the pair's operands are in registers)
+    //   PCOL    c' 32 .. 39 of both windows of a pair, ro 16 rt .. +15: the row pass's K block 2 is the first window's bytes 32 .. 47 (as
+    //           always) and block 3 the second window's (the first window's operand read fetches them there; the column tiles of one
+    //           window have zero taps on block 3); M < 8 <-> the first window's column 32 + M, M >= 8 <-> the second's column 32 + M - 8
+    //   CORNER  c' 32 .. 39, ro 32 .. 36 of all four windows: PCOL's rows 32 .. 47 of pair 1 in register 2, of pair 0 in register 3
+    // Per four windows 80 MFMAs and 25 epilogues instead of 108 and 36 (three 16 x 16 tiles per axis, the third overlapping the second).
+    // Every output the taps read is written exactly once; per pair, both windows' operands are read before the first store.
+    const unsigned a_off = (unsigned)(n16 * OD_PITCH + 16 * g4);                                             // the lane's 16 operand bytes in a row tile
+    const unsigned a_offp = g4 == 3 ? (unsigned)(OD_WIN_BYTES + n16 * OD_PITCH + 32) : a_off;               // (first window of a pair) block 3: the second's bytes 32 ..
+    const unsigned o_own = (unsigned)((n16 + 3) * OD_PITCH + 4 + 4 * g4);                                    // OWN (0, 0)
+    const unsigned o_prow = (unsigned)((n16 >= 8 ? OD_WIN_BYTES : 0) + ((n16 & 7) + 35) * OD_PITCH + 4 + 4 * g4);          // PROW of column tile 0
+    const unsigned o_pcol = (unsigned)((g4 >= 2 ? OD_WIN_BYTES : 0) + (n16 + 3) * OD_PITCH + 36 + 4 * (g4 & 1));          // PCOL of row tile 0
+    const unsigned o_corner = (unsigned)((n16 < 8 ? 2 : 0) * OD_WIN_BYTES + (g4 >= 2 ? OD_WIN_BYTES : 0) + ((n16 & 7) + 35) * OD_PITCH + 36 + 4 * (g4 & 1));
+    // per window (wave-uniform): where it lies, and whether its tiles take the per-lane epilogue — an edge window (H4 merge), or one whose
+    // outputs straddle blur_wvec (ties-to-even columns x < wvec, half up beyond).  Idle slots copy the tie mode of the slot before them.
+    int xsw[OD_KPW], yqw[OD_KPW];
+    uint32_t tww[OD_KPW];
+    bool genw[OD_KPW];
+#pragma unroll
+    for (int q = 0; q < OD_KPW; q++) {
+        const unsigned posq = (unsigned)__builtin_amdgcn_readlane((int)kp.pos, 16 * q);
+        xsw[q] = ((int)(posq & 0xFFFF) - 22) & ~3;
+        yqw[q] = (int)(posq >> 16);
+        const bool lo = xsw[q] + 4 < L.wvec, hi = xsw[q] + 40 < L.wvec;
+        const bool liveq = q == 0 || k0 + q < cnt;
+        tww[q] = liveq ? (lo ? 1u : 0u) : tww[q > 0 ? q - 1 : 0];
+        genw[q] = liveq && (((fixmask >> (4 + q)) & 1u) || lo != hi);
+    }
+    constexpr uint32_t CADD = 257 * 32896 + 0x7FFF;           // the centring offsets + the rounding constant (+ 1 more where half up)
+    const v4i c128 = {128, 128, 128, 128}, zero = {0, 0, 0, 0};
+    // row pass of one column tile: z[t] = S - 32768 for Mid rows 16 t + 4 g + i, split into the column pass's two int8 operands (registers 0 .. 2;
+    // the caller sets register 3: the other window's register 2, or anything where its taps are zero).
+    auto row_pass = [&](const v4i (&A)[3], const v4i& T, v4i& HI, v4i& LO) {
+        v4i z[3];
+#pragma unroll
+        for (int t = 0; t < 3; t++) z[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], T, c128, 0, 0, 0);
 #pragma unroll
         for (int t = 0; t < 3; t++) {
-            A[t].x = (int)((uint32_t)A[t].x ^ 0x80808080u); A[t].y = (int)((uint32_t)A[t].y ^ 0x80808080u);
-            A[t].z = (int)((uint32_t)A[t].z ^ 0x80808080u); A[t].w = (int)((uint32_t)A[t].w ^ 0x80808080u);
-        }
-#pragma unroll
-        for (int ct = 0; ct < 3; ct++) {
-            // row pass of column tile ct: z[t] = S - 32768 for Mid rows 16 t + 4 g + i, column c' = col0(ct) + n
-            const v4i c128 = {128, 128, 128, 128};
-            v4i z[3];
-#pragma unroll
-            for (int t = 0; t < 3; t++) z[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], Trow[ct], c128, 0, 0, 0);
-            int h4[4] = {0, 0, 0, 0}, l4[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int t = 0; t < 3; t++) {
-                const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)z[t][1], (uint32_t)z[t][0], 0x05010400u);      // lo0 lo1 hi0 hi1
-                const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)z[t][3], (uint32_t)z[t][2], 0x05010400u);
-                l4[t] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
-                h4[t] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
-            }
-            const v4i HI = {h4[0], h4[1], h4[2], h4[3]}, LO = {l4[0], l4[1], l4[2], l4[3]};
-            const int X0 = xs + 4 + od_col0(ct) + 4 * g4;    // level column of the lane's first output byte (a multiple of 4)
-            const uint32_t tw = X0 < L.wvec ? 1u : 0u;       // ties-to-even columns (blur_wvec is a multiple of 4)
-            const uint32_t cadd = (uint32_t)(257 * 32896 + 0x7FFF) + (tw ^ 1u);      // the centring offsets + the rounding constant (+ 1 more: half up)
-            uint32_t keepc = 0;                              // (edge windows) bytes of the dword whose column lies outside the level
-            if (edge) {
-#pragma unroll
-                for (int bb = 0; bb < 4; bb++) keepc |= ((unsigned)(X0 + bb) < (unsigned)L.w ? 0u : 0xFFu) << (8 * bb);
-            }
-#pragma unroll
-            for (int rt = 0; rt < 3; rt++) {
-                const v4i zero = {0, 0, 0, 0};
-                v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(HI, Tcol[rt], zero, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[i] = (int)(((uint32_t)acc[i] << 8) + cadd);
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(LO, Tcol[rt], acc, 0, 0, 0);
-                uint32_t qv[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    // + bit 16 (ties to even; the half-up columns carry their + 1 in `cadd`): shift, and, add — three 2-cycle instructions instead of a
-                    // bit-field extract and a three-operand add at 4 cycles each (profiles/r02_valu_issue_rates2.txt)
-                    const uint32_t t = (uint32_t)acc[i];
-                    qv[i] = t + ((t >> 16) & tw);
-                }
-                const us2v lo2 = __builtin_elementwise_min(as_us2v(__builtin_amdgcn_perm(qv[1], qv[0], 0x07060302u)), as_us2v(0x00FF00FFu));
-                const us2v hi2 = __builtin_elementwise_min(as_us2v(__builtin_amdgcn_perm(qv[3], qv[2], 0x07060302u)), as_us2v(0x00FF00FFu));
-                uint32_t o = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi2), __builtin_bit_cast(uint32_t, lo2), 0x06040200u);
-                uint32_t* dst = reinterpret_cast<uint32_t*>(W + o_off + (od_row0(rt) * OD_PITCH + od_col0(ct)));
-                if (edge) {
-                    // out-of-level positions keep the plain reflected pixel (H4): per-byte merge with what the window holds
-                    const int Y = yq - 18 + od_row0(rt) + n16;
-                    const uint32_t keep = (unsigned)Y < (unsigned)L.h ? keepc : 0xFFFFFFFFu;
-                    o = (o & ~keep) | (*dst & keep);
-                }
-                *dst = o;
-            }
+            const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)z[t][1], (uint32_t)z[t][0], 0x05010400u);      // lo0 lo1 hi0 hi1
+            const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)z[t][3], (uint32_t)z[t][2], 0x05010400u);
+            LO[t] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
+            HI[t] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
         }
     };
+    const uint32_t c255 = 255;
+    // column pass of one tile + rounding + saturation + the aligned store.  The lane's dword is output columns cb .. cb + 3 of output row ro
+    // of the window at column xs_l / row yq_l (GEN only: per-lane tie mode and H4 merge; otherwise the pair's uniform tie mode `twu`).
+    auto epilogue = [&](auto GEN, const v4i& HI, const v4i& LO, const v4i& T, uint8_t* dst, int xs_l, int yq_l, int cb, int ro, uint32_t twu) {
+        constexpr bool gen = decltype(GEN)::value;
+        uint32_t tw = twu, keep = 0;
+        if (gen) {
+            const int X0 = xs_l + 4 + cb;                    // level column of the lane's first output byte (a multiple of 4)
+            tw = X0 < L.wvec ? 1u : 0u;
+            uint32_t keepc = 0;                              // bytes whose column lies outside the level
+#pragma unroll
+            for (int bb = 0; bb < 4; bb++) keepc |= ((unsigned)(X0 + bb) < (unsigned)L.w ? 0u : 0xFFu) << (8 * bb);
+            keep = (unsigned)(yq_l - 18 + ro) < (unsigned)L.h ? keepc : 0xFFFFFFFFu;
+        }
+        const uint32_t cadd = CADD + (tw ^ 1u);
+        v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(HI, T, zero, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[i] = (int)(((uint32_t)acc[i] << 8) + cadd);
+        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(LO, T, acc, 0, 0, 0);
+        uint32_t q[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t t = (uint32_t)acc[i];
+            q[i] = t + ((t >> 16) & tw);                     // + bit 16 on ties-to-even columns (v_and_b32_sdwa + v_add)
+        }
+        // saturate the high halves and pack them: one SDWA min per byte (WORD_1 in, BYTE_i out, the other bytes kept)
+        uint32_t o;
+        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD" : "=v"(o) : "v"(q[0]), "v"(c255));
+        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:DWORD" : "+v"(o) : "v"(q[1]), "v"(c255));
+        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:DWORD" : "+v"(o) : "v"(q[2]), "v"(c255));
+        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:DWORD" : "+v"(o) : "v"(q[3]), "v"(c255));
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+        if (gen) o = (o & ~keep) | (*d & keep);              // out-of-level positions keep the plain reflected pixel (H4)
+        *d = o;
+    };
+    int hc[2] = {0, 0}, lc[2] = {0, 0};                      // the corner's operands: register 2 of each pair's PCOL row pass (Mid rows 32 .. 47)
+    // (the pair's wave-uniform values come in as scalars: the per-window arrays stay unindexed by the loop counter, i.e. out of scratch)
+    auto blur_pair = [&](auto GEN, int p, int xs0, int yq0, int xs1, int yq1, uint32_t twu) {
+        uint8_t* W = win0 + 2 * p * OD_WIN_BYTES;
+        v4i A0[3], A1[3];
+        {
+            const unsigned r0 = (unsigned)(uintptr_t)(lptr_t)(W + a_offp), r1 = (unsigned)(uintptr_t)(lptr_t)(W + OD_WIN_BYTES + a_off);
+            asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:768\n\tds_read_b128 %2, %6 offset:1536\n\t"
+                         "ds_read_b128 %3, %7\n\tds_read_b128 %4, %7 offset:768\n\tds_read_b128 %5, %7 offset:1536\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(A0[0]), "=&v"(A0[1]), "=&v"(A0[2]), "=&v"(A1[0]), "=&v"(A1[1]), "=&v"(A1[2]) : "v"(r0), "v"(r1) : "memory");
+        }
+#pragma unroll
+        for (int t = 0; t < 3; t++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) { A0[t][e] = (int)((uint32_t)A0[t][e] ^ 0x80808080u); A1[t][e] = (int)((uint32_t)A1[t][e] ^ 0x80808080u); }
+        const int xs_r = n16 >= 8 ? xs1 : xs0, yq_r = n16 >= 8 ? yq1 : yq0;       // (GEN) PROW lanes' window
+        const int xs_c = g4 >= 2 ? xs1 : xs0, yq_c = g4 >= 2 ? yq1 : yq0;         // (GEN) PCOL lanes' window
+        {
+            v4i HP, LP;
+            row_pass(A0, Trow[2], HP, LP);
+            HP[3] = HP[2]; LP[3] = LP[2];                    // (zero taps in PCOL)
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++)
+                epilogue(GEN, HP, LP, Tcol[rt], W + o_pcol + 16 * rt * OD_PITCH, xs_c, yq_c, 32 + 4 * (g4 & 1), 16 * rt + n16, twu);
+            if (p == 0) { hc[0] = HP[2]; lc[0] = LP[2]; hc[1] = HP[2]; lc[1] = LP[2]; }      // (pair 1 idle: its corner lanes get pair 0's rows)
+            else { hc[1] = HP[2]; lc[1] = LP[2]; }
+        }
+#pragma unroll
+        for (int ct = 0; ct < 2; ct++) {
+            v4i H0, L0, H1, L1;
+            row_pass(A0, Trow[ct], H0, L0);
+            row_pass(A1, Trow[ct], H1, L1);
+            H0[3] = H1[2]; L0[3] = L1[2];                    // (PROW's second window; zero taps in OWN)
+            H1[3] = H1[2]; L1[3] = L1[2];
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++) {
+                epilogue(GEN, H0, L0, Tcol[rt], W + o_own + (16 * rt * OD_PITCH + 16 * ct), xs0, yq0, 16 * ct + 4 * g4, 16 * rt + n16, twu);
+                epilogue(GEN, H1, L1, Tcol[rt], W + OD_WIN_BYTES + o_own + (16 * rt * OD_PITCH + 16 * ct), xs1, yq1, 16 * ct + 4 * g4, 16 * rt + n16, twu);
+            }
+            epilogue(GEN, H0, L0, Tcol[2], W + o_prow + 16 * ct, xs_r, yq_r, 16 * ct + 4 * g4, 32 + (n16 & 7), twu);
+        }
+    };
+    const int nlive = min(cnt - k0, OD_KPW);                 // (wave-uniform) 1 .. 4
 #pragma unroll 1
-    for (int q = 0; q < OD_KPW; q++) {
-        if (q > 0 && k0 + q >= cnt) continue;                // wave-uniform
-        const unsigned posq = (unsigned)__builtin_amdgcn_readlane((int)kp.pos, 16 * q);
-        const int xq = posq & 0xFFFF, yq = posq >> 16;
-        const int xs = (xq - 22) & ~3;
-        uint8_t* W = win0 + q * OD_WIN_BYTES;
-        if ((fixmask >> (4 + q)) & 1u) blur_window(std::true_type{}, W, xs, yq);      // (wave-uniform)
-        else blur_window(std::false_type{}, W, xs, yq);
+    for (int p = 0; p < 2; p++) {
+        if (p > 0 && nlive <= 2) continue;                   // wave-uniform
+        const int xs0 = p ? xsw[2] : xsw[0], yq0 = p ? yqw[2] : yqw[0], xs1 = p ? xsw[3] : xsw[1], yq1 = p ? yqw[3] : yqw[1];
+        const uint32_t tw0 = p ? tww[2] : tww[0], tw1 = p ? tww[3] : tww[1];
+        if ((p ? genw[2] || genw[3] : genw[0] || genw[1]) || tw0 != tw1) blur_pair(std::true_type{}, p, xs0, yq0, xs1, yq1, tw0);
+        else blur_pair(std::false_type{}, p, xs0, yq0, xs1, yq1, tw0);
+    }
+    {
+        const bool gen = genw[0] || genw[1] || genw[2] || genw[3] || tww[0] != tww[1] || tww[0] != tww[2] || tww[0] != tww[3];
+        const int wsc = (n16 < 8 ? 2 : 0) + (g4 >= 2 ? 1 : 0);
+        const int xs_k = wsc == 0 ? xsw[0] : wsc == 1 ? xsw[1] : wsc == 2 ? xsw[2] : xsw[3];
+        const int yq_k = wsc == 0 ? yqw[0] : wsc == 1 ? yqw[1] : wsc == 2 ? yqw[2] : yqw[3];
+        const v4i HC = {hc[1], hc[1], hc[1], hc[0]}, LC = {lc[1], lc[1], lc[1], lc[0]};      // (registers 0, 1: zero taps)
+        if (gen) epilogue(std::true_type{}, HC, LC, Tcol[2], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7), tww[0]);
+        else epilogue(std::false_type{}, HC, LC, Tcol[2], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7), tww[0]);
     }
     wave_lds_fence();
 
@@ -468,10 +538,11 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
         b.out_kps[(long long)frame * b.cap + out_idx] = o;
     }
 }
+// four waves per SIMD (four workgroups per CU: what the LDS allows) need <= 128 VGPRs; without the bound the paired blur's scheduler takes 130
 template <bool FMA>
-__global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od(Batch b) { k_describe_od_body<FMA, false>(b); }
+__global__ __launch_bounds__(OD_WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_describe_od(Batch b) { k_describe_od_body<FMA, false>(b); }
 template <bool FMA>
-__global__ __launch_bounds__(OD_WAVES * 64) void k_describe_od_gather(Batch b) { k_describe_od_body<FMA, true>(b); }
+__global__ __launch_bounds__(OD_WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_describe_od_gather(Batch b) { k_describe_od_body<FMA, true>(b); }
 
 // every level must offer 48 readable bytes per row and be at least 64 px wide (the border fix-up's case analysis), rows single-reflect
 bool describe_od_supported(const Batch& b, const HostGeom& hg) {
