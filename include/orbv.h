@@ -19,7 +19,8 @@
  *                                  (called at src/Frame.cc:285 and src/KeyFrame.cc:63 with levelsup = 4)
  *   orbv_score              <- TemplatedVocabulary::score(const BowVector&, const BowVector&)  TemplatedVocabulary.h:1198-1203,
  *                                  DBoW2/ScoringObject.cpp (called at src/KeyFrameDatabase.cc:132,:248, src/LoopClosing.cc:127);
- *                                  a host function (a merge walk over two short sorted lists)
+ *                                  a host function (a merge walk over two short sorted lists; orb_slam_amd/csrc/orbv_score.h, the
+ *                                  code the key-frame database's scoring kernel runs, include/orbd.h)
  *
  * Output forms.  A BowVector (std::map<WordId, WordValue>) is returned as two parallel arrays in ascending word
  * order; a FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: node ids ascending, fv_off[j]..fv_off[j+1]

@@ -50,6 +50,9 @@ EXPORTS_V = [
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_info", "orbv_descend", "orbv_descend_device",
     "orbv_transform", "orbv_transform_batch_device", "orbv_score",
 ]
+# include/orbd.h (key-frame database)
+EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_batch_device", "orbd_erase", "orbd_clear",
+             "orbd_query_batch_device", "orbd_query"]
 
 
 class OrbxError(RuntimeError):
@@ -191,6 +194,16 @@ def lib():
         L.orbv_transform_batch_device.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbv_score.argtypes = [vp, vp, vp, ci, vp, vp, ci]
         L.orbv_score.restype = ctypes.c_double
+        L.orbd_create.argtypes = [vp, ci, ci, ctypes.POINTER(vp)]
+        L.orbd_destroy.argtypes = [vp]
+        L.orbd_destroy.restype = None
+        L.orbd_size.argtypes = [vp]
+        L.orbd_add.argtypes = [vp, ci, vp, vp, ci]
+        L.orbd_add_batch_device.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp]
+        L.orbd_erase.argtypes = [vp, ci]
+        L.orbd_clear.argtypes = [vp]
+        L.orbd_query_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+        L.orbd_query.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
         _LIB = L
     return _LIB
 
@@ -729,3 +742,79 @@ def bow_ranges_batch_device(d_fvq_node, d_fvq_off, d_nfv_q, d_fvt_node, d_fvt_of
     rc = lib().orbs_bow_ranges_batch_device(d_fvq_node, d_fvq_off, d_nfv_q, d_fvt_node, d_fvt_off, d_nfv_t, cap, nproblems, d_qrange, d_nq, stream or None)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbs_bow_ranges_batch_device")
+
+
+class KeyFrameDatabase:
+    """The device half of ORB_SLAM::KeyFrameDatabase (reference src/KeyFrameDatabase.cc) over include/orbd.h: key frames are
+    caller-chosen slots; query() returns what DetectLoopCandidates / DetectRelocalisationCandidates compute from the inverted
+    file (the key frames sharing words in lKFsSharingWords order, their counts, the 0.8 threshold and the scores above it).
+    The KeyFrame-walking rest is host C++ (orb_slam_amd/cpp/KeyFrameDatabase.cc) or, for tests, tests/kfdb_ref.py."""
+
+    def __init__(self, voc, capacity, device=0):
+        self.h = ctypes.c_void_p()
+        self.device = device
+        rc = lib().orbd_create(voc.h, capacity, device, ctypes.byref(self.h))
+        if rc != ORBX_OK:
+            self.h = None
+            raise OrbxError(rc, "orbd_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orbd_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except TypeError:           # interpreter shutdown
+            pass
+
+    def __len__(self):
+        return lib().orbd_size(self.h)
+
+    def add(self, slot, ids, vals):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        assert len(ids) == len(vals)
+        rc = lib().orbd_add(self.h, slot, ids.ctypes.data, vals.ctypes.data, len(ids))
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbd_add")
+
+    def add_batch_device(self, slots, d_bow_id, d_bow_val, d_n_bow, cap, d_status=None, stream=0):
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        rc = lib().orbd_add_batch_device(self.h, slots.ctypes.data, len(slots), d_bow_id, d_bow_val, d_n_bow, cap, d_status, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbd_add_batch_device")
+
+    def erase(self, slot):
+        rc = lib().orbd_erase(self.h, slot)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbd_erase")
+
+    def clear(self):
+        rc = lib().orbd_clear(self.h)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbd_clear")
+
+    def query(self, ids, vals, excl=(), out_cap=None):
+        """-> dict(slot, words, score, min_common, excl_words); raises OrbxError(ORBX_ERR_CAPACITY) when out_cap is too small"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        excl = np.ascontiguousarray(excl, dtype=np.int32)
+        cap = lib().orbd_size(self.h) if out_cap is None else out_cap
+        slot = np.zeros(max(cap, 1), np.int32); words = np.zeros(max(cap, 1), np.int32); score = np.zeros(max(cap, 1), np.float64)
+        xw = np.zeros(max(len(excl), 1), np.int32)
+        ns, mc = ctypes.c_int(), ctypes.c_int()
+        rc = lib().orbd_query(self.h, ids.ctypes.data, vals.ctypes.data, len(ids), excl.ctypes.data, len(excl), xw.ctypes.data,
+                              slot.ctypes.data, words.ctypes.data, score.ctypes.data, cap, ctypes.byref(ns), ctypes.byref(mc), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbd_query (n_share=%d)" % ns.value)
+        n = ns.value
+        return dict(slot=slot[:n], words=words[:n], score=score[:n], min_common=mc.value, excl_words=xw[:len(excl)])
+
+    def query_batch_device(self, nq, d_bow_id, d_bow_val, d_n_bow, qcap, d_excl_off, d_excl_slot, d_excl_words, d_share_slot, d_share_words,
+                           d_share_score, out_cap, d_n_share, d_min_common, d_status, stream=0):
+        rc = lib().orbd_query_batch_device(self.h, nq, d_bow_id, d_bow_val, d_n_bow, qcap, d_excl_off, d_excl_slot, d_excl_words, d_share_slot,
+                                           d_share_words, d_share_score, out_cap, d_n_share, d_min_common, d_status, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbd_query_batch_device")

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "orbv.h"
+#include "orbv_score.h"
 #include "orbx.h"
 #include "orbx_host.h"
 
@@ -468,37 +469,10 @@ int orbv_transform(const orbv_vocabulary* v, const uint8_t* desc, int n, int lev
     return ORBX_OK;
 }
 
-// DBoW2/ScoringObject.cpp: the six merge walks (the reference's lower_bound jumps only skip keys that cannot match)
+// DBoW2/ScoringObject.cpp: the six merge walks (orbv_score.h, shared with the key-frame database's scoring kernel)
 double orbv_score(const orbv_vocabulary* v, const uint32_t* id1, const double* val1, int n1, const uint32_t* id2, const double* val2, int n2) {
     if (!v) return 0.0;
-    const int sc = v->scoring;
-    const double log_eps = log(DBL_EPSILON);
-    double s = 0;
-    int i = 0, j = 0;
-    while (i < n1 && j < n2) {
-        if (id1[i] == id2[j]) {
-            const double a = val1[i], b = val2[j];
-            if (sc == ORBV_L1_NORM) s += fabs(a - b) - fabs(a) - fabs(b);
-            else if (sc == ORBV_L2_NORM || sc == ORBV_DOT_PRODUCT) s += a * b;
-            else if (sc == ORBV_CHI_SQUARE) { if (a + b != 0.0) s += a * b / (a + b); }
-            else if (sc == ORBV_KL) { if (a != 0 && b != 0) s += a * log(a / b); }
-            else s += sqrt(a * b);
-            i++; j++;
-        } else if (id1[i] < id2[j]) {
-            if (sc == ORBV_KL) s += val1[i] * (log(val1[i]) - log_eps);
-            i++;
-        } else {
-            j++;
-        }
-    }
-    if (sc == ORBV_L1_NORM) return -s / 2.0;
-    if (sc == ORBV_L2_NORM) return s >= 1 ? 1.0 : 1.0 - sqrt(1.0 - s);
-    if (sc == ORBV_CHI_SQUARE) return 2. * s;
-    if (sc == ORBV_KL) {
-        for (; i < n1; i++) if (val1[i] != 0) s += val1[i] * (log(val1[i]) - log_eps);
-        return s;
-    }
-    return s;
+    return orbv::score_walk(v->scoring, id1, val1, n1, id2, val2, n2);
 }
 
 }  // extern "C"
