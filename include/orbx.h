@@ -12,6 +12,8 @@
  *   orbx_get_levels                 <- ORBextractor::GetLevels()                           include/ORBextractor.h:47-48
  *   orbx_get_scale_factor           <- ORBextractor::GetScaleFactor()                      include/ORBextractor.h:50-51
  *   orbx_extract_batch_device       <- the same operator(), throughput form (device-resident frames, many per call)
+ *   orbx_to_gray_device, orbx_extract_color, orbx_extract_batch_device_color, orbx_extract_batch_color
+ *                                   <- Tracking::GrabImage's cvtColor(CV_RGB2GRAY / CV_BGR2GRAY) in front of Frame::Frame   src/Tracking.cc:185-195
  *   orbm_hamming256                 <- ORBmatcher::DescriptorDistance(const Mat&,const Mat&) include/ORBmatcher.h:44, src/ORBmatcher.cc:1794-1810
  *   orbm_match_top2[_masked][_device|_batch_device]
  *                                   <- the best / second-best scan shared by every ORBmatcher search
@@ -172,6 +174,55 @@ int orbx_extract_batch_device_phases(orbx_extractor* h, const uint8_t* d_imgs, i
 int orbx_extract_batch(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt,
                        int where, orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap,
                        int32_t* d_status, void* stream);
+
+/* ---- colour frames (src/Tracking.cc:185-195) ---------------------------------------------------
+ * Tracking::GrabImage converts every 3-channel camera frame with cvtColor(CV_RGB2GRAY) or cvtColor(CV_BGR2GRAY), picked by Camera.RGB
+ * (Data/Settings.yaml: 1 = RGB, 0 = BGR), and builds the Frame on that gray image (Frame::im).  These calls do the conversion on the GPU.
+ * The gray level is OpenCV 2.4's RGB2Gray<uchar> (imgproc/src/color.cpp), in integers:
+ *     gray = (R*4899 + G*9617 + B*1868 + 8192) >> 14
+ * (pure red 76, green 150, blue 29, white 255).  For 4-channel pixels (CV_RGBA2GRAY / CV_BGRA2GRAY) the fourth byte is ignored.  OpenCV
+ * builds that route cvtColor through IPP are not covered.  Every key point, descriptor and status of a colour call
+ * equals that of the matching gray call on the converted frame; fmt == ORBX_PIX_GRAY8 gives exactly the gray call's outputs.
+ * Pixel rows are read exactly: w * channels bytes of each colour row, nothing past them.
+ * Host-checkable arguments: an unknown fmt, a row stride < w * channels, a gray row stride < w give ORBX_ERR_ARG; an empty geometry
+ * gives ORBX_EMPTY; no usable GPU gives ORBX_ERR_DEVICE (there is no CPU fallback). */
+#define ORBX_PIX_GRAY8  0   /* 1 byte per pixel */
+#define ORBX_PIX_RGB8   1   /* bytes R, G, B   (Camera.RGB: 1) */
+#define ORBX_PIX_BGR8   2   /* bytes B, G, R   (Camera.RGB: 0; OpenCV's own order) */
+#define ORBX_PIX_RGBA8  3   /* bytes R, G, B, A (A ignored) */
+#define ORBX_PIX_BGRA8  4   /* bytes B, G, R, A (A ignored) */
+
+/* The conversion alone: nframes DEVICE frames, frame f at d_src + f*src_frame_stride, rows src_row_stride bytes apart, into the DEVICE gray
+ * planes d_gray + f*gray_frame_stride, rows gray_row_stride bytes apart (exactly w bytes of each gray row are written).  Asynchronous on
+ * `stream`.  Frame strides must be >= 0, and the gray frames of one call must not overlap (ORBX_ERR_ARG).  Fastest when every base and
+ * stride is a multiple of 16. */
+int orbx_to_gray_device(const uint8_t* d_src, int nframes, int w, int hgt, ptrdiff_t src_row_stride, ptrdiff_t src_frame_stride, int fmt,
+                        uint8_t* d_gray, ptrdiff_t gray_row_stride, ptrdiff_t gray_frame_stride, void* stream);
+
+/* orbx_extract on a colour host frame: GrabImage + Frame::Frame as one call.  The frame is staged in pinned, device-mapped memory and
+ * converted by the kernel that fetches it; gray_out (optional host buffer of w*hgt bytes, NULL = not wanted) receives the gray image
+ * (Frame::im).  Synchronous. */
+int orbx_extract_color(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_t stride, int fmt,
+                       orbx_keypoint* kps, uint8_t* desc, int cap, int* n_out, uint8_t* gray_out);
+
+/* orbx_extract_batch_device on colour frames.  d_gray == NULL: each launch group is converted into a gray ring of the handle (one launch
+ * group, 16-byte aligned, pitch w rounded up to 16; allocated on the first such call) and extracted from there.  d_gray != NULL: DEVICE gray
+ * planes for all nframes frames (frame f at d_gray + f*gray_frame_stride, rows gray_row_stride bytes apart, not overlapping), written by the
+ * conversion and then read by the extraction in place, so they follow the pitched-row rule of orbx_extract_batch_device.  Frame f0 + f of
+ * a launch group uses fallback-hint slot f, as there.  There is no phased variant of this call. */
+int orbx_extract_batch_device_color(orbx_extractor* h, const uint8_t* d_imgs, int nframes, int w, int hgt,
+                                    ptrdiff_t row_stride, ptrdiff_t frame_stride, int fmt,
+                                    orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status,
+                                    uint8_t* d_gray, ptrdiff_t gray_row_stride, ptrdiff_t gray_frame_stride, void* stream);
+
+/* orbx_extract_batch on colour frames: the same pointer array, `where`, outputs and ordering rules (row_strides[f] >= w * channels and
+ * < 2^24).  ORBX_FRAMES_ON_DEVICE frames are read in place by the conversion kernel; ORBX_FRAMES_ON_HOST frames (pinned or pageable) are
+ * uploaded per launch group into one of two colour buffers of the handle on the internal copy stream (allocated on the first such call)
+ * while the previous group computes.  Each launch group is converted into the handle's gray ring and extracted from there.  There is no
+ * phased variant of this call. */
+int orbx_extract_batch_color(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt,
+                             int where, int fmt, orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap,
+                             int32_t* d_status, void* stream);
 
 /* ---- matcher ---------------------------------------------------------------------------------- */
 /* Hamming distance of two 256-bit descriptors (pure, re-entrant, host). */

@@ -25,6 +25,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 EXPORTS = [
     "orbx_default_params", "orbx_create", "orbx_destroy", "orbx_get_levels", "orbx_get_scale_factor",
     "orbx_max_keypoints", "orbx_last_error", "orbx_build_id", "orbx_extract", "orbx_extract_batch_device", "orbx_extract_batch_device_phases", "orbx_extract_batch",
+    "orbx_to_gray_device", "orbx_extract_color", "orbx_extract_batch_device_color", "orbx_extract_batch_color",
     "orbm_hamming256", "orbm_match_top2", "orbm_match_top2_device", "orbm_match_top2_batch_device", "orbm_match_top2_masked", "orbm_match_top2_masked_device",
     "orbm_count_accepted", "orbm_match_top2_segments", "orbm_match_top2_segments_device", "orbm_distinctive", "orbm_distinctive_device",
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_download",
@@ -135,6 +136,10 @@ def lib():
         L.orbx_extract_batch_device.argtypes = [vp, vp, ci, ci, ci, pd, pd, vp, vp, vp, ci, vp, vp]
         L.orbx_extract_batch_device_phases.argtypes = [vp, vp, ci, ci, ci, pd, pd, vp, vp, vp, ci, vp, vp, ci]
         L.orbx_extract_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp]
+        L.orbx_to_gray_device.argtypes = [vp, ci, ci, ci, pd, pd, ci, vp, pd, pd, vp]
+        L.orbx_extract_color.argtypes = [vp, vp, ci, ci, pd, ci, vp, vp, ci, ctypes.POINTER(ci), vp]
+        L.orbx_extract_batch_device_color.argtypes = [vp, vp, ci, ci, ci, pd, pd, ci, vp, vp, vp, ci, vp, vp, pd, pd, vp]
+        L.orbx_extract_batch_color.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp]
         L.orbm_hamming256.argtypes = [vp, vp]
         L.orbm_match_top2.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci]
         L.orbm_match_top2_device.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp]
@@ -251,6 +256,85 @@ def frame_table(frames):
             shape[1], shape[0], keep)
 
 
+# pixel formats of the colour entry points (include/orbx.h ORBX_PIX_*): Tracking::GrabImage's cvtColor in front of the extractor
+PIX_GRAY8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = 0, 1, 2, 3, 4
+PIX_CHANNELS = {PIX_GRAY8: 1, PIX_RGB8: 3, PIX_BGR8: 3, PIX_RGBA8: 4, PIX_BGRA8: 4}
+
+
+def pix_channels(fmt):
+    """bytes per pixel of an ORBX_PIX_* format; ValueError for an unknown one"""
+    if fmt not in PIX_CHANNELS:
+        raise ValueError("unknown pixel format %r" % (fmt,))
+    return PIX_CHANNELS[fmt]
+
+
+def color_layout(frame, fmt):
+    """(pointer, w, h, row stride in bytes, on device, keep) of one (H, W, C) uint8 frame of format fmt (C = its channels; a GRAY8 frame may
+    also be (H, W)).  Any row stride is accepted; the pixels of a row must be packed (pixel stride C, channel stride 1).  Host frames that
+    are not are copied (`keep` holds what must stay alive during the call); device frames raise.  Needs no GPU."""
+    ch = pix_channels(fmt)
+    if hasattr(frame, "data_ptr"):                 # torch tensor (device or host)
+        import torch
+        if frame.dtype != torch.uint8:
+            raise ValueError("frames must be uint8")
+        f = frame.unsqueeze(-1) if frame.dim() == 2 and ch == 1 else frame
+        if f.dim() != 3 or f.shape[2] != ch:
+            raise ValueError("format %d wants (H, W, %d) frames, got %s" % (fmt, ch, tuple(frame.shape)))
+        if f.stride(2) != 1 or f.stride(1) != ch or f.stride(0) < f.shape[1] * ch:
+            if f.is_cuda:
+                raise ValueError("device frame pixels must be packed (stride(1) == channels, stride(2) == 1)")
+            f = f.contiguous()
+        return f.data_ptr(), int(f.shape[1]), int(f.shape[0]), int(f.stride(0)), bool(f.is_cuda), f
+    a = np.asarray(frame)
+    if a.dtype != np.uint8:
+        raise ValueError("frames must be uint8")
+    if a.ndim == 2 and ch == 1:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] != ch:
+        raise ValueError("format %d wants (H, W, %d) frames, got %s" % (fmt, ch, a.shape))
+    if a.strides[2] != 1 or a.strides[1] != ch or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+    return a.ctypes.data, int(a.shape[1]), int(a.shape[0]), int(a.strides[0]), False, a
+
+
+def color_frame_table(frames, fmt):
+    """frame_table for colour frames: (where, pointers, row strides, w, h, keep) of a list of (H, W, C) uint8 frames of one size and format
+    (see color_layout).  CUDA tensors give the device form, numpy arrays and CPU tensors the host form.  Needs no GPU."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("no frames")
+    lay = [color_layout(f, fmt) for f in frames]
+    if len({l[4] for l in lay}) != 1:
+        raise ValueError("frames mix device and host memory")
+    if len({(l[1], l[2]) for l in lay}) != 1:
+        raise ValueError("frames differ in size")
+    return (FRAMES_ON_DEVICE if lay[0][4] else FRAMES_ON_HOST, np.array([l[0] for l in lay], dtype=np.uint64),
+            np.array([l[3] for l in lay], dtype=np.int64), lay[0][1], lay[0][2], [l[5] for l in lay])
+
+
+def to_gray_device(d_src, nframes, w, h, src_row_stride, src_frame_stride, fmt, d_gray, gray_row_stride, gray_frame_stride, stream=0):
+    """orbx_to_gray_device on integer device addresses.  Asynchronous on `stream`."""
+    pix_channels(fmt)
+    rc = lib().orbx_to_gray_device(d_src, nframes, w, h, src_row_stride, src_frame_stride, fmt, d_gray, gray_row_stride, gray_frame_stride,
+                                   stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_to_gray_device")
+
+
+def to_gray(frames, fmt, stream=0):
+    """(F, H, W, C) or (H, W, C) CUDA uint8 tensor (rows and frames at any stride, packed pixels) -> new (F, H, W) / (H, W) gray tensor"""
+    import torch
+    one = frames.dim() == 3
+    x = frames.unsqueeze(0) if one else frames
+    ch = pix_channels(fmt)
+    if not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != ch or x.stride(3) != 1 or x.stride(2) != ch:
+        raise ValueError("to_gray wants a CUDA uint8 (F, H, W, %d) tensor with packed pixels" % ch)
+    F, h, w = x.shape[:3]
+    out = torch.empty((F, h, w), dtype=torch.uint8, device=x.device)
+    to_gray_device(x.data_ptr(), F, w, h, x.stride(1), x.stride(0), fmt, out.data_ptr(), w, w * h, stream)
+    return out[0] if one else out
+
+
 class ORBextractor:
     """Same constructor arguments as the reference ORBextractor(nfeatures, scaleFactor, nlevels, scoreType, fastTh)
     (include/ORBextractor.h:38) plus device placement; __call__(image) is operator()."""
@@ -322,6 +406,46 @@ class ORBextractor:
         where, ptrs, strides, w, h, keep = frame_table(frames)
         rc = self.L.orbx_extract_batch(self.h, ptrs.ctypes.data, strides.ctypes.data, len(ptrs), w, h, where, d_kps, d_desc, d_n, cap,
                                        d_status or None, stream or None)
+        del keep
+        if rc != ORBX_OK:
+            raise self._err(rc)
+
+    def extract_color(self, image, fmt, want_gray=False):
+        """orbx_extract_color: image (H, W, C) uint8 of format fmt (PIX_*), any row stride.  Returns (keypoints, descriptors), plus the
+        gray image (Frame::im) when want_gray."""
+        ptr, w, hh, rs, on_dev, keep = color_layout(image, fmt)
+        if on_dev:
+            raise ValueError("extract_color takes a host frame")
+        if w == 0 or hh == 0:
+            return None   # reference: silent return, outputs untouched
+        cap = self.max_keypoints
+        kps = np.zeros(cap, dtype=KP_DTYPE)
+        desc = np.zeros((cap, 32), dtype=np.uint8)
+        gray = np.empty((hh, w), dtype=np.uint8) if want_gray else None
+        n = ctypes.c_int(0)
+        rc = self.L.orbx_extract_color(self.h, ptr, w, hh, rs, fmt, kps.ctypes.data, desc.ctypes.data, cap, ctypes.byref(n),
+                                       gray.ctypes.data if want_gray else None)
+        del keep
+        if rc != ORBX_OK:
+            raise self._err(rc)
+        res = (kps[:n.value].copy(), desc[:n.value].copy())
+        return res + (gray,) if want_gray else res
+
+    def extract_batch_device_color(self, d_imgs, nframes, w, h, row_stride, frame_stride, fmt, d_kps, d_desc, d_n, cap, d_status=0, d_gray=0,
+                                   gray_row_stride=0, gray_frame_stride=0, stream=0):
+        """orbx_extract_batch_device_color on integer device addresses (d_gray = 0: the handle's gray ring).  Asynchronous."""
+        pix_channels(fmt)
+        rc = self.L.orbx_extract_batch_device_color(self.h, d_imgs, nframes, w, h, row_stride, frame_stride, fmt, d_kps, d_desc, d_n, cap,
+                                                    d_status or None, d_gray or None, gray_row_stride, gray_frame_stride, stream or None)
+        if rc != ORBX_OK:
+            raise self._err(rc)
+
+    def extract_batch_color(self, frames, fmt, d_kps, d_desc, d_n, cap, d_status=0, stream=0):
+        """orbx_extract_batch_color: frames is a list of (H, W, C) uint8 frames of one size (see color_frame_table: CUDA tensors = device
+        form, numpy arrays or CPU tensors = host form); outputs as in extract_batch."""
+        where, ptrs, strides, w, h, keep = color_frame_table(frames, fmt)
+        rc = self.L.orbx_extract_batch_color(self.h, ptrs.ctypes.data, strides.ctypes.data, len(ptrs), w, h, where, fmt, d_kps, d_desc, d_n,
+                                             cap, d_status or None, stream or None)
         del keep
         if rc != ORBX_OK:
             raise self._err(rc)

@@ -63,10 +63,62 @@ public:
         _keypoints.assign(kps_.begin(), kps_.begin() + n);            // reference :746-747,:777
     }
 
+    // Tracking::GrabImage + the extraction of Frame::Frame in one call (reference src/Tracking.cc:185-195, src/Frame.cc:57-60): a colour
+    // image (CV_8UC3 / CV_8UC4; rgb = Camera.RGB, true for R, G, B byte order, false for B, G, R) is converted to gray on the GPU
+    // (cvtColor CV_RGB2GRAY / CV_BGR2GRAY; a fourth channel is ignored), a gray one (CV_8UC1) is copied, as GrabImage does.  imGray
+    // receives the gray image (what Frame keeps as Frame::im); keypoints / descriptors are what operator() gives for imGray
+    // (orbx_extract_color).
+    void GrabImage(const cv::Mat& im, bool rgb, cv::Mat& imGray, std::vector<cv::KeyPoint>& keypoints, cv::Mat& descriptors) {
+        if (im.empty()) return;                                      // reference :721-722: outputs untouched
+        const int fmt = pixFormat(channelsOf(im), rgb);
+        cv::Mat gray(im.rows, im.cols, CV_8UC1);
+        kps_.resize(cap_);
+        desc_.resize((size_t)cap_ * 32);
+        int n = 0;
+        const int rc = orbx_extract_color(h_, im.data, im.cols, im.rows, (ptrdiff_t)im.step, fmt, reinterpret_cast<orbx_keypoint*>(kps_.data()),
+                                          desc_.data(), cap_, &n, gray.data);
+        if (rc == ORBX_EMPTY) return;
+        if (rc != ORBX_OK) throw std::runtime_error(std::string("orbx_extract_color: ") + orbx_last_error(h_));
+        imGray = gray;
+        if (n == 0) descriptors.release();                           // reference :738-739
+        else {
+            descriptors.create(n, 32, CV_8U);
+            for (int i = 0; i < n; i++) std::memcpy(descriptors.ptr(i), desc_.data() + (size_t)i * 32, 32);
+        }
+        keypoints.assign(kps_.begin(), kps_.begin() + n);
+    }
+
     // Several host images of one size, any step each, in one call (orbx_extract_batch, host form: launch groups of maxBatch frames, the
     // upload of one overlapping the kernels of the previous one).  keypoints[i] / descriptors[i] are exactly what operator() gives for
     // images[i], descriptors[i] released when it has no features.
     void ExtractBatch(const std::vector<cv::Mat>& images, std::vector<std::vector<cv::KeyPoint> >& keypoints, std::vector<cv::Mat>& descriptors) {
+        extractBatch(images, ORBX_PIX_GRAY8, keypoints, descriptors);
+    }
+    // The same for colour images (all CV_8UC3 or all CV_8UC4; rgb as in GrabImage), converted to gray on the GPU per launch group
+    // (orbx_extract_batch_color): keypoints[i] / descriptors[i] are what GrabImage gives for images[i].
+    void ExtractBatch(const std::vector<cv::Mat>& images, bool rgb, std::vector<std::vector<cv::KeyPoint> >& keypoints, std::vector<cv::Mat>& descriptors) {
+        const int fmt = images.empty() ? ORBX_PIX_GRAY8 : pixFormat(channelsOf(images[0]), rgb);
+        for (const cv::Mat& m : images)
+            if (pixFormat(channelsOf(m), rgb) != fmt) throw std::invalid_argument("ExtractBatch: images differ in channels");
+        extractBatch(images, fmt, keypoints, descriptors);
+    }
+
+    int inline GetLevels() { return nlevels_; }
+    float inline GetScaleFactor() { return (float)scaleFactor_; }
+
+private:
+    // CV_MAT_CN of the matrix type (read from type(): the stand-in matrices some builds of this header see have no channels())
+    static int channelsOf(const cv::Mat& m) { return ((m.type() >> 3) & 511) + 1; }
+    static int pixFormat(int channels, bool rgb) {
+        switch (channels) {
+            case 1: return ORBX_PIX_GRAY8;
+            case 3: return rgb ? ORBX_PIX_RGB8 : ORBX_PIX_BGR8;
+            case 4: return rgb ? ORBX_PIX_RGBA8 : ORBX_PIX_BGRA8;
+            default: throw std::invalid_argument("ORBextractor: images must have 1, 3 or 4 channels");
+        }
+    }
+
+    void extractBatch(const std::vector<cv::Mat>& images, int fmt, std::vector<std::vector<cv::KeyPoint> >& keypoints, std::vector<cv::Mat>& descriptors) {
         const int F = (int)images.size();
         keypoints.assign(F, std::vector<cv::KeyPoint>());
         descriptors.resize(F);
@@ -88,10 +140,13 @@ public:
             batchCap_ = F;
         }
         int32_t* dn = static_cast<int32_t*>(dN_);
-        const int rc = orbx_extract_batch(h_, ptrs.data(), steps.data(), F, w, hgt, ORBX_FRAMES_ON_HOST, static_cast<orbx_keypoint*>(dKps_),
-                                          static_cast<uint8_t*>(dDesc_), dn, cap_, dn + F, nullptr);
+        const int rc = fmt == ORBX_PIX_GRAY8
+            ? orbx_extract_batch(h_, ptrs.data(), steps.data(), F, w, hgt, ORBX_FRAMES_ON_HOST, static_cast<orbx_keypoint*>(dKps_),
+                                 static_cast<uint8_t*>(dDesc_), dn, cap_, dn + F, nullptr)
+            : orbx_extract_batch_color(h_, ptrs.data(), steps.data(), F, w, hgt, ORBX_FRAMES_ON_HOST, fmt, static_cast<orbx_keypoint*>(dKps_),
+                                       static_cast<uint8_t*>(dDesc_), dn, cap_, dn + F, nullptr);
         if (rc == ORBX_EMPTY) return;
-        if (rc != ORBX_OK) throw std::runtime_error(std::string("orbx_extract_batch: ") + orbx_last_error(h_));
+        if (rc != ORBX_OK) throw std::runtime_error(std::string(fmt == ORBX_PIX_GRAY8 ? "orbx_extract_batch: " : "orbx_extract_batch_color: ") + orbx_last_error(h_));
         std::vector<int32_t> ns((size_t)2 * F);
         kps_.resize((size_t)F * cap_);
         desc_.resize((size_t)F * cap_ * 32);
@@ -111,10 +166,6 @@ public:
         }
     }
 
-    int inline GetLevels() { return nlevels_; }
-    float inline GetScaleFactor() { return (float)scaleFactor_; }
-
-private:
     void freeBatch() {
         orbx_device_free(device_, dKps_);
         orbx_device_free(device_, dDesc_);

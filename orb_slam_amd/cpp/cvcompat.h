@@ -14,6 +14,8 @@
 
 #define CV_8U 0
 #define CV_8UC1 0
+#define CV_8UC3 16      // CV_MAKETYPE(CV_8U, 3): colour camera frames (Tracking::GrabImage's input)
+#define CV_8UC4 24
 
 namespace cv {
 
@@ -42,30 +44,38 @@ struct KeyPoint {
 };
 static_assert(sizeof(KeyPoint) == 28, "cv::KeyPoint must be 28 bytes");
 
-// 8-bit single-channel 2-D matrix: enough of cv::Mat for image in / descriptor out
+// 8-bit 2-D matrix of 1, 3 or 4 interleaved channels (CV_8UC1 / CV_8UC3 / CV_8UC4): enough of cv::Mat for image in / descriptor out.
+// Any other type argument is taken as CV_8UC1, as before the colour types existed.
 class Mat {
 public:
     int rows, cols;
     size_t step;
     uchar* data;
     Mat() : rows(0), cols(0), step(0), data(nullptr) {}
-    Mat(int r, int c, int /*type*/) { create(r, c, CV_8UC1); }
-    Mat(int r, int c, int /*type*/, void* ext, size_t step_ = 0) : rows(r), cols(c), step(step_ ? step_ : (size_t)c), data((uchar*)ext) {}
-    void create(int r, int c, int /*type*/) {
-        if (r == rows && c == cols && owner_ && step == (size_t)c) return;
-        owner_ = std::make_shared<std::vector<uchar>>((size_t)r * c);
-        rows = r; cols = c; step = (size_t)c; data = owner_->data();
+    Mat(int r, int c, int type) { create(r, c, type); }
+    Mat(int r, int c, int type, void* ext, size_t step_ = 0)
+        : rows(r), cols(c), step(step_ ? step_ : (size_t)c * elem_size(type)), data((uchar*)ext), type_(norm_type(type)) {}
+    void create(int r, int c, int type) {
+        type = norm_type(type);
+        if (r == rows && c == cols && type == type_ && owner_ && step == (size_t)c * elem_size(type)) return;
+        owner_ = std::make_shared<std::vector<uchar>>((size_t)r * c * elem_size(type));
+        rows = r; cols = c; type_ = type; step = (size_t)c * elem_size(type); data = owner_->data();
     }
     void release() { owner_.reset(); rows = cols = 0; step = 0; data = nullptr; }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
-    int type() const { return CV_8UC1; }
+    int type() const { return type_; }
+    int channels() const { return (type_ >> 3) + 1; }
+    size_t elemSize() const { return (size_t)channels(); }
     template <typename T> T* ptr(int r = 0) { return (T*)(data + (size_t)r * step); }
     template <typename T> const T* ptr(int r = 0) const { return (const T*)(data + (size_t)r * step); }
     uchar* ptr(int r = 0) { return data + (size_t)r * step; }
     const uchar* ptr(int r = 0) const { return data + (size_t)r * step; }
-    Mat row(int r) const { Mat m(1, cols, CV_8UC1, data + (size_t)r * step, step); m.owner_ = owner_; return m; }
-    bool isContinuous() const { return step == (size_t)cols; }
+    Mat row(int r) const { Mat m(1, cols, type_, data + (size_t)r * step, step); m.owner_ = owner_; return m; }
+    bool isContinuous() const { return step == (size_t)cols * elemSize(); }
 private:
+    static int norm_type(int type) { return type == CV_8UC3 || type == CV_8UC4 ? type : CV_8UC1; }
+    static size_t elem_size(int type) { return (size_t)(norm_type(type) >> 3) + 1; }
+    int type_ = CV_8UC1;
     std::shared_ptr<std::vector<uchar>> owner_;
 };
 

@@ -64,13 +64,23 @@ struct orbx_extractor {
     Event tab_ev[TAB_RING];
     int tab_next = 0;
     std::vector<ImgSrc> last_tab;     // the last gather group's table (orbx_debug_fetch of level 0)
-    // host form: two device frame buffers of one launch group each (pitch w rounded up to 16), two pinned staging buffers for pageable
-    // frames, and the copy stream.  up_ev[i]: the upload into buffer i is done; kern_ev[i]: the kernels that read buffer i are done.
+    // host form: two device frame buffers of one launch group each (pitch: the row's bytes rounded up to 16), two pinned staging buffers
+    // for pageable frames, and the copy stream.  up_ev[i]: the upload into buffer i is done; kern_ev[i]: the kernels that read buffer i are done.
     Stream up;
-    DevBuf d_hbuf[2];
-    PinnedBuf h_stage[2];
-    Event up_ev[2], kern_ev[2];
-    int hnext = 0;
+    struct __attribute__((visibility("hidden"))) HostUpload {
+        DevBuf d[2];
+        PinnedBuf stage[2];
+        Event up_ev[2], kern_ev[2];
+        int next = 0;
+    };
+    HostUpload hup;              // gray frames (orbx_extract_batch)
+    HostUpload cup;              // colour frames (orbx_extract_batch_color): allocated on the first colour host call
+    // colour forms: the gray level 0 of one launch group (pitch w rounded up to 16), converted from the caller's colour frames and read by
+    // the contiguous pipeline; the one-frame call's pinned, device-mapped colour staging and gray copy (d_cimg1: ORBX_ZERO_COPY=0 only).
+    // All allocated on the first colour call that needs them: gray-only callers pay for none.
+    DevBuf d_cring;
+    PinnedBuf h_cimg1, h_gray1;
+    DevBuf d_cimg1;
 };
 
 template <typename T>
@@ -162,10 +172,20 @@ static int launch_group(orbx_extractor* h, const Batch& b, hipStream_t stream, i
     return ORBX_OK;
 }
 
-// device form of orbx_extract_batch: one table per launch group, the kernels read the caller's frames through it
-static int extract_gather(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, orbx_keypoint* d_kps,
-                          uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
+static int ensure_cring(orbx_extractor* h, int w, int hgt, size_t& pitch);
+static int convert(orbx_extractor* h, const uint8_t* src, ptrdiff_t srs, ptrdiff_t sfs, const ImgSrc* tab, unsigned long long tab_bits, int n, int w,
+                   int hgt, int fmt, uint8_t* dst, ptrdiff_t drs, ptrdiff_t dfs, uint8_t* dst2, hipStream_t stream);
+
+// device form of orbx_extract_batch[_color]: one table per launch group; the kernels read the caller's frames through it (gray), or the
+// conversion kernel does and writes the handle's gray ring, which the contiguous path then reads (colour)
+static int extract_gather(orbx_extractor* h, int fmt, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt,
+                          orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
     const int mb = h->p.max_batch;
+    size_t gp = 0;
+    if (fmt != ORBX_PIX_GRAY8) {
+        const int rc = ensure_cring(h, w, hgt, gp);
+        if (rc != ORBX_OK) return rc;
+    }
     const size_t tab_bytes = (size_t)orbx_extractor::TAB_RING * mb * sizeof(ImgSrc);
     HIPCHK(h, h->d_tab.ensure(tab_bytes));
     HIPCHK(h, h->h_tab.ensure(tab_bytes, hipHostMallocDefault));
@@ -180,7 +200,7 @@ static int extract_gather(orbx_extractor* h, const uint8_t* const* imgs, const p
         unsigned long long bits = 0;
         long long min_stride = LLONG_MAX;
         for (int i = 0; i < n; i++) {
-            const long long s = row_strides ? (long long)row_strides[f0 + i] : (long long)w;
+            const long long s = row_strides ? (long long)row_strides[f0 + i] : (long long)w * pix_channels(fmt);
             ht[i].data = imgs[f0 + i];
             ht[i].row_stride = s;
             bits |= (uintptr_t)imgs[f0 + i] | (unsigned long long)s;
@@ -189,29 +209,67 @@ static int extract_gather(orbx_extractor* h, const uint8_t* const* imgs, const p
         HIPCHK(h, hipMemcpyAsync(dt, ht, (size_t)n * sizeof(ImgSrc), hipMemcpyHostToDevice, stream));
         Batch b;
         group_batch(h, b, f0, n, d_kps, d_desc, d_n, cap, d_status);
-        b.img_row_stride = min_stride;
-        b.img_tab = dt;
-        b.img_tab_bits = bits;
-        b.img_tab_min_stride = min_stride;
+        if (fmt == ORBX_PIX_GRAY8) {
+            b.img_row_stride = min_stride;
+            b.img_tab = dt;
+            b.img_tab_bits = bits;
+            b.img_tab_min_stride = min_stride;
+        } else {
+            const int rc = convert(h, nullptr, 0, 0, dt, bits, n, w, hgt, fmt, h->d_cring.as(), (ptrdiff_t)gp, (ptrdiff_t)(gp * hgt), nullptr, stream);
+            if (rc != ORBX_OK) return rc;
+            b.img = h->d_cring.as();
+            b.img_row_stride = (long long)gp;
+            b.img_frame_stride = (long long)(gp * hgt);
+        }
         const int rc = launch_group(h, b, stream);
         if (rc != ORBX_OK) return rc;
         HIPCHK(h, hipEventRecord(h->tab_ev[slot], stream));
-        h->last_tab.assign(ht, ht + n);
+        if (fmt == ORBX_PIX_GRAY8) h->last_tab.assign(ht, ht + n);
     }
     return ORBX_OK;
 }
 
-// host form of orbx_extract_batch: each launch group is uploaded into one of two device buffers on the copy stream (pinned frames straight
-// from the caller's memory, pageable ones through a pinned staging buffer filled by this thread) while the previous group computes, and then
-// runs the contiguous path on that buffer
-static int extract_host(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt, orbx_keypoint* d_kps,
-                        uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
+// the handle's gray ring for the colour forms: one launch group of w x hgt planes, pitch w rounded up to 16 (grown with the geometry:
+// nothing queued may still use the old ring)
+static int ensure_cring(orbx_extractor* h, int w, int hgt, size_t& pitch) {
+    pitch = ((size_t)w + 15) & ~(size_t)15;
+    const size_t bytes = pitch * hgt * h->p.max_batch;
+    if (h->d_cring.size() < bytes) {
+        HIPCHK(h, hipDeviceSynchronize());
+        HIPCHK(h, h->d_cring.ensure(bytes));
+    }
+    return ORBX_OK;
+}
+
+// queues the conversion of n contiguous frames into gray planes
+static int convert(orbx_extractor* h, const uint8_t* src, ptrdiff_t srs, ptrdiff_t sfs, const ImgSrc* tab, unsigned long long tab_bits, int n, int w,
+                   int hgt, int fmt, uint8_t* dst, ptrdiff_t drs, ptrdiff_t dfs, uint8_t* dst2, hipStream_t stream) {
+    ColorArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_row_stride = srs; a.src_frame_stride = sfs; a.tab = tab; a.tab_bits = tab_bits;
+    a.dst = dst; a.dst2 = dst2; a.dst_row_stride = drs; a.dst_frame_stride = dfs; a.w = w; a.h = hgt;
+    const int rc = launch_to_gray(a, n, fmt, stream);
+    if (rc != ORBX_OK) h->err = rc == ORBX_ERR_ARG ? "frame too large for the conversion kernel" : "kernel launch failed (no gfx950 code object for this device?)";
+    return rc;
+}
+
+// host form of orbx_extract_batch[_color]: each launch group is uploaded into one of two device buffers of U on the copy stream (pinned frames
+// straight from the caller's memory, pageable ones through a pinned staging buffer filled by this thread) while the previous group computes,
+// and then runs the contiguous path on that buffer (gray) or on the gray ring the conversion writes from it (colour)
+static int extract_host(orbx_extractor* h, orbx_extractor::HostUpload& U, int fmt, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes,
+                        int w, int hgt, orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, hipStream_t stream) {
     const int mb = h->p.max_batch;
-    const size_t P = ((size_t)w + 15) & ~(size_t)15, fb = P * hgt;
+    const size_t rowb = (size_t)w * pix_channels(fmt);                 // bytes of a frame row
+    const size_t P = (rowb + 15) & ~(size_t)15, fb = P * hgt;
+    size_t gp = 0;
+    if (fmt != ORBX_PIX_GRAY8) {
+        const int rc = ensure_cring(h, w, hgt, gp);
+        if (rc != ORBX_OK) return rc;
+    }
     HIPCHK(h, h->up.ensure());
     for (int i = 0; i < 2; i++) {
-        HIPCHK(h, h->up_ev[i].ensure());
-        HIPCHK(h, h->kern_ev[i].ensure());
+        HIPCHK(h, U.up_ev[i].ensure());
+        HIPCHK(h, U.kern_ev[i].ensure());
     }
     std::vector<char> pinned(nframes);
     bool any_pageable = false;
@@ -223,62 +281,73 @@ static int extract_host(orbx_extractor* h, const uint8_t* const* imgs, const ptr
     }
     // grown with the geometry (nothing queued may still use the old buffers); the pinned staging buffers only once a pageable frame comes
     const size_t bytes = fb * mb;
-    const bool stage = any_pageable || h->h_stage[0].size() > 0;
+    const bool stage = any_pageable || U.stage[0].size() > 0;
     bool grow = false;
-    for (int i = 0; i < 2; i++) grow |= h->d_hbuf[i].size() < bytes || (stage && h->h_stage[i].size() < bytes);
+    for (int i = 0; i < 2; i++) grow |= U.d[i].size() < bytes || (stage && U.stage[i].size() < bytes);
     if (grow) {
         HIPCHK(h, hipDeviceSynchronize());
         for (int i = 0; i < 2; i++) {
-            HIPCHK(h, h->d_hbuf[i].ensure(bytes));
-            if (stage) HIPCHK(h, h->h_stage[i].ensure(bytes, hipHostMallocDefault));
+            HIPCHK(h, U.d[i].ensure(bytes));
+            if (stage) HIPCHK(h, U.stage[i].ensure(bytes, hipHostMallocDefault));
         }
     }
     for (int f0 = 0; f0 < nframes; f0 += mb) {
         const int n = std::min(mb, nframes - f0);
-        const int i = h->hnext;
-        h->hnext ^= 1;
-        uint8_t* dbuf = h->d_hbuf[i].as();
-        uint8_t* stage = h->h_stage[i].as();
-        HIPCHK(h, hipStreamWaitEvent(h->up, h->kern_ev[i], 0));   // the kernels of the group that last read buffer i
+        const int i = U.next;
+        U.next ^= 1;
+        uint8_t* dbuf = U.d[i].as();
+        uint8_t* stage = U.stage[i].as();
+        HIPCHK(h, hipStreamWaitEvent(h->up, U.kern_ev[i], 0));    // the kernels of the group that last read buffer i
         bool stage_free = false;
         for (int j = 0; j < n;) {
             const uint8_t* src = imgs[f0 + j];
-            const ptrdiff_t s = row_strides ? row_strides[f0 + j] : (ptrdiff_t)w;
+            const ptrdiff_t s = row_strides ? row_strides[f0 + j] : (ptrdiff_t)rowb;
             if (pinned[f0 + j]) {
-                HIPCHK(h, hipMemcpy2DAsync(dbuf + j * fb, P, src, (size_t)s, (size_t)w, (size_t)hgt, hipMemcpyHostToDevice, h->up));
+                HIPCHK(h, hipMemcpy2DAsync(dbuf + j * fb, P, src, (size_t)s, rowb, (size_t)hgt, hipMemcpyHostToDevice, h->up));
                 j++;
                 continue;
             }
             if (!stage_free) {                                    // its last upload (two groups back) has been read out
-                HIPCHK(h, hipEventSynchronize(h->up_ev[i]));
+                HIPCHK(h, hipEventSynchronize(U.up_ev[i]));
                 stage_free = true;
             }
             int j1 = j;                                           // a run of pageable frames: one copy
             for (; j1 < n && !pinned[f0 + j1]; j1++) {
                 const uint8_t* fs = imgs[f0 + j1];
-                const ptrdiff_t fst = row_strides ? row_strides[f0 + j1] : (ptrdiff_t)w;
+                const ptrdiff_t fst = row_strides ? row_strides[f0 + j1] : (ptrdiff_t)rowb;
                 uint8_t* d = stage + j1 * fb;
-                if (fst == (ptrdiff_t)P) memcpy(d, fs, fb - (P - (size_t)w));      // (the last row: w bytes, not P)
-                else for (int y = 0; y < hgt; y++) memcpy(d + y * P, fs + (ptrdiff_t)y * fst, (size_t)w);
+                if (fst == (ptrdiff_t)P) memcpy(d, fs, fb - (P - rowb));           // (the last row: its bytes, not P)
+                else for (int y = 0; y < hgt; y++) memcpy(d + y * P, fs + (ptrdiff_t)y * fst, rowb);
             }
             HIPCHK(h, hipMemcpyAsync(dbuf + j * fb, stage + j * fb, (size_t)(j1 - j) * fb, hipMemcpyHostToDevice, h->up));
             j = j1;
         }
-        HIPCHK(h, hipEventRecord(h->up_ev[i], h->up));
-        HIPCHK(h, hipStreamWaitEvent(stream, h->up_ev[i], 0));
+        HIPCHK(h, hipEventRecord(U.up_ev[i], h->up));
+        HIPCHK(h, hipStreamWaitEvent(stream, U.up_ev[i], 0));
         Batch b;
         group_batch(h, b, f0, n, d_kps, d_desc, d_n, cap, d_status);
-        b.img = dbuf;
-        b.img_row_stride = (long long)P;
-        b.img_frame_stride = (long long)fb;
+        if (fmt == ORBX_PIX_GRAY8) {
+            b.img = dbuf;
+            b.img_row_stride = (long long)P;
+            b.img_frame_stride = (long long)fb;
+        } else {
+            int rc = convert(h, dbuf, (ptrdiff_t)P, (ptrdiff_t)fb, nullptr, 0, n, w, hgt, fmt, h->d_cring.as(), (ptrdiff_t)gp, (ptrdiff_t)(gp * hgt), nullptr, stream);
+            if (rc != ORBX_OK) return rc;
+            HIPCHK(h, hipEventRecord(U.kern_ev[i], stream));      // buffer i is read out once converted
+            b.img = h->d_cring.as();
+            b.img_row_stride = (long long)gp;
+            b.img_frame_stride = (long long)(gp * hgt);
+        }
         const int rc = launch_group(h, b, stream);
         if (rc != ORBX_OK) return rc;
-        HIPCHK(h, hipEventRecord(h->kern_ev[i], stream));
+        if (fmt == ORBX_PIX_GRAY8) HIPCHK(h, hipEventRecord(U.kern_ev[i], stream));
     }
     // every caller frame has been read once both uploads are done (pinned frames are DMA'd from the caller's memory)
-    for (int i = 0; i < 2; i++) HIPCHK(h, hipEventSynchronize(h->up_ev[i]));
+    for (int i = 0; i < 2; i++) HIPCHK(h, hipEventSynchronize(U.up_ev[i]));
     return ORBX_OK;
 }
+
+static int extract_one(orbx_extractor* h, int w, int hgt, int dstride, size_t bytes, orbx_keypoint* kps, uint8_t* desc, int* n_out);
 
 extern "C" {
 
@@ -412,8 +481,8 @@ int orbx_extract_batch(orbx_extractor* h, const uint8_t* const* imgs, const ptrd
     if (cap < h->hg.g.nslots) { h->err = "cap < orbx_max_keypoints()"; return ORBX_ERR_CAPACITY; }
     h->ph_done = 0;                                              // the handle's scratch now holds this call's groups: no phased call may continue
     hipStream_t stream = (hipStream_t)stream_;
-    if (where == ORBX_FRAMES_ON_HOST) return extract_host(h, imgs, row_strides, nframes, w, hgt, d_kps, d_desc, d_n, cap, d_status, stream);
-    return extract_gather(h, imgs, row_strides, nframes, w, d_kps, d_desc, d_n, cap, d_status, stream);
+    if (where == ORBX_FRAMES_ON_HOST) return extract_host(h, h->hup, ORBX_PIX_GRAY8, imgs, row_strides, nframes, w, hgt, d_kps, d_desc, d_n, cap, d_status, stream);
+    return extract_gather(h, ORBX_PIX_GRAY8, imgs, row_strides, nframes, w, hgt, d_kps, d_desc, d_n, cap, d_status, stream);
 }
 
 int orbx_extract(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_t stride, orbx_keypoint* kps, uint8_t* desc, int cap,
@@ -445,6 +514,16 @@ int orbx_extract(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_
     } else {
         HIPCHK(h, hipMemcpy2DAsync(h->d_img1, dstride, img, stride, w, hgt, hipMemcpyHostToDevice, h->s1));
     }
+    return extract_one(h, w, hgt, dstride, bytes, kps, desc, n_out);
+}
+
+}  // extern "C"
+
+// the rest of the one-frame call once its gray frame is queued into d_img1 (pitch dstride) on s1: the launch group, the results
+static int extract_one(orbx_extractor* h, int w, int hgt, int dstride, size_t bytes, orbx_keypoint* kps, uint8_t* desc, int* n_out) {
+    const int need = h->hg.g.nslots;
+    const size_t kps_off = 64, desc_off = kps_off + ((size_t)need * sizeof(orbx_keypoint) + 63) / 64 * 64, out_bytes = desc_off + (size_t)need * 32;
+    int rc;
     uint8_t* out = h->zero_copy ? h->h_out1.mapped() : h->d_out1.as();
     int32_t* d_n = reinterpret_cast<int32_t*>(out);
     // (Replaying the launch group from a HIP graph was measured and does not help: 188 vs 181 us - the latency is the
@@ -464,6 +543,136 @@ int orbx_extract(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_
     }
     *n_out = n;
     return ORBX_OK;
+}
+
+extern "C" {
+
+// ---- colour frames (src/Tracking.cc:185-195) ------------------------------------------------------
+static int color_args(int fmt, int w, ptrdiff_t row_stride) {
+    const int ch = pix_channels(fmt);
+    if (ch == 0) return ORBX_ERR_ARG;
+    return row_stride < (ptrdiff_t)w * ch ? ORBX_ERR_ARG : ORBX_OK;
+}
+
+int orbx_to_gray_device(const uint8_t* d_src, int nframes, int w, int hgt, ptrdiff_t src_row_stride, ptrdiff_t src_frame_stride, int fmt,
+                        uint8_t* d_gray, ptrdiff_t gray_row_stride, ptrdiff_t gray_frame_stride, void* stream) {
+    if (pix_channels(fmt) == 0) return ORBX_ERR_ARG;
+    if (nframes <= 0 || w <= 0 || hgt <= 0) return ORBX_EMPTY;
+    if (!d_src || !d_gray || color_args(fmt, w, src_row_stride) != ORBX_OK || gray_row_stride < w || src_frame_stride < 0 || gray_frame_stride < 0 ||
+        (nframes > 1 && gray_frame_stride < gray_row_stride * (hgt - 1) + w))
+        return ORBX_ERR_ARG;
+    int dev = 0, ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return ORBX_ERR_DEVICE;
+    ColorArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_src; a.src_row_stride = src_row_stride; a.src_frame_stride = src_frame_stride;
+    a.dst = d_gray; a.dst_row_stride = gray_row_stride; a.dst_frame_stride = gray_frame_stride; a.w = w; a.h = hgt;
+    return launch_to_gray(a, nframes, fmt, (hipStream_t)stream);
+}
+
+int orbx_extract_color(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_t stride, int fmt, orbx_keypoint* kps, uint8_t* desc, int cap,
+                       int* n_out, uint8_t* gray_out) {
+    if (!h) return ORBX_ERR_ARG;
+    if (pix_channels(fmt) == 0) { h->err = "unknown pixel format"; return ORBX_ERR_ARG; }
+    if (!img || w <= 0 || hgt <= 0) return ORBX_EMPTY;   // reference: silent return, outputs untouched
+    if (!kps || !desc || !n_out || color_args(fmt, w, stride) != ORBX_OK) { h->err = "bad argument"; return ORBX_ERR_ARG; }
+    if (fmt == ORBX_PIX_GRAY8) {                          // GrabImage's copyTo, then the gray call
+        const int rc = orbx_extract(h, img, w, hgt, stride, kps, desc, cap, n_out);
+        if (rc == ORBX_OK && gray_out)
+            for (int y = 0; y < hgt; y++) memcpy(gray_out + (size_t)y * w, img + (ptrdiff_t)y * stride, (size_t)w);
+        return rc;
+    }
+    HIPCHK(h, hipSetDevice(h->p.device));
+    int rc = ensure_geometry(h, w, hgt);
+    if (rc != ORBX_OK) return rc;
+    const int need = h->hg.g.nslots;
+    if (cap < need) { h->err = "cap < orbx_max_keypoints()"; return ORBX_ERR_CAPACITY; }
+    const int dstride = (w + 63) / 64 * 64;
+    const size_t bytes = (size_t)dstride * hgt;
+    const size_t rowb = (size_t)w * pix_channels(fmt), cpitch = (rowb + 15) & ~(size_t)15;
+    const size_t kps_off = 64, desc_off = kps_off + ((size_t)need * sizeof(orbx_keypoint) + 63) / 64 * 64, out_bytes = desc_off + (size_t)need * 32;
+    HIPCHK(h, h->d_img1.ensure(bytes));
+    HIPCHK(h, h->h_cimg1.ensure(cpitch * hgt, hipHostMallocMapped));
+    if (gray_out) HIPCHK(h, h->h_gray1.ensure(bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(h, h->d_out1.ensure(out_bytes));
+    HIPCHK(h, h->h_out1.ensure(out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(h, h->s1.ensure());
+    // the colour frame is staged in pinned memory; the conversion kernel fetches it from there (device-mapped, k_ingest's job) and writes
+    // the gray level 0 (and, if wanted, the same bytes into the pinned, device-mapped gray copy)
+    for (int y = 0; y < hgt; y++) memcpy(h->h_cimg1.as() + (size_t)y * cpitch, img + (ptrdiff_t)y * stride, rowb);
+    const uint8_t* src = h->h_cimg1.mapped();
+    if (!h->zero_copy) {
+        HIPCHK(h, h->d_cimg1.ensure(cpitch * hgt));
+        HIPCHK(h, hipMemcpyAsync(h->d_cimg1, h->h_cimg1, cpitch * hgt, hipMemcpyHostToDevice, h->s1));
+        src = h->d_cimg1.as();
+    }
+    if ((rc = convert(h, src, (ptrdiff_t)cpitch, 0, nullptr, 0, 1, w, hgt, fmt, h->d_img1.as(), dstride, 0, gray_out ? h->h_gray1.mapped() : nullptr, h->s1)) != ORBX_OK)
+        return rc;
+    rc = extract_one(h, w, hgt, dstride, bytes, kps, desc, n_out);
+    if (rc == ORBX_OK && gray_out)
+        for (int y = 0; y < hgt; y++) memcpy(gray_out + (size_t)y * w, h->h_gray1.as() + (size_t)y * dstride, (size_t)w);
+    return rc;
+}
+
+int orbx_extract_batch_device_color(orbx_extractor* h, const uint8_t* d_imgs, int nframes, int w, int hgt, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                                    int fmt, orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, uint8_t* d_gray,
+                                    ptrdiff_t gray_row_stride, ptrdiff_t gray_frame_stride, void* stream_) {
+    if (!h) return ORBX_ERR_ARG;
+    if (pix_channels(fmt) == 0) { h->err = "unknown pixel format"; return ORBX_ERR_ARG; }
+    if (!d_imgs || nframes <= 0 || w <= 0 || hgt <= 0) return ORBX_EMPTY;
+    if (!d_kps || !d_desc || !d_n || cap < 1 || color_args(fmt, w, row_stride) != ORBX_OK || frame_stride < 0 ||
+        (d_gray && (gray_row_stride < w || gray_frame_stride < 0 || (nframes > 1 && gray_frame_stride < gray_row_stride * (hgt - 1) + w)))) {
+        h->err = "bad argument";
+        return ORBX_ERR_ARG;
+    }
+    if (fmt == ORBX_PIX_GRAY8 && !d_gray) return orbx_extract_batch_device(h, d_imgs, nframes, w, hgt, row_stride, frame_stride, d_kps, d_desc, d_n, cap, d_status, stream_);
+    HIPCHK(h, hipSetDevice(h->p.device));
+    int rc = ensure_geometry(h, w, hgt);
+    if (rc != ORBX_OK) return rc;
+    if (cap < h->hg.g.nslots) { h->err = "cap < orbx_max_keypoints()"; return ORBX_ERR_CAPACITY; }
+    size_t gp = 0;
+    if (!d_gray && (rc = ensure_cring(h, w, hgt, gp)) != ORBX_OK) return rc;
+    h->ph_done = 0;                                              // the handle's scratch now holds this call's groups: no phased call may continue
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int f0 = 0; f0 < nframes; f0 += h->p.max_batch) {
+        const int n = std::min(h->p.max_batch, nframes - f0);
+        uint8_t* g = d_gray ? d_gray + (ptrdiff_t)f0 * gray_frame_stride : h->d_cring.as();
+        const ptrdiff_t grs = d_gray ? gray_row_stride : (ptrdiff_t)gp, gfs = d_gray ? gray_frame_stride : (ptrdiff_t)(gp * hgt);
+        if ((rc = convert(h, d_imgs + (ptrdiff_t)f0 * frame_stride, row_stride, frame_stride, nullptr, 0, n, w, hgt, fmt, g, grs, gfs, nullptr, stream)) != ORBX_OK)
+            return rc;
+        Batch b;
+        group_batch(h, b, f0, n, d_kps, d_desc, d_n, cap, d_status);
+        b.img = g;
+        b.img_row_stride = grs;
+        b.img_frame_stride = gfs;
+        if ((rc = launch_group(h, b, stream)) != ORBX_OK) return rc;
+    }
+    return ORBX_OK;
+}
+
+int orbx_extract_batch_color(orbx_extractor* h, const uint8_t* const* imgs, const ptrdiff_t* row_strides, int nframes, int w, int hgt, int where, int fmt,
+                             orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_n, int cap, int32_t* d_status, void* stream_) {
+    if (!h) return ORBX_ERR_ARG;
+    const int ch = pix_channels(fmt);
+    if (ch == 0) { h->err = "unknown pixel format"; return ORBX_ERR_ARG; }
+    if (nframes <= 0 || w <= 0 || hgt <= 0) return ORBX_EMPTY;
+    if (!imgs || (where != ORBX_FRAMES_ON_DEVICE && where != ORBX_FRAMES_ON_HOST) || !d_kps || !d_desc || !d_n || cap < 1) {
+        h->err = "bad argument";
+        return ORBX_ERR_ARG;
+    }
+    if (fmt == ORBX_PIX_GRAY8) return orbx_extract_batch(h, imgs, row_strides, nframes, w, hgt, where, d_kps, d_desc, d_n, cap, d_status, stream_);
+    for (int f = 0; f < nframes; f++) {
+        const ptrdiff_t s = row_strides ? row_strides[f] : (ptrdiff_t)w * ch;
+        if (!imgs[f] || s < (ptrdiff_t)w * ch || s >= ((ptrdiff_t)1 << 24)) { h->err = "bad frame pointer or row stride"; return ORBX_ERR_ARG; }
+    }
+    HIPCHK(h, hipSetDevice(h->p.device));
+    int rc = ensure_geometry(h, w, hgt);
+    if (rc != ORBX_OK) return rc;
+    if (cap < h->hg.g.nslots) { h->err = "cap < orbx_max_keypoints()"; return ORBX_ERR_CAPACITY; }
+    h->ph_done = 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (where == ORBX_FRAMES_ON_HOST) return extract_host(h, h->cup, fmt, imgs, row_strides, nframes, w, hgt, d_kps, d_desc, d_n, cap, d_status, stream);
+    return extract_gather(h, fmt, imgs, row_strides, nframes, w, hgt, d_kps, d_desc, d_n, cap, d_status, stream);
 }
 
 // ---- diagnostics ---------------------------------------------------------------------------------

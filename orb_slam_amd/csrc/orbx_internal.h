@@ -265,6 +265,33 @@ static inline unsigned long long level0_bits(const Batch& b) {
 // Smallest level-0 row stride of a launch group.
 static inline long long level0_min_stride(const Batch& b) { return b.img_tab ? b.img_tab_min_stride : b.img_row_stride; }
 
+// One launch of the colour -> gray conversion (k_color.hip): nframes frames from `src` (frame f at src + f*src_frame_stride) or, when `tab`
+// is set, from the DEVICE table tab[f] (gather forms; tab_bits = OR of its bases and row strides), to dst + f*dst_frame_stride, and the
+// same bytes to dst2 (optional, same strides: the pinned, device-mapped gray copy of the one-frame call).  Passed by value (kernarg).
+struct ColorArgs {
+    const uint8_t* src;
+    long long src_row_stride, src_frame_stride;
+    const ImgSrc* tab;
+    unsigned long long tab_bits;
+    uint8_t* dst;
+    uint8_t* dst2;
+    long long dst_row_stride, dst_frame_stride;
+    int w, h;
+    int f0;              // first frame of the launch (set by launch_to_gray)
+    int cpr, items;      // 16-pixel chunks per row, chunks per frame (set by launch_to_gray)
+};
+// ORBX_PIX_* -> bytes per pixel (0: unknown format)
+static inline int pix_channels(int fmt) {
+    switch (fmt) {
+        case ORBX_PIX_GRAY8: return 1;
+        case ORBX_PIX_RGB8: case ORBX_PIX_BGR8: return 3;
+        case ORBX_PIX_RGBA8: case ORBX_PIX_BGRA8: return 4;
+        default: return 0;
+    }
+}
+// k_color.hip: queue the conversion of nframes frames on `stream` (ORBX_ERR_ARG for a frame of 2^31 chunks or more)
+int launch_to_gray(const ColorArgs& a, int nframes, int fmt, hipStream_t stream);
+
 // Host-side geometry builder result.
 struct HostGeom {
     DevGeom g;
