@@ -54,6 +54,8 @@ EXPORTS_V = [
 # include/orbd.h (key-frame database)
 EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_batch_device", "orbd_erase", "orbd_clear",
              "orbd_query_batch_device", "orbd_query"]
+EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
+             "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track"]
 
 
 class OrbxError(RuntimeError):
@@ -97,6 +99,33 @@ class SearchParams(ctypes.Structure):
     """orbs_params"""
     _fields_ = [("rule", ctypes.c_int32), ("th", ctypes.c_int32), ("ratio", ctypes.c_float), ("check_orientation", ctypes.c_int32)]
 
+
+class View(ctypes.Structure):
+    """orbp_view: one pose + camera + (view_cos_limit, th) of Tracking's local-map search"""
+    _fields_ = [("Rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("Ow", ctypes.c_float * 3),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_x", ctypes.c_int32), ("max_x", ctypes.c_int32), ("min_y", ctypes.c_int32), ("max_y", ctypes.c_int32),
+                ("view_cos_limit", ctypes.c_float), ("th", ctypes.c_float), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, Rcw, tcw, Ow, fx, fy, cx, cy, min_x, max_x, min_y, max_y, view_cos_limit=0.5, th=1.0):
+        v = cls()
+        v.Rcw[:] = [float(x) for x in np.asarray(Rcw, np.float32).reshape(9)]
+        v.tcw[:] = [float(x) for x in np.asarray(tcw, np.float32).reshape(3)]
+        v.Ow[:] = [float(x) for x in np.asarray(Ow, np.float32).reshape(3)]
+        v.fx, v.fy, v.cx, v.cy = float(fx), float(fy), float(cx), float(cy)
+        v.min_x, v.max_x, v.min_y, v.max_y = int(min_x), int(max_x), int(min_y), int(max_y)
+        v.view_cos_limit, v.th, v.mode, v.reserved = float(view_cos_limit), float(th), 0, 0
+        return v
+
+
+# orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
+VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
+                       ("cx", np.float32), ("cy", np.float32), ("min_x", np.int32), ("max_x", np.int32), ("min_y", np.int32),
+                       ("max_y", np.int32), ("view_cos_limit", np.float32), ("th", np.float32), ("mode", np.int32), ("reserved", np.int32)])
+RECORD_DTYPE = np.dtype([("in_view", np.uint8), ("pad", np.uint8, 3), ("u", np.float32), ("v", np.float32), ("view_cos", np.float32),
+                         ("level", np.int32)])
+assert VIEW_DTYPE.itemsize == ctypes.sizeof(View) == 108 and RECORD_DTYPE.itemsize == 20
 
 GRID_COLS, GRID_ROWS = 64, 48
 GRID_CELLS = GRID_COLS * GRID_ROWS
@@ -209,6 +238,21 @@ def lib():
         L.orbd_clear.argtypes = [vp]
         L.orbd_query_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
         L.orbd_query.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
+        L.orbp_create.argtypes = [ci, ci, ctypes.POINTER(vp)]
+        L.orbp_destroy.argtypes = [vp]
+        L.orbp_destroy.restype = None
+        L.orbp_capacity.argtypes = [vp]
+        L.orbp_size.argtypes = [vp]
+        L.orbp_clear.argtypes = [vp]
+        L.orbp_put.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+        L.orbp_put_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        L.orbp_erase.argtypes = [vp, vp, ci]
+        L.orbp_get.argtypes = [vp, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp]
+        L.orbp_project_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.orbp_track_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, ctypes.POINTER(Bounds), cf, vp, vp, vp, vp, vp, ci, vp, ci,
+                                              vp, vp, vp, vp, vp, vp]
+        L.orbp_track.argtypes = [vp, ctypes.POINTER(View), vp, ci, vp, ci, vp, ctypes.POINTER(Bounds), cf, vp, vp, vp, vp, vp, ci, ci, ci,
+                                 vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
         _LIB = L
     return _LIB
 
@@ -942,3 +986,123 @@ class KeyFrameDatabase:
                                            d_share_words, d_share_score, out_cap, d_n_share, d_min_common, d_status, stream or None)
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbd_query_batch_device")
+
+
+class MapPointTable:
+    """The local map's points in HBM (include/orbp.h): position, mean viewing direction, scale-invariance distances and descriptor per
+    caller-chosen slot; project / track run Frame::isInFrustum and Tracking's local-map search for whole batches of poses."""
+
+    def __init__(self, capacity, device=0):
+        self.h = ctypes.c_void_p()
+        self.device = device
+        rc = lib().orbp_create(capacity, device, ctypes.byref(self.h))
+        if rc != ORBX_OK:
+            self.h = None
+            raise OrbxError(rc, "orbp_create")
+        self.capacity = capacity
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orbp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except TypeError:           # interpreter shutdown
+            pass
+
+    def __len__(self):
+        return lib().orbp_size(self.h)
+
+    def put(self, slots, pos, normal, min_dist, max_dist, desc=None):
+        """host arrays; desc=None keeps the stored descriptors (every slot must then be live)"""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(slots)
+        pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(n, 3)
+        normal = np.ascontiguousarray(normal, dtype=np.float32).reshape(n, 3)
+        dmin = np.ascontiguousarray(min_dist, dtype=np.float32).reshape(n)
+        dmax = np.ascontiguousarray(max_dist, dtype=np.float32).reshape(n)
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(n, 32)
+        rc = lib().orbp_put(self.h, slots.ctypes.data, n, pos.ctypes.data, normal.ctypes.data, dmin.ctypes.data, dmax.ctypes.data,
+                            desc.ctypes.data if desc is not None else None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_put")
+
+    def put_device(self, slots, d_pos, d_normal, d_min_dist, d_max_dist, d_desc=0, stream=0):
+        """slots: host array; the data: device pointers as ints (d_desc 0 keeps the stored descriptors)"""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        rc = lib().orbp_put_device(self.h, slots.ctypes.data, len(slots), d_pos, d_normal, d_min_dist, d_max_dist, d_desc or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_put_device")
+
+    def erase(self, slots):
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        rc = lib().orbp_erase(self.h, slots.ctypes.data, len(slots))
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_erase")
+
+    def clear(self):
+        rc = lib().orbp_clear(self.h)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_clear")
+
+    def get(self, slot):
+        """-> None for a free slot, else dict(pos, normal, min_dist, max_dist, desc)"""
+        live = ctypes.c_int()
+        pos = np.zeros(3, np.float32); nrm = np.zeros(3, np.float32); dmin = np.zeros(1, np.float32); dmax = np.zeros(1, np.float32)
+        desc = np.zeros(32, np.uint8)
+        rc = lib().orbp_get(self.h, slot, ctypes.byref(live), pos.ctypes.data, nrm.ctypes.data, dmin.ctypes.data, dmax.ctypes.data, desc.ctypes.data)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_get")
+        return dict(pos=pos, normal=nrm, min_dist=dmin[0], max_dist=dmax[0], desc=desc) if live.value else None
+
+    def project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
+                             d_overflow, qcap, stream=0):
+        """device pointers as ints (0 = NULL); factors: host float array (mvScaleFactors)"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_project_batch_device(self.h, d_views, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap, d_skip or None,
+                                             d_rec or None, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq, d_overflow, qcap, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_project_batch_device")
+
+    def track_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, bounds, ratio, d_kps_un, d_desc, d_cell_off,
+                           d_cell_feat, d_nt, cap, d_claimed, qcap, d_rec, d_t2slot, d_nmatches, d_nq, d_overflow, stream=0):
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_track_batch_device(self.h, d_views, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap, d_skip or None,
+                                           ctypes.byref(bounds), ratio, d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt, cap, d_claimed or None, qcap,
+                                           d_rec or None, d_t2slot, d_nmatches, d_nq, d_overflow, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_track_batch_device")
+
+    def track(self, view, factors, bounds, ratio, kps_un, desc, cell_off, cell_feat, claimed=None, list=None, skip=None, qcap=None,
+              want_records=True):
+        """One view, host arrays (the latency form): -> dict(t2slot, nmatches, nvisible, rec).  list=None: all live slots (records by slot).
+        Raises OrbxError(ORBX_ERR_CAPACITY) when more than qcap points are visible."""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        kps_un = np.ascontiguousarray(kps_un)
+        nt = len(kps_un)
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(nt, 32)
+        cell_off = np.ascontiguousarray(cell_off, dtype=np.int32)
+        cell_feat = np.ascontiguousarray(cell_feat, dtype=np.int32)
+        assert kps_un.dtype.itemsize == 28 and len(cell_off) == GRID_CELLS + 1
+        if claimed is not None:
+            claimed = np.ascontiguousarray(claimed, dtype=np.uint8)
+        if list is not None:
+            list = np.ascontiguousarray(list, dtype=np.int32)
+        nlist = self.capacity if list is None else len(list)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            assert len(skip) == nlist
+        qcap = qcap or max(1, min(nlist, 8192))
+        rec = np.zeros(max(nlist, 1), RECORD_DTYPE) if want_records else None
+        t2slot = np.full(max(nt, 1), -1, np.int32)
+        nm, nv = ctypes.c_int(), ctypes.c_int()
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        rc = lib().orbp_track(self.h, ctypes.byref(view), f.ctypes.data, len(f), ptr(list), nlist, ptr(skip), ctypes.byref(bounds), ratio,
+                              ptr(kps_un), ptr(desc), ptr(cell_off), ptr(cell_feat), ptr(claimed), nt, 0, qcap, ptr(rec), ptr(t2slot),
+                              ctypes.byref(nm), ctypes.byref(nv), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_track (nvisible=%d)" % nv.value)
+        return dict(t2slot=t2slot[:nt], nmatches=nm.value, nvisible=nv.value, rec=rec[:nlist] if rec is not None else None)

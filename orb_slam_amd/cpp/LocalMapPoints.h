@@ -1,0 +1,70 @@
+// ORB_SLAM::LocalMapPoints — the local map's points mirrored on the MI355X (include/orbp.h), and the loop of
+// Tracking::SearchReferencePointsInFrustum (reference src/Tracking.cc:699-726) as one call: Frame::isInFrustum on every listed map
+// point, the write-back of the five mTrack* fields, IncreaseVisible(), and ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th)
+// on the GPU.  Host C++ written against the reference's Frame / MapPoint member names; links the C ABI only.
+//
+// A map point is mirrored by Put (which reads GetWorldPos, GetNormal, Get{Min,Max}DistanceInvariance, GetDescriptor) and dropped by
+// Forget.  Both only touch host memory; the device table is brought up to date in ONE orbp_put / orbp_erase at the start of the next
+// search, so a bundle adjustment that moves thousands of points costs one upload.  The table grows by doubling.
+// Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
+// There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
+#pragma once
+#include <cstdint>
+#include <unordered_map>
+#include <vector>
+
+#include "orbp.h"
+#include "MapPoint.h"
+#include "Frame.h"
+
+namespace ORB_SLAM {
+
+class MapPoint;
+class Frame;
+
+class LocalMapPoints {
+public:
+    // nnratio: mfNNratio of the ORBmatcher Tracking uses for this search (0.8).  refresh_every_call: every listed point is Put again
+    // on each search, for callers who do not hook the map; the default trusts the hooks.
+    explicit LocalMapPoints(float nnratio = 0.8f, bool refresh_every_call = false, int capacity = 4096, int device = 0);
+    ~LocalMapPoints();
+    LocalMapPoints(const LocalMapPoints&) = delete;
+    LocalMapPoints& operator=(const LocalMapPoints&) = delete;
+
+    // mirrors pMP into its slot (the first call assigns one)
+    void Put(MapPoint* pMP);
+    // frees pMP's slot; unknown points are ignored
+    void Forget(MapPoint* pMP);
+
+    // src/Tracking.cc:699-726.  Points with mnLastFrameSeen == F.mnId or isBad() are passed over; every other listed point gets
+    // mbTrackInView and, when visible, mTrackProjX/Y, mnTrackScaleLevel, mTrackViewCos and IncreaseVisible(); *nToMatch counts them.
+    // F.mvpMapPoints[idx] receives the matched points; returns SearchByProjection's return value.  F.mTcw must hold the pose
+    // (UpdatePoseMatrices need not have been called).  Listed points not yet mirrored are Put on the way.
+    int SearchReferencePointsInFrustum(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, float th, int* nToMatch = 0);
+
+    std::size_t size() const { return slot_.size(); }
+    int capacity() const { return capacity_; }
+
+private:
+    void flush();
+    void grow();
+    void mirror(int slot, MapPoint* pMP);
+
+    orbp_map* map_ = nullptr;
+    float ratio_;
+    bool refresh_;
+    int capacity_, device_;
+    std::unordered_map<MapPoint*, int> slot_;
+    std::vector<MapPoint*> owner_;               // per slot; NULL = free
+    std::vector<int32_t> free_;                  // free slots, lowest on top
+    std::vector<uint8_t> dirty_, dead_;          // per slot: to upload / to erase at the next flush
+    std::vector<int32_t> dirty_list_, dead_list_;
+    std::vector<float> pos_, nrm_, dmin_, dmax_; // host copy of the table (re-uploaded when it grows)
+    std::vector<uint8_t> desc_;
+    // per call
+    std::vector<int32_t> list_, t2slot_, cell_off_, cell_feat_;
+    std::vector<uint8_t> skip_, claimed_;
+    std::vector<orbp_record> rec_;
+};
+
+}  // namespace ORB_SLAM

@@ -1,0 +1,161 @@
+// Drives ORB_SLAM::LocalMapPoints (orb_slam_amd/cpp/LocalMapPoints.cc, over the stand-in Frame.h / MapPoint.h of this directory)
+// through a script; tests/test_gpu_mappoints_dropin.py builds the script, computes what the reference would leave behind with
+// tests/frustum_ref.py and the CPU oracle, and compares.  Floats travel as the hex of their bit pattern.
+//
+//   harness SCRIPT
+//
+// Script lines:
+//   cam fx fy cx cy MINX MAXX MINY MAXY invw invh      Frame's statics
+//   factors N f ...                                    mvScaleFactors
+//   new REFRESH CAPACITY                               LocalMapPoints(0.8f, REFRESH, CAPACITY)
+//   mp ID x y z nx ny nz dmin dmax DESC                creates (or changes, WITHOUT Put) map point ID; DESC = 64 hex digits
+//   put ID | forget ID | bad ID 0|1 | seen ID FRAMEID  Put / Forget / the bad flag / mnLastFrameSeen
+//   frame FRAMEID N, then N lines "x y octave DESC"    a frame: key points filed in mGrid by Frame::PosInGrid's rule
+//   pose r00 .. r22 t0 t1 t2                           mTcw
+//   hold IDX ID                                        F.mvpMapPoints[IDX] = map point ID
+//   search th K id ...       -> "S ret nToMatch size capacity", per listed point "P id inview u v cos level visible lastseen",
+//                               then "M idx id" for every feature that holds a map point
+//   time th REPS K id ...    -> "T ms" the mean wall time of one SearchReferencePointsInFrustum call (matches undone between calls)
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <sstream>
+#include <string>
+
+#include "Frame.h"
+#include "LocalMapPoints.h"
+#include "MapPoint.h"
+
+namespace ORB_SLAM {
+float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
+int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
+float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
+}
+using namespace ORB_SLAM;
+
+namespace {
+
+float rdf(std::istringstream& in) {
+    std::string h;
+    in >> h;
+    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+unsigned bitsof(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+void rddesc(std::istringstream& in, unsigned char* d) {
+    std::string h;
+    in >> h;
+    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
+}
+std::vector<MapPoint*> rdlist(std::istringstream& in, std::map<long, std::unique_ptr<MapPoint> >& mps) {
+    int k = 0;
+    in >> k;
+    std::vector<MapPoint*> v(k);
+    for (int i = 0; i < k; i++) { long id; in >> id; v[i] = mps.at(id).get(); }
+    return v;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream f(argv[1]);
+    std::string line;
+    std::map<long, std::unique_ptr<MapPoint> > mps;
+    std::unique_ptr<LocalMapPoints> L;
+    Frame F;
+    std::vector<float> factors;
+    while (std::getline(f, line)) {
+        std::istringstream in(line);
+        std::string op;
+        if (!(in >> op)) continue;
+        if (op == "cam") {
+            Frame::fx = rdf(in); Frame::fy = rdf(in); Frame::cx = rdf(in); Frame::cy = rdf(in);
+            in >> Frame::mnMinX >> Frame::mnMaxX >> Frame::mnMinY >> Frame::mnMaxY;
+            Frame::mfGridElementWidthInv = rdf(in); Frame::mfGridElementHeightInv = rdf(in);
+        } else if (op == "factors") {
+            int n; in >> n;
+            factors.resize(n);
+            for (int i = 0; i < n; i++) factors[i] = rdf(in);
+        } else if (op == "new") {
+            int refresh, cap; in >> refresh >> cap;
+            L.reset(new LocalMapPoints(0.8f, refresh != 0, cap));
+        } else if (op == "mp") {
+            long id; in >> id;
+            if (!mps.count(id)) { mps[id].reset(new MapPoint); mps[id]->mnId = id; }
+            MapPoint& m = *mps[id];
+            for (int k = 0; k < 3; k++) m.mWorldPos.at<float>(k) = rdf(in);
+            for (int k = 0; k < 3; k++) m.mNormalVector.at<float>(k) = rdf(in);
+            m.mfMinDistance = rdf(in); m.mfMaxDistance = rdf(in);
+            rddesc(in, m.mDescriptor.ptr<unsigned char>(0));
+        } else if (op == "put") { long id; in >> id; L->Put(mps.at(id).get());
+        } else if (op == "forget") { long id; in >> id; L->Forget(mps.at(id).get());
+        } else if (op == "bad") { long id; int v; in >> id >> v; mps.at(id)->mbBad = v != 0;
+        } else if (op == "seen") { long id; unsigned long fid; in >> id >> fid; mps.at(id)->mnLastFrameSeen = fid;
+        } else if (op == "frame") {
+            int n; in >> F.mnId >> n;
+            F.mvKeysUn.assign(n, cv::KeyPoint());
+            F.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            F.mvpMapPoints.assign(n, nullptr);
+            F.mnScaleLevels = (int)factors.size();
+            F.mvScaleFactors = factors;
+            for (int x = 0; x < FRAME_GRID_COLS; x++) for (int y = 0; y < FRAME_GRID_ROWS; y++) F.mGrid[x][y].clear();
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                cv::KeyPoint& kp = F.mvKeysUn[i];
+                kp.pt.x = rdf(kin); kp.pt.y = rdf(kin);
+                kin >> kp.octave;
+                rddesc(kin, F.mDescriptors.ptr<unsigned char>(i));
+                const int px = (int)std::round((kp.pt.x - Frame::mnMinX) * Frame::mfGridElementWidthInv);      // Frame::PosInGrid
+                const int py = (int)std::round((kp.pt.y - Frame::mnMinY) * Frame::mfGridElementHeightInv);
+                if (px >= 0 && px < FRAME_GRID_COLS && py >= 0 && py < FRAME_GRID_ROWS) F.mGrid[px][py].push_back(i);
+            }
+        } else if (op == "pose") {
+            F.mTcw = cv::Mat(4, 4, CV_32F);
+            for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) F.mTcw.at<float>(r, c) = r == c ? 1.f : 0.f;
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) F.mTcw.at<float>(r, c) = rdf(in);
+            for (int r = 0; r < 3; r++) F.mTcw.at<float>(r, 3) = rdf(in);
+        } else if (op == "hold") {
+            int idx; long id; in >> idx >> id;
+            F.mvpMapPoints[idx] = mps.at(id).get();
+        } else if (op == "search") {
+            const float th = rdf(in);
+            const std::vector<MapPoint*> v = rdlist(in, mps);
+            int nToMatch = -1;
+            const int ret = L->SearchReferencePointsInFrustum(F, v, th, &nToMatch);
+            printf("S %d %d %zu %d\n", ret, nToMatch, L->size(), L->capacity());
+            for (MapPoint* m : v)
+                printf("P %lu %d %08x %08x %08x %d %d %lu\n", m->mnId, m->mbTrackInView ? 1 : 0, bitsof(m->mTrackProjX), bitsof(m->mTrackProjY),
+                       bitsof(m->mTrackViewCos), m->mnTrackScaleLevel, m->mnVisible, m->mnLastFrameSeen);
+            for (size_t i = 0; i < F.mvpMapPoints.size(); i++)
+                if (F.mvpMapPoints[i]) printf("M %zu %lu\n", i, F.mvpMapPoints[i]->mnId);
+        } else if (op == "time") {
+            const float th = rdf(in);
+            int reps; in >> reps;
+            const std::vector<MapPoint*> v = rdlist(in, mps);
+            const std::vector<MapPoint*> held = F.mvpMapPoints;
+            double total = 0;
+            for (int r = -3; r < reps; r++) {
+                F.mvpMapPoints = held;
+                const auto t0 = std::chrono::steady_clock::now();
+                L->SearchReferencePointsInFrustum(F, v, th);
+                const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                if (r >= 0) total += dt;
+            }
+            F.mvpMapPoints = held;
+            printf("T %.6f\n", total / reps);
+        } else {
+            fprintf(stderr, "unknown script line: %s\n", line.c_str());
+            return 2;
+        }
+    }
+    return 0;
+}
