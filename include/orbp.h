@@ -12,6 +12,12 @@
  *                                   (RadiusByViewingCos, th, scale factor, levels)               src/ORBmatcher.cc:57-72, :127-133
  *   orbp_track[_batch_device]    <- the loop of Tracking::SearchReferencePointsInFrustum          src/Tracking.cc:699-726
  *                                   (projection + orbs_window_search_batch_device with ORBS_RULE_MAPPOINTS, TH_HIGH)
+ *   orbp_project_source_batch_device, orbp_track_source[_batch_device]
+ *                                <- int ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, float th)   src/ORBmatcher.cc:1507-1620
+ *                                   (Tracking::TrackWithMotionModel, src/Tracking.cc:565; ORBP_MODE_LAST_FRAME)
+ *                                   int ORBmatcher::SearchByProjection(Frame& Current, KeyFrame*, const set<MapPoint*>&, float th, int ORBdist)
+ *                                   src/ORBmatcher.cc:1622-1746 (Tracking::Relocalisation, src/Tracking.cc:960, :974; ORBP_MODE_KEYFRAME)
+ *                                   (projection + orbs_window_search_batch_device with ORBS_RULE_BEST and the rotation check)
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -26,9 +32,22 @@
  * The window of a visible point: r = viewCos > 0.998 (as double) ? 2.5f : 4.0f; r *= th unless th == 1; radius
  * r * factors[level]; levels [level - 1, level].
  *
+ *
+ * Arithmetic of the two source-frame modes (src/ORBmatcher.cc:1529-1542 and :1647-1660 are the same text), every step a single IEEE
+ * operation:
+ *   Pc as above; there is NO depth test (the reference has none here: a point behind the camera that lands inside the bounds is
+ *   searched); invz = (float)(1.0 / (double)PcZ); u = fx*PcX*invz + cx, v likewise, float, left to right;
+ *   u < (float)mnMinX || u > (float)mnMaxX rejects, same for v (inclusive bounds).
+ *   ORBP_MODE_LAST_FRAME (:1544-1554): level = the source key point's octave; an octave outside [0, nlevels) is passed over (the
+ *   reference would index mvScaleFactors out of bounds); the query's descriptor is the SOURCE FRAME's row.
+ *   ORBP_MODE_KEYFRAME (:1662-1679): PO = P - Ow in float; dist3D = (float)sqrt(sum of (double)PO[i]*(double)PO[i]);
+ *   ratio = dist3D / minDistance (float); level = min(lower_bound(factors, ratio), nlevels - 1); the query's descriptor is the TABLE's
+ *   (pMP->GetDescriptor()).
+ *   Both: radius th * factors[level] (float), levels [level - 1, level + 1], angle = the source key point's angle.
+ *
  * ONE DELIBERATE DEVIATION.  Where the reference leaves u or v NaN (PcZ == 0 together with PcX == 0 or PcY == 0: a point at
  * the camera centre) all its comparisons fail, the point passes with a NaN window and GetFeaturesInArea converts NaN to
- * int, which is undefined.  Here a point whose u or v is NaN is not visible.
+ * int, which is undefined.  Here a point whose u or v is NaN is not visible, and is not a query in the source-frame modes.
  * The reference built with -march=native lets GCC fuse some of these expressions (fp_contract); this stage
  * implements the unfused evaluation only.
  *
@@ -53,7 +72,9 @@ extern "C" {
 #define ORBP_MAX_CAPACITY (1 << 24)   /* slots of one table */
 #define ORBP_MAX_VIEWS    (1 << 16)   /* problems of one call */
 
-#define ORBP_MODE_FRAME 0             /* Frame::isInFrustum; the key-frame-side projections are a later mode */
+#define ORBP_MODE_FRAME 0             /* Frame::isInFrustum; the key-frame-side projections (Fuse, the loop searches) are a later mode */
+#define ORBP_MODE_LAST_FRAME 1        /* orbp_*_source*: the list is the last frame's features (motion-model tracking) */
+#define ORBP_MODE_KEYFRAME 2          /* orbp_*_source*: the list is a key frame's features (relocalisation) */
 
 typedef struct orbp_map orbp_map;
 
@@ -66,7 +87,7 @@ typedef struct orbp_view {
     int32_t min_x, max_x, min_y, max_y;      /* Frame::mnMinX, mnMaxX, mnMinY, mnMaxY */
     float view_cos_limit;                    /* 0.5 in Tracking */
     float th;                                /* SearchByProjection's th: 1 or 5 in Tracking */
-    int32_t mode;                            /* ORBP_MODE_FRAME */
+    int32_t mode;                            /* ORBP_MODE_*; view_cos_limit is not read by the source-frame modes */
     int32_t reserved;                        /* 0 */
 } orbp_view;
 
@@ -145,6 +166,54 @@ int orbp_track(orbp_map* map, const orbp_view* view, const float* factors, int n
                const uint8_t* skip, const orbf_bounds* b, float ratio, const orbx_keypoint* kps_un, const uint8_t* desc,
                const int32_t* cell_off, const int32_t* cell_feat, const uint8_t* claimed, int nt, int frame_on_device, int qcap,
                orbp_record* rec, int32_t* t2slot, int* nmatches, int* nvisible, void* stream);
+
+/* ---- The projection searches whose queries are the features of a SOURCE frame: the last frame (ORBP_MODE_LAST_FRAME) or a key
+ * frame (ORBP_MODE_KEYFRAME); the mode is each view's `mode`.  The arithmetic is stated at the top of this file.
+ *
+ * List entry i of problem p is feature i of its source frame: d_list[p*lcap + i] is the map slot of that feature's map point (-1:
+ * it has none), i < d_nlist[p] (clamped to [0, lcap]); d_list and d_nlist are required.  d_skip (may be NULL) carries mvbOutlier[i]
+ * (last frame) resp. isBad() || sAlreadyFound.count(pMP) (key frame).  An entry whose slot is out of range or not live is passed
+ * over too.  d_src_kps + p*lcap: the source frame's key points in feature order (octave and angle are read; mvKeys and mvKeysUn
+ * agree in both).  d_src_desc + p*32*lcap: its descriptors (16-byte aligned); read by last-frame views only, may be NULL when
+ * every view is a key-frame view.
+ * Outputs per problem, compacted in list order, in the layout orbs_window_search_batch_device reads: d_qxyr[3*qcap], d_qlev[2*qcap],
+ * d_qdesc[32*qcap] (16-byte aligned), d_qangle[qcap]; d_qpos[qcap] the list position (= source feature index) of each query.
+ * d_nq[p] is always the true count; when it exceeds qcap only the first qcap queries are written and d_overflow[p] = 1 (else 0).
+ * A view whose mode is ORBP_MODE_FRAME or unknown (or a last-frame view without d_src_desc) sees nothing: d_nq[p] = 0,
+ * d_overflow[p] = ORBX_ERR_ARG.  Asynchronous on `stream`; allocates nothing. */
+int orbp_project_source_batch_device(orbp_map* map, const orbp_view* d_views, int nviews, const float* factors, int nlevels,
+                                     const int32_t* d_list, const int32_t* d_nlist, int lcap, const uint8_t* d_skip,
+                                     const orbx_keypoint* d_src_kps, const uint8_t* d_src_desc, float* d_qxyr, int32_t* d_qlev,
+                                     uint8_t* d_qdesc, float* d_qangle, int32_t* d_qpos, int32_t* d_nq, int32_t* d_overflow, int qcap,
+                                     void* stream);
+
+/* Projection, then on the same stream orbs_window_search_batch_device with ORBS_RULE_BEST, prm->th (TH_HIGH for the last frame,
+ * ORBdist for a key frame), prm->check_orientation and the queries' angles against the current frames on the device (laid out as
+ * for orbp_track_batch_device; d_claimed, may be NULL, marks current features that hold a map point), then the result by source
+ * feature: d_t2pos[p*cap + idx] = the source feature matched to current feature idx (-1 none; CurrentFrame.mvpMapPoints[idx] =
+ * Source.mvpMapPoints[that]), d_t2slot (may be NULL) its map slot, d_nmatches[p] the reference's return value (after the rotation
+ * filter).  prm->rule must be ORBS_RULE_BEST; prm->ratio is not used.  Scratch and ORBX_ERR_CAPACITY as orbp_track_batch_device. */
+int orbp_track_source_batch_device(orbp_map* map, const orbp_view* d_views, int nviews, const float* factors, int nlevels,
+                                   const int32_t* d_list, const int32_t* d_nlist, int lcap, const uint8_t* d_skip,
+                                   const orbx_keypoint* d_src_kps, const uint8_t* d_src_desc, const orbf_bounds* b, const orbs_params* prm,
+                                   const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat,
+                                   const int32_t* d_nt, int cap, const uint8_t* d_claimed, int qcap, int32_t* d_t2pos, int32_t* d_t2slot,
+                                   int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, void* stream);
+
+/* One view, synchronous: the latency form, one pinned block up and one down.  view, factors, list / skip (nlist entries), t2pos[nt],
+ * t2slot[nt] (may be NULL), *nmatches and *nvisible (may be NULL) are HOST memory.  The source frame (src_kps[nlist], src_desc[32*nlist];
+ * src_desc may be NULL for a key-frame view) is host memory, or device memory when src_on_device != 0; the current frame likewise
+ * with frame_on_device (as orbp_track).  A caller who keeps both frames on the device uploads the view, the list and the skip flags
+ * only.  ORBX_ERR_ARG for a view of ORBP_MODE_FRAME or an unknown mode; ORBX_ERR_CAPACITY when more than qcap entries project
+ * inside the bounds (*nvisible then holds the count; nothing else is written).  stream NULL: the map's own stream.
+ * With both frames in HOST memory the call uploads what the host-query route uploads and more (two whole frames instead of the
+ * queries): it is there for callers such as ORB_SLAM::LocalMapPoints, not as the fast path, and has not been measured against that
+ * route (NOTES.md §14); the form this interface is built for keeps both frames on the device. */
+int orbp_track_source(orbp_map* map, const orbp_view* view, const float* factors, int nlevels, const int32_t* list, int nlist,
+                      const uint8_t* skip, const orbx_keypoint* src_kps, const uint8_t* src_desc, int src_on_device, const orbf_bounds* b,
+                      const orbs_params* prm, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
+                      const int32_t* cell_feat, const uint8_t* claimed, int nt, int frame_on_device, int qcap, int32_t* t2pos,
+                      int32_t* t2slot, int* nmatches, int* nvisible, void* stream);
 
 #ifdef __cplusplus
 }

@@ -55,7 +55,10 @@ EXPORTS_V = [
 EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_batch_device", "orbd_erase", "orbd_clear",
              "orbd_query_batch_device", "orbd_query"]
 EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
-             "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track"]
+             "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
+             "orbp_track_source_batch_device", "orbp_track_source"]
+# orbp_view.mode
+MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME = 0, 1, 2
 
 
 class OrbxError(RuntimeError):
@@ -253,6 +256,11 @@ def lib():
                                               vp, vp, vp, vp, vp, vp]
         L.orbp_track.argtypes = [vp, ctypes.POINTER(View), vp, ci, vp, ci, vp, ctypes.POINTER(Bounds), cf, vp, vp, vp, vp, vp, ci, ci, ci,
                                  vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
+        L.orbp_project_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.orbp_track_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
+                                                     vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+        L.orbp_track_source.argtypes = [vp, ctypes.POINTER(View), vp, ci, vp, ci, vp, vp, vp, ci, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
+                                        vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
         _LIB = L
     return _LIB
 
@@ -1106,3 +1114,67 @@ class MapPointTable:
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_track (nvisible=%d)" % nv.value)
         return dict(t2slot=t2slot[:nt], nmatches=nm.value, nvisible=nv.value, rec=rec[:nlist] if rec is not None else None)
+
+    def project_source_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_src_kps, d_src_desc, d_qxyr, d_qlev, d_qdesc,
+                                    d_qangle, d_qpos, d_nq, d_overflow, qcap, stream=0):
+        """the queries of the last-frame / key-frame projection searches (view.mode = MODE_LAST_FRAME / MODE_KEYFRAME): device pointers as ints"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_project_source_batch_device(self.h, d_views, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap,
+                                                    d_skip or None, d_src_kps or None, d_src_desc or None, d_qxyr, d_qlev, d_qdesc, d_qangle, d_qpos,
+                                                    d_nq, d_overflow, qcap, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_project_source_batch_device")
+
+    def track_source_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_src_kps, d_src_desc, bounds, th, check_orientation,
+                                  d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt, cap, d_claimed, qcap, d_t2pos, d_t2slot, d_nmatches, d_nq,
+                                  d_overflow, stream=0):
+        """th: TH_HIGH (last frame) or ORBdist (key frame)"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        prm = SearchParams(RULE_BEST, int(th), 0.0, 1 if check_orientation else 0)
+        rc = lib().orbp_track_source_batch_device(self.h, d_views, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap, d_skip or None,
+                                                  d_src_kps or None, d_src_desc or None, ctypes.byref(bounds), ctypes.byref(prm), d_kps_un, d_desc,
+                                                  d_cell_off, d_cell_feat, d_nt, cap, d_claimed or None, qcap, d_t2pos, d_t2slot or None, d_nmatches,
+                                                  d_nq, d_overflow, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_track_source_batch_device")
+
+    def track_source(self, view, factors, list, skip, src_kps, src_desc, bounds, th, check_orientation, kps_un, desc, cell_off, cell_feat,
+                     claimed=None, nt=None, qcap=None):
+        """One view (the latency form): -> dict(t2pos, t2slot, nmatches, nvisible).  list / skip: host arrays.  The source frame (src_kps, src_desc)
+        and the current frame (kps_un, desc, cell_off, cell_feat, claimed) are host arrays, or device pointers as ints (each frame all of one kind;
+        nt must then be given for the current frame).  Raises OrbxError(ORBX_ERR_CAPACITY) when more than qcap entries project inside."""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        list = np.ascontiguousarray(list, dtype=np.int32)
+        nlist = len(list)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            assert len(skip) == nlist
+        src_dev = isinstance(src_kps, int)
+        if not src_dev:
+            src_kps = np.ascontiguousarray(src_kps)
+            assert src_kps.dtype.itemsize == 28 and len(src_kps) == nlist
+            if src_desc is not None:
+                src_desc = np.ascontiguousarray(src_desc, dtype=np.uint8).reshape(nlist, 32)
+        frame_dev = isinstance(kps_un, int)
+        if not frame_dev:
+            kps_un = np.ascontiguousarray(kps_un)
+            nt = len(kps_un)
+            desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(nt, 32)
+            cell_off = np.ascontiguousarray(cell_off, dtype=np.int32)
+            cell_feat = np.ascontiguousarray(cell_feat, dtype=np.int32)
+            assert kps_un.dtype.itemsize == 28 and len(cell_off) == GRID_CELLS + 1
+            if claimed is not None:
+                claimed = np.ascontiguousarray(claimed, dtype=np.uint8)
+        qcap = qcap or max(1, min(nlist, 8192))
+        t2pos = np.full(max(nt, 1), -1, np.int32)
+        t2slot = np.full(max(nt, 1), -1, np.int32)
+        nm, nv = ctypes.c_int(), ctypes.c_int()
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        prm = SearchParams(RULE_BEST, int(th), 0.0, 1 if check_orientation else 0)
+        rc = lib().orbp_track_source(self.h, ctypes.byref(view), f.ctypes.data, len(f), ptr(list), nlist, ptr(skip), ptr(src_kps), ptr(src_desc),
+                                     1 if src_dev else 0, ctypes.byref(bounds), ctypes.byref(prm), ptr(kps_un), ptr(desc), ptr(cell_off),
+                                     ptr(cell_feat), ptr(claimed), nt, 1 if frame_dev else 0, qcap, ptr(t2pos), ptr(t2slot), ctypes.byref(nm),
+                                     ctypes.byref(nv), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_track_source (nvisible=%d)" % nv.value)
+        return dict(t2pos=t2pos[:nt], t2slot=t2slot[:nt], nmatches=nm.value, nvisible=nv.value)

@@ -124,6 +124,24 @@ void LocalMapPoints::flush() {
     if (rc != ORBX_OK) fail("orbp_put", rc);
 }
 
+// the view of F: mRcw, mtcw as UpdatePoseMatrices slices them from mTcw; mOw = -mRcw.t()*mtcw as the product of the negated transpose,
+// a float sum per row started from 0; the camera and its bounds; F's grid goes into cell_off_ / cell_feat_
+void LocalMapPoints::viewOf(Frame& F, orbp_view& V, orbf_bounds& b) {
+    std::memset(&V, 0, sizeof(V));
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) V.Rcw[r * 3 + c] = F.mTcw.at<float>(r, c);
+        V.tcw[r] = F.mTcw.at<float>(r, 3);
+    }
+    for (int r = 0; r < 3; r++) {
+        float s = 0.0f;
+        for (int k = 0; k < 3; k++) s += -V.Rcw[k * 3 + r] * V.tcw[k];
+        V.Ow[r] = s;
+    }
+    V.fx = Frame::fx; V.fy = Frame::fy; V.cx = Frame::cx; V.cy = Frame::cy;
+    orbm_access::GridOf(F, b, cell_off_, cell_feat_);
+    V.min_x = b.min_x; V.max_x = b.max_x; V.min_y = b.min_y; V.max_y = b.max_y;
+}
+
 int LocalMapPoints::SearchReferencePointsInFrustum(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, float th, int* nToMatch) {
     const int n = (int)vpLocalMapPoints.size();
     if (nToMatch) *nToMatch = 0;
@@ -138,23 +156,9 @@ int LocalMapPoints::SearchReferencePointsInFrustum(Frame& F, const std::vector<M
         skip_[i] = 0;
     }
     flush();
-    // the view: mRcw, mtcw as UpdatePoseMatrices slices them from mTcw; mOw = -mRcw.t()*mtcw as the product of the negated transpose,
-    // a float sum per row started from 0
     orbp_view V;
-    std::memset(&V, 0, sizeof(V));
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) V.Rcw[r * 3 + c] = F.mTcw.at<float>(r, c);
-        V.tcw[r] = F.mTcw.at<float>(r, 3);
-    }
-    for (int r = 0; r < 3; r++) {
-        float s = 0.0f;
-        for (int k = 0; k < 3; k++) s += -V.Rcw[k * 3 + r] * V.tcw[k];
-        V.Ow[r] = s;
-    }
-    V.fx = Frame::fx; V.fy = Frame::fy; V.cx = Frame::cx; V.cy = Frame::cy;
     orbf_bounds b;
-    orbm_access::GridOf(F, b, cell_off_, cell_feat_);
-    V.min_x = b.min_x; V.max_x = b.max_x; V.min_y = b.min_y; V.max_y = b.max_y;
+    viewOf(F, V, b);
     V.view_cos_limit = 0.5f;                                                       // :709
     V.th = th;
     V.mode = ORBP_MODE_FRAME;

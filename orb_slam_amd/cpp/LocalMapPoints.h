@@ -10,6 +10,7 @@
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
 #include <cstdint>
+#include <set>
 #include <unordered_map>
 #include <vector>
 
@@ -21,6 +22,7 @@ namespace ORB_SLAM {
 
 class MapPoint;
 class Frame;
+class KeyFrame;
 
 class LocalMapPoints {
 public:
@@ -42,6 +44,15 @@ public:
     // (UpdatePoseMatrices need not have been called).  Listed points not yet mirrored are Put on the way.
     int SearchReferencePointsInFrustum(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, float th, int* nToMatch = 0);
 
+    // The two projection searches that run before it (LocalMapPointsSource.cc; both link only when that file is built in):
+    // ORBmatcher::SearchByProjection(Frame&, const Frame&, float) of Tracking::TrackWithMotionModel (src/Tracking.cc:565) and
+    // ORBmatcher::SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, float, int) of Tracking::Relocalisation (:960, :974).
+    // CurrentFrame.mvpMapPoints[idx] is written exactly as the reference writes it; the return value is the reference's.
+    // checkOrientation is the ORBmatcher's mbCheckOrientation.  Points not yet mirrored are Put on the way.
+    int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, float th, bool checkOrientation = true);
+    int SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
+                           bool checkOrientation = true);
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
@@ -49,6 +60,10 @@ private:
     void flush();
     void grow();
     void mirror(int slot, MapPoint* pMP);
+    void viewOf(Frame& F, orbp_view& V, orbf_bounds& b);
+    // vpSource[i]: the map point of source feature i (NULL: none); skip_ is filled by the caller
+    int searchSource(Frame& CurrentFrame, int mode, const std::vector<MapPoint*>& vpSource, const cv::KeyPoint* srcKeys,
+                     const unsigned char* srcDesc, float th, int ORBdist, bool checkOrientation);
 
     orbp_map* map_ = nullptr;
     float ratio_;
@@ -62,7 +77,7 @@ private:
     std::vector<float> pos_, nrm_, dmin_, dmax_; // host copy of the table (re-uploaded when it grows)
     std::vector<uint8_t> desc_;
     // per call
-    std::vector<int32_t> list_, t2slot_, cell_off_, cell_feat_;
+    std::vector<int32_t> list_, t2slot_, t2pos_, cell_off_, cell_feat_;
     std::vector<uint8_t> skip_, claimed_;
     std::vector<orbp_record> rec_;
 };

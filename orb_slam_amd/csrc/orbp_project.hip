@@ -12,8 +12,15 @@
 //              the survivor writes its window, list position and descriptor at base + rank: list order without atomics.
 //              Three f64 multiply-adds, one f64 sqrt and two f64 divides per point; the stage is bound by the latency of
 //              the gathered 64 bytes per entry.
+//   k_project_source  the same walk for the two projection searches whose list is a source frame's features (orbp.h, ORBP_MODE_LAST_FRAME
+//              and ORBP_MODE_KEYFRAME; reference src/ORBmatcher.cc:1507-1746): entry i is feature i of the last frame or of a key frame,
+//              the test is the projection and the image bounds only, and a survivor writes the window th * factors[level] over the
+//              levels [level-1, level+1], its angle and the source frame's (last frame) or the table's (key frame) descriptor.
+//              The key point's octave and angle do not depend on the slot, so their loads leave with the list's and overlap the
+//              dependent list -> live -> geometry chain that bounds the stage.
 //   k_t2slot   orbp_track*: turns the search's feature -> query table into feature -> map slot through the list positions the
 //              projection left (d_qpos); features without a match, or beyond the frame's count, get -1.
+//   k_t2source orbp_track_source*: feature -> query becomes feature -> source feature index (and map slot).
 // With one workgroup per view the one-view call walks its list as a serial chain of 256-entry tiles (two barriers and a dependent
 // list -> live -> geometry load each): its latency grows linearly with the list length.
 #include <hip/hip_runtime.h>
@@ -165,6 +172,108 @@ __global__ __launch_bounds__(TPB) void k_project(const orbp_view* views, Factors
     }
 }
 
+// Rcw * P + tcw as the reference's cv::Mat product evaluates it (in_frustum above)
+__device__ __forceinline__ void to_camera(const orbp_view& V, const float P[3], float Pc[3]) {
+    for (int r = 0; r < 3; r++) {
+        float s = 0.0f;
+        s = s + V.Rcw[r * 3] * P[0];
+        s = s + V.Rcw[r * 3 + 1] * P[1];
+        s = s + V.Rcw[r * 3 + 2] * P[2];
+        Pc[r] = s + V.tcw[r];
+    }
+}
+
+// src/ORBmatcher.cc:1529-1542 (= :1647-1660) for one point: no depth test; true = inside the image bounds
+__device__ __forceinline__ bool project_source(const orbp_view& V, const float P[3], float& u, float& v) {
+    float Pc[3];
+    to_camera(V, P, Pc);
+    const float invz = (float)(1.0 / (double)Pc[2]);
+    u = V.fx * Pc[0] * invz + V.cx;
+    v = V.fy * Pc[1] * invz + V.cy;
+    if (u < (float)V.min_x || u > (float)V.max_x) return false;
+    if (v < (float)V.min_y || v > (float)V.max_y) return false;
+    return !(u != u || v != v);                            // the documented deviation: a NaN projection is not a query
+}
+
+// src/ORBmatcher.cc:1662-1669: the level predicted from the distance to the camera centre
+__device__ __forceinline__ int predicted_level(const orbp_view& V, const Factors& F, const float P[3], float dmin) {
+    double s2 = 0.0;
+    for (int k = 0; k < 3; k++) {
+        const double d = (double)(P[k] - V.Ow[k]);
+        s2 = s2 + d * d;
+    }
+    const float ratio = (float)sqrt(s2) / dmin;
+    int lv = 0;
+    for (int k = 0; k < F.n; k++) lv += F.f[k] < ratio ? 1 : 0;       // std::lower_bound on the ascending table
+    return lv >= F.n ? F.n - 1 : lv;
+}
+
+__global__ __launch_bounds__(TPB) void k_project_source(const orbp_view* views, Factors F, int capacity, const float* geom, const uint8_t* tdesc,
+                                                        const uint8_t* live, const int32_t* list, const int32_t* nlist, int lcap,
+                                                        const uint8_t* skip, const orbx_keypoint* src_kps, const uint8_t* src_desc, float* qxyr,
+                                                        int32_t* qlev, uint8_t* qdesc, float* qangle, int32_t* qpos, int32_t* nq,
+                                                        int32_t* nq_clamped, int32_t* overflow, int qcap) {
+    __shared__ orbp_view V;
+    __shared__ int wave_total[WAVES];
+    const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    if (tid < (int)(sizeof(orbp_view) / 4)) reinterpret_cast<uint32_t*>(&V)[tid] = reinterpret_cast<const uint32_t*>(views + p)[tid];
+    __syncthreads();
+    int n = nlist[p];
+    n = n < 0 ? 0 : (n > lcap ? lcap : n);
+    const bool from_last = V.mode == ORBP_MODE_LAST_FRAME;
+    const bool known_mode = (from_last && src_desc) || V.mode == ORBP_MODE_KEYFRAME;
+    if (!known_mode) n = 0;                                            // reported below: such a view sees nothing
+    const size_t lb = (size_t)p * lcap, qb = (size_t)p * qcap;
+    const float th = V.th;
+    int base = 0;                                                      // queries before this tile (uniform)
+    for (int i0 = 0; i0 < n; i0 += TPB) {
+        const int i = i0 + tid;
+        bool vis = false;
+        float u = 0.0f, v = 0.0f, angle = 0.0f;
+        int level = 0, slot = -1;
+        if (i < n) {
+            slot = list[lb + i];
+            const int octave = src_kps[lb + i].octave;                 // independent of the slot: in flight with the list
+            angle = src_kps[lb + i].angle;
+            if (!(skip && skip[lb + i]) && slot >= 0 && slot < capacity && live[slot]) {
+                const float4* g = reinterpret_cast<const float4*>(geom) + (size_t)slot * 2;
+                const float4 g0 = g[0];
+                const float P[3] = {g0.x, g0.y, g0.z};
+                level = from_last ? octave : predicted_level(V, F, P, g[1].z);
+                vis = level >= 0 && level < F.n && project_source(V, P, u, v);
+            }
+        }
+        const unsigned long long m = __ballot(vis);
+        if ((tid & 63) == 0) wave_total[wave] = __popcll(m);
+        __syncthreads();
+        int before = base, total = 0;
+        for (int w = 0; w < WAVES; w++) {
+            const int c = wave_total[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        const int q = before + lane_rank(m);
+        if (vis && q < qcap) {
+            float* o = qxyr + (qb + q) * 3;
+            o[0] = u; o[1] = v; o[2] = th * F.f[level];
+            qlev[(qb + q) * 2] = level - 1;
+            qlev[(qb + q) * 2 + 1] = level + 1;
+            qangle[qb + q] = angle;
+            qpos[qb + q] = i;
+            const uint4* d = from_last ? reinterpret_cast<const uint4*>(src_desc) + (lb + i) * 2 : reinterpret_cast<const uint4*>(tdesc) + (size_t)slot * 2;
+            uint4* od = reinterpret_cast<uint4*>(qdesc) + (qb + q) * 2;
+            od[0] = d[0]; od[1] = d[1];
+        }
+        base += total;
+        __syncthreads();                                               // wave_total is rewritten by the next tile
+    }
+    if (tid == 0) {
+        nq[p] = base;
+        if (nq_clamped) nq_clamped[p] = base > qcap ? qcap : base;
+        overflow[p] = !known_mode ? ORBX_ERR_ARG : (base > qcap ? 1 : 0);
+    }
+}
+
 __global__ __launch_bounds__(TPB) void k_t2slot(const int32_t* t2q, const int32_t* qpos, const int32_t* list, const int32_t* nt, int cap, int qcap,
                                                 int lcap, int32_t* t2slot) {
     const int p = blockIdx.y, idx = blockIdx.x * TPB + threadIdx.x;
@@ -178,6 +287,22 @@ __global__ __launch_bounds__(TPB) void k_t2slot(const int32_t* t2q, const int32_
         }
     }
     t2slot[(size_t)p * cap + idx] = out;
+}
+
+__global__ __launch_bounds__(TPB) void k_t2source(const int32_t* t2q, const int32_t* qpos, const int32_t* list, const int32_t* nt, int cap, int qcap,
+                                                  int lcap, int32_t* t2pos, int32_t* t2slot) {
+    const int p = blockIdx.y, idx = blockIdx.x * TPB + threadIdx.x;
+    if (idx >= cap) return;
+    int pos = -1, slot = -1;
+    if (idx < nt[p]) {
+        const int q = t2q[(size_t)p * cap + idx];
+        if (q >= 0 && q < qcap) {
+            pos = qpos[(size_t)p * qcap + q];
+            slot = list[(size_t)p * lcap + pos];
+        }
+    }
+    t2pos[(size_t)p * cap + idx] = pos;
+    if (t2slot) t2slot[(size_t)p * cap + idx] = slot;
 }
 
 }  // namespace orbp
@@ -291,10 +416,11 @@ void launch_project(orbp_map* m, const orbp_view* d_views, int nviews, const orb
 // the query arrays between projection and search, carved from one buffer
 struct Scratch {
     float* qxyr; int32_t* qlev; uint8_t* qdesc; int32_t* qpos; int32_t* nq_clamped; int32_t* q2t; int32_t* t2q;
-    static size_t bytes(int nviews, int cap, int qcap) {
+    float* qangle;                                     // the source-frame searches only (with_angle)
+    static size_t bytes(int nviews, int cap, int qcap, bool with_angle = false) {
         const size_t nqc = (size_t)nviews * qcap;
         return al256(nqc * 12) + al256(nqc * 8) + al256(nqc * 32) + al256(nqc * 4) + al256((size_t)nviews * 4) + al256(nqc * 4) +
-               al256((size_t)nviews * cap * 4);
+               al256((size_t)nviews * cap * 4) + (with_angle ? al256(nqc * 4) : 0);
     }
     Scratch(uint8_t* b, int nviews, int cap, int qcap) {
         const size_t nqc = (size_t)nviews * qcap;
@@ -304,7 +430,8 @@ struct Scratch {
         qpos = (int32_t*)b; b += al256(nqc * 4);
         nq_clamped = (int32_t*)b; b += al256((size_t)nviews * 4);
         q2t = (int32_t*)b; b += al256(nqc * 4);
-        t2q = (int32_t*)b;
+        t2q = (int32_t*)b; b += al256((size_t)nviews * cap * 4);
+        qangle = (float*)b;
     }
 };
 
@@ -329,6 +456,44 @@ int track_locked(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::
                                                    nullptr, nullptr, S.nq_clamped, qcap, nviews, S.q2t, S.t2q, nullptr, nullptr, d_nmatches, st);
     if (rc != ORBX_OK) { (void)m->end(st); return rc; }
     orbp::k_t2slot<<<dim3((cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(S.t2q, S.qpos, d_list, d_nt, cap, qcap, lcap, d_t2slot);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, m->end(st));
+    return ORBX_OK;
+}
+
+void launch_project_source(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const int32_t* d_list, const int32_t* d_nlist,
+                           int lcap, const uint8_t* d_skip, const orbx_keypoint* d_src_kps, const uint8_t* d_src_desc, float* d_qxyr, int32_t* d_qlev,
+                           uint8_t* d_qdesc, float* d_qangle, int32_t* d_qpos, int32_t* d_nq, int32_t* d_nq_clamped, int32_t* d_overflow, int qcap,
+                           hipStream_t st) {
+    orbp::k_project_source<<<nviews, orbp::TPB, 0, st>>>(d_views, F, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(),
+                                                         d_list, d_nlist, lcap, d_skip, d_src_kps, d_src_desc, d_qxyr, d_qlev, d_qdesc, d_qangle, d_qpos,
+                                                         d_nq, d_nq_clamped, d_overflow, qcap);
+}
+
+// what the source-frame walks need beyond check_walk: a list (entry i is feature i of the source frame) and its key points
+int check_source(const orbp_map* m, const void* d_views, int nviews, const int32_t* d_list, const int32_t* d_nlist, int lcap, int qcap,
+                 const void* d_src_kps, const void* d_src_desc) {
+    if (!m || nviews < 0 || nviews > ORBP_MAX_VIEWS || lcap < 1 || qcap < 1) return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    if (!d_views || !d_list || !d_nlist || !d_src_kps || ((uintptr_t)d_src_desc & 15)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+int track_source_locked(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const int32_t* d_list, const int32_t* d_nlist,
+                        int lcap, const uint8_t* d_skip, const orbx_keypoint* d_src_kps, const uint8_t* d_src_desc, const orbf_bounds* b,
+                        const orbs_params& prm, const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int32_t* d_cell_off,
+                        const int32_t* d_cell_feat, const int32_t* d_nt, int cap, const uint8_t* d_claimed, int qcap, int32_t* d_t2pos,
+                        int32_t* d_t2slot, int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, uint8_t* scratch, hipStream_t st) {
+    const Scratch S(scratch, nviews, cap, qcap);
+    HIPCHK(m, m->begin(st));
+    launch_project_source(m, d_views, nviews, F, d_list, d_nlist, lcap, d_skip, d_src_kps, d_src_desc, S.qxyr, S.qlev, S.qdesc, S.qangle, S.qpos, d_nq,
+                          S.nq_clamped, d_overflow, qcap, st);
+    HIPCHK(m, hipGetLastError());
+    const int rc = orbs_window_search_batch_device(b, &prm, d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt, cap, d_claimed, S.qxyr, S.qlev, S.qdesc,
+                                                   S.qangle, nullptr, S.nq_clamped, qcap, nviews, S.q2t, S.t2q, nullptr, nullptr, d_nmatches, st);
+    if (rc != ORBX_OK) { (void)m->end(st); return rc; }
+    orbp::k_t2source<<<dim3((cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(S.t2q, S.qpos, d_list, d_nt, cap, qcap, lcap, d_t2pos,
+                                                                                           d_t2slot);
     HIPCHK(m, hipGetLastError());
     HIPCHK(m, m->end(st));
     return ORBX_OK;
@@ -585,6 +750,141 @@ int orbp_track(orbp_map* m, const orbp_view* view, const float* factors, int nle
     *nmatches = cnt[2];
     if (nt > 0) std::memcpy(t2slot, h + o_t2s, (size_t)nt * 4);
     if (rec && nlist > 0) std::memcpy(rec, h + o_rec, (size_t)nlist * sizeof(orbp_record));
+    return ORBX_OK;
+}
+
+int orbp_project_source_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                                     const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const orbx_keypoint* d_src_kps,
+                                     const uint8_t* d_src_desc, float* d_qxyr, int32_t* d_qlev, uint8_t* d_qdesc, float* d_qangle, int32_t* d_qpos,
+                                     int32_t* d_nq, int32_t* d_overflow, int qcap, void* stream) {
+    orbp::Factors F;
+    if (check_source(m, d_views, nviews, d_list, d_nlist, lcap, qcap, d_src_kps, d_src_desc) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    if (!d_qxyr || !d_qlev || !d_qdesc || ((uintptr_t)d_qdesc & 15) || !d_qangle || !d_qpos || !d_nq || !d_overflow) return ORBX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(m->mu);
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    HIPCHK(m, m->begin(st));
+    launch_project_source(m, d_views, nviews, F, d_list, d_nlist, lcap, d_skip, d_src_kps, d_src_desc, d_qxyr, d_qlev, d_qdesc, d_qangle, d_qpos, d_nq,
+                          nullptr, d_overflow, qcap, st);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, m->end(st));
+    return ORBX_OK;
+}
+
+int orbp_track_source_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                                   const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const orbx_keypoint* d_src_kps,
+                                   const uint8_t* d_src_desc, const orbf_bounds* b, const orbs_params* prm, const orbx_keypoint* d_kps_un,
+                                   const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat, const int32_t* d_nt, int cap,
+                                   const uint8_t* d_claimed, int qcap, int32_t* d_t2pos, int32_t* d_t2slot, int32_t* d_nmatches, int32_t* d_nq,
+                                   int32_t* d_overflow, void* stream) {
+    orbp::Factors F;
+    if (check_source(m, d_views, nviews, d_list, d_nlist, lcap, qcap, d_src_kps, d_src_desc) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (!b || !prm || prm->rule != ORBS_RULE_BEST || cap < 1 || cap > ORBF_MAX_FEATURES || qcap > ORBF_MAX_FEATURES) return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    if (!d_kps_un || !d_desc || !d_cell_off || !d_cell_feat || !d_nt || !d_t2pos || !d_nmatches || !d_nq || !d_overflow) return ORBX_ERR_ARG;
+    if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
+    std::lock_guard<std::mutex> lk(m->mu);
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    const int rc = grow(m, m->scratch, Scratch::bytes(nviews, cap, qcap, true));
+    if (rc != ORBX_OK) return rc;
+    return track_source_locked(m, d_views, nviews, F, d_list, d_nlist, lcap, d_skip, d_src_kps, d_src_desc, b, *prm, d_kps_un, d_desc, d_cell_off,
+                               d_cell_feat, d_nt, cap, d_claimed, qcap, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow, m->scratch.as<uint8_t>(),
+                               stream ? (hipStream_t)stream : (hipStream_t)m->own);
+}
+
+int orbp_track_source(orbp_map* m, const orbp_view* view, const float* factors, int nlevels, const int32_t* list, int nlist, const uint8_t* skip,
+                      const orbx_keypoint* src_kps, const uint8_t* src_desc, int src_on_device, const orbf_bounds* b, const orbs_params* prm,
+                      const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off, const int32_t* cell_feat, const uint8_t* claimed,
+                      int nt, int frame_on_device, int qcap, int32_t* t2pos, int32_t* t2slot, int* nmatches, int* nvisible, void* stream) {
+    orbp::Factors F;
+    if (!m || !view || !b || !prm || prm->rule != ORBS_RULE_BEST || nlist < 0 || nt < 0 || nt > ORBF_MAX_FEATURES || qcap < 1 ||
+        qcap > ORBF_MAX_FEATURES)
+        return ORBX_ERR_ARG;
+    if (fill_factors(factors, nlevels, F) != ORBX_OK) return ORBX_ERR_ARG;
+    const bool from_last = view->mode == ORBP_MODE_LAST_FRAME;
+    if (!from_last && view->mode != ORBP_MODE_KEYFRAME) return ORBX_ERR_ARG;
+    if (nlist > 0 && (!list || !src_kps || (from_last && !src_desc))) return ORBX_ERR_ARG;
+    if (src_on_device && ((uintptr_t)src_desc & 15)) return ORBX_ERR_ARG;
+    if (!nmatches || (nt > 0 && (!kps_un || !desc || !cell_feat || !t2pos)) || !cell_off) return ORBX_ERR_ARG;
+    const int cap = std::max(nt, 1), lcap = std::max(nlist, 1);
+    if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
+    std::lock_guard<std::mutex> lk(m->mu);
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    // one pinned block up, one down: [view | nt, nlist | list | skip | source frame (host form) | frame (host form)] and
+    // [nq, overflow, nmatches | t2pos | t2slot]
+    const bool up_src = !src_on_device && nlist > 0, up_src_desc = up_src && from_last, up_frame = !frame_on_device;
+    size_t o = 0;
+    const size_t o_view = o; o += al256(sizeof(orbp_view));
+    const size_t o_nt = o; o += 256;                                   // nt, nlist
+    const size_t o_list = o; o += al256((size_t)lcap * 4);
+    const size_t o_skip = o; o += skip ? al256((size_t)lcap) : 0;
+    const size_t o_skps = o; o += up_src ? al256((size_t)lcap * sizeof(orbx_keypoint)) : 0;
+    const size_t o_sdesc = o; o += up_src_desc ? al256((size_t)lcap * 32) : 0;
+    const size_t o_kps = o; o += up_frame ? al256((size_t)cap * sizeof(orbx_keypoint)) : 0;
+    const size_t o_desc = o; o += up_frame ? al256((size_t)cap * 32) : 0;
+    const size_t o_coff = o; o += up_frame ? al256((size_t)(ORBF_GRID_CELLS + 1) * 4) : 0;
+    const size_t o_cfeat = o; o += up_frame ? al256((size_t)cap * 4) : 0;
+    const size_t o_claim = o; o += up_frame && claimed ? al256((size_t)cap) : 0;
+    const size_t up_bytes = o;
+    const size_t o_cnt = o; o += 256;                                  // nq, overflow, nmatches
+    const size_t o_t2p = o; o += al256((size_t)cap * 4);
+    const size_t o_t2s = o; o += t2slot ? al256((size_t)cap * 4) : 0;
+    const size_t io_bytes = o;
+    const size_t total = io_bytes + Scratch::bytes(1, cap, qcap, true);
+    if (m->h_one.size() < io_bytes) {
+        if (m->chained) HIPCHK(m, hipEventSynchronize(m->chain));
+        HIPCHK(m, m->h_one.ensure(io_bytes + io_bytes / 2, hipHostMallocDefault));
+    }
+    int rc = grow(m, m->one, total + total / 2);
+    if (rc != ORBX_OK) return rc;
+    uint8_t* h = m->h_one.as<uint8_t>();
+    uint8_t* d = m->one.as<uint8_t>();
+    std::memcpy(h + o_view, view, sizeof(orbp_view));
+    reinterpret_cast<int32_t*>(h + o_nt)[0] = nt;
+    reinterpret_cast<int32_t*>(h + o_nt)[1] = nlist;
+    if (nlist > 0) std::memcpy(h + o_list, list, (size_t)nlist * 4);
+    if (skip && nlist > 0) std::memcpy(h + o_skip, skip, (size_t)nlist);
+    if (up_src) std::memcpy(h + o_skps, src_kps, (size_t)nlist * sizeof(orbx_keypoint));
+    if (up_src_desc) std::memcpy(h + o_sdesc, src_desc, (size_t)nlist * 32);
+    if (up_frame) {
+        std::memcpy(h + o_kps, kps_un, (size_t)nt * sizeof(orbx_keypoint));
+        std::memcpy(h + o_desc, desc, (size_t)nt * 32);
+        std::memcpy(h + o_coff, cell_off, (size_t)(ORBF_GRID_CELLS + 1) * 4);
+        std::memcpy(h + o_cfeat, cell_feat, (size_t)nt * 4);
+        if (claimed) std::memcpy(h + o_claim, claimed, (size_t)nt);
+    }
+    HIPCHK(m, m->begin(st));
+    HIPCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    int32_t* d_cnt = reinterpret_cast<int32_t*>(d + o_cnt);
+    // with nlist == 0 nothing is read through the source pointers; the kernel still wants them non-NULL for a last-frame view
+    const orbx_keypoint* d_skps = up_src ? reinterpret_cast<const orbx_keypoint*>(d + o_skps) : (nlist > 0 ? src_kps : reinterpret_cast<const orbx_keypoint*>(d));
+    const uint8_t* d_sdesc = up_src_desc ? d + o_sdesc : (nlist > 0 ? src_desc : d);
+    rc = track_source_locked(m, reinterpret_cast<const orbp_view*>(d + o_view), 1, F, reinterpret_cast<const int32_t*>(d + o_list),
+                             reinterpret_cast<const int32_t*>(d + o_nt) + 1, lcap, skip ? d + o_skip : nullptr, d_skps, d_sdesc, b, *prm,
+                             up_frame ? reinterpret_cast<const orbx_keypoint*>(d + o_kps) : kps_un, up_frame ? d + o_desc : desc,
+                             up_frame ? reinterpret_cast<const int32_t*>(d + o_coff) : cell_off,
+                             up_frame ? reinterpret_cast<const int32_t*>(d + o_cfeat) : cell_feat, reinterpret_cast<const int32_t*>(d + o_nt), cap,
+                             up_frame ? (claimed ? d + o_claim : nullptr) : claimed, qcap, reinterpret_cast<int32_t*>(d + o_t2p),
+                             t2slot ? reinterpret_cast<int32_t*>(d + o_t2s) : nullptr, d_cnt + 2, d_cnt, d_cnt + 1, d + io_bytes, st);
+    if (rc != ORBX_OK) return rc;
+    HIPCHK(m, hipMemcpyAsync(h + o_cnt, d + o_cnt, io_bytes - o_cnt, hipMemcpyDeviceToHost, st));
+    HIPCHK(m, m->end(st));
+    HIPCHK(m, hipStreamSynchronize(st));
+    const int32_t* cnt = reinterpret_cast<const int32_t*>(h + o_cnt);
+    if (nvisible) *nvisible = cnt[0];
+    if (cnt[1]) return ORBX_ERR_CAPACITY;
+    *nmatches = cnt[2];
+    if (nt > 0) {
+        std::memcpy(t2pos, h + o_t2p, (size_t)nt * 4);
+        if (t2slot) std::memcpy(t2slot, h + o_t2s, (size_t)nt * 4);
+    }
     return ORBX_OK;
 }
 

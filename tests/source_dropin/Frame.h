@@ -1,0 +1,34 @@
+// Stand-in ORB_SLAM::Frame for the harness of LocalMapPoints' last-frame / key-frame searches: the public members of the reference's
+// include/Frame.h that LocalMapPoints.cc, LocalMapPointsSource.cc and ORBmatcherAccess.h read, under the reference's names and types.
+// cvmini.h and MapPoint.h are the stand-ins of tests/mappoints_dropin.
+#pragma once
+#include <cstddef>
+#include <vector>
+
+#include "cvmini.h"
+
+#define FRAME_GRID_ROWS 48
+#define FRAME_GRID_COLS 64
+
+namespace ORB_SLAM {
+
+class MapPoint;
+class KeyFrame;
+
+class Frame {
+public:
+    static float fx, fy, cx, cy;
+    static int mnMinX, mnMaxX, mnMinY, mnMaxY;
+    static float mfGridElementWidthInv, mfGridElementHeightInv;
+    std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
+    cv::Mat mDescriptors;
+    std::vector<MapPoint*> mvpMapPoints;
+    std::vector<bool> mvbOutlier;
+    std::vector<std::size_t> mGrid[FRAME_GRID_COLS][FRAME_GRID_ROWS];
+    cv::Mat mTcw;
+    long unsigned int mnId = 0;
+    int mnScaleLevels = 0;
+    std::vector<float> mvScaleFactors;
+};
+
+}  // namespace ORB_SLAM

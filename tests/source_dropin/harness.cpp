@@ -1,0 +1,182 @@
+// Drives the two projection searches of ORB_SLAM::LocalMapPoints (orb_slam_amd/cpp/LocalMapPointsSource.cc, over the stand-in Frame.h /
+// KeyFrame.h of this directory and the MapPoint.h of tests/mappoints_dropin) through a script; tests/test_gpu_source_dropin.py builds the
+// script, computes what the reference would leave behind with tests/source_ref.py and the CPU oracle, and compares.  Floats travel as
+// the hex of their bit pattern.
+//
+//   harness SCRIPT
+//
+// Script lines:
+//   cam fx fy cx cy MINX MAXX MINY MAXY invw invh      Frame's statics
+//   factors N f ...                                    mvScaleFactors
+//   new REFRESH CAPACITY                               LocalMapPoints(0.8f, REFRESH, CAPACITY)
+//   mp ID x y z nx ny nz dmin dmax DESC                creates (or changes, WITHOUT Put) map point ID; DESC = 64 hex digits
+//   put ID | forget ID | bad ID 0|1                    Put / Forget / the bad flag
+//   frame N, then N lines "x y octave angle DESC"      the current frame: key points filed in mGrid by Frame::PosInGrid's rule
+//   pose r00 .. r22 t0 t1 t2                           the current frame's mTcw
+//   hold IDX ID                                        CurrentFrame.mvpMapPoints[IDX] = map point ID
+//   last N, then N lines "octave angle DESC ID OUTLIER"    the last frame (ID -1: the feature has no map point)
+//   kf N, then N lines "octave angle ID"               the key frame
+//   found K id ...                                     sAlreadyFound
+//   search_last th CHECK         -> "S ret size capacity", then "M idx id" for every current feature that holds a map point
+//   search_kf th ORBDIST CHECK   -> the same
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <set>
+#include <sstream>
+#include <string>
+
+#include "Frame.h"
+#include "KeyFrame.h"
+#include "LocalMapPoints.h"
+#include "MapPoint.h"
+
+namespace ORB_SLAM {
+float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
+int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
+float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
+}
+using namespace ORB_SLAM;
+
+namespace {
+
+float rdf(std::istringstream& in) {
+    std::string h;
+    in >> h;
+    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+void rddesc(std::istringstream& in, unsigned char* d) {
+    std::string h;
+    in >> h;
+    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
+}
+void report(int ret, const LocalMapPoints& L, const Frame& F) {
+    printf("S %d %zu %d\n", ret, L.size(), L.capacity());
+    for (size_t i = 0; i < F.mvpMapPoints.size(); i++)
+        if (F.mvpMapPoints[i]) printf("M %zu %lu\n", i, F.mvpMapPoints[i]->mnId);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream f(argv[1]);
+    std::string line;
+    std::map<long, std::unique_ptr<MapPoint> > mps;
+    std::unique_ptr<LocalMapPoints> L;
+    Frame F, Last;
+    KeyFrame KF;
+    std::set<MapPoint*> found;
+    std::vector<float> factors;
+    while (std::getline(f, line)) {
+        std::istringstream in(line);
+        std::string op;
+        if (!(in >> op)) continue;
+        if (op == "cam") {
+            Frame::fx = rdf(in); Frame::fy = rdf(in); Frame::cx = rdf(in); Frame::cy = rdf(in);
+            in >> Frame::mnMinX >> Frame::mnMaxX >> Frame::mnMinY >> Frame::mnMaxY;
+            Frame::mfGridElementWidthInv = rdf(in); Frame::mfGridElementHeightInv = rdf(in);
+        } else if (op == "factors") {
+            int n; in >> n;
+            factors.resize(n);
+            for (int i = 0; i < n; i++) factors[i] = rdf(in);
+        } else if (op == "new") {
+            int refresh, cap; in >> refresh >> cap;
+            L.reset(new LocalMapPoints(0.8f, refresh != 0, cap));
+        } else if (op == "mp") {
+            long id; in >> id;
+            if (!mps.count(id)) { mps[id].reset(new MapPoint); mps[id]->mnId = id; }
+            MapPoint& m = *mps[id];
+            for (int k = 0; k < 3; k++) m.mWorldPos.at<float>(k) = rdf(in);
+            for (int k = 0; k < 3; k++) m.mNormalVector.at<float>(k) = rdf(in);
+            m.mfMinDistance = rdf(in); m.mfMaxDistance = rdf(in);
+            rddesc(in, m.mDescriptor.ptr<unsigned char>(0));
+        } else if (op == "put") { long id; in >> id; L->Put(mps.at(id).get());
+        } else if (op == "forget") { long id; in >> id; L->Forget(mps.at(id).get());
+        } else if (op == "bad") { long id; int v; in >> id >> v; mps.at(id)->mbBad = v != 0;
+        } else if (op == "frame") {
+            int n; in >> n;
+            F.mvKeysUn.assign(n, cv::KeyPoint());
+            F.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            F.mvpMapPoints.assign(n, nullptr);
+            F.mnScaleLevels = (int)factors.size();
+            F.mvScaleFactors = factors;
+            for (int x = 0; x < FRAME_GRID_COLS; x++) for (int y = 0; y < FRAME_GRID_ROWS; y++) F.mGrid[x][y].clear();
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                cv::KeyPoint& kp = F.mvKeysUn[i];
+                kp.pt.x = rdf(kin); kp.pt.y = rdf(kin);
+                kin >> kp.octave;
+                kp.angle = rdf(kin);
+                rddesc(kin, F.mDescriptors.ptr<unsigned char>(i));
+                const int px = (int)std::round((kp.pt.x - Frame::mnMinX) * Frame::mfGridElementWidthInv);      // Frame::PosInGrid
+                const int py = (int)std::round((kp.pt.y - Frame::mnMinY) * Frame::mfGridElementHeightInv);
+                if (px >= 0 && px < FRAME_GRID_COLS && py >= 0 && py < FRAME_GRID_ROWS) F.mGrid[px][py].push_back(i);
+            }
+            F.mvKeys = F.mvKeysUn;
+        } else if (op == "pose") {
+            F.mTcw = cv::Mat(4, 4, CV_32F);
+            for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) F.mTcw.at<float>(r, c) = r == c ? 1.f : 0.f;
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) F.mTcw.at<float>(r, c) = rdf(in);
+            for (int r = 0; r < 3; r++) F.mTcw.at<float>(r, 3) = rdf(in);
+        } else if (op == "hold") {
+            int idx; long id; in >> idx >> id;
+            F.mvpMapPoints[idx] = mps.at(id).get();
+        } else if (op == "last") {
+            int n; in >> n;
+            Last.mvKeys.assign(n, cv::KeyPoint());
+            Last.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            Last.mvpMapPoints.assign(n, nullptr);
+            Last.mvbOutlier.assign(n, false);
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                long id; int outlier;
+                kin >> Last.mvKeys[i].octave;
+                Last.mvKeys[i].angle = rdf(kin);
+                rddesc(kin, Last.mDescriptors.ptr<unsigned char>(i));
+                kin >> id >> outlier;
+                if (id >= 0) Last.mvpMapPoints[i] = mps.at(id).get();
+                Last.mvbOutlier[i] = outlier != 0;
+            }
+            Last.mvKeysUn = Last.mvKeys;
+        } else if (op == "kf") {
+            int n; in >> n;
+            KF.mvKeysUn.assign(n, cv::KeyPoint());
+            KF.mvpMapPoints.assign(n, nullptr);
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                long id;
+                kin >> KF.mvKeysUn[i].octave;
+                KF.mvKeysUn[i].angle = rdf(kin);
+                kin >> id;
+                if (id >= 0) KF.mvpMapPoints[i] = mps.at(id).get();
+            }
+        } else if (op == "found") {
+            int k; in >> k;
+            found.clear();
+            for (int i = 0; i < k; i++) { long id; in >> id; found.insert(mps.at(id).get()); }
+        } else if (op == "search_last") {
+            const float th = rdf(in);
+            int check; in >> check;
+            report(L->SearchByProjection(F, Last, th, check != 0), *L, F);
+        } else if (op == "search_kf") {
+            const float th = rdf(in);
+            int orbdist, check; in >> orbdist >> check;
+            report(L->SearchByProjection(F, &KF, found, th, orbdist, check != 0), *L, F);
+        } else {
+            fprintf(stderr, "unknown script line: %s\n", line.c_str());
+            return 2;
+        }
+    }
+    return 0;
+}
