@@ -57,6 +57,9 @@ EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_b
 EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
              "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
              "orbp_track_source_batch_device", "orbp_track_source"]
+# include/orbt.h (triangulation of new map points)
+EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate"]
+(T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
 # orbp_view.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME = 0, 1, 2
 
@@ -121,6 +124,23 @@ class View(ctypes.Structure):
         v.view_cos_limit, v.th, v.mode, v.reserved = float(view_cos_limit), float(th), 0, 0
         return v
 
+
+class TriCamera(ctypes.Structure):
+    """orbt_camera: one key frame's pose and camera"""
+    _fields_ = [("Rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("Ow", ctypes.c_float * 3),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float)]
+
+
+class TriPair(ctypes.Structure):
+    """orbt_pair: (mpCurrentKeyFrame, pKF2) and mfScaleFactor of the first"""
+    _fields_ = [("kf1", TriCamera), ("kf2", TriCamera), ("scale_factor", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+TRI_CAMERA_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
+                             ("cx", np.float32), ("cy", np.float32)])
+# orbt_pair as a numpy record (arrays of pairs are uploaded as they are)
+TRI_PAIR_DTYPE = np.dtype([("kf1", TRI_CAMERA_DTYPE), ("kf2", TRI_CAMERA_DTYPE), ("scale_factor", np.float32), ("reserved", np.int32)])
+assert TRI_PAIR_DTYPE.itemsize == ctypes.sizeof(TriPair) == 160
 
 # orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
 VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
@@ -261,6 +281,9 @@ def lib():
                                                      vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
         L.orbp_track_source.argtypes = [vp, ctypes.POINTER(View), vp, ci, vp, ci, vp, vp, vp, ci, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
                                         vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
+        L.orbt_triangulate_batch_device.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    ci, vp, vp, vp]
+        L.orbt_triangulate.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ci), ci]
         _LIB = L
     return _LIB
 
@@ -888,6 +911,49 @@ def triangulation_search_batch_device(th, check_orientation, d_F12, level_sigma2
                                                       nproblems, d_q2t, d_t2q, d_best or None, d_second or None, d_nmatches, stream or None)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbs_triangulation_search_batch_device")
+
+
+def _level_tables(factors1, sigma2_1, factors2, sigma2_2):
+    t = [np.ascontiguousarray(x, dtype=np.float32) for x in (factors1, sigma2_1, factors2, sigma2_2)]
+    if len({len(x) for x in t}) != 1:
+        raise ValueError("the four level tables must have one length")
+    return t
+
+
+def triangulate_batch_device(d_pairs, npairs, factors1, sigma2_1, factors2, sigma2_2, d_kps1, d_n1, cap1, stride1, d_kps2, d_n2, cap2, d_q2t, d_qindex,
+                             d_nq, qcap, d_status, d_x3d, d_v, d_match12, d_acc_idx, d_acc_x3d, d_count, d_overflow, ocap, d_qvalid=0, d_claimed=0,
+                             stream=0):
+    """the match loop of LocalMapping::CreateNewMapPoints over the matches the triangulation search left on the device (include/orbt.h);
+    device pointers as ints (0 = NULL), the level tables host float arrays (mvScaleFactors / mvLevelSigma2 of KF1 and KF2)"""
+    f1, s1, f2, s2 = _level_tables(factors1, sigma2_1, factors2, sigma2_2)
+    rc = lib().orbt_triangulate_batch_device(d_pairs, npairs, f1.ctypes.data, s1.ctypes.data, f2.ctypes.data, s2.ctypes.data, len(f1), d_kps1, d_n1, cap1,
+                                             stride1, d_kps2, d_n2, cap2, d_q2t, d_qindex or None, d_nq, qcap, d_status, d_x3d, d_v or None, d_match12,
+                                             d_acc_idx, d_acc_x3d, d_count, d_overflow, ocap, d_qvalid or None, d_claimed or None, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbt_triangulate_batch_device")
+
+
+def triangulate(pair, factors1, sigma2_1, factors2, sigma2_2, kps1, kps2, match12, ocap=None, want_v=True, device=0):
+    """one pair, host arrays, synchronous: pair = a TRI_PAIR_DTYPE record, match12 = vMatches12.
+    -> (status[n1], x3d[n1, 3], v[n1, 4] or None, acc_idx[count, 2], acc_x3d[count, 3]); OrbxError(ORBX_ERR_CAPACITY) when more than ocap are accepted"""
+    f1, s1, f2, s2 = _level_tables(factors1, sigma2_1, factors2, sigma2_2)
+    pr = np.ascontiguousarray(pair, dtype=TRI_PAIR_DTYPE).reshape(1)
+    k1 = np.ascontiguousarray(kps1, dtype=KP_DTYPE); k2 = np.ascontiguousarray(kps2, dtype=KP_DTYPE)
+    m12 = np.ascontiguousarray(match12, dtype=np.int32)
+    n1, n2 = len(k1), len(k2)
+    if len(m12) != n1:
+        raise ValueError("match12 must have one entry per feature of KF1")
+    ocap = max(n1, 1) if ocap is None else ocap
+    status = np.zeros(max(n1, 1), np.uint8); x3d = np.zeros((max(n1, 1), 3), np.float32)
+    v = np.zeros((max(n1, 1), 4), np.float32) if want_v else None
+    acc_idx = np.zeros((max(ocap, 1), 2), np.int32); acc_x3d = np.zeros((max(ocap, 1), 3), np.float32)
+    count = ctypes.c_int(0)
+    rc = lib().orbt_triangulate(pr.ctypes.data, f1.ctypes.data, s1.ctypes.data, f2.ctypes.data, s2.ctypes.data, len(f1), k1.ctypes.data if n1 else None, n1,
+                                k2.ctypes.data if n2 else None, n2, m12.ctypes.data if n1 else None, status.ctypes.data, x3d.ctypes.data,
+                                v.ctypes.data if want_v else None, acc_idx.ctypes.data, acc_x3d.ctypes.data, ocap, ctypes.byref(count), device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbt_triangulate (accepted: %d)" % count.value)
+    return status[:n1], x3d[:n1], (v[:n1] if want_v else None), acc_idx[:count.value], acc_x3d[:count.value]
 
 
 def epipolar_bound(sigma2):
