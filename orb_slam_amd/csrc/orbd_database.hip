@@ -279,16 +279,7 @@ __global__ __launch_bounds__(TPB) void k_query(QueryArgs a) {
 // ------------------------------------------------------------------------------------------------ host side
 namespace {
 
-// selects the database's device for one entry point and gives the caller's current device back
-struct DeviceScope {
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-    int prev = -1;
-    bool ok = false;
-};
+using orbx::DeviceScope;
 
 struct SlotHost {
     int32_t off = 0, res = 0;    // segment offset and reserved length in the arena
@@ -314,16 +305,9 @@ struct __attribute__((visibility("hidden"))) orbd_database {
     orbx::DevBuf d_tab, stage, q_stage;
     orbx::PinnedBuf h_tab;
     orbx::Stream own;
-    orbx::Event chain, tab_done;
-    bool chained = false, tab_pending = false;
-
-    // every piece of device work on the database waits for the previous one, whichever stream carried it
-    hipError_t begin(hipStream_t st) { return chained ? hipStreamWaitEvent(st, chain, 0) : hipSuccess; }
-    hipError_t end(hipStream_t st) {
-        const hipError_t e = hipEventRecord(chain, st);
-        chained = chained || e == hipSuccess;
-        return e;
-    }
+    orbx::Chain chain;                   // every piece of device work on the database waits for the previous one, whichever stream carried it
+    orbx::Event tab_done;
+    bool tab_pending = false;
 };
 
 namespace {
@@ -349,7 +333,7 @@ int reserve(orbd_database* db, long long need, hipStream_t st) {
     std::vector<int32_t> tab;
     int32_t pos = 0;
     for (int s : order) { tab.insert(tab.end(), {s, pos, db->slots[s].res}); db->slots[s].off = pos; pos += db->slots[s].res; }
-    HIPTRY(db->begin(st));
+    HIPTRY(db->chain.begin(st));
     if (!order.empty()) {
         orbx::DevBuf d;
         HIPTRY(d.ensure(tab.size() * 4));
@@ -364,7 +348,7 @@ int reserve(orbd_database* db, long long need, hipStream_t st) {
     db->ent_val = std::move(val);
     db->ent_slot = std::move(slot);
     HIPTRY(db->list.ensure((size_t)cap * 4));
-    HIPTRY(db->end(st));
+    HIPTRY(db->chain.end(st));
     db->arena_cap = cap;
     db->arena_hi = pos;
     db->dirty = true;
@@ -409,7 +393,7 @@ int launch_add(orbd_database* db, const int32_t* slots, int nframes, const uint3
     if (rc != ORBX_OK) return rc;
     if (db->tab_pending) HIPTRY(hipEventSynchronize(db->tab_done));
     std::copy(slots, slots + nframes, db->h_tab.as<int32_t>());
-    HIPTRY(db->begin(st));
+    HIPTRY(db->chain.begin(st));
     HIPTRY(hipMemcpyAsync(db->d_tab.as(), db->h_tab.as(), (size_t)nframes * 4, hipMemcpyHostToDevice, st));
     HIPTRY(hipEventRecord(db->tab_done, st));
     db->tab_pending = true;
@@ -417,7 +401,7 @@ int launch_add(orbd_database* db, const int32_t* slots, int nframes, const uint3
                                                db->ent_id.as<uint32_t>(), db->ent_val.as<double>(), db->ent_slot.as<int32_t>(),
                                                db->slot_off.as<int32_t>(), db->slot_n.as<int32_t>(), db->slot_seq.as<uint32_t>(), d_status);
     HIPTRY(hipGetLastError());
-    HIPTRY(db->end(st));
+    HIPTRY(db->chain.end(st));
     for (int f = 0; f < nframes; f++) {
         SlotHost& h = db->slots[slots[f]];
         h.present = true;
@@ -464,7 +448,7 @@ int orbd_create(const orbv_vocabulary* voc, int capacity, int device, orbd_datab
         db->word_off.ensure(((size_t)nw + 1) * 4) != hipSuccess || db->cursor.ensure(((size_t)nw + 1) * 4) != hipSuccess ||
         db->keys.ensure((size_t)db->rows * db->sort_cap * 8) != hipSuccess || db->vals.ensure((size_t)db->rows * db->sort_cap * 4) != hipSuccess ||
         (capacity > orbd::LDS_SLOTS && db->cnt_rank.ensure((size_t)db->rows * capacity * 8) != hipSuccess) ||
-        db->list.ensure(4) != hipSuccess || db->own.ensure() != hipSuccess || db->chain.ensure() != hipSuccess ||
+        db->list.ensure(4) != hipSuccess || db->own.ensure() != hipSuccess || db->chain.ev.ensure() != hipSuccess ||
         db->tab_done.ensure() != hipSuccess)
         return fail(ORBX_ERR_DEVICE);
     if (hipMemset(db->slot_off.as(), 0, (size_t)capacity * 4) != hipSuccess ||
@@ -479,7 +463,7 @@ int orbd_create(const orbv_vocabulary* voc, int capacity, int device, orbd_datab
 void orbd_destroy(orbd_database* db) {
     if (!db) return;
     DeviceScope ds(db->device);
-    if (db->chained) (void)hipEventSynchronize(db->chain);      // the last piece of device work on the database
+    (void)db->chain.wait();                                     // the last piece of device work on the database
     delete db;
 }
 
@@ -496,7 +480,7 @@ int orbd_add(orbd_database* db, int slot, const uint32_t* ids, const double* val
     hipStream_t st = db->own;
     // one staging block: n ids, n values, the count (reused across adds; the add is synchronous)
     const size_t o_val = ((size_t)n * 4 + 7) & ~(size_t)7, o_n = o_val + (size_t)n * 8;
-    HIPTRY(db->begin(st));
+    HIPTRY(db->chain.begin(st));
     HIPTRY(hipStreamSynchronize(st));
     HIPTRY(db->stage.ensure(o_n + 4));
     const int32_t nn = n;
@@ -537,9 +521,9 @@ int orbd_erase(orbd_database* db, int slot) {
     DeviceScope ds(db->device);
     if (!ds.ok) return ORBX_ERR_DEVICE;
     hipStream_t st = db->own;
-    HIPTRY(db->begin(st));
+    HIPTRY(db->chain.begin(st));
     HIPTRY(hipMemsetAsync(db->slot_n.as<int32_t>() + slot, 0xff, 4, st));
-    HIPTRY(db->end(st));
+    HIPTRY(db->chain.end(st));
     h.present = false;
     db->n_present--;
     db->live_res -= h.res;
@@ -553,9 +537,9 @@ int orbd_clear(orbd_database* db) {
     DeviceScope ds(db->device);
     if (!ds.ok) return ORBX_ERR_DEVICE;
     hipStream_t st = db->own;
-    HIPTRY(db->begin(st));
+    HIPTRY(db->chain.begin(st));
     HIPTRY(hipMemsetAsync(db->slot_n.as(), 0xff, (size_t)db->capacity * 4, st));
-    HIPTRY(db->end(st));
+    HIPTRY(db->chain.end(st));
     for (SlotHost& h : db->slots) h = SlotHost{};
     db->n_present = 0;
     db->slot_hi = 0;
@@ -569,7 +553,7 @@ static int query_locked(orbd_database* db, int nq, const uint32_t* d_bow_id, con
                         const int32_t* d_excl_off, const int32_t* d_excl_slot, int32_t* d_excl_words, int32_t* d_share_slot,
                         int32_t* d_share_words, double* d_share_score, int out_cap, int32_t* d_n_share, int32_t* d_min_common,
                         int32_t* d_status, hipStream_t st) {
-    HIPTRY(db->begin(st));
+    HIPTRY(db->chain.begin(st));
     if (db->dirty) HIPTRY(rebuild(db, st));
     orbd::QueryArgs a;
     a.nq = nq; a.qcap = qcap; a.n_words = db->n_words; a.capacity = db->capacity; a.slot_hi = db->slot_hi;
@@ -588,7 +572,7 @@ static int query_locked(orbd_database* db, int nq, const uint32_t* d_bow_id, con
     else
         orbd::k_query<false><<<grid, orbd::TPB, 0, st>>>(a);
     HIPTRY(hipGetLastError());
-    HIPTRY(db->end(st));
+    HIPTRY(db->chain.end(st));
     return ORBX_OK;
 }
 
@@ -618,26 +602,26 @@ int orbd_query(orbd_database* db, const uint32_t* ids, const double* vals, int n
     if (!ds.ok) return ORBX_ERR_DEVICE;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(db->own);
     // one staging block, kept by the database (it grows, never shrinks): the query (ids, values, count), the exclusion CSR, the outputs
-    size_t total = 0;
-    auto place = [&](size_t bytes) { const size_t o = total; total = (o + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; };
-    const size_t o_val = place((size_t)n * 8), o_id = place((size_t)n * 4), o_n = place(4), o_xoff = place(8);
-    const size_t o_xs = place((size_t)n_excl * 4), o_xw = place((size_t)n_excl * 4);
-    const size_t o_score = place((size_t)out_cap * 8), o_slot = place((size_t)out_cap * 4), o_words = place((size_t)out_cap * 4);
-    const size_t o_res = place(12);
-    HIPTRY(db->begin(st));
+    orbx::Layout L;
+    const auto s_val = L.add<double>(n);
+    const auto s_id = L.add<uint32_t>(n);
+    const auto s_n = L.add<int32_t>(1), s_xoff = L.add<int32_t>(2), s_xs = L.add<int32_t>(n_excl), s_xw = L.add<int32_t>(n_excl);
+    const auto s_score = L.add<double>(out_cap);
+    const auto s_slot = L.add<int32_t>(out_cap), s_words = L.add<int32_t>(out_cap), s_res = L.add<int32_t>(3);
+    HIPTRY(db->chain.begin(st));
     HIPTRY(hipStreamSynchronize(st));       // the staging block is free once earlier work on the database is done
-    HIPTRY(db->q_stage.ensure(total));
+    HIPTRY(db->q_stage.ensure(L.total()));
     uint8_t* base = db->q_stage.as();
-    uint32_t* q_id = reinterpret_cast<uint32_t*>(base + o_id);
-    double* q_val = reinterpret_cast<double*>(base + o_val);
-    double* r_score = reinterpret_cast<double*>(base + o_score);
-    int32_t* q_n = reinterpret_cast<int32_t*>(base + o_n);
-    int32_t* x_off = reinterpret_cast<int32_t*>(base + o_xoff);
-    int32_t* x_slot = reinterpret_cast<int32_t*>(base + o_xs);
-    int32_t* x_words = reinterpret_cast<int32_t*>(base + o_xw);
-    int32_t* r_slot = reinterpret_cast<int32_t*>(base + o_slot);
-    int32_t* r_words = reinterpret_cast<int32_t*>(base + o_words);
-    int32_t* res = reinterpret_cast<int32_t*>(base + o_res);      // n_share, min_common, status
+    uint32_t* q_id = L.at(base, s_id);
+    double* q_val = L.at(base, s_val);
+    double* r_score = L.at(base, s_score);
+    int32_t* q_n = L.at(base, s_n);
+    int32_t* x_off = L.at(base, s_xoff);
+    int32_t* x_slot = L.at(base, s_xs);
+    int32_t* x_words = L.at(base, s_xw);
+    int32_t* r_slot = L.at(base, s_slot);
+    int32_t* r_words = L.at(base, s_words);
+    int32_t* res = L.at(base, s_res);       // n_share, min_common, status
     const int32_t hn = n, hx[2] = {0, n_excl};
     if (n > 0) {
         HIPTRY(hipMemcpyAsync(q_id, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));

@@ -7,9 +7,8 @@
 //       2. one lane per match entry: the parallax test, the 4 x 4 matrix, its null vector by a cyclic Jacobi iteration on A'A in
 //          FP64 (both 4 x 4 matrices stay in registers: every loop is unrolled, no indexed array survives), the six tests; the result
 //          goes to the slot of the match's idx1;
-//       3. the workgroup walks idx1 in ascending order; accepted features are ranked inside their wave by ballot + mbcnt, the wave
-//          totals meet in LDS, and a survivor writes (idx1, idx2, x3D) at base + rank and updates the two flags: ascending idx1
-//          without atomics.
+//       3. the workgroup walks idx1 in ascending order; accepted features are ranked in that order (orbx::tile_rank) and a survivor
+//          writes (idx1, idx2, x3D) at base + rank and updates the two flags: ascending idx1 without atomics.
 //   About 60 bytes in and 40 out per match and a few thousand FP64 operations: at 20 pairs of a few hundred matches the launch is
 //   bound by its latency (the dependent rotations of one lane), not by the FP64 rate or by HBM.
 #include <hip/hip_runtime.h>
@@ -17,6 +16,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "orbp_device.h"
 #include "orbt.h"
 #include "orbx_host.h"
 
@@ -30,10 +30,6 @@ struct Levels {
     float f1[ORBS_MAX_LEVELS], s1[ORBS_MAX_LEVELS], f2[ORBS_MAX_LEVELS], s2[ORBS_MAX_LEVELS];
     int n;
 };
-
-__device__ __forceinline__ int lane_rank(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // one Jacobi rotation of the symmetric S (both halves kept) in the (P, Q) plane, accumulated into V
 template <int P, int Q>
@@ -186,7 +182,7 @@ __global__ __launch_bounds__(TPB) void k_triangulate(const orbt_pair* pairs, Lev
                                                      int ocap, uint8_t* qvalid, uint8_t* claimed) {
     __shared__ orbt_pair P;
     __shared__ int wave_total[WAVES];
-    const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    const int p = blockIdx.x, tid = threadIdx.x;
     if (tid < (int)(sizeof(orbt_pair) / 4)) reinterpret_cast<uint32_t*>(&P)[tid] = reinterpret_cast<const uint32_t*>(pairs + p)[tid];
     int n1 = n1s[stride1 ? p : 0], n2 = n2s[p], nq = nqs[p];
     n1 = n1 < 0 ? 0 : (n1 > cap1 ? cap1 : n1);
@@ -222,17 +218,8 @@ __global__ __launch_bounds__(TPB) void k_triangulate(const orbt_pair* pairs, Lev
     for (int i0 = 0; i0 < n1; i0 += TPB) {
         const int i = i0 + tid;
         const bool acc = i < n1 && status[bo + i] == ORBT_ACCEPTED;
-        const unsigned long long m = __ballot(acc);
-        if ((tid & 63) == 0) wave_total[wave] = __popcll(m);
-        __syncthreads();
-        int before = base, total = 0;
-        for (int w = 0; w < WAVES; w++) {
-            const int c = wave_total[w];
-            before += w < wave ? c : 0;
-            total += c;
-        }
+        const int k = orbx::tile_rank(acc, wave_total, base);
         if (acc) {
-            const int k = before + lane_rank(m);
             const int idx2 = match12[bo + i];                          // in [0, n2): an accepted match passed the range test
             if (k < ocap) {
                 acc_idx[(ba + k) * 2] = i;
@@ -244,8 +231,6 @@ __global__ __launch_bounds__(TPB) void k_triangulate(const orbt_pair* pairs, Lev
             if (qvalid) qvalid[b1 + i] = 0;
             if (claimed) claimed[b2 + idx2] = 1;
         }
-        base += total;
-        __syncthreads();                                               // wave_total is rewritten by the next tile
     }
     if (tid == 0) {
         count[p] = base;

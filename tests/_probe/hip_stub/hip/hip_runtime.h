@@ -1,5 +1,6 @@
 // Host-only stand-in for the part of the HIP runtime that orb_slam_amd/csrc/orbx_host.h uses: allocations come from malloc, copies
-// are memcpy, and `hip_stub_fail` makes the next n-th creating call fail.  `hip_stub_live` counts what is held.
+// are memcpy, and `hip_stub_fail` makes the next n-th creating call fail.  `hip_stub_live` counts what is held; `hip_stub_device` is the
+// current device (hip_stub_ndev of them), `hip_stub_waits` counts the waits on an event (by a stream or by the host).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -36,3 +37,14 @@ inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hip_
 inline hipError_t hipEventDestroy(hipEvent_t e) { return hip_stub_free(e); }
 inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) { std::memcpy(dst, src, bytes); return hipSuccess; }
 inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "hipErrorOutOfMemory"; }
+
+inline int hip_stub_device = 0, hip_stub_ndev = 2, hip_stub_waits = 0;
+inline hipError_t hipGetDevice(int* d) { *d = hip_stub_device; return hipSuccess; }
+inline hipError_t hipSetDevice(int d) {
+    if (d < 0 || d >= hip_stub_ndev) return hipErrorOutOfMemory;
+    hip_stub_device = d;
+    return hipSuccess;
+}
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { return e ? hipSuccess : hipErrorOutOfMemory; }
+inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { hip_stub_waits++; return hipSuccess; }
+inline hipError_t hipEventSynchronize(hipEvent_t) { hip_stub_waits++; return hipSuccess; }

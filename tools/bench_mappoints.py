@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the device map-point table (include/orbp.h) against the route without it, on one GPU in one session:
-  device route  orbp_track_batch_device: views in HBM -> frustum test + windows (k_project) -> window search -> feature -> slot table
+  device route  orbp_track_batch_device: views in HBM -> frustum test + windows (k_project<false>) -> window search -> feature -> slot table (k_t2source)
   host route    frustum test + query packing in C++ on one host core (tools/mappoints_host_route.cpp), upload of the query arrays,
                 orbs_window_search_batch_device
 and one orbp_track call (host frame, host list) against the same host route for one view.  Both routes are first shown equal on the timed

@@ -3,6 +3,7 @@
 route ORBmatcher.cc takes, on one GPU in one session:
   new route         the source frame and the current frame stay on the device; only the view, the list and the skip flags go up
                     (batch: orbp_track_source_batch_device on device arrays; one view: orbp_track_source with both frames on the device)
+                    k_project<true> -> window search -> k_t2source, the walk and the gather orbp_track* runs as k_project<false>
   host-query route  projection loop + query packing in C++ on one host core (tools/source_host_route.cpp), upload of xyr, levels,
                     descriptor and angle of every query, orbs_window_search_batch_device
 for one view of 1000 source features and for batches of 64 and 512 views, both modes.  The one-view form with HOST frames is timed as
