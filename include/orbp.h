@@ -18,6 +18,9 @@
  *                                   int ORBmatcher::SearchByProjection(Frame& Current, KeyFrame*, const set<MapPoint*>&, float th, int ORBdist)
  *                                   src/ORBmatcher.cc:1622-1746 (Tracking::Relocalisation, src/Tracking.cc:960, :974; ORBP_MODE_KEYFRAME)
  *                                   (projection + orbs_window_search_batch_device with ORBS_RULE_BEST and the rotation check)
+ *   orbp_refresh[_batch_device]  <- void MapPoint::UpdateNormalAndDepth()                         src/MapPoint.cc:273-312
+ *                                   void MapPoint::ComputeDistinctiveDescriptors()               src/MapPoint.cc:185-250
+ *                                   (the producer of what orbp_put takes from the caller; stated with the entry points below)
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -101,7 +104,7 @@ typedef struct orbp_record {
 } orbp_record;
 
 /* ORBX_ERR_ARG for capacity outside [1, ORBP_MAX_CAPACITY] or a NULL `out`; ORBX_ERR_DEVICE without a usable GPU.
- * Device memory: 65 bytes per slot; the scratch of orbp_track* is allocated on first use and kept. */
+ * Device memory: 65 bytes per slot; the scratch of orbp_track* and the block of orbp_refresh are allocated on first use and kept. */
 int orbp_create(int capacity, int device, orbp_map** out);
 void orbp_destroy(orbp_map* map);
 int orbp_capacity(const orbp_map* map);
@@ -121,7 +124,8 @@ int orbp_put_device(orbp_map* map, const int32_t* slots, int n, const float* d_p
                     const float* d_max_dist, const uint8_t* d_desc, void* stream);
 /* Frees n slots (host array); a slot that is not live is a no-op.  ORBX_ERR_ARG for a slot out of range. */
 int orbp_erase(orbp_map* map, const int32_t* slots, int n);
-/* Reads one slot back (synchronous; for tests).  *live = 0 and nothing else written for a free slot.  pos[3], normal[3], desc[32]. */
+/* Reads one slot back (synchronous; for tests).  *live = 0 and nothing else written for a free slot (the device's flag decides: see
+ * orbp_refresh_batch_device).  pos[3], normal[3], desc[32]. */
 int orbp_get(orbp_map* map, int slot, int* live, float* pos, float* normal, float* min_dist, float* max_dist, uint8_t* desc);
 
 /* The frustum test and the search windows for nviews problems.  All arrays are device buffers except `factors`
@@ -214,6 +218,89 @@ int orbp_track_source(orbp_map* map, const orbp_view* view, const float* factors
                       const orbs_params* prm, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
                       const int32_t* cell_feat, const uint8_t* claimed, int nt, int frame_on_device, int qcap, int32_t* t2pos,
                       int32_t* t2slot, int* nmatches, int* nvisible, void* stream);
+
+/* ---- The refresh of map points from their observations: MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:273-312) and
+ * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:185-250) for n slots in one launch, written into the table in place.
+ * The key frames are read where orbs_* and orbt_* read them: nkf frames of `cap` features each, key frame k's undistorted key points
+ * at d_kf_kps + k*cap and its descriptors at d_kf_desc + k*32*cap (16-byte aligned).
+ *
+ * Point i (slot slots[i], position P = d_pos + 3*i, or the stored one when d_pos is NULL) has the observations
+ * d_obs[2*j], d_obs[2*j + 1] = {kf, idx} for d_obs_off[i] <= j < d_obs_off[i + 1], in the order the reference iterates its
+ * std::map<KeyFrame*, size_t>, which is pointer order: the float sum below depends on it, and the caller supplies it.  d_ref[i] is
+ * the position INSIDE that segment of the observation by mpRefKF.
+ *
+ * Arithmetic, every step a single IEEE operation in the reference's order, no contraction, the cv::Mat primitives as DESIGN.md §2:
+ *   ORBP_REFRESH_NORMAL_DEPTH.  For every observation in listed order, bad key frames INCLUDED (the reference does not skip them here):
+ *     d = P - Ow_kf in float; s = sqrt(sum of (double)d[i]*(double)d[i]), a double sum from 0.0 in index order;
+ *     unit[i] = (float)((double)d[i] / s); normal[i] = normal[i] + unit[i] in float, from 0.0f.
+ *   mNormalVector[i] = (float)((double)normal[i] / (double)N), N the number of observations.
+ *   PC = P - Ow_ref in float; dist = (float)sqrt(double sum of squares); level = the octave of key point idx of the reference key frame;
+ *   scaleFactor = factors[1] (KeyFrame::GetScaleFactor() defaults to level 1: nlevels >= 2 is required);
+ *   mfMinDistance = ((1.0f / scaleFactor) * dist) / factors[level]; mfMaxDistance = (scaleFactor * dist) * factors[nlevels - 1 - level],
+ *   floats, left to right.
+ *   ORBP_REFRESH_DESCRIPTOR.  The observations whose key frame is not bad (d_kf_bad), in listed order; none: the stored descriptor is
+ *   kept (a slot that was free gets 32 zero bytes: the reference's mDescriptor is empty there).  Otherwise the row with the least
+ *   vDists[(int)(0.5*(N' - 1))] of the N' x N' Hamming distances, the self distance included, the first such row on ties (what
+ *   orbm_distinctive defines); the slot's 32 bytes become that key frame's row.
+ *
+ * Cases that cannot be evaluated are passed over, never dereferenced, and named in orbp_refreshed.status; the first that applies:
+ *   ORBP_REFRESH_SKIPPED     d_skip[i] != 0 (mbBad: both functions return at once)
+ *   ORBP_REFRESH_EMPTY       no observations (the reference divides by n == 0 and reads through a null mpRefKF entry)
+ *   ORBP_REFRESH_BAD_INDEX   a kf outside [0, nkf), an idx outside [0, cap), or (with ORBP_REFRESH_NORMAL_DEPTH) d_ref[i] outside the segment
+ *   ORBP_REFRESH_BAD_OCTAVE  the reference observation's octave is outside [0, nlevels)     (ORBP_REFRESH_NORMAL_DEPTH only)
+ *   ORBP_REFRESH_NONFINITE   the normal or a distance is not finite: a point on a camera centre (ORBP_REFRESH_NORMAL_DEPTH only)
+ * In every one of them the slot is unchanged, position and descriptor included, and a slot that was free stays free.
+ * ORBP_REFRESH_NONFINITE is a DELIBERATE DEVIATION in the spirit of the NaN rule above: the reference stores the NaN, after which
+ * isInFrustum's comparisons all fail for that point; here the record still carries the computed values and the table keeps the old.
+ *
+ * The record: normal / min_dist / max_dist as computed (zero without ORBP_REFRESH_NORMAL_DEPTH or before they were computed),
+ * best_obs the position inside the segment (bad key frames counted) of the chosen observation and best_median its median (-1 and
+ * INT32_MAX where no descriptor was chosen). */
+#define ORBP_REFRESH_NORMAL_DEPTH 1
+#define ORBP_REFRESH_DESCRIPTOR   2
+
+#define ORBP_REFRESH_OK          0
+#define ORBP_REFRESH_SKIPPED     1
+#define ORBP_REFRESH_EMPTY       2
+#define ORBP_REFRESH_BAD_INDEX   3
+#define ORBP_REFRESH_BAD_OCTAVE  4
+#define ORBP_REFRESH_NONFINITE   5
+
+typedef struct orbp_refreshed {
+    float normal[3];
+    float min_dist, max_dist;
+    int32_t best_obs;
+    int32_t best_median;
+    int32_t status;                          /* ORBP_REFRESH_* */
+} orbp_refreshed;
+
+/* All d_* are device arrays, read when the stream reaches the call; `slots` (n entries) and `factors` (nlevels) are HOST arrays.
+ *   d_pos (3n floats, may be NULL = keep the stored position); with d_pos a slot that is not live becomes live (the new map point),
+ *       which needs both `what` bits; without d_pos every slot must be live.
+ *   d_obs_off[n + 1] (ascending), d_obs (int32 pairs, 8-byte aligned), d_ref[n] (read with ORBP_REFRESH_NORMAL_DEPTH only, may be NULL otherwise),
+ *   d_skip[n] (may be NULL), d_kf_ow[3*nkf] (the key frames' camera centres, read with ORBP_REFRESH_NORMAL_DEPTH), d_kf_bad[nkf] (may
+ *   be NULL: none is bad), d_kf_kps (read with ORBP_REFRESH_NORMAL_DEPTH), d_kf_desc (read with ORBP_REFRESH_DESCRIPTOR; 16-byte aligned),
+ *   d_out[n] (may be NULL).
+ * ORBX_ERR_ARG, with the table unchanged, for n < 0, a slot out of range or listed twice, a free slot without d_pos or without both
+ * bits, `what` zero or with an unknown bit, nlevels outside [2, ORBS_MAX_LEVELS], nkf < 1, cap < 1, nkf * cap >= 2^31, a NULL or
+ * misaligned array that `what` reads.  Asynchronous on `stream` (NULL: the map's own), inside the handle's event chain; allocates
+ * nothing once the slot table has its size.
+ * The host's count of live slots (orbp_size, and what later calls accept as live) takes a new slot as live from this call on,
+ * whatever its status turns out to be: the device's flag, which the searches and orbp_get read, stays 0 for a status other than
+ * ORBP_REFRESH_OK.  Erase such a slot or refresh it again; orbp_refresh below knows the statuses and keeps the count exact. */
+int orbp_refresh_batch_device(orbp_map* map, const int32_t* slots, int n, const float* d_pos, const int32_t* d_obs_off, const int32_t* d_obs,
+                              const int32_t* d_ref, const uint8_t* d_skip, const float* d_kf_ow, const uint8_t* d_kf_bad,
+                              const orbx_keypoint* d_kf_kps, const uint8_t* d_kf_desc, int nkf, int cap, const float* factors, int nlevels,
+                              int what, orbp_refreshed* d_out, void* stream);
+
+/* The same with HOST arrays in and out, synchronous: the latency / test form, one pinned block up and one down.  pos, obs_off, obs,
+ * ref, skip, kf_ow, kf_bad and out[n] (may be NULL) are host memory; the key frames' features (kf_kps, kf_desc) are host memory, or
+ * device memory when kf_on_device != 0 (a caller who keeps its key frames resident uploads the lists and the camera centres only).
+ * Checked here in addition: obs_off[0] >= 0 and obs_off ascending.  A new slot whose status is not ORBP_REFRESH_OK stays free on
+ * the host's side too. */
+int orbp_refresh(orbp_map* map, const int32_t* slots, int n, const float* pos, const int32_t* obs_off, const int32_t* obs, const int32_t* ref,
+                 const uint8_t* skip, const float* kf_ow, const uint8_t* kf_bad, const orbx_keypoint* kf_kps, const uint8_t* kf_desc,
+                 int kf_on_device, int nkf, int cap, const float* factors, int nlevels, int what, orbp_refreshed* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,8 +10,8 @@
  *   orbt_triangulate[_batch_device] <- the body of the match loop of LocalMapping::CreateNewMapPoints   src/LocalMapping.cc:269-353
  *                                      and what its AddMapPoint calls (:360-361) mean to the NEXT search: idx1 holds a map point now
  *                                      (d_qvalid cleared), idx2 holds one now (d_claimed set)
- * What stays with the caller: the choice of neighbours and the baseline test (:230-243), ComputeF12, `new MapPoint`, AddObservation,
- * ComputeDistinctiveDescriptors, UpdateNormalAndDepth.
+ * What stays with the caller: the choice of neighbours and the baseline test (:230-243), ComputeF12, `new MapPoint`, AddObservation.
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth of the new points are orbp_refresh* (orbp.h), from the observation lists.
  *
  * Arithmetic, per match (idx1, idx2) with kp1 = KF1's undistorted key point idx1 and kp2 = KF2's idx2.  Every step is ONE IEEE
  * operation in the reference's order, no contraction; the cv::Mat primitives are evaluated as DESIGN.md §2 lists them:

@@ -56,12 +56,15 @@ EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_b
              "orbd_query_batch_device", "orbd_query"]
 EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
              "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
-             "orbp_track_source_batch_device", "orbp_track_source"]
+             "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh"]
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
 # orbp_view.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME = 0, 1, 2
+# orbp_refresh*: `what` bits and orbp_refreshed.status
+REFRESH_NORMAL_DEPTH, REFRESH_DESCRIPTOR = 1, 2
+(REFRESH_OK, REFRESH_SKIPPED, REFRESH_EMPTY, REFRESH_BAD_INDEX, REFRESH_BAD_OCTAVE, REFRESH_NONFINITE) = range(6)
 
 
 class OrbxError(RuntimeError):
@@ -149,6 +152,10 @@ VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np
 RECORD_DTYPE = np.dtype([("in_view", np.uint8), ("pad", np.uint8, 3), ("u", np.float32), ("v", np.float32), ("view_cos", np.float32),
                          ("level", np.int32)])
 assert VIEW_DTYPE.itemsize == ctypes.sizeof(View) == 108 and RECORD_DTYPE.itemsize == 20
+# orbp_refreshed
+REFRESHED_DTYPE = np.dtype([("normal", np.float32, 3), ("min_dist", np.float32), ("max_dist", np.float32), ("best_obs", np.int32),
+                            ("best_median", np.int32), ("status", np.int32)])
+assert REFRESHED_DTYPE.itemsize == 32
 
 GRID_COLS, GRID_ROWS = 64, 48
 GRID_CELLS = GRID_COLS * GRID_ROWS
@@ -276,6 +283,8 @@ def lib():
                                               vp, vp, vp, vp, vp, vp]
         L.orbp_track.argtypes = [vp, ctypes.POINTER(View), vp, ci, vp, ci, vp, ctypes.POINTER(Bounds), cf, vp, vp, vp, vp, vp, ci, ci, ci,
                                  vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
+        L.orbp_refresh_batch_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]
+        L.orbp_refresh.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, vp]
         L.orbp_project_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_track_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
                                                      vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
@@ -1131,6 +1140,49 @@ class MapPointTable:
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_get")
         return dict(pos=pos, normal=nrm, min_dist=dmin[0], max_dist=dmax[0], desc=desc) if live.value else None
+
+    def refresh_batch_device(self, slots, d_pos, d_obs_off, d_obs, d_ref, d_skip, d_kf_ow, d_kf_bad, d_kf_kps, d_kf_desc, nkf, cap, factors,
+                             what=REFRESH_NORMAL_DEPTH | REFRESH_DESCRIPTOR, d_out=0, stream=0):
+        """MapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors for the listed slots, in place and asynchronous.  slots, factors: host
+        arrays; everything else device pointers as ints (0 = NULL: d_pos keeps the stored positions)"""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_refresh_batch_device(self.h, slots.ctypes.data, len(slots), d_pos or None, d_obs_off or None, d_obs or None, d_ref or None,
+                                             d_skip or None, d_kf_ow or None, d_kf_bad or None, d_kf_kps or None, d_kf_desc or None, nkf, cap,
+                                             f.ctypes.data, len(f), what, d_out or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_refresh_batch_device")
+
+    def refresh(self, slots, obs_off, obs, ref, kf_ow, kf_kps, kf_desc, factors, pos=None, skip=None, kf_bad=None, nkf=None, cap=None,
+                what=REFRESH_NORMAL_DEPTH | REFRESH_DESCRIPTOR):
+        """The same with host arrays, synchronous (the latency form): -> the records (REFRESHED_DTYPE[n]).  obs: (total, 2) int32 pairs {kf, idx};
+        kf_kps (nkf, cap) KP_DTYPE and kf_desc (nkf, cap, 32) are host arrays, or device pointers as ints (nkf and cap must then be given)."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(slots)
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        obs_off = np.ascontiguousarray(obs_off, dtype=np.int32)
+        obs = np.ascontiguousarray(obs, dtype=np.int32).reshape(-1, 2)
+        assert len(obs_off) == n + 1 and (n == 0 or len(obs) >= obs_off[-1])
+        opt = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)
+        ref = opt(ref, np.int32, n); pos = opt(pos, np.float32, (n, 3)); skip = opt(skip, np.uint8, n)
+        kf_dev = isinstance(kf_kps, int) or isinstance(kf_desc, int)
+        if not kf_dev:
+            if kf_kps is not None:
+                kf_kps = np.ascontiguousarray(kf_kps)
+                assert kf_kps.dtype.itemsize == 28 and kf_kps.ndim == 2
+                nkf, cap = kf_kps.shape
+            if kf_desc is not None:
+                kf_desc = np.ascontiguousarray(kf_desc, dtype=np.uint8)
+                assert kf_desc.ndim == 3 and kf_desc.shape[2] == 32 and (kf_kps is None or kf_desc.shape[:2] == kf_kps.shape)
+                nkf, cap = kf_desc.shape[:2]
+        kf_ow = opt(kf_ow, np.float32, (nkf, 3)); kf_bad = opt(kf_bad, np.uint8, nkf)
+        out = np.zeros(max(n, 1), REFRESHED_DTYPE)
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        rc = lib().orbp_refresh(self.h, ptr(slots), n, ptr(pos), ptr(obs_off), ptr(obs), ptr(ref), ptr(skip), ptr(kf_ow), ptr(kf_bad), ptr(kf_kps),
+                                ptr(kf_desc), 1 if kf_dev else 0, nkf, cap, f.ctypes.data, len(f), what, ptr(out), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_refresh")
+        return out[:n]
 
     def project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
                              d_overflow, qcap, stream=0):

@@ -34,7 +34,11 @@ LocalMapPoints::LocalMapPoints(float nnratio, bool refresh_every_call, int capac
     for (int s = capacity_ - 1; s >= 0; s--) free_.push_back(s);
 }
 
-LocalMapPoints::~LocalMapPoints() { orbp_destroy(map_); }
+LocalMapPoints::~LocalMapPoints() {
+    orbp_destroy(map_);
+    if (d_kf_kps_) orbx_device_free(device_, d_kf_kps_);
+    if (d_kf_desc_) orbx_device_free(device_, d_kf_desc_);
+}
 
 void LocalMapPoints::grow() {
     const int old = capacity_;

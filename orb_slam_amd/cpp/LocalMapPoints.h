@@ -6,6 +6,9 @@
 // A map point is mirrored by Put (which reads GetWorldPos, GetNormal, Get{Min,Max}DistanceInvariance, GetDescriptor) and dropped by
 // Forget.  Both only touch host memory; the device table is brought up to date in ONE orbp_put / orbp_erase at the start of the next
 // search, so a bundle adjustment that moves thousands of points costs one upload.  The table grows by doubling.
+// Refresh (LocalMapPointsRefresh.cc) replaces the pair MapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors + Put: the listed points'
+// observation lists and their key frames' camera centres go up, the normal, the two distances and the descriptor are computed on the GPU
+// from key frames whose features stay resident (orbp_refresh), and land in the table's slots directly.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
@@ -53,6 +56,17 @@ public:
     int SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const std::set<MapPoint*>& sAlreadyFound, float th, int ORBdist,
                            bool checkOrientation = true);
 
+    // MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:273-312) and, with `descriptors`, MapPoint::ComputeDistinctiveDescriptors (:185-250) for
+    // the listed points (LocalMapPointsRefresh.cc; links only when that file is built in).  Reads isBad(), GetWorldPos(), GetObservations() in
+    // the map's order, GetReferenceKeyFrame(), and of the key frames GetCameraCenter(), isBad(), GetScaleFactors() and, once per key frame,
+    // GetKeyPointsUn() and GetDescriptors().  The table's slots and this object's mirror are brought up to date; record i is what the two
+    // functions would have left in vpMPs[i] (orbp.h: orbp_refreshed; status ORBP_REFRESH_SKIPPED for a null or bad point), for the caller to
+    // store: MapPoint's members are not reached into.  A point not yet mirrored gets its slot here when `descriptors` is set and is Put
+    // first otherwise; a new point whose status is not ORBP_REFRESH_OK stays unmirrored.
+    std::vector<orbp_refreshed> Refresh(const std::vector<MapPoint*>& vpMPs, bool descriptors = true);
+    // gives up pKF's row of the resident key-frame store: call it when a key frame is deleted
+    void ForgetKeyFrame(KeyFrame* pKF);
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
@@ -76,6 +90,16 @@ private:
     std::vector<int32_t> dirty_list_, dead_list_;
     std::vector<float> pos_, nrm_, dmin_, dmax_; // host copy of the table (re-uploaded when it grows)
     std::vector<uint8_t> desc_;
+    // the key frames Refresh has seen: one row of feat_cap_ key points and descriptors each, resident on the device
+    int keyFrameRow(KeyFrame* pKF);
+    void growKeyFrames(int rows, int feats);
+    std::unordered_map<KeyFrame*, int> kf_row_;
+    std::vector<KeyFrame*> kf_owner_;            // per row; NULL = free
+    std::vector<int32_t> kf_free_;
+    std::vector<uint8_t> kf_resident_;           // per row: its features are on the device
+    void* d_kf_kps_ = nullptr;
+    void* d_kf_desc_ = nullptr;
+    int kf_rows_ = 0, feat_cap_ = 0;
     // per call
     std::vector<int32_t> list_, t2slot_, t2pos_, cell_off_, cell_feat_;
     std::vector<uint8_t> skip_, claimed_;

@@ -1,5 +1,5 @@
 // The argument groups of the map-point walk (orbp_project.hip) and the layouts of the blocks an orbp_map keeps for them.  Host C++
-// only: tests/_probe/host_owners.cpp holds the layouts against their sizes without a GPU.
+// only: tests/_probe/host_owners.cpp and tests/_probe/refresh_host.cpp hold the layouts against their sizes without a GPU.
 #pragma once
 #include <cstring>
 
@@ -81,6 +81,89 @@ struct TrackBlock {
         result = L.add<int32_t>(3); t2pos = L.add<int32_t>(cap, f.source); t2slot = L.add<int32_t>(cap, f.t2slot); rec = L.add<orbp_record>(lcap, f.rec);
         L.end_download();
         q.reserve(L, 1, cap, qcap, f.source);
+    }
+};
+
+// mvScaleFactors, by value into the kernels
+struct Factors {
+    float f[ORBS_MAX_LEVELS];
+    int n;
+};
+
+// what orbp_refresh* reads: the points' lists and the key-frame store (device pointers by the time the kernel sees them)
+struct RefreshLists { const float* pos; const int32_t* obs_off; const int32_t* obs; const int32_t* ref; const uint8_t* skip; };
+struct KeyFrames { const float* ow; const uint8_t* bad; const orbx_keypoint* kps; const uint8_t* desc; int nkf, cap; };
+
+// what the refresh kernel reads and writes (orbp_refresh.hip); `slots` is the uploaded slot table
+struct Refresh {
+    int n;
+    const int32_t* slots;
+    RefreshLists L;
+    KeyFrames K;
+    int what;
+    float* geom;
+    uint8_t* tdesc;
+    uint8_t* live;
+    orbp_refreshed* out;
+};
+hipError_t launch_refresh(const Refresh& a, const Factors& F, hipStream_t st);
+
+// The arguments of orbp_refresh* that do not need the handle.  on_device: the lists are device memory (orbp_refresh_batch_device), so
+// only their presence can be checked; else obs_off is walked.  kf_device: d_kf_desc is a device address and must be 16-byte aligned (a
+// host array is copied into an aligned slot).
+inline int check_refresh(int n, const RefreshLists& L, const KeyFrames& K, const float* factors, int nlevels, int what, bool on_device, bool kf_device) {
+    if (n < 0 || !factors || nlevels < 2 || nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
+    if (what == 0 || (what & ~(ORBP_REFRESH_NORMAL_DEPTH | ORBP_REFRESH_DESCRIPTOR))) return ORBX_ERR_ARG;
+    if (K.nkf < 1 || K.cap < 1 || (long long)K.nkf * K.cap >= (1ll << 31)) return ORBX_ERR_ARG;
+    if (n == 0) return ORBX_OK;
+    if (!L.obs_off || !L.obs || (on_device && ((uintptr_t)L.obs & 7))) return ORBX_ERR_ARG;       // the pairs are read as one 8-byte load
+    if ((what & ORBP_REFRESH_NORMAL_DEPTH) && (!L.ref || !K.ow || !K.kps)) return ORBX_ERR_ARG;
+    if ((what & ORBP_REFRESH_DESCRIPTOR) && (!K.desc || (kf_device && ((uintptr_t)K.desc & 15)))) return ORBX_ERR_ARG;
+    if (!on_device) {
+        if (L.obs_off[0] < 0) return ORBX_ERR_ARG;
+        for (int i = 0; i < n; i++)
+            if (L.obs_off[i + 1] < L.obs_off[i]) return ORBX_ERR_ARG;
+    }
+    return ORBX_OK;
+}
+
+// The block of orbp_refresh, one pinned copy up and one down:
+//   up    [pos | obs_off | obs | ref | skip | kf_ow | kf_bad | kf_kps | kf_desc]     (absent: what the caller does not pass, and the
+//                                                                                     key frames' features when they are on the device)
+//   down  [out]
+// `out` is always present: the host needs the statuses for its live flags.
+struct RefreshBlock {
+    Layout L;
+    Layout::Slot<float> pos, kf_ow;
+    Layout::Slot<int32_t> obs_off, obs, ref;
+    Layout::Slot<uint8_t> skip, kf_bad, kf_desc;
+    Layout::Slot<orbx_keypoint> kf_kps;
+    Layout::Slot<orbp_refreshed> out;
+    int n, nobs, nkf;
+    size_t nfeat;                                      // nkf * cap
+    RefreshBlock(int n_, int nobs_, const RefreshLists& l, const KeyFrames& k, bool kf_upload) : n(n_), nobs(nobs_), nkf(k.nkf), nfeat((size_t)k.nkf * k.cap) {
+        pos = L.add<float>((size_t)n * 3, l.pos != nullptr); obs_off = L.add<int32_t>((size_t)n + 1); obs = L.add<int32_t>((size_t)nobs * 2);
+        ref = L.add<int32_t>(n, l.ref != nullptr); skip = L.add<uint8_t>(n, l.skip != nullptr);
+        kf_ow = L.add<float>((size_t)nkf * 3, k.ow != nullptr); kf_bad = L.add<uint8_t>(nkf, k.bad != nullptr);
+        kf_kps = L.add<orbx_keypoint>(nfeat, kf_upload && k.kps); kf_desc = L.add<uint8_t>(nfeat * 32, kf_upload && k.desc);
+        L.end_upload();
+        out = L.add<orbp_refreshed>(n);
+        L.end_download();
+    }
+    // copies the caller's host arrays into the pinned block h and names them inside the device block d; the key frames' features are
+    // passed through when they are not part of the block
+    void stage(uint8_t* h, uint8_t* d, const RefreshLists& l, const KeyFrames& k, RefreshLists& dl, KeyFrames& dk) const {
+        if (pos.present) std::memcpy(Layout::at(h, pos), l.pos, (size_t)n * 12);
+        std::memcpy(Layout::at(h, obs_off), l.obs_off, ((size_t)n + 1) * 4);
+        if (nobs > 0) std::memcpy(Layout::at(h, obs), l.obs, (size_t)nobs * 8);
+        if (ref.present) std::memcpy(Layout::at(h, ref), l.ref, (size_t)n * 4);
+        if (skip.present) std::memcpy(Layout::at(h, skip), l.skip, (size_t)n);
+        if (kf_ow.present) std::memcpy(Layout::at(h, kf_ow), k.ow, (size_t)nkf * 12);
+        if (kf_bad.present) std::memcpy(Layout::at(h, kf_bad), k.bad, (size_t)nkf);
+        if (kf_kps.present) std::memcpy(Layout::at(h, kf_kps), k.kps, nfeat * sizeof(orbx_keypoint));
+        if (kf_desc.present) std::memcpy(Layout::at(h, kf_desc), k.desc, nfeat * 32);
+        dl = {Layout::at(d, pos), Layout::at(d, obs_off), Layout::at(d, obs), Layout::at(d, ref), Layout::at(d, skip)};
+        dk = {Layout::at(d, kf_ow), Layout::at(d, kf_bad), kf_kps.present ? Layout::at(d, kf_kps) : k.kps, kf_desc.present ? Layout::at(d, kf_desc) : k.desc, k.nkf, k.cap};
     }
 };
 

@@ -19,6 +19,7 @@
 //              th * factors[level] over the levels [level-1, level+1], its angle and the source frame's (last frame) or the table's
 //              (key frame) descriptor.  The key point's octave and angle do not depend on the slot, so their loads leave with the
 //              list's and overlap the dependent list -> live -> geometry chain that bounds the stage.
+//   (k_refresh, the refresh of slots from their observations, is orbp_refresh.hip; its host side is refresh_locked below.)
 //   k_t2source orbp_track*: turns the search's feature -> query table into feature -> list position (the source feature index of
 //              orbp_track_source*) and feature -> map slot through the list positions the projection left (d_qpos); features
 //              without a match, or beyond the frame's count, get -1.  Either output may be absent, and so may the list (identity).
@@ -39,11 +40,6 @@ namespace orbp {
 
 constexpr int TPB = 256;              // one workgroup: four waves
 constexpr int WAVES = TPB / 64;
-
-struct Factors {
-    float f[ORBS_MAX_LEVELS];
-    int n;
-};
 
 // what one walk reads and writes
 struct Walk {
@@ -247,7 +243,7 @@ struct orbp_map {
     uint32_t stamp_now = 0;
     orbx::DevBuf geom, desc, d_live, d_tab, scratch;
     orbx::PinnedBuf h_tab;
-    orbx::Block one, put;                             // the blocks of the one-view calls and of orbp_put
+    orbx::Block one, put, refresh;                    // the blocks of the one-view calls, of orbp_put and of orbp_refresh
     orbx::Stream own;
     orbx::Chain chain;                                // device work on the map is ordered across the callers' streams
     orbx::Event tab_done;
@@ -305,6 +301,23 @@ int put_locked(orbp_map* m, const int32_t* slots, int n, const float* d_pos, con
     for (int i = 0; i < n; i++)
         if (!m->live[slots[i]]) { m->live[slots[i]] = 1; m->n_live++; }
     return ORBX_OK;
+}
+
+// Inside the caller's link of the chain: the slot table goes up as for a put, one launch refreshes the slots in place.  The host's
+// live flags are the caller's business: orbp_refresh knows the statuses, orbp_refresh_batch_device does not.
+int refresh_locked(orbp_map* m, const int32_t* slots, int n, const orbp::RefreshLists& L, const orbp::KeyFrames& K, const orbp::Factors& F, int what,
+                   orbp_refreshed* d_out, hipStream_t st) {
+    const int rc = upload_slots(m, slots, n, st);
+    if (rc != ORBX_OK) return rc;
+    const orbp::Refresh a{n, m->d_tab.as<int32_t>(), L, K, what, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), d_out};
+    HIPCHK(m, orbp::launch_refresh(a, F, st));
+    return ORBX_OK;
+}
+
+// the slots of a refresh: range, no slot twice, and a free slot only as a new map point (a position and both parts)
+int check_refresh_slots(orbp_map* m, const int32_t* slots, int n, bool with_pos, int what) {
+    const bool may_create = with_pos && what == (ORBP_REFRESH_NORMAL_DEPTH | ORBP_REFRESH_DESCRIPTOR);
+    return check_slots(m, slots, n, true, !may_create);
 }
 
 int fill_factors(const float* factors, int nlevels, orbp::Factors& F) {
@@ -587,12 +600,85 @@ int orbp_get(orbp_map* m, int slot, int* live, float* pos, float* normal, float*
     DeviceScope ds(m->device);
     if (!ds.ok) return ORBX_ERR_DEVICE;
     HIPCHK(m, m->chain.wait());
+    // a slot that orbp_refresh_batch_device was to create is live on the host and free on the device when its status was not OK
+    uint8_t d_live = 0;
+    HIPCHK(m, hipMemcpy(&d_live, m->d_live.as<uint8_t>() + slot, 1, hipMemcpyDeviceToHost));
+    *live = d_live;
+    if (!*live) return ORBX_OK;
     float g[8];
     HIPCHK(m, hipMemcpy(g, m->geom.as<float>() + (size_t)slot * 8, 32, hipMemcpyDeviceToHost));
     HIPCHK(m, hipMemcpy(desc, m->desc.as<uint8_t>() + (size_t)slot * 32, 32, hipMemcpyDeviceToHost));
     for (int k = 0; k < 3; k++) { pos[k] = g[k]; normal[k] = g[3 + k]; }
     *min_dist = g[6];
     *max_dist = g[7];
+    return ORBX_OK;
+}
+
+int orbp_refresh_batch_device(orbp_map* m, const int32_t* slots, int n, const float* d_pos, const int32_t* d_obs_off, const int32_t* d_obs,
+                              const int32_t* d_ref, const uint8_t* d_skip, const float* d_kf_ow, const uint8_t* d_kf_bad, const orbx_keypoint* d_kf_kps,
+                              const uint8_t* d_kf_desc, int nkf, int cap, const float* factors, int nlevels, int what, orbp_refreshed* d_out,
+                              void* stream) {
+    const orbp::RefreshLists L{d_pos, d_obs_off, d_obs, d_ref, d_skip};
+    const orbp::KeyFrames K{d_kf_ow, d_kf_bad, d_kf_kps, d_kf_desc, nkf, cap};
+    orbp::Factors F;
+    if (!m || orbp::check_refresh(n, L, K, factors, nlevels, what, true, true) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK) return ORBX_ERR_ARG;
+    if (n == 0) return ORBX_OK;
+    if (!slots) return ORBX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (check_refresh_slots(m, slots, n, d_pos != nullptr, what) != ORBX_OK) return ORBX_ERR_ARG;
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    HIPCHK(m, m->chain.begin(st));
+    Link link(m->chain, st);
+    const int rc = refresh_locked(m, slots, n, L, K, F, what, d_out, st);
+    if (rc != ORBX_OK) return rc;
+    HIPCHK(m, link.end());
+    for (int i = 0; i < n; i++)                                        // the statuses stay on the device: orbp.h
+        if (!m->live[slots[i]]) { m->live[slots[i]] = 1; m->n_live++; }
+    return ORBX_OK;
+}
+
+int orbp_refresh(orbp_map* m, const int32_t* slots, int n, const float* pos, const int32_t* obs_off, const int32_t* obs, const int32_t* ref,
+                 const uint8_t* skip, const float* kf_ow, const uint8_t* kf_bad, const orbx_keypoint* kf_kps, const uint8_t* kf_desc, int kf_on_device,
+                 int nkf, int cap, const float* factors, int nlevels, int what, orbp_refreshed* out, void* stream) {
+    const orbp::RefreshLists L{pos, obs_off, obs, ref, skip};
+    const orbp::KeyFrames K{kf_ow, kf_bad, kf_kps, kf_desc, nkf, cap};
+    orbp::Factors F;
+    if (!m || orbp::check_refresh(n, L, K, factors, nlevels, what, false, kf_on_device != 0) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (n == 0) return ORBX_OK;
+    if (!slots) return ORBX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (check_refresh_slots(m, slots, n, pos != nullptr, what) != ORBX_OK) return ORBX_ERR_ARG;
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    const orbp::RefreshBlock B(n, obs_off[n], L, K, kf_on_device == 0);
+    const size_t up_bytes = B.L.upload(), total = B.L.total();
+    if (!m->refresh.fits(total, total)) {
+        size_t want = std::max<size_t>(4096, m->refresh.h.size());
+        while (want < total) want *= 2;
+        const int rc = grow(m, m->refresh, want, want);
+        if (rc != ORBX_OK) return rc;
+    }
+    uint8_t* h = m->refresh.h.as();
+    uint8_t* d = m->refresh.d.as();
+    orbp::RefreshLists dl;
+    orbp::KeyFrames dk;
+    B.stage(h, d, L, K, dl, dk);
+    HIPCHK(m, m->chain.begin(st));
+    Link link(m->chain, st);                                           // every way out leaves the copies below behind the chain
+    HIPCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    const int rc = refresh_locked(m, slots, n, dl, dk, F, what, Layout::at(d, B.out), st);
+    if (rc != ORBX_OK) return rc;
+    HIPCHK(m, hipMemcpyAsync(h + up_bytes, d + up_bytes, total - up_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(m, link.end());
+    HIPCHK(m, hipStreamSynchronize(st));
+    const orbp_refreshed* res = Layout::at(h, B.out);
+    for (int i = 0; i < n; i++)
+        if (res[i].status == ORBP_REFRESH_OK && !m->live[slots[i]]) { m->live[slots[i]] = 1; m->n_live++; }
+    if (out) std::memcpy(out, res, (size_t)n * sizeof(orbp_refreshed));
     return ORBX_OK;
 }
 

@@ -1,0 +1,176 @@
+// Drives ORB_SLAM::LocalMapPoints::Refresh (orb_slam_amd/cpp/LocalMapPointsRefresh.cc, over the stand-in MapPoint.h / KeyFrame.h of this
+// directory and the Frame.h of tests/mappoints_dropin) through a script; tests/test_gpu_refresh_dropin.py builds the script and compares
+// with tests/refresh_ref.py.  Floats travel as the hex of their bit pattern.
+//
+//   harness SCRIPT
+//
+// Script lines (cam, factors, new, mp, put, bad, frame, pose and search as tests/mappoints_dropin/harness.cpp):
+//   kfs N                                              N key frames in one array, so that pointer order = index order
+//   kf K ox oy oz BAD N, then N lines "octave DESC"    key frame K: camera centre, bad flag, its key points' octaves and descriptors
+//   kfow K ox oy oz | kfbad K 0|1                      a key frame moved (bundle adjustment) / its bad flag
+//   obs ID REFKF N k idx ...                           map point ID's observations and mpRefKF (REFKF -1: none of them)
+//   refresh DESCRIPTORS K id ...                       -> "F size capacity fetched", fetched = GetKeyPointsUn calls so far over all key frames,
+//                                                         then per listed point "R id status nx ny nz dmin dmax best_obs best_median"
+//   forgetkf K                                         ForgetKeyFrame
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <sstream>
+#include <string>
+
+#include "Frame.h"
+#include "KeyFrame.h"
+#include "LocalMapPoints.h"
+#include "MapPoint.h"
+
+namespace ORB_SLAM {
+float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
+int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
+float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
+}
+using namespace ORB_SLAM;
+
+namespace {
+
+float rdf(std::istringstream& in) {
+    std::string h;
+    in >> h;
+    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+unsigned bitsof(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+void rddesc(std::istringstream& in, unsigned char* d) {
+    std::string h;
+    in >> h;
+    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
+}
+std::vector<MapPoint*> rdlist(std::istringstream& in, std::map<long, std::unique_ptr<MapPoint> >& mps) {
+    int k = 0;
+    in >> k;
+    std::vector<MapPoint*> v(k);
+    for (int i = 0; i < k; i++) { long id; in >> id; v[i] = id < 0 ? nullptr : mps.at(id).get(); }
+    return v;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream f(argv[1]);
+    std::string line;
+    std::map<long, std::unique_ptr<MapPoint> > mps;
+    std::vector<KeyFrame> kfs;
+    std::unique_ptr<LocalMapPoints> L;
+    Frame F;
+    std::vector<float> factors;
+    while (std::getline(f, line)) {
+        std::istringstream in(line);
+        std::string op;
+        if (!(in >> op)) continue;
+        if (op == "cam") {
+            Frame::fx = rdf(in); Frame::fy = rdf(in); Frame::cx = rdf(in); Frame::cy = rdf(in);
+            in >> Frame::mnMinX >> Frame::mnMaxX >> Frame::mnMinY >> Frame::mnMaxY;
+            Frame::mfGridElementWidthInv = rdf(in); Frame::mfGridElementHeightInv = rdf(in);
+        } else if (op == "factors") {
+            int n; in >> n;
+            factors.resize(n);
+            for (int i = 0; i < n; i++) factors[i] = rdf(in);
+        } else if (op == "new") {
+            int refresh, cap; in >> refresh >> cap;
+            L.reset(new LocalMapPoints(0.8f, refresh != 0, cap));
+        } else if (op == "mp") {
+            long id; in >> id;
+            if (!mps.count(id)) { mps[id].reset(new MapPoint); mps[id]->mnId = id; }
+            MapPoint& m = *mps[id];
+            for (int k = 0; k < 3; k++) m.mWorldPos.at<float>(k) = rdf(in);
+            for (int k = 0; k < 3; k++) m.mNormalVector.at<float>(k) = rdf(in);
+            m.mfMinDistance = rdf(in); m.mfMaxDistance = rdf(in);
+            rddesc(in, m.mDescriptor.ptr<unsigned char>(0));
+        } else if (op == "put") { long id; in >> id; L->Put(mps.at(id).get());
+        } else if (op == "bad") { long id; int v; in >> id >> v; mps.at(id)->mbBad = v != 0;
+        } else if (op == "kfs") {
+            int n; in >> n;
+            kfs.assign(n, KeyFrame());
+        } else if (op == "kf") {
+            int k, bad, n; in >> k;
+            KeyFrame& K = kfs.at(k);
+            K.Ow = cv::Mat(3, 1, CV_32F);
+            for (int c = 0; c < 3; c++) K.Ow.at<float>(c) = rdf(in);
+            in >> bad >> n;
+            K.mbBad = bad != 0;
+            K.mvScaleFactors = factors;
+            K.mvKeysUn.assign(n, cv::KeyPoint());
+            K.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                kin >> K.mvKeysUn[i].octave;
+                rddesc(kin, K.mDescriptors.ptr<unsigned char>(i));
+            }
+        } else if (op == "kfow") { int k; in >> k; for (int c = 0; c < 3; c++) kfs.at(k).Ow.at<float>(c) = rdf(in);
+        } else if (op == "kfbad") { int k, v; in >> k >> v; kfs.at(k).mbBad = v != 0;
+        } else if (op == "forgetkf") { int k; in >> k; L->ForgetKeyFrame(&kfs.at(k));
+        } else if (op == "obs") {
+            long id; int refkf, n; in >> id >> refkf >> n;
+            MapPoint& m = *mps.at(id);
+            m.mObservations.clear();
+            for (int i = 0; i < n; i++) { int k; size_t idx; in >> k >> idx; m.mObservations[&kfs.at(k)] = idx; }
+            m.mpRefKF = refkf < 0 ? nullptr : &kfs.at(refkf);
+        } else if (op == "refresh") {
+            int descriptors; in >> descriptors;
+            const std::vector<MapPoint*> v = rdlist(in, mps);
+            const std::vector<orbp_refreshed> r = L->Refresh(v, descriptors != 0);
+            int fetched = 0;
+            for (const KeyFrame& K : kfs) fetched += K.getKeys;
+            printf("F %zu %d %d\n", L->size(), L->capacity(), fetched);
+            for (size_t i = 0; i < v.size(); i++)
+                printf("R %ld %d %08x %08x %08x %08x %08x %d %d\n", v[i] ? (long)v[i]->mnId : -1L, r[i].status, bitsof(r[i].normal[0]), bitsof(r[i].normal[1]),
+                       bitsof(r[i].normal[2]), bitsof(r[i].min_dist), bitsof(r[i].max_dist), r[i].best_obs, r[i].best_median);
+        } else if (op == "frame") {
+            int n; in >> F.mnId >> n;
+            F.mvKeysUn.assign(n, cv::KeyPoint());
+            F.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            F.mvpMapPoints.assign(n, nullptr);
+            F.mnScaleLevels = (int)factors.size();
+            F.mvScaleFactors = factors;
+            for (int x = 0; x < FRAME_GRID_COLS; x++) for (int y = 0; y < FRAME_GRID_ROWS; y++) F.mGrid[x][y].clear();
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                cv::KeyPoint& kp = F.mvKeysUn[i];
+                kp.pt.x = rdf(kin); kp.pt.y = rdf(kin);
+                kin >> kp.octave;
+                rddesc(kin, F.mDescriptors.ptr<unsigned char>(i));
+                const int px = (int)std::round((kp.pt.x - Frame::mnMinX) * Frame::mfGridElementWidthInv);      // Frame::PosInGrid
+                const int py = (int)std::round((kp.pt.y - Frame::mnMinY) * Frame::mfGridElementHeightInv);
+                if (px >= 0 && px < FRAME_GRID_COLS && py >= 0 && py < FRAME_GRID_ROWS) F.mGrid[px][py].push_back(i);
+            }
+        } else if (op == "pose") {
+            F.mTcw = cv::Mat(4, 4, CV_32F);
+            for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) F.mTcw.at<float>(r, c) = r == c ? 1.f : 0.f;
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) F.mTcw.at<float>(r, c) = rdf(in);
+            for (int r = 0; r < 3; r++) F.mTcw.at<float>(r, 3) = rdf(in);
+        } else if (op == "search") {
+            const float th = rdf(in);
+            const std::vector<MapPoint*> v = rdlist(in, mps);
+            int nToMatch = -1;
+            const int ret = L->SearchReferencePointsInFrustum(F, v, th, &nToMatch);
+            printf("S %d %d %zu %d\n", ret, nToMatch, L->size(), L->capacity());
+            for (MapPoint* m : v)
+                printf("P %lu %d %08x %08x %08x %d %d\n", m->mnId, m->mbTrackInView ? 1 : 0, bitsof(m->mTrackProjX), bitsof(m->mTrackProjY),
+                       bitsof(m->mTrackViewCos), m->mnTrackScaleLevel, m->mnVisible);
+            for (size_t i = 0; i < F.mvpMapPoints.size(); i++)
+                if (F.mvpMapPoints[i]) printf("M %zu %lu\n", i, F.mvpMapPoints[i]->mnId);
+        } else {
+            fprintf(stderr, "unknown script line: %s\n", line.c_str());
+            return 2;
+        }
+    }
+    return 0;
+}
