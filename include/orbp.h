@@ -21,6 +21,9 @@
  *   orbp_refresh[_batch_device]  <- void MapPoint::UpdateNormalAndDepth()                         src/MapPoint.cc:273-312
  *                                   void MapPoint::ComputeDistinctiveDescriptors()               src/MapPoint.cc:185-250
  *                                   (the producer of what orbp_put takes from the caller; stated with the entry points below)
+ *   orbp_fuse[_batch_device]     <- the search of int ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>&, float th)   src/ORBmatcher.cc:1016-1134
+ *                                   for every call LocalMapping::SearchInNeighbors makes (src/LocalMapping.cc:373-450; ORBP_MODE_FUSE);
+ *                                   Replace / AddObservation / AddMapPoint stay with the caller
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -47,6 +50,23 @@
  *   ratio = dist3D / minDistance (float); level = min(lower_bound(factors, ratio), nlevels - 1); the query's descriptor is the TABLE's
  *   (pMP->GetDescriptor()).
  *   Both: radius th * factors[level] (float), levels [level - 1, level + 1], angle = the source key point's angle.
+ *
+ * Arithmetic of ORBP_MODE_FUSE (src/ORBmatcher.cc:1040-1113), per list entry, the first rejection that applies names its status:
+ *   the entry is skipped, or its slot out of range or free -> ORBP_FUSE_SKIPPED;
+ *   Pc as above; PcZ < 0.0f -> ORBP_FUSE_DEPTH;
+ *   invz = 1.0f / PcZ (which rounds as the reference's (float)(1.0 / (double)PcZ) does); x = PcX*invz; y = PcY*invz; u = fx*x + cx;
+ *   v = fy*y + cy, floats, left to right: NOT the association of the modes above;
+ *   KeyFrame::IsInImage: u >= (float)min_x && u < (float)max_x && v >= (float)min_y && v < (float)max_y, else ORBP_FUSE_IMAGE.  The upper
+ *   bounds are EXCLUSIVE here.  A NaN or infinite u or v fails this test in the reference too: this mode has no deviation;
+ *   PO = P - Ow in float; dist = (float)sqrt(sum of (double)PO[i]*(double)PO[i]); dist < minDistance || dist > maxDistance -> ORBP_FUSE_DISTANCE;
+ *   dot = sum of (double)PO[i]*(double)Pn[i]; dot < 0.5 * (double)dist, compared as doubles -> ORBP_FUSE_ANGLE (view_cos_limit is not read);
+ *   level = min(lower_bound(factors, dist / minDistance), nlevels - 1) (float division); radius = th * factors[level] (float);
+ *   the window of Frame::GetFeaturesInArea(u, v, radius, level - 1, level) over the key frame's grid: cells ix outer, iy inner, cell
+ *   ix*48 + iy, the cell's features in CSR order; a feature is kept when |kx - u| <= radius && |ky - v| <= radius and
+ *   level - 1 <= octave <= level; a strictly smaller Hamming distance wins, so among equal distances the FIRST feature in that order wins (not
+ *   the lowest index); no cell window or no feature kept -> ORBP_FUSE_EMPTY;
+ *   best distance <= orb_dist -> ORBP_FUSE_FUSED with that feature, else ORBP_FUSE_FAR and no feature.
+ * Nothing is claimed and there is no ratio, second distance or rotation check: every entry is on its own.
  *
  * ONE DELIBERATE DEVIATION.  Where the reference leaves u or v NaN (PcZ == 0 together with PcX == 0 or PcY == 0: a point at
  * the camera centre) all its comparisons fail, the point passes with a NaN window and GetFeaturesInArea converts NaN to
@@ -75,9 +95,11 @@ extern "C" {
 #define ORBP_MAX_CAPACITY (1 << 24)   /* slots of one table */
 #define ORBP_MAX_VIEWS    (1 << 16)   /* problems of one call */
 
-#define ORBP_MODE_FRAME 0             /* Frame::isInFrustum; the key-frame-side projections (Fuse, the loop searches) are a later mode */
+#define ORBP_MODE_FRAME 0             /* Frame::isInFrustum */
 #define ORBP_MODE_LAST_FRAME 1        /* orbp_*_source*: the list is the last frame's features (motion-model tracking) */
 #define ORBP_MODE_KEYFRAME 2          /* orbp_*_source*: the list is a key frame's features (relocalisation) */
+#define ORBP_MODE_FUSE 3              /* orbp_fuse*: map points into key frames (LocalMapping's Fuse).  To orbp_project* / orbp_track* it is an unknown
+                                         mode; the loop-closing projections (the Scw overload of Fuse, SearchBySim3) have no mode */
 
 typedef struct orbp_map orbp_map;
 
@@ -104,7 +126,7 @@ typedef struct orbp_record {
 } orbp_record;
 
 /* ORBX_ERR_ARG for capacity outside [1, ORBP_MAX_CAPACITY] or a NULL `out`; ORBX_ERR_DEVICE without a usable GPU.
- * Device memory: 65 bytes per slot; the scratch of orbp_track* and the block of orbp_refresh are allocated on first use and kept. */
+ * Device memory: 65 bytes per slot; the scratch of orbp_track* and the blocks of orbp_refresh and orbp_fuse are allocated on first use and kept. */
 int orbp_create(int capacity, int device, orbp_map** out);
 void orbp_destroy(orbp_map* map);
 int orbp_capacity(const orbp_map* map);
@@ -301,6 +323,58 @@ int orbp_refresh_batch_device(orbp_map* map, const int32_t* slots, int n, const 
 int orbp_refresh(orbp_map* map, const int32_t* slots, int n, const float* pos, const int32_t* obs_off, const int32_t* obs, const int32_t* ref,
                  const uint8_t* skip, const float* kf_ow, const uint8_t* kf_bad, const orbx_keypoint* kf_kps, const uint8_t* kf_desc,
                  int kf_on_device, int nkf, int cap, const float* factors, int nlevels, int what, orbp_refreshed* out, void* stream);
+
+/* ---- Fuse: the search of ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>&, float th) (src/ORBmatcher.cc:1016-1134) for many key frames in
+ * one launch; the arithmetic is stated at the top of this file (ORBP_MODE_FUSE).  View p is a key frame's pose and camera (th = Fuse's th,
+ * mode = ORBP_MODE_FUSE, view_cos_limit not read) and walks the slots d_list[p*lcap + i], i < d_nlist[p] (clamped to [0, lcap]); d_skip (may be
+ * NULL) passes entry p*lcap + i over, as does a slot that is out of range or free.  It searches key frame d_frame[p] (d_frame == NULL: key
+ * frame p) of the nframes key frames laid out as for orbp_track_batch_device: d_kps_un / d_desc / d_cell_feat + f*cap, d_cell_off +
+ * f*(ORBF_GRID_CELLS+1), d_nt[f] features (clamped to [0, cap]); the grid precondition of orbs.h applies.  So one launch covers
+ * SearchInNeighbors' forward loop (the views are the target key frames, every list the current key frame's points) and one more its reverse
+ * call (one view, the candidates).  b: the key frames' image bounds and grid; orb_dist: ORBmatcher::TH_LOW in the reference.
+ *
+ * Outputs for every i < d_nlist[p], at p*lcap + i: d_best_idx the feature the point fuses into (-1 unless the status is ORBP_FUSE_FUSED),
+ * d_best_dist the least distance of the window (INT32_MAX where nothing was scanned or kept), d_rec (may be NULL) the projection and the
+ * status.  Entries at i >= d_nlist[p] are not written.  A view whose mode is not ORBP_MODE_FUSE or whose key frame is outside [0, nframes)
+ * writes -1 / INT32_MAX / ORBP_FUSE_SKIPPED for its entries.  What Fuse does with a fused point (Replace, or AddObservation + AddMapPoint)
+ * depends on the order of the points and on isBad() / IsInKeyFrame() as earlier points left them: that loop is the caller's, and the
+ * result here does not depend on it.
+ *
+ * ORBX_ERR_ARG before anything touches the GPU for nviews outside [0, ORBP_MAX_VIEWS], lcap < 1, nviews * lcap >= 2^31, cap outside
+ * [1, ORBF_MAX_FEATURES], nframes < 1, nframes * cap >= 2^31, nlevels outside [1, ORBS_MAX_LEVELS], orb_dist outside [0, 256], a NULL
+ * required array, d_desc not 16-byte aligned, another array not 4-byte aligned.  Asynchronous on `stream` (NULL: the map's own), inside
+ * the handle's event chain; allocates nothing. */
+#define ORBP_FUSE_FUSED    0
+#define ORBP_FUSE_SKIPPED  1
+#define ORBP_FUSE_DEPTH    2
+#define ORBP_FUSE_IMAGE    3
+#define ORBP_FUSE_DISTANCE 4
+#define ORBP_FUSE_ANGLE    5
+#define ORBP_FUSE_EMPTY    6
+#define ORBP_FUSE_FAR      7
+
+typedef struct orbp_fused {
+    float u, v;                              /* the projection; zero before it is computed (ORBP_FUSE_SKIPPED, ORBP_FUSE_DEPTH) */
+    int32_t level;                           /* the predicted level; zero before it is computed (and for ORBP_FUSE_IMAGE, _DISTANCE, _ANGLE) */
+    int32_t status;                          /* ORBP_FUSE_* */
+} orbp_fused;
+
+int orbp_fuse_batch_device(orbp_map* map, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                           const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const orbf_bounds* b, int orb_dist,
+                           const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat,
+                           const int32_t* d_nt, int nframes, int cap, const int32_t* d_frame, int32_t* d_best_idx, int32_t* d_best_dist,
+                           orbp_fused* d_rec, void* stream);
+
+/* The same with HOST arrays in and out, synchronous: the latency / test form, one pinned block up and one down.  views, list, nlist, skip, nt
+ * (nframes entries), frame (nviews entries, may be NULL) and the outputs (nviews * lcap entries each; rec may be NULL) are host memory and
+ * need no alignment; the key frames' arrays (kps_un, desc, cell_off, cell_feat: the whole batch layout is copied) are host memory, or
+ * device memory when frames_on_device != 0 (a caller who keeps its key frames resident uploads the views and the lists only).  Checked
+ * here in addition: ORBX_ERR_ARG for a view whose mode is not ORBP_MODE_FUSE or whose key frame is outside [0, nframes).  The block is
+ * allocated on first use and kept. */
+int orbp_fuse(orbp_map* map, const orbp_view* views, int nviews, const float* factors, int nlevels, const int32_t* list, const int32_t* nlist,
+              int lcap, const uint8_t* skip, const orbf_bounds* b, int orb_dist, const orbx_keypoint* kps_un, const uint8_t* desc,
+              const int32_t* cell_off, const int32_t* cell_feat, const int32_t* nt, int nframes, int cap, int frames_on_device,
+              const int32_t* frame, int32_t* best_idx, int32_t* best_dist, orbp_fused* rec, void* stream);
 
 #ifdef __cplusplus
 }

@@ -56,12 +56,15 @@ EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_b
              "orbd_query_batch_device", "orbd_query"]
 EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
              "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
-             "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh"]
+             "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh", "orbp_fuse_batch_device",
+             "orbp_fuse"]
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
 # orbp_view.mode
-MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME = 0, 1, 2
+MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE = 0, 1, 2, 3
+# orbp_fused.status
+(FUSE_FUSED, FUSE_SKIPPED, FUSE_DEPTH, FUSE_IMAGE, FUSE_DISTANCE, FUSE_ANGLE, FUSE_EMPTY, FUSE_FAR) = range(8)
 # orbp_refresh*: `what` bits and orbp_refreshed.status
 REFRESH_NORMAL_DEPTH, REFRESH_DESCRIPTOR = 1, 2
 (REFRESH_OK, REFRESH_SKIPPED, REFRESH_EMPTY, REFRESH_BAD_INDEX, REFRESH_BAD_OCTAVE, REFRESH_NONFINITE) = range(6)
@@ -156,6 +159,9 @@ assert VIEW_DTYPE.itemsize == ctypes.sizeof(View) == 108 and RECORD_DTYPE.itemsi
 REFRESHED_DTYPE = np.dtype([("normal", np.float32, 3), ("min_dist", np.float32), ("max_dist", np.float32), ("best_obs", np.int32),
                             ("best_median", np.int32), ("status", np.int32)])
 assert REFRESHED_DTYPE.itemsize == 32
+# orbp_fused
+FUSED_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("level", np.int32), ("status", np.int32)])
+assert FUSED_DTYPE.itemsize == 16
 
 GRID_COLS, GRID_ROWS = 64, 48
 GRID_CELLS = GRID_COLS * GRID_ROWS
@@ -285,6 +291,8 @@ def lib():
                                  vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
         L.orbp_refresh_batch_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp]
         L.orbp_refresh.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, vp]
+        L.orbp_fuse_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.orbp_fuse.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]
         L.orbp_project_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_track_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
                                                      vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
@@ -1183,6 +1191,58 @@ class MapPointTable:
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_refresh")
         return out[:n]
+
+    def fuse_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, bounds, orb_dist, d_kps_un, d_desc, d_cell_off, d_cell_feat,
+                          d_nt, nframes, cap, d_frame, d_best_idx, d_best_dist, d_rec=0, stream=0):
+        """The search of ORBmatcher::Fuse(pKF, vpMapPoints, th) for nviews key-frame views in one launch, asynchronous.  factors: host array;
+        everything else device pointers as ints (0 = NULL: d_skip, d_frame, d_rec)"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_fuse_batch_device(self.h, d_views or None, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap, d_skip or None,
+                                          ctypes.addressof(bounds), orb_dist, d_kps_un or None, d_desc or None, d_cell_off or None, d_cell_feat or None,
+                                          d_nt or None, nframes, cap, d_frame or None, d_best_idx or None, d_best_dist or None, d_rec or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_fuse_batch_device")
+
+    def fuse(self, views, factors, lists, nlist, bounds, orb_dist, kps_un, desc, cell_off, cell_feat, nt, skip=None, frame=None, nframes=None, cap=None,
+             best_idx=None, best_dist=None, rec=None):
+        """The same with host arrays, synchronous: -> (best_idx i32[nviews, lcap], best_dist i32[nviews, lcap], rec FUSED_DTYPE[nviews, lcap]);
+        entries at i >= nlist[p] are left as they are (-1 / INT32_MAX / zero when the arrays are made here).  views: VIEW_DTYPE[nviews];
+        lists (nviews, lcap) int32 slots.  The key frames in the batch layout: kps_un (nframes, cap) KP_DTYPE, desc (nframes, cap, 32),
+        cell_off (nframes, GRID_CELLS + 1), cell_feat (nframes, cap) are host arrays, or device pointers as ints (nframes and cap must then
+        be given); nt (nframes) and frame (nviews, optional) are host arrays."""
+        views = np.ascontiguousarray(views, dtype=VIEW_DTYPE).reshape(-1)
+        nviews = len(views)
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        lists = lists.reshape(nviews, -1) if nviews else lists.reshape(0, lists.shape[-1] if lists.ndim == 2 and lists.shape[-1] else 1)
+        lcap = lists.shape[1]
+        nlist = np.ascontiguousarray(nlist, dtype=np.int32).reshape(nviews)
+        opt = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)
+        skip = opt(skip, np.uint8, (nviews, lcap)); frame = opt(frame, np.int32, nviews)
+        on_dev = isinstance(kps_un, int)
+        if not on_dev:
+            kps_un = np.ascontiguousarray(kps_un)
+            assert kps_un.dtype.itemsize == 28 and kps_un.ndim == 2
+            nframes, cap = kps_un.shape
+            desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(nframes, cap, 32)
+            cell_off = np.ascontiguousarray(cell_off, dtype=np.int32).reshape(nframes, GRID_CELLS + 1)
+            cell_feat = np.ascontiguousarray(cell_feat, dtype=np.int32).reshape(nframes, cap)
+        nt = np.ascontiguousarray(nt, dtype=np.int32).reshape(nframes)
+        if best_idx is None:
+            best_idx = np.full((nviews, lcap), -1, np.int32)
+        if best_dist is None:
+            best_dist = np.full((nviews, lcap), np.iinfo(np.int32).max, np.int32)
+        if rec is None:
+            rec = np.zeros((nviews, lcap), FUSED_DTYPE)
+        assert best_idx.dtype == np.int32 and best_dist.dtype == np.int32 and rec.dtype == FUSED_DTYPE
+        assert all(a.flags.c_contiguous and a.size == nviews * lcap for a in (best_idx, best_dist, rec))
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        rc = lib().orbp_fuse(self.h, ptr(views), nviews, f.ctypes.data, len(f), ptr(lists), ptr(nlist), lcap, ptr(skip), ctypes.addressof(bounds), orb_dist,
+                             ptr(kps_un), ptr(desc), ptr(cell_off), ptr(cell_feat), ptr(nt), nframes, cap, 1 if on_dev else 0, ptr(frame), ptr(best_idx),
+                             ptr(best_dist), ptr(rec), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_fuse")
+        return best_idx, best_dist, rec
 
     def project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
                              d_overflow, qcap, stream=0):

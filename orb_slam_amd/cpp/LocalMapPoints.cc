@@ -38,6 +38,8 @@ LocalMapPoints::~LocalMapPoints() {
     orbp_destroy(map_);
     if (d_kf_kps_) orbx_device_free(device_, d_kf_kps_);
     if (d_kf_desc_) orbx_device_free(device_, d_kf_desc_);
+    if (d_kf_cell_off_) orbx_device_free(device_, d_kf_cell_off_);
+    if (d_kf_cell_feat_) orbx_device_free(device_, d_kf_cell_feat_);
 }
 
 void LocalMapPoints::grow() {

@@ -9,6 +9,9 @@
 // Refresh (LocalMapPointsRefresh.cc) replaces the pair MapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors + Put: the listed points'
 // observation lists and their key frames' camera centres go up, the normal, the two distances and the descriptor are computed on the GPU
 // from key frames whose features stay resident (orbp_refresh), and land in the table's slots directly.
+// Fuse / FuseInNeighbors (LocalMapPointsFuse.cc) replace ORBmatcher::Fuse(pKF, vpMapPoints, th) as LocalMapping::SearchInNeighbors calls it: the
+// search of every target key frame is one orbp_fuse over the same resident key frames, whose rows then carry their grid too; Replace /
+// AddObservation / AddMapPoint stay the reference's in-order loop on the host.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
@@ -67,6 +70,18 @@ public:
     // gives up pKF's row of the resident key-frame store: call it when a key frame is deleted
     void ForgetKeyFrame(KeyFrame* pKF);
 
+    // int ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>&, float th) (src/ORBmatcher.cc:1016-1134) with the reference's signature and effects
+    // (LocalMapPointsFuse.cc; links only when that file and LocalMapPointsRefresh.cc are built in).  Reads of the key frame GetRotation(),
+    // GetTranslation(), GetCameraCenter(), fx, fy, cx, cy, GetScaleFactors(), GetScaleLevels(), GetMapPoint() and, once per key frame,
+    // GetKeyPointsUn(), GetDescriptors() and its grid (ORBmatcherAccess.h); of the points isBad() and IsInKeyFrame() as of each iteration;
+    // calls Replace() or AddObservation() + AddMapPoint() as the reference does.  Points not yet mirrored are Put on the way.
+    int Fuse(KeyFrame* pKF, std::vector<MapPoint*>& vpMapPoints, float th = 2.5);
+    // Lines :398-430 of LocalMapping::SearchInNeighbors (src/LocalMapping.cc): pCurrent's points into every target key frame (one orbp_fuse for all
+    // of them, then the reference's loop per target in order), the candidate list built from the targets as the reference builds it (it
+    // sets MapPoint::mnFuseCandidateForKF), and the candidates into pCurrent (one more orbp_fuse, then the loop).  nFused (may be NULL)
+    // receives the return value of each of the vpTargetKFs.size() + 1 Fuse calls this replaces.
+    void FuseInNeighbors(KeyFrame* pCurrent, const std::vector<KeyFrame*>& vpTargetKFs, float th = 2.5, std::vector<int>* nFused = 0);
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
@@ -90,15 +105,24 @@ private:
     std::vector<int32_t> dirty_list_, dead_list_;
     std::vector<float> pos_, nrm_, dmin_, dmax_; // host copy of the table (re-uploaded when it grows)
     std::vector<uint8_t> desc_;
-    // the key frames Refresh has seen: one row of feat_cap_ key points and descriptors each, resident on the device
+    // the key frames Refresh and Fuse have seen: one row of feat_cap_ key points and descriptors each, resident on the device, and (once Fuse
+    // has needed it) the row's grid CSR
     int keyFrameRow(KeyFrame* pKF);
     void growKeyFrames(int rows, int feats);
+    void residentForFuse(const std::vector<KeyFrame*>& kfs);
+    // best_idx of orbp_fuse for views[p] = (targets[p], *lists[p]) -> best[p][i]
+    void searchFuse(const std::vector<KeyFrame*>& targets, const std::vector<const std::vector<MapPoint*>*>& lists, float th,
+                    std::vector<std::vector<int32_t> >& best);
     std::unordered_map<KeyFrame*, int> kf_row_;
     std::vector<KeyFrame*> kf_owner_;            // per row; NULL = free
     std::vector<int32_t> kf_free_;
     std::vector<uint8_t> kf_resident_;           // per row: its features are on the device
+    std::vector<uint8_t> kf_grid_resident_;      // per row: its grid is on the device
+    std::vector<int32_t> kf_nt_;                 // per row: its number of features
     void* d_kf_kps_ = nullptr;
     void* d_kf_desc_ = nullptr;
+    void* d_kf_cell_off_ = nullptr;
+    void* d_kf_cell_feat_ = nullptr;
     int kf_rows_ = 0, feat_cap_ = 0;
     // per call
     std::vector<int32_t> list_, t2slot_, t2pos_, cell_off_, cell_feat_;

@@ -24,13 +24,20 @@ void LocalMapPoints::growKeyFrames(int rows, int feats) {
     static_assert(sizeof(cv::KeyPoint) == sizeof(orbx_keypoint), "cv::KeyPoint and orbx_keypoint share one layout");
     if (d_kf_kps_) orbx_device_free(device_, d_kf_kps_);
     if (d_kf_desc_) orbx_device_free(device_, d_kf_desc_);
-    d_kf_kps_ = d_kf_desc_ = nullptr;
+    if (d_kf_cell_off_) orbx_device_free(device_, d_kf_cell_off_);
+    if (d_kf_cell_feat_) orbx_device_free(device_, d_kf_cell_feat_);
+    d_kf_kps_ = d_kf_desc_ = d_kf_cell_off_ = d_kf_cell_feat_ = nullptr;
     int rc = orbx_device_alloc(device_, (size_t)rows * feats * sizeof(orbx_keypoint), &d_kf_kps_);
     if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)rows * feats * 32, &d_kf_desc_);
+    // the rows' grids, for Fuse (LocalMapPointsFuse.cc fills them): 12 KiB per row
+    if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)rows * (ORBF_GRID_CELLS + 1) * 4, &d_kf_cell_off_);
+    if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)rows * feats * 4, &d_kf_cell_feat_);
     if (rc != ORBX_OK) fail("orbx_device_alloc (key-frame store)", rc);
     for (int r = rows - 1; r >= kf_rows_; r--) kf_free_.push_back(r);
     kf_owner_.resize(rows, nullptr);
     kf_resident_.assign(rows, 0);
+    kf_grid_resident_.assign(rows, 0);
+    kf_nt_.assign(rows, 0);
     kf_rows_ = rows;
     feat_cap_ = feats;
 }
@@ -44,6 +51,7 @@ int LocalMapPoints::keyFrameRow(KeyFrame* pKF) {
     kf_row_[pKF] = row;
     kf_owner_[row] = pKF;
     kf_resident_[row] = 0;
+    kf_grid_resident_[row] = 0;
     return row;
 }
 
@@ -52,6 +60,7 @@ void LocalMapPoints::ForgetKeyFrame(KeyFrame* pKF) {
     if (it == kf_row_.end()) return;
     kf_owner_[it->second] = nullptr;
     kf_resident_[it->second] = 0;
+    kf_grid_resident_[it->second] = 0;
     kf_free_.push_back(it->second);
     kf_row_.erase(it);
 }
@@ -137,6 +146,7 @@ std::vector<orbp_refreshed> LocalMapPoints::Refresh(const std::vector<MapPoint*>
         }
         if (rc != ORBX_OK) fail("orbx_device_upload (key frame)", rc);
         kf_resident_[row] = 1;
+        kf_nt_[row] = (int32_t)nf;
     }
 
     // slots: what is pending goes up first, then the new points take theirs (a table that has to grow is re-uploaded from the mirror)

@@ -1,5 +1,6 @@
 // The argument groups of the map-point walk (orbp_project.hip) and the layouts of the blocks an orbp_map keeps for them.  Host C++
-// only: tests/_probe/host_owners.cpp and tests/_probe/refresh_host.cpp hold the layouts against their sizes without a GPU.
+// only: tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp and tests/_probe/fuse_host.cpp hold the layouts against their sizes
+// without a GPU.
 #pragma once
 #include <cstring>
 
@@ -164,6 +165,98 @@ struct RefreshBlock {
         if (kf_desc.present) std::memcpy(Layout::at(h, kf_desc), k.desc, nfeat * 32);
         dl = {Layout::at(d, pos), Layout::at(d, obs_off), Layout::at(d, obs), Layout::at(d, ref), Layout::at(d, skip)};
         dk = {Layout::at(d, kf_ow), Layout::at(d, kf_bad), kf_kps.present ? Layout::at(d, kf_kps) : k.kps, kf_desc.present ? Layout::at(d, kf_desc) : k.desc, k.nkf, k.cap};
+    }
+};
+
+// what orbp_fuse* reads beyond the lists: the key frames in the batch layout (row f at f*cap, its grid at f*(ORBF_GRID_CELLS+1)), and the row
+// each view searches (frame == NULL: view p searches row p)
+struct FuseFrames { const orbx_keypoint* kps_un; const uint8_t* desc; const int32_t* cell_off; const int32_t* cell_feat; const int32_t* nt; int nframes, cap; const int32_t* frame; };
+struct FuseOut { int32_t* best_idx; int32_t* best_dist; orbp_fused* rec; };
+
+// what the fuse kernel reads and writes (orbp_fuse.hip); p0: the first view of the launch
+struct Fuse {
+    const orbp_view* views;
+    int capacity;                                      // the table
+    const float* geom;
+    const uint8_t* tdesc;
+    const uint8_t* live;
+    Lists L;
+    FuseFrames K;
+    orbf_bounds b;
+    int orb_dist;
+    FuseOut out;
+    int p0;
+};
+hipError_t launch_fuse(const Fuse& a, int nviews, const Factors& F, hipStream_t st);
+
+// The arguments of orbp_fuse* that do not need the handle.  on_device: views, lists and outputs are device memory (orbp_fuse_batch_device),
+// so only their presence and alignment can be checked; else the views' modes and rows are walked.  frames_device: the key frames are device
+// addresses, their descriptors read in 16-byte pieces (host arrays are copied into aligned slots).
+inline int check_fuse(const orbp_view* views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
+                      const FuseFrames& K, const FuseOut& out, bool on_device, bool frames_device) {
+    if (nviews < 0 || nviews > ORBP_MAX_VIEWS || L.lcap < 1 || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
+    if (!b || orb_dist < 0 || orb_dist > 256) return ORBX_ERR_ARG;
+    if (K.cap < 1 || K.cap > ORBF_MAX_FEATURES || K.nframes < 1 || (long long)K.nframes * K.cap >= (1ll << 31)) return ORBX_ERR_ARG;
+    if ((long long)nviews * L.lcap >= (1ll << 31)) return ORBX_ERR_ARG;                               // the outputs are indexed p*lcap + i
+    if (nviews == 0) return ORBX_OK;
+    if (!views || !L.list || !L.nlist || !K.kps_un || !K.desc || !K.cell_off || !K.cell_feat || !K.nt || !out.best_idx || !out.best_dist) return ORBX_ERR_ARG;
+    if (frames_device && (((uintptr_t)K.desc & 15) || (((uintptr_t)K.kps_un | (uintptr_t)K.cell_off | (uintptr_t)K.cell_feat) & 3))) return ORBX_ERR_ARG;
+    if (on_device) {
+        const uintptr_t words = (uintptr_t)views | (uintptr_t)L.list | (uintptr_t)L.nlist | (uintptr_t)K.nt | (uintptr_t)K.frame | (uintptr_t)out.best_idx |
+                                (uintptr_t)out.best_dist | (uintptr_t)out.rec;
+        if (words & 3) return ORBX_ERR_ARG;
+    } else {
+        for (int p = 0; p < nviews; p++) {
+            const int f = K.frame ? K.frame[p] : p;
+            if (views[p].mode != ORBP_MODE_FUSE || f < 0 || f >= K.nframes) return ORBX_ERR_ARG;
+        }
+    }
+    return ORBX_OK;
+}
+
+// The block of orbp_fuse, one pinned copy up and one down:
+//   up    [views | nlist | frame | nt | list | skip | kps_un | desc | cell_off | cell_feat]     (absent: frame and skip when the caller passes none,
+//                                                                                                the key frames' arrays when they are on the device)
+//   down  [best_idx | best_dist | rec]                                                          (rec absent when the caller wants none)
+struct FuseBlock {
+    Layout L;
+    Layout::Slot<orbp_view> views;
+    Layout::Slot<int32_t> nlist, frame, nt, list, cell_off, cell_feat, best_idx, best_dist;
+    Layout::Slot<uint8_t> skip, desc;
+    Layout::Slot<orbx_keypoint> kps;
+    Layout::Slot<orbp_fused> rec;
+    int nviews, nframes;
+    size_t nent, nfeat;                                // nviews * lcap, nframes * cap
+    FuseBlock(int nviews_, const Lists& l, const FuseFrames& k, bool frames_upload, bool with_rec)
+        : nviews(nviews_), nframes(k.nframes), nent((size_t)nviews_ * l.lcap), nfeat((size_t)k.nframes * k.cap) {
+        views = L.add<orbp_view>(nviews); nlist = L.add<int32_t>(nviews); frame = L.add<int32_t>(nviews, k.frame != nullptr); nt = L.add<int32_t>(nframes);
+        list = L.add<int32_t>(nent); skip = L.add<uint8_t>(nent, l.skip != nullptr);
+        kps = L.add<orbx_keypoint>(nfeat, frames_upload); desc = L.add<uint8_t>(nfeat * 32, frames_upload);
+        cell_off = L.add<int32_t>((size_t)nframes * (ORBF_GRID_CELLS + 1), frames_upload); cell_feat = L.add<int32_t>(nfeat, frames_upload);
+        L.end_upload();
+        best_idx = L.add<int32_t>(nent); best_dist = L.add<int32_t>(nent); rec = L.add<orbp_fused>(nent, with_rec);
+        L.end_download();
+    }
+    // copies the caller's host arrays into the pinned block h and names everything inside the device block d; key frames that are not part
+    // of the block are passed through
+    void stage(uint8_t* h, uint8_t* d, const orbp_view* v, const Lists& l, const FuseFrames& k, const orbp_view*& dv, Lists& dl, FuseFrames& dk, FuseOut& dout) const {
+        std::memcpy(Layout::at(h, views), v, (size_t)nviews * sizeof(orbp_view));
+        std::memcpy(Layout::at(h, nlist), l.nlist, (size_t)nviews * 4);
+        if (frame.present) std::memcpy(Layout::at(h, frame), k.frame, (size_t)nviews * 4);
+        std::memcpy(Layout::at(h, nt), k.nt, (size_t)nframes * 4);
+        std::memcpy(Layout::at(h, list), l.list, nent * 4);
+        if (skip.present) std::memcpy(Layout::at(h, skip), l.skip, nent);
+        if (kps.present) {
+            std::memcpy(Layout::at(h, kps), k.kps_un, nfeat * sizeof(orbx_keypoint));
+            std::memcpy(Layout::at(h, desc), k.desc, nfeat * 32);
+            std::memcpy(Layout::at(h, cell_off), k.cell_off, (size_t)nframes * (ORBF_GRID_CELLS + 1) * 4);
+            std::memcpy(Layout::at(h, cell_feat), k.cell_feat, nfeat * 4);
+        }
+        dv = Layout::at(d, views);
+        dl = {Layout::at(d, list), Layout::at(d, nlist), l.lcap, Layout::at(d, skip)};
+        dk = {kps.present ? Layout::at(d, kps) : k.kps_un, kps.present ? Layout::at(d, desc) : k.desc, kps.present ? Layout::at(d, cell_off) : k.cell_off,
+              kps.present ? Layout::at(d, cell_feat) : k.cell_feat, Layout::at(d, nt), k.nframes, k.cap, Layout::at(d, frame)};
+        dout = {Layout::at(d, best_idx), Layout::at(d, best_dist), Layout::at(d, rec)};
     }
 };
 

@@ -20,6 +20,7 @@
 //              (key frame) descriptor.  The key point's octave and angle do not depend on the slot, so their loads leave with the
 //              list's and overlap the dependent list -> live -> geometry chain that bounds the stage.
 //   (k_refresh, the refresh of slots from their observations, is orbp_refresh.hip; its host side is refresh_locked below.)
+//   (k_fuse, the search of LocalMapping's Fuse over (view, entry), is orbp_fuse.hip; its host side is orbp_fuse* below.)
 //   k_t2source orbp_track*: turns the search's feature -> query table into feature -> list position (the source feature index of
 //              orbp_track_source*) and feature -> map slot through the list positions the projection left (d_qpos); features
 //              without a match, or beyond the frame's count, get -1.  Either output may be absent, and so may the list (identity).
@@ -77,18 +78,6 @@ __global__ __launch_bounds__(TPB) void k_erase(int n, const int32_t* slots, uint
     if (i < n) live[slots[i]] = 0;
 }
 
-// Rcw * P + tcw as the reference's cv::Mat product evaluates it.  Every operation here and below is a single IEEE operation in the
-// reference's order (the build has -ffp-contract=off; `0.0f + x` is not an identity in IEEE arithmetic and is kept).
-__device__ __forceinline__ void to_camera(const orbp_view& V, const float P[3], float Pc[3]) {
-    for (int r = 0; r < 3; r++) {
-        float s = 0.0f;
-        s = s + V.Rcw[r * 3] * P[0];
-        s = s + V.Rcw[r * 3 + 1] * P[1];
-        s = s + V.Rcw[r * 3 + 2] * P[2];
-        Pc[r] = s + V.tcw[r];
-    }
-}
-
 // src/Frame.cc:151-160 (= src/ORBmatcher.cc:1529-1542, :1647-1660): the projection of a point in camera coordinates; true = inside
 // the image bounds.  The documented deviation: a NaN projection is outside.
 __device__ __forceinline__ bool to_image(const orbp_view& V, const float Pc[3], float& u, float& v) {
@@ -100,13 +89,6 @@ __device__ __forceinline__ bool to_image(const orbp_view& V, const float Pc[3], 
     return !(u != u || v != v);
 }
 
-// std::lower_bound on the ascending table, clipped to the last level
-__device__ __forceinline__ int level_of(const Factors& F, float ratio) {
-    int lv = 0;
-    for (int k = 0; k < F.n; k++) lv += F.f[k] < ratio ? 1 : 0;
-    return lv >= F.n ? F.n - 1 : lv;
-}
-
 // src/Frame.cc:137-198 for one point; true = visible
 __device__ __forceinline__ bool in_frustum(const orbp_view& V, const Factors& F, const float4 g0, const float4 g1, float& u, float& v,
                                            float& view_cos, int& level) {
@@ -115,11 +97,8 @@ __device__ __forceinline__ bool in_frustum(const orbp_view& V, const Factors& F,
     float Pc[3];
     to_camera(V, P, Pc);
     if (Pc[2] < 0.0f || !to_image(V, Pc, u, v)) return false;
-    double PO[3];
-    for (int k = 0; k < 3; k++) PO[k] = (double)(P[k] - V.Ow[k]);
-    double s2 = 0.0, dot = 0.0;
-    for (int k = 0; k < 3; k++) s2 = s2 + PO[k] * PO[k];
-    const float dist = (float)sqrt(s2);
+    double PO[3], dot = 0.0;
+    const float dist = centre_distance(V, P, PO);
     if (dist < dmin || dist > dmax) return false;
     for (int k = 0; k < 3; k++) dot = dot + PO[k] * (double)Pn[k];
     view_cos = (float)(dot / (double)dist);
@@ -130,12 +109,8 @@ __device__ __forceinline__ bool in_frustum(const orbp_view& V, const Factors& F,
 
 // src/ORBmatcher.cc:1662-1669: the level predicted from the distance to the camera centre
 __device__ __forceinline__ int predicted_level(const orbp_view& V, const Factors& F, const float P[3], float dmin) {
-    double s2 = 0.0;
-    for (int k = 0; k < 3; k++) {
-        const double d = (double)(P[k] - V.Ow[k]);
-        s2 = s2 + d * d;
-    }
-    return level_of(F, (float)sqrt(s2) / dmin);
+    double PO[3];
+    return level_of(F, centre_distance(V, P, PO) / dmin);
 }
 
 template <bool SOURCE>
@@ -243,7 +218,7 @@ struct orbp_map {
     uint32_t stamp_now = 0;
     orbx::DevBuf geom, desc, d_live, d_tab, scratch;
     orbx::PinnedBuf h_tab;
-    orbx::Block one, put, refresh;                    // the blocks of the one-view calls, of orbp_put and of orbp_refresh
+    orbx::Block one, put, refresh, fuse;              // the blocks of the one-view calls, of orbp_put, of orbp_refresh and of orbp_fuse
     orbx::Stream own;
     orbx::Chain chain;                                // device work on the map is ordered across the callers' streams
     orbx::Event tab_done;
@@ -679,6 +654,80 @@ int orbp_refresh(orbp_map* m, const int32_t* slots, int n, const float* pos, con
     for (int i = 0; i < n; i++)
         if (res[i].status == ORBP_REFRESH_OK && !m->live[slots[i]]) { m->live[slots[i]] = 1; m->n_live++; }
     if (out) std::memcpy(out, res, (size_t)n * sizeof(orbp_refreshed));
+    return ORBX_OK;
+}
+
+int orbp_fuse_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                           const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const orbf_bounds* b, int orb_dist, const orbx_keypoint* d_kps_un,
+                           const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat, const int32_t* d_nt, int nframes, int cap,
+                           const int32_t* d_frame, int32_t* d_best_idx, int32_t* d_best_dist, orbp_fused* d_rec, void* stream) {
+    const orbp::Lists L{d_list, d_nlist, lcap, d_skip};
+    const orbp::FuseFrames K{d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt, nframes, cap, d_frame};
+    const orbp::FuseOut out{d_best_idx, d_best_dist, d_rec};
+    orbp::Factors F;
+    if (!m || orbp::check_fuse(d_views, nviews, factors, nlevels, L, b, orb_dist, K, out, true, true) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    std::lock_guard<std::mutex> lk(m->mu);
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    HIPCHK(m, m->chain.begin(st));
+    Link link(m->chain, st);
+    const orbp::Fuse a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), L, K, *b, orb_dist, out, 0};
+    HIPCHK(m, orbp::launch_fuse(a, nviews, F, st));
+    HIPCHK(m, link.end());
+    return ORBX_OK;
+}
+
+int orbp_fuse(orbp_map* m, const orbp_view* views, int nviews, const float* factors, int nlevels, const int32_t* list, const int32_t* nlist, int lcap,
+              const uint8_t* skip, const orbf_bounds* b, int orb_dist, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
+              const int32_t* cell_feat, const int32_t* nt, int nframes, int cap, int frames_on_device, const int32_t* frame, int32_t* best_idx,
+              int32_t* best_dist, orbp_fused* rec, void* stream) {
+    const orbp::Lists L{list, nlist, lcap, skip};
+    const orbp::FuseFrames K{kps_un, desc, cell_off, cell_feat, nt, nframes, cap, frame};
+    const orbp::FuseOut out{best_idx, best_dist, rec};
+    orbp::Factors F;
+    if (!m || orbp::check_fuse(views, nviews, factors, nlevels, L, b, orb_dist, K, out, false, frames_on_device != 0) != ORBX_OK ||
+        fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    std::lock_guard<std::mutex> lk(m->mu);
+    DeviceScope ds(m->device);
+    if (!ds.ok) return ORBX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    const orbp::FuseBlock B(nviews, L, K, frames_on_device == 0, rec != nullptr);
+    const size_t up_bytes = B.L.upload(), total = B.L.total();
+    if (!m->fuse.fits(total, total)) {
+        size_t want = std::max<size_t>(4096, m->fuse.h.size());
+        while (want < total) want *= 2;
+        const int rc = grow(m, m->fuse, want, want);
+        if (rc != ORBX_OK) return rc;
+    }
+    uint8_t* h = m->fuse.h.as();
+    uint8_t* d = m->fuse.d.as();
+    const orbp_view* dv;
+    orbp::Lists dl;
+    orbp::FuseFrames dk;
+    orbp::FuseOut dout;
+    B.stage(h, d, views, L, K, dv, dl, dk, dout);
+    HIPCHK(m, m->chain.begin(st));
+    Link link(m->chain, st);                                           // every way out leaves the copies below behind the chain
+    HIPCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    const orbp::Fuse a{dv, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), dl, dk, *b, orb_dist, dout, 0};
+    HIPCHK(m, orbp::launch_fuse(a, nviews, F, st));
+    HIPCHK(m, hipMemcpyAsync(h + up_bytes, d + up_bytes, total - up_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(m, link.end());
+    HIPCHK(m, hipStreamSynchronize(st));
+    // only what the kernel wrote reaches the caller: entries at i >= nlist[p] stay as they were
+    for (int p = 0; p < nviews; p++) {
+        const int n = std::min(std::max(nlist[p], 0), lcap);
+        const size_t e = (size_t)p * lcap;
+        if (n == 0) continue;
+        std::memcpy(best_idx + e, Layout::at(h, B.best_idx) + e, (size_t)n * 4);
+        std::memcpy(best_dist + e, Layout::at(h, B.best_dist) + e, (size_t)n * 4);
+        if (rec) std::memcpy(rec + e, Layout::at(h, B.rec) + e, (size_t)n * sizeof(orbp_fused));
+    }
     return ORBX_OK;
 }
 

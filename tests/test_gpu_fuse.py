@@ -1,0 +1,362 @@
+"""orbp_fuse / orbp_fuse_batch_device (include/orbp.h, ORBP_MODE_FUSE) on the GPU: the search of ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>&,
+float th) for many key-frame views in one launch, over map points that stay in the table.  Device = restatement (tests/fuse_ref.py, which
+tests/test_fuse_ref_pin.py holds against the reference's own function), all equal: best_idx, best_dist and the records, u and v bit for bit,
+through the device form, the host form, the host form with resident key frames, and capi.MapPointTable's methods for them."""
+import numpy as np
+import pytest
+import torch
+
+import frustum_ref as fr
+import fuse_ref as fz
+import fuse_scenes as fs
+import oracle_lib as ol
+from orb_slam_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+CAP, LCAP, TABLE = 512, 768, 4096
+INT_MAX = np.iinfo(np.int32).max
+FILL_IDX, FILL_DIST, FILL_BYTE = -77, 123456, 0xEE
+
+
+def dev(a):
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.uint8) if a.dtype.names else a).cuda()
+
+
+def batch_layout(frames, b):
+    """key frames (kps, desc, off, feat) in the batch layout of cap CAP -> (kps_un, desc, cell_off, cell_feat, nt)"""
+    n = len(frames)
+    kps = np.zeros((n, CAP), capi.KP_DTYPE); desc = np.zeros((n, CAP, 32), np.uint8)
+    off = np.zeros((n, capi.GRID_CELLS + 1), np.int32); feat = np.zeros((n, CAP), np.int32); nt = np.zeros(n, np.int32)
+    for f, (k, d, o, ft) in enumerate(frames):
+        nt[f] = len(k)
+        kps[f, :len(k)] = k; desc[f, :len(k)] = d; off[f] = o; feat[f, :len(ft)] = ft
+    return kps, desc, off, feat, nt
+
+
+def expect(views, factors, b, orb_dist, table, live, lists, nlist, skip, frames, frame, fill=True):
+    """the restatement for every view -> (best_idx, best_dist, rec) of shape (nviews, lcap), entries at i >= nlist[p] as pre-filled"""
+    nviews, lcap = lists.shape
+    idx = np.full((nviews, lcap), FILL_IDX, np.int32); dist = np.full((nviews, lcap), FILL_DIST, np.int32)
+    rec = np.frombuffer(bytes([FILL_BYTE]) * (nviews * lcap * 16), capi.FUSED_DTYPE).reshape(nviews, lcap).copy()
+    for p in range(nviews):
+        n = int(nlist[p])
+        sl = lists[p, :n]
+        inside = (sl >= 0) & (sl < len(live))
+        s = np.where(inside, sl, 0)
+        off = ~inside | (live[s] == 0) | (skip[p, :n] != 0 if skip is not None else False)
+        k, d, o, ft = frames[frame[p] if frame is not None else p]
+        w = fz.fuse(views[p], factors, b, orb_dist, table["pos"][s], table["normal"][s], table["dmin"][s], table["dmax"][s], table["desc"][s], k, d, o, ft, off=off)
+        idx[p, :n] = w["best_idx"]; dist[p, :n] = w["best_dist"]
+        rec["u"][p, :n] = w["u"]; rec["v"][p, :n] = w["v"]; rec["level"][p, :n] = w["level"]; rec["status"][p, :n] = w["status"]
+    return idx, dist, rec
+
+
+def same(got, want, what):
+    gi, gd, gr = got
+    wi, wd, wr = want
+    assert np.array_equal(gi, wi), (what, "best_idx", np.argwhere(gi != wi)[:8].tolist())
+    assert np.array_equal(gd, wd), (what, "best_dist", np.argwhere(gd != wd)[:8].tolist())
+    assert np.array_equal(gr["status"], wr["status"]), (what, "status", np.argwhere(gr["status"] != wr["status"])[:8].tolist())
+    assert np.array_equal(gr["level"], wr["level"]), (what, "level")
+    for k in ("u", "v"):
+        # bit for bit; a NaN (0 * inf: a point on the optical axis at depth 0) is a NaN on both sides, its sign the machine's choice
+        ok = (gr[k].view(np.uint32) == wr[k].view(np.uint32)) | (np.isnan(gr[k]) & np.isnan(wr[k]))
+        assert ok.all(), (what, k, np.argwhere(~ok)[:8].tolist())
+
+
+def run_forms(tab, vrec, factors, b, orb_dist, lists, nlist, skip, layout, frame, want, forms=("device", "host", "resident")):
+    """the same call through every form, each against `want`; the outputs are pre-filled so that entries past nlist show a stray write"""
+    nviews, lcap = lists.shape
+    kps, desc, off, feat, nt = layout
+    nframes = len(nt)
+
+    def filled():
+        return (np.full((nviews, lcap), FILL_IDX, np.int32), np.full((nviews, lcap), FILL_DIST, np.int32),
+                np.frombuffer(bytes([FILL_BYTE]) * (nviews * lcap * 16), capi.FUSED_DTYPE).reshape(nviews, lcap).copy())
+
+    d_k, d_d, d_o, d_f = dev(kps), dev(desc), dev(off), dev(feat)
+    for form in forms:
+        if form == "device":
+            i0, d0, r0 = filled()
+            d_i, d_dist, d_r = dev(i0), dev(d0), dev(r0)
+            d_v, d_l, d_n, d_nt = dev(vrec), dev(lists), dev(nlist), dev(nt)
+            d_s = dev(skip) if skip is not None else None
+            d_fr = dev(frame) if frame is not None else None
+            tab.fuse_batch_device(d_v.data_ptr(), nviews, factors, d_l.data_ptr(), d_n.data_ptr(), lcap, d_s.data_ptr() if d_s is not None else 0, b, orb_dist,
+                                  d_k.data_ptr(), d_d.data_ptr(), d_o.data_ptr(), d_f.data_ptr(), d_nt.data_ptr(), nframes, CAP,
+                                  d_fr.data_ptr() if d_fr is not None else 0, d_i.data_ptr(), d_dist.data_ptr(), d_r.data_ptr(),
+                                  torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            got = d_i.cpu().numpy(), d_dist.cpu().numpy(), d_r.cpu().numpy().view(capi.FUSED_DTYPE).reshape(nviews, lcap)
+        else:
+            i0, d0, r0 = filled()
+            if form == "host":
+                got = tab.fuse(vrec, factors, lists, nlist, b, orb_dist, kps, desc, off, feat, nt, skip=skip, frame=frame, best_idx=i0, best_dist=d0, rec=r0)
+            else:
+                got = tab.fuse(vrec, factors, lists, nlist, b, orb_dist, d_k.data_ptr(), d_d.data_ptr(), d_o.data_ptr(), d_f.data_ptr(), nt, skip=skip, frame=frame,
+                               nframes=nframes, cap=CAP, best_idx=i0, best_dist=d0, rec=r0)
+        same(got, want, form)
+
+
+# ---- random scenes at general poses: the shapes
+@pytest.fixture(scope="module")
+def world():
+    """four key frames of nt 512, 300, 1, 0 (cap 512), a general pose each, and a table whose points were aimed at them"""
+    rng = np.random.default_rng(31)
+    b = fs.bounds()
+    factors8 = fr.scale_factors(8)
+    frames = [fs.keyframe(rng, n, b, crowd=(n == 300)) for n in (512, 300, 1, 0)]
+    poses = [fs.general_view(rng, b) for _ in frames]
+    groups = [fs.points(rng, poses[f], factors8, frames[f][0], frames[f][1], 800) for f in range(4)]
+    table = {k: np.concatenate([g[k] for g in groups]) for k in ("pos", "normal", "dmin", "dmax", "desc")}
+    live = np.ones(TABLE, np.uint8)
+    live[3200:] = 0                                                    # 3200 points in slots 0..3199
+    live[rng.integers(0, 3200, 150)] = 0                               # free slots among them
+    pad = {k: np.concatenate([v, np.zeros((TABLE - 3200,) + v.shape[1:], v.dtype)]) for k, v in table.items()}
+    tab = capi.MapPointTable(TABLE)
+    s = np.nonzero(live)[0].astype(np.int32)
+    tab.put(s, pad["pos"][s], pad["normal"][s], pad["dmin"][s], pad["dmax"][s], pad["desc"][s])
+    yield dict(b=b, frames=frames, poses=poses, table=pad, live=live, tab=tab, layout=batch_layout(frames, b))
+    tab.close()
+
+
+def lists_for(rng, frame_of_view, nlist):
+    """view p lists mostly the points aimed at its key frame, some aimed elsewhere, and the slots -1, TABLE and a free one"""
+    nviews = len(nlist)
+    lists = rng.integers(0, 3200, (nviews, LCAP)).astype(np.int32)
+    for p, f in enumerate(frame_of_view):
+        own = rng.random(LCAP) < 0.85
+        lists[p, own] = rng.integers(800 * f, 800 * (f + 1), int(own.sum()))
+        lists[p, rng.integers(0, LCAP, 6)] = [-1, TABLE, TABLE + 5, -2**31, 3500, 2**31 - 1]
+    skip = (rng.random((nviews, LCAP)) < 0.06).astype(np.uint8)
+    return lists, np.asarray(nlist, np.int32), skip
+
+
+CALLS = {
+    "three_views_frame_p": ((700, 255, 1), None),
+    "three_views_permuted_shared_row": ((256, 257, 0), (3, 0, 0)),
+    "one_view_long": ((700,), (1,)),
+    "one_view_single_entry": ((1,), None),
+    "three_views_into_small_frames": ((257, 700, 255), (2, 3, 1)),
+}
+
+
+@pytest.mark.parametrize("nlevels,th", [(8, 2.5), (8, 4.0), (1, 4.0)])
+@pytest.mark.parametrize("call", sorted(CALLS))
+def test_shapes(world, call, nlevels, th):
+    nlist, frame = CALLS[call]
+    rng = np.random.default_rng(len(call) * 100 + nlevels)
+    fr_of = list(frame) if frame is not None else list(range(len(nlist)))
+    lists, nlist, skip = lists_for(rng, fr_of, nlist)
+    factors = fr.scale_factors(nlevels)
+    views = []
+    for f in fr_of:
+        v = dict(world["poses"][f])
+        v["th"] = F32(th)
+        views.append(v)
+    vrec = np.concatenate([fz.view_record(v) for v in views])
+    frame = None if frame is None else np.asarray(frame, np.int32)
+    want = expect(views, factors, world["b"], 50, world["table"], world["live"], lists, nlist, skip, world["frames"], frame)
+    if call == "three_views_frame_p" and nlevels == 8:
+        hist = np.bincount(want[2]["status"][0, :700], minlength=8)
+        assert (hist[:8] >= 10).all(), hist                                # every status in one list
+    run_forms(world["tab"], vrec, factors, world["b"], 50, lists, nlist, skip, world["layout"], frame, want)
+    if call == "one_view_long":                                            # without skip flags and records
+        want2 = expect(views, factors, world["b"], 50, world["table"], world["live"], lists, nlist, None, world["frames"], frame)
+        got = world["tab"].fuse(vrec, factors, lists, nlist, world["b"], 50, *world["layout"], frame=frame)
+        assert np.array_equal(got[0][0, :700], want2[0][0, :700]) and np.array_equal(got[1][0, :700], want2[1][0, :700])
+        assert (got[0][0, 700:] == -1).all() and (got[1][0, 700:] == INT_MAX).all()
+
+
+# ---- planted entries: a camera whose projection is exact (identity pose, fx = fy = 2, centre 0, points at depth 2: u = X, v = Y)
+def exact_view(b, th):
+    return fr.make_view(np.eye(3), np.zeros(3), np.zeros(3), 2.0, 2.0, 0.0, 0.0, b.min_x, b.max_x, b.min_y, b.max_y, th=th)
+
+
+def planted_keyframe(rng, b):
+    """random features left of x = 400 and, spaced 40 px and more apart to the right of it, the features the planted points aim at -> (frame, named indices)"""
+    k0, d0, _, _ = fs.keyframe(rng, 200, b, x_max=400.0)
+    named, xs, ys, octs, descs = {}, [], [], [], []
+
+    def add(name, x, y, octave, desc=None):
+        named[name] = 200 + len(xs)
+        xs.append(x); ys.append(y); octs.append(octave)
+        descs.append(rng.integers(0, 256, 32, dtype=np.uint8) if desc is None else desc)
+
+    add("d50", 440.0, 40.0, 1); add("d51", 480.0, 40.0, 1)
+    add("level0", 520.0, 40.0, 0); add("clip7", 560.0, 40.0, 7); add("clip6", 600.0, 40.0, 6)
+    # two features with one descriptor in neighbouring grid columns (x = 503 files into column 50, x = 507 into column 51): the one in the
+    # earlier column is visited first and has the HIGHER index
+    twin = rng.integers(0, 256, 32, dtype=np.uint8)
+    add("twin_col51", 507.0, 120.0, 1, twin); add("twin_col50", 503.0, 120.0, 1, twin)
+    for name, x, y in (("edge_left", 1.0, 200.0), ("edge_right", 634.0, 200.0), ("edge_top", 450.0, 1.0), ("edge_bottom", 450.0, 474.0), ("corner", 634.0, 474.0)):
+        add(name, x, y, 1)
+    add("on_min_x", 0.0, 300.0, 1); add("on_min_y", 450.0, 0.0, 1)
+    crowd_desc = rng.integers(0, 256, (70, 32), dtype=np.uint8)
+    for j in range(70):                                                # 70 features in the one cell (column 56, row 30)
+        add("crowd%d" % j, 556.0 + 0.1 * (j % 8), 296.0 + 0.1 * (j // 8), 1, crowd_desc[j])
+    n = 200 + len(xs)
+    k = np.zeros(n, capi.KP_DTYPE); k[:200] = k0
+    k["x"][200:], k["y"][200:], k["octave"][200:] = xs, ys, octs
+    k["size"][200:], k["class_id"][200:] = 31, -1
+    d = np.concatenate([d0, np.array(descs, np.uint8)])
+    off, feat = ol.frame_grid(b, k)
+    col = lambda i: int(np.searchsorted(off, np.nonzero(feat == i)[0][0], side="right") - 1) // capi.GRID_ROWS
+    assert col(named["twin_col50"]) == 50 and col(named["twin_col51"]) == 51 and named["twin_col50"] > named["twin_col51"]
+    c = int(np.searchsorted(off, np.nonzero(feat == named["crowd0"])[0][0], side="right") - 1)
+    assert off[c + 1] - off[c] >= 64
+    return (k, d, off, feat), named
+
+
+@pytest.mark.parametrize("th", [2.5, 4.0])
+def test_planted_entries(th):
+    rng = np.random.default_rng(7)
+    b = fs.bounds()
+    factors = fr.scale_factors(8)
+    frame, named = planted_keyframe(rng, b)
+    k, d = frame[0], frame[1]
+    V = exact_view(b, th)
+    rows = []                                                          # (name, X, Y, Z, level or None, normal or None, dmin, dmax, desc, expected status)
+
+    def aim(name, X, Y, level, desc, status, Z=2.0, normal=None, dmin=None, dmax=None):
+        rows.append(dict(name=name, P=np.array([X, Y, Z], F32), level=level, normal=normal, dmin=dmin, dmax=dmax, desc=desc, status=status))
+
+    rnd = lambda: rng.integers(0, 256, 32, dtype=np.uint8)
+    at = lambda name: (float(k["x"][named[name]]), float(k["y"][named[name]]))
+    aim("u_on_min_x", 0.0, 300.0, 1, d[named["on_min_x"]], fz.FUSED)            # u == min_x: inside
+    aim("u_on_max_x", 640.0, 300.0, 1, rnd(), fz.IMAGE)                         # u == max_x: outside
+    aim("v_on_min_y", 450.0, 0.0, 1, d[named["on_min_y"]], fz.FUSED)
+    aim("v_on_max_y", 450.0, 480.0, 1, rnd(), fz.IMAGE)
+    aim("z_plus_zero", 100.0, 100.0, 1, rnd(), fz.IMAGE, Z=0.0)                 # PcZ = +0: not behind the camera, u = v = +inf
+    aim("z_minus_zero", 100.0, 100.0, 1, rnd(), fz.IMAGE, Z=-0.0)               # the sum starts from +0.0f: PcZ is +0 again
+    aim("z_minus_zero_negx", -100.0, 100.0, 1, rnd(), fz.IMAGE, Z=-0.0)
+    aim("z_zero_on_axis", 0.0, 0.0, 1, rnd(), fz.IMAGE, Z=0.0)                  # 0 * inf: NaN fails IsInImage in the reference too
+    aim("z_negative", 100.0, 100.0, 1, rnd(), fz.DEPTH, Z=-2.0)
+    aim("z_tiny_negative", 100.0, 100.0, 1, rnd(), fz.DEPTH, Z=-1e-30)
+    aim("dist_eq_min_and_max", *at("level0"), 0, d[named["level0"]], fz.FUSED, dmin="dist", dmax="dist")
+    aim("dist_below_min", *at("level0"), 0, rnd(), fz.DISTANCE, dmin="above")
+    aim("dist_above_max", *at("level0"), 0, rnd(), fz.DISTANCE, dmax="below")
+    aim("level0", *at("level0"), 0, flip(rng, d[named["level0"]], 3), fz.FUSED)          # levels [-1, 0]
+    aim("level0_misses_octave1", *at("d50"), 0, d[named["d50"]], fz.EMPTY)
+    aim("clip_to_7", *at("clip7"), 7, d[named["clip7"]], fz.FUSED, dmin="far")          # lower_bound = 8, clipped to 7
+    aim("clip_to_7_takes_6", *at("clip6"), 7, d[named["clip6"]], fz.FUSED, dmin="far")
+    aim("dist50", *at("d50"), 1, flip(rng, d[named["d50"]], 50), fz.FUSED)
+    aim("dist51", *at("d51"), 1, flip(rng, d[named["d51"]], 51), fz.FAR)
+    aim("twins", 505.0, 120.0, 1, d[named["twin_col50"]], fz.FUSED)
+    for name in ("edge_left", "edge_right", "edge_top", "edge_bottom", "corner"):
+        aim(name, *at(name), 1, flip(rng, d[named[name]], 5), fz.FUSED)
+    aim("empty_window", 420.0, 400.0, 1, rnd(), fz.EMPTY)
+    aim("crowded_cell", 556.3, 296.4, 1, flip(rng, d[named["crowd37"]], 2), fz.FUSED)
+    # dot == 0.5 * dist exactly: P on the optical axis at depth 4, the normal's third component 0.5 (and the float below it: rejected)
+    aim("dot_eq_half_dist", 0.0, 0.0, 1, rnd(), fz.EMPTY, Z=4.0, normal=np.array([0.5, 0.25, 0.5], F32))
+    aim("dot_below_half_dist", 0.0, 0.0, 1, rnd(), fz.ANGLE, Z=4.0, normal=np.array([0.5, 0.25, np.nextafter(F32(0.5), F32(0))], F32))
+
+    n = len(rows)
+    pos = np.stack([r["P"] for r in rows])
+    _, dist = fz.centre_distance(V, pos)
+    nrm = np.zeros((n, 3), F32); dmin = np.zeros(n, F32); dmax = np.zeros(n, F32)
+    for i, r in enumerate(rows):
+        with np.errstate(all="ignore"):
+            nrm[i] = r["normal"] if r["normal"] is not None else (pos[i].astype(np.float64) / max(float(dist[i]), 1e-30)).astype(F32)
+        dmin[i] = {None: fs.min_distance_for(dist[i], r["level"], factors), "dist": dist[i], "above": np.nextafter(dist[i], F32(np.inf)),
+                   "far": F32(dist[i] / F32(100))}[r["dmin"]]
+        dmax[i] = {None: F32(dist[i] * F32(2)), "dist": dist[i], "below": np.nextafter(dist[i], F32(0))}[r["dmax"]]
+    desc = np.stack([r["desc"] for r in rows])
+    table = dict(pos=pos, normal=nrm, dmin=dmin, dmax=dmax, desc=desc)
+    live = np.ones(n + 4, np.uint8)
+    live[n:] = 0                                                       # free slots behind the planted points
+    tab = capi.MapPointTable(n + 4)
+    try:
+        s = np.arange(n, dtype=np.int32)
+        tab.put(s, pos, nrm, dmin, dmax, desc)
+        extra = [n, -1, n + 4, 0]                                      # a free slot, slot -1, slot == capacity, and point 0 once more under a skip flag
+        lists = np.zeros((1, 64), np.int32)
+        lists[0, :n] = s; lists[0, n:n + 4] = extra
+        nlist = np.array([n + 4], np.int32)
+        skip = np.zeros((1, 64), np.uint8); skip[0, n + 3] = 1
+        padded = {key: np.concatenate([v, np.zeros((4,) + v.shape[1:], v.dtype)]) for key, v in table.items()}
+        want = expect([V], factors, b, 50, padded, live, lists, nlist, skip, [frame], None)
+        st = want[2]["status"][0]
+        for i, r in enumerate(rows):
+            assert st[i] == r["status"], (r["name"], fz.STATUS[st[i]], fz.STATUS[r["status"]])
+        assert (st[n:n + 4] == fz.SKIPPED).all()
+        by = {r["name"]: i for i, r in enumerate(rows)}
+        wi, wd, wr = want
+        assert wr["u"][0, by["u_on_min_x"]] == F32(b.min_x) and wr["u"][0, by["u_on_max_x"]] == F32(b.max_x)
+        assert wr["v"][0, by["v_on_min_y"]] == F32(b.min_y) and wr["v"][0, by["v_on_max_y"]] == F32(b.max_y)
+        assert np.isposinf(wr["u"][0, by["z_minus_zero"]]) and np.isneginf(wr["u"][0, by["z_minus_zero_negx"]]) and np.isnan(wr["u"][0, by["z_zero_on_axis"]])
+        assert wd[0, by["dist50"]] == 50 and wi[0, by["dist50"]] == named["d50"] and wd[0, by["dist51"]] == 51 and wi[0, by["dist51"]] == -1
+        assert wi[0, by["twins"]] == named["twin_col50"] and wd[0, by["twins"]] == 0        # the first in traversal, not the lowest index
+        assert wi[0, by["crowded_cell"]] == named["crowd37"] and wi[0, by["clip_to_7_takes_6"]] == named["clip6"]
+        assert wr["level"][0, by["level0"]] == 0 and wr["level"][0, by["clip_to_7"]] == 7
+        layout = batch_layout([frame], b)
+        run_forms(tab, fz.view_record(V), factors, b, 50, lists, nlist, skip, layout, None, want)
+        # orb_dist moves the line between FUSED and FAR and nothing else
+        want49 = expect([V], factors, b, 49, padded, live, lists, nlist, skip, [frame], None)
+        assert want49[2]["status"][0, by["dist50"]] == fz.FAR
+        run_forms(tab, fz.view_record(V), factors, b, 49, lists, nlist, skip, layout, None, want49, forms=("device",))
+    finally:
+        tab.close()
+
+
+def flip(rng, d, k):
+    return fs.flip_bits(rng, d, k)
+
+
+def test_views_that_cannot_be_searched(world):
+    """a view of another mode and a key frame out of range: the device form marks their entries, the host form refuses the call; the
+    existing entry points do not know the mode"""
+    rng = np.random.default_rng(3)
+    lists, nlist, skip = lists_for(rng, [0, 0, 0, 0], (300, 300, 300, 300))
+    factors = fr.scale_factors(8)
+    views = [world["poses"][0]] * 4
+    vrec = np.concatenate([fz.view_record(v) for v in views])
+    vrec["mode"][1] = capi.MODE_FRAME
+    frame = np.array([0, 0, 4, -1], np.int32)
+    want = expect(views, factors, world["b"], 50, world["table"], world["live"], lists, nlist, skip, world["frames"], np.array([0, 0, 0, 0], np.int32))
+    for p in (1, 2, 3):
+        want[0][p, :300] = -1; want[1][p, :300] = INT_MAX
+        want[2][p, :300] = np.zeros(1, capi.FUSED_DTYPE)
+        want[2]["status"][p, :300] = fz.SKIPPED
+    assert (want[2]["status"][0, :300] == fz.FUSED).sum() > 30
+    run_forms(world["tab"], vrec, factors, world["b"], 50, lists, nlist, skip, world["layout"], frame, want, forms=("device",))
+    tab = world["tab"]
+    for bad_views, bad_frame in ((vrec, np.zeros(4, np.int32)), (np.concatenate([fz.view_record(v) for v in views]), frame)):
+        with pytest.raises(capi.OrbxError) as e:
+            tab.fuse(bad_views, factors, lists, nlist, world["b"], 50, *world["layout"], frame=bad_frame)
+        assert e.value.code == capi.ORBX_ERR_ARG
+    with pytest.raises(capi.OrbxError) as e:                               # nviews > nframes without a frame table
+        tab.fuse(np.concatenate([fz.view_record(v) for v in views] * 2), factors, np.zeros((8, 4), np.int32), np.zeros(8, np.int32), world["b"], 50, *world["layout"])
+    assert e.value.code == capi.ORBX_ERR_ARG
+    # ORBP_MODE_FUSE in orbp_project_batch_device: an unknown mode, as before
+    one = fz.view_record(world["poses"][0])
+    qcap = 64
+    d_v, d_l, d_n = dev(one), dev(lists[:1]), dev(nlist[:1])
+    outs = [torch.zeros(qcap * 3, dtype=torch.float32, device="cuda"), torch.zeros(qcap * 2, dtype=torch.int32, device="cuda"),
+            torch.zeros(qcap * 32, dtype=torch.uint8, device="cuda"), torch.zeros(qcap, dtype=torch.int32, device="cuda"),
+            torch.full((1,), 9, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")]
+    tab.project_batch_device(d_v.data_ptr(), 1, factors, d_l.data_ptr(), d_n.data_ptr(), LCAP, 0, 0, *[t.data_ptr() for t in outs], qcap)
+    torch.cuda.synchronize()
+    assert int(outs[4][0]) == 0 and int(outs[5][0]) == capi.ORBX_ERR_ARG
+
+
+def test_argument_checks(world):
+    """the checks on the host, before anything touches the GPU (tests/test_fuse_host.py walks them all without one)"""
+    tab, b = world["tab"], world["b"]
+    factors = fr.scale_factors(8)
+    vrec = fz.view_record(world["poses"][0])
+    lists, nlist = np.zeros((1, 4), np.int32), np.array([4], np.int32)
+    ok = lambda **kw: tab.fuse(vrec, kw.get("factors", factors), lists, nlist, b, kw.get("orb_dist", 50), *world["layout"])
+    ok()
+    for kw in (dict(orb_dist=-1), dict(orb_dist=257), dict(factors=np.ones(17, F32)), dict(factors=np.zeros(0, F32))):
+        with pytest.raises(capi.OrbxError) as e:
+            ok(**kw)
+        assert e.value.code == capi.ORBX_ERR_ARG
+    d_desc = dev(world["layout"][1])
+    with pytest.raises(capi.OrbxError) as e:                               # resident descriptors off a 16-byte boundary
+        tab.fuse(vrec, factors, lists, nlist, b, 50, dev(world["layout"][0]).data_ptr(), d_desc.data_ptr() + 4, 8, 8, world["layout"][4], nframes=4, cap=CAP)
+    assert e.value.code == capi.ORBX_ERR_ARG
+    assert tab.fuse(np.zeros(0, capi.VIEW_DTYPE), factors, np.zeros((0, 4), np.int32), np.zeros(0, np.int32), b, 50, *world["layout"])[0].shape == (0, 4)
