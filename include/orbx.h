@@ -340,6 +340,9 @@ int orbx_debug_geometry(const orbx_params* p, int w, int hgt, int32_t* out, int 
  * out_perm[i] = original index of the element that ends up at position i (n <= 13000) */
 int orbx_debug_nth_element(const float* resp, int n, int nth, int32_t* out_perm, int device);
 int orbx_debug_eval_math(int kind, const float* in0, const float* in1, float* out0, float* out1, int n, int device);
+/* evaluate the device's FAST compass pre-test (k_fast_cells phase A1) on n dword quintuples at threshold t: c = four centre pixels,
+ * e / w = the pixels 3 to their right / left, nn / ss = 3 rows above / below; out: the flag of pixel j in bit 8 j + 7 */
+int orbx_debug_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t, int device);
 
 #ifdef __cplusplus
 }

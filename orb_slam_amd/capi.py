@@ -31,7 +31,7 @@ EXPORTS = [
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_download",
     "orbx_stream_create", "orbx_stream_create_priority", "orbx_stream_destroy", "orbx_stream_synchronize", "orbx_event_create", "orbx_event_destroy", "orbx_event_record",
     "orbx_stream_wait_event", "orbx_device_copy_async", "orbx_host_alloc", "orbx_host_free", "orbx_device_upload_async", "orbx_device_download_async", "orbx_debug_set_stop_after", "orbx_debug_set_blur_on_demand", "orbx_debug_level_size", "orbx_debug_fetch",
-    "orbx_debug_eval_math", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
+    "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
     "orbm_debug_set_match_path",
     "orbm_debug_get_match_path",
 ]
@@ -230,6 +230,7 @@ def lib():
         L.orbx_debug_fetch.argtypes = [vp, ci, ci, ci, vp, cl]
         L.orbx_debug_fetch.restype = cl
         L.orbx_debug_eval_math.argtypes = [ci, vp, vp, vp, vp, ci, ci]
+        L.orbx_debug_eval_compass.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci]
         L.orbx_debug_nth_element.argtypes = [vp, ci, ci, vp, ci]
         L.orbx_debug_geometry.argtypes = [ctypes.POINTER(Params), ci, ci, vp, ci]
         L.orbx_debug_stage_timing.argtypes = [vp, ci]
@@ -734,6 +735,17 @@ def eval_math(kind, in0, in1=None, device=0):
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbx_debug_eval_math")
     return out0, out1
+
+
+def eval_compass(c, e, w, n, s, t, device=0):
+    """the device's FAST compass pre-test (k_fast_cells phase A1) on dword quintuples at threshold t: the flag of pixel j is bit 8 j + 7"""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (c, e, w, n, s)]
+    assert all(a.shape == arrs[0].shape for a in arrs)
+    out = np.empty_like(arrs[0])
+    rc = lib().orbx_debug_eval_compass(*[a.ctypes.data for a in arrs], out.ctypes.data, arrs[0].size, int(t), device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_debug_eval_compass")
+    return out
 
 
 class ORBVocabulary:

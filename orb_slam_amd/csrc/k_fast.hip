@@ -55,12 +55,13 @@ __device__ __forceinline__ int fast_score_raw(const uint8_t* c, int S, int v, in
 // index per lane, block-wide queues with a barrier per phase — took 1.51 ms per 1024 VGA frames, this one 1.11.)
 //   * everything is addressed by the pixel's BYTE OFFSET q inside the staged LDS image (pitch S): the score plane has the
 //     image's layout, so ring / neighbour addresses are q +- dy*S + dx with no division anywhere in the dense or sparse phases;
-//   * A1 is SWAR: a lane tests 4 horizontally adjacent pixels (one aligned dword) per step.  Bytes are unpacked to two
-//     16-bit-field dwords (even / odd pixels); with the bias K = 0x8000 - t - 1 per field, "x < v - t" is bit 15 of (v + K) - x
-//     and "x > v + t" is bit 15 of x + (K - v) — plain v_add / v_sub / v_and / v_or / v_bitop3, which issue at twice the rate of
-//     v_min / v_max / v_cmp on gfx950 (profiles/r01_valu_issue_rates.txt, r02_valu_issue_rates2.txt).  Rule: a 9-arc of the
-//     16-ring contains ring 0 or 8 AND ring 4 or 12, so a corner needs (N | S) & (E | W) beyond the threshold with one polarity —
-//     an exact necessary condition.  (gfx950 serves unaligned ds_read_b32, but slowly: reading the E / W dwords that way instead
+//   * A1 is SWAR: a lane tests 4 horizontally adjacent pixels (one aligned dword) per step, on the bytes as they lie, with
+//     v_lerp_u8 (four byte averages (a + b + (c & 1)) >> 1 per instruction, nothing carries between bytes): h = avg(x, ~v, t & 1)
+//     is (255 + x - v + (t & 1)) >> 1, and bit 7 of avg(h, K) against two constants of the threshold says "x > v + t" and
+//     "x <= v - t" (compass4_dev below; rounds 2-6 unpacked the bytes into 16-bit fields and compared by biased adds: 47
+//     instructions per step against 18).  Rule: a 9-arc of the 16-ring contains ring 0 or 8 AND ring 4 or 12, so a corner needs
+//     (N | S) & (E | W) beyond the threshold with one polarity — a necessary condition, and the filter is a superset of it by the
+//     one difference v - x == t.  (gfx950 serves unaligned ds_read_b32, but slowly: reading the E / W dwords that way instead
 //     of two v_alignbyte cost +44 % on the kernel);
 //   * flagged dwords are queued per WAVE (ballot + mbcnt, no atomics), expanded to pixels, pair-tested and scored by the same
 //     wave in full-wave slices: no workgroup barrier between staging and the NMS;
@@ -79,6 +80,40 @@ static_assert(sizeof(FastHdr) == 64, "LDS carve");
 __device__ __forceinline__ int lane_rank(unsigned long long m) {   // number of set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
+// A1's arithmetic: the compass test of four packed pixels by byte averages (orb_math.h: avg_u8, compass_kb / compass_kd; one v_lerp_u8
+// per avg4_u8 of the host form compass4_flags, which tests/test_gpu_fast_compass.py holds this against): 1 v_not + 12 v_lerp_u8 + 5
+// logic ops per dword-step where the 16-bit SWAR form of rounds 2-6 took 47.  The dark side passes the one extra difference
+// v - x == t (orb_math.h says why).  The exact form (four more first-level averages with the other rounding bit, 16 v_lerp_u8) was
+// measured beside this one and lost on the headline and every stream but S-lowtex (NOTES.md 8.2d): the extra flags cost less than
+// the four instructions.
+struct CompassK { uint32_t R, KB, KD; };      // r, kb, kd in every byte (wave-uniform)
+__device__ __forceinline__ CompassK compass_consts(int t) {      // (t > 254: the filter of 254, see orb_math.h; the exact score rejects what it passes)
+    CompassK k;
+    k.R = (uint32_t)compass_r(t) * 0x01010101u;
+    k.KB = (uint32_t)compass_kb(t) * 0x01010101u;
+    k.KD = (uint32_t)compass_kd(t) * 0x01010101u;
+    return k;
+}
+__device__ __forceinline__ uint32_t compass4_dev(uint32_t C, uint32_t E, uint32_t W, uint32_t Nn, uint32_t Ss, const CompassK& k) {
+    const uint32_t nc = ~C;
+    const uint32_t hN = __builtin_amdgcn_lerp(Nn, nc, k.R), hS = __builtin_amdgcn_lerp(Ss, nc, k.R);
+    const uint32_t hE = __builtin_amdgcn_lerp(E, nc, k.R), hW = __builtin_amdgcn_lerp(W, nc, k.R);
+    const uint32_t br = (__builtin_amdgcn_lerp(hN, k.KB, 0u) | __builtin_amdgcn_lerp(hS, k.KB, 0u)) &
+                        (__builtin_amdgcn_lerp(hE, k.KB, 0u) | __builtin_amdgcn_lerp(hW, k.KB, 0u));
+    const uint32_t dN = __builtin_amdgcn_lerp(hN, k.KD, 0u), dS = __builtin_amdgcn_lerp(hS, k.KD, 0u);
+    const uint32_t dE = __builtin_amdgcn_lerp(hE, k.KD, 0u), dW = __builtin_amdgcn_lerp(hW, k.KD, 0u);
+    return (br | ~((dN & dS) | (dE & dW))) & 0x80808080u;
+}
+// (diagnostics, beside k_eval_math: the device compass test on caller-supplied dwords)
+__global__ void k_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = compass4_dev(c[i], e[i], w[i], nn[i], ss[i], compass_consts(t));
+}
+int launch_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t) {
+    hipLaunchKernelGGL(k_eval_compass, dim3((n + 255) / 256), dim3(256), 0, 0, c, e, w, nn, ss, out, n, t);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
 template <bool ALIGNED, int NT, int PPT, bool GATHER = false>
 __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int item, uint8_t* smem) {
     constexpr int NW = NT / 64;
@@ -234,13 +269,13 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
     auto expand_step = [&](const uint32_t* q, int m) {
         uint32_t e = 0;
         if (lane < m) e = q[lane];
-        const int idx = (int)(e & 0x3FFFu);
+        const int idx = (int)((e & 0x7Fu) | ((e >> 1) & 0x3F80u));          // the 14-bit dword index lies around flag bit 7 (see the push in `round`)
         int r, d;
         split_px(idx, nd, inv_nd, r, d);
         const int col0 = 4 * d - x_first;                                   // band column of the dword's first pixel
-        // flag bits: pixel 0 -> bit 15, 1 -> bit 14, 2 -> bit 31, 3 -> bit 30
-        const int f[4] = {(int)((e >> 15) & 1u) & (int)((unsigned)col0 < (unsigned)cw), (int)((e >> 14) & 1u) & (int)((unsigned)(col0 + 1) < (unsigned)cw),
-                          (int)((e >> 31) & 1u) & (int)((unsigned)(col0 + 2) < (unsigned)cw), (int)((e >> 30) & 1u) & (int)((unsigned)(col0 + 3) < (unsigned)cw)};
+        // flag bits: pixel j -> bit 8 j + 7
+        const int f[4] = {(int)((e >> 7) & 1u) & (int)((unsigned)col0 < (unsigned)cw), (int)((e >> 15) & 1u) & (int)((unsigned)(col0 + 1) < (unsigned)cw),
+                          (int)((e >> 23) & 1u) & (int)((unsigned)(col0 + 2) < (unsigned)cw), (int)((e >> 31) & 1u) & (int)((unsigned)(col0 + 3) < (unsigned)cw)};
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const unsigned long long mk = __ballot(f[j]);
@@ -252,22 +287,9 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
         }
     };
 
-    // A1: SWAR compass test, 4 pixels per lane and step (see the header of this section)
-    const uint32_t M8 = 0x00FF00FFu, HH = 0x80008000u;
-    uint32_t KD = (uint32_t)(0x8000 - tmin - 1) * 0x00010001u;
-    auto compass4 = [&](uint32_t C, uint32_t E, uint32_t W, uint32_t Nn, uint32_t Ss) -> uint32_t {
-        uint32_t P[2];
-#pragma unroll
-        for (int hlf = 0; hlf < 2; hlf++) {
-            const uint32_t c = hlf ? (C >> 8) & M8 : C & M8, n = hlf ? (Nn >> 8) & M8 : Nn & M8, s = hlf ? (Ss >> 8) & M8 : Ss & M8,
-                           e = hlf ? (E >> 8) & M8 : E & M8, w = hlf ? (W >> 8) & M8 : W & M8;
-            const uint32_t vd = c + KD, vb = KD - c;
-            const uint32_t dk = ((vd - n) | (vd - s)) & ((vd - e) | (vd - w));
-            const uint32_t br = ((n + vb) | (s + vb)) & ((e + vb) | (w + vb));
-            P[hlf] = dk | br;
-        }
-        return (P[0] & HH) | ((P[1] & HH) >> 1);
-    };
+    // A1: compass test by byte averages, 4 pixels per lane and step (see the header of this section; constants: orb_math.h)
+    CompassK K = compass_consts(tmin);
+    auto compass4 = [&](uint32_t C, uint32_t E, uint32_t W, uint32_t Nn, uint32_t Ss) -> uint32_t { return compass4_dev(C, E, W, Nn, Ss, K); };
     const int i_begin = 3 * nd, i_end = (ch + 3) * nd;          // dwords of the scored rows (all columns of the staged image)
     constexpr int RG = NW * 64 * PPT;                            // dwords per round of the workgroup
     auto round = [&](auto full_c, int base) {
@@ -291,7 +313,7 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
             if (!FULL && i >= i_end) Q = 0;
             const unsigned long long mk = __ballot(Q != 0);
             if (mk) {
-                if (Q) q0[n0 + lane_rank(mk)] = Q | (uint32_t)i;
+                if (Q) q0[n0 + lane_rank(mk)] = Q | (uint32_t)(i + (i & ~0x7F));      // flags at bits 7 / 15 / 23 / 31, the index (< 2^14) in bits 0-6 and 8-14
                 n0 += __popcll(mk);
                 if (n0 >= 64) { n0 -= 64; expand_step(q0 + n0, 64); }          // q0 never holds more than 63 + 64
             }
@@ -367,7 +389,7 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
     __syncthreads();                                 // every wave has read n_hi
     clear_lds();
     tmin = 7;
-    KD = (uint32_t)(0x8000 - 7 - 1) * 0x00010001u;
+    K = compass_consts(7);
     n0 = n1 = n2 = n3 = 0;
     __syncthreads();
     }

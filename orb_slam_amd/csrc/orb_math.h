@@ -138,6 +138,38 @@ ORBX_HD int fast9_score(const int d[16], int tmin) {
     return s >= tmin ? s : 0;
 }
 
+// ---- FAST compass pre-test by byte averages (k_fast.hip phase A1) ------------------------------
+// avg_u8 is one byte of v_lerp_u8: (a + b + (c & 1)) >> 1, the sum nine bits wide.  With x a ring pixel, v the centre, d = x - v,
+// t the threshold and r = t & 1 (so that t + r is even):
+//   h = avg_u8(x, 255 - v, r) = (255 + d + r) >> 1              in 0..255, monotone in d
+//   bright:  bit 7 of avg_u8(h, compass_kb(t), 0)  is SET   <=>  h >= 128 + (t + r) / 2      <=>  d >  t      (exact)
+//   dark:    bit 7 of avg_u8(h, compass_kd(t), 0)  is CLEAR <=>  h <= (254 + r - t) / 2      <=>  d <= -t     (d < -t, and d == -t)
+// The dark side admits the one extra difference d == -t (253 + r - t is always odd, so no constant cuts h between -t and -t - 1: h
+// was rounded with the bright side's r).  The test is a filter in front of the exact score, so a superset changes no result.
+// Valid for 0 <= t <= 254; a larger t is clamped to 254: the filter then passes d = 255 and d <= -254 although nothing is a corner
+// at such a threshold, and the exact score (fast_score_raw: s >= tmin) rejects those pixels as it rejects every other false flag.
+// tests/test_fast_compass_host.py runs every (x, v, t).
+ORBX_HD int avg_u8(int a, int b, int c) { return (a + b + (c & 1)) >> 1; }
+ORBX_HD int compass_t(int t) { return t < 0 ? 0 : t > 254 ? 254 : t; }
+ORBX_HD int compass_r(int t) { return compass_t(t) & 1; }
+ORBX_HD int compass_kb(int t) { return 128 - (compass_t(t) + compass_r(t)) / 2; }
+ORBX_HD int compass_kd(int t) { return 255 - (254 + compass_r(t) - compass_t(t)) / 2; }
+// the same on four packed pixels (host form of the kernel's compass4; on the device each avg4_u8 is one v_lerp_u8): the flag of pixel j
+// is bit 8 j + 7.  C: centres, E / W: pixels x + 3 / x - 3, N / S: rows y - 3 / y + 3; R, KB, KD: r, kb, kd in every byte.
+ORBX_HD uint32_t avg4_u8(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t o = 0;
+    for (int j = 0; j < 4; j++) o |= (uint32_t)avg_u8((int)((a >> (8 * j)) & 255u), (int)((b >> (8 * j)) & 255u), (int)((c >> (8 * j)) & 1u)) << (8 * j);
+    return o;
+}
+ORBX_HD uint32_t compass4_flags(uint32_t C, uint32_t E, uint32_t W, uint32_t N, uint32_t S, int t) {
+    const uint32_t R = (uint32_t)compass_r(t) * 0x01010101u, KB = (uint32_t)compass_kb(t) * 0x01010101u, KD = (uint32_t)compass_kd(t) * 0x01010101u;
+    const uint32_t nc = ~C;
+    const uint32_t hN = avg4_u8(N, nc, R), hS = avg4_u8(S, nc, R), hE = avg4_u8(E, nc, R), hW = avg4_u8(W, nc, R);
+    const uint32_t br = (avg4_u8(hN, KB, 0) | avg4_u8(hS, KB, 0)) & (avg4_u8(hE, KB, 0) | avg4_u8(hW, KB, 0));
+    const uint32_t dk = (avg4_u8(hN, KD, 0) & avg4_u8(hS, KD, 0)) | (avg4_u8(hE, KD, 0) & avg4_u8(hW, KD, 0));
+    return (br | ~dk) & 0x80808080u;
+}
+
 // ---- cv::resize INTER_LINEAR 8U, one output pixel ----------------------------------------------
 // s00,s01: source row sy0 at sx, sx+1; s10,s11: row sy1.  a0,a1 / b0,b1: 11-bit fixed-point weights.
 ORBX_HD int resize_px(int s00, int s01, int s10, int s11, int a0, int a1, int b0, int b1) {

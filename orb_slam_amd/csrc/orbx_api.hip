@@ -9,6 +9,7 @@
 
 namespace orbx {
 int launch_eval_math(int kind, const float* in0, const float* in1, float* out0, float* out1, int n);
+int launch_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t);
 void stage_timer_collect(StageTimer& t);
 int launch_debug_nth(const float* d_resp, int n, int nth, int* d_out);
 int launch_ingest(uint8_t* d_dst, const uint8_t* mapped_src, size_t bytes, hipStream_t stream);
@@ -845,6 +846,20 @@ int orbx_debug_eval_math(int kind, const float* in0, const float* in1, float* ou
     if (rc != ORBX_OK) return rc;
     HIPTRY(s.get(out0, o0, n));
     if (out1) HIPTRY(s.get(out1, o1, n));
+    return ORBX_OK;
+}
+
+int orbx_debug_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t, int device) {
+    if (n <= 0) return ORBX_OK;
+    if (!c || !e || !w || !nn || !ss || !out || t < 0) return ORBX_ERR_ARG;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto ic = s.in(c, n), ie = s.in(e, n), iw = s.in(w, n), in_ = s.in(nn, n), is = s.in(ss, n);
+    const auto o = s.out<uint32_t>(n);
+    HIPTRY(s.alloc());
+    const int rc = launch_eval_compass(s[ic], s[ie], s[iw], s[in_], s[is], s[o], n, t);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(out, o, n));
     return ORBX_OK;
 }
 
