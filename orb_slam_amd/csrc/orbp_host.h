@@ -1,6 +1,7 @@
-// The argument groups of the map-point walk (orbp_project.hip) and the layouts of the blocks an orbp_map keeps for them.  Host C++
-// only: tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp and tests/_probe/fuse_host.cpp hold the layouts against their sizes
-// without a GPU.
+// The argument groups of the map-point walk (orbp_project.hip) and the layouts its synchronous host forms give the one block an orbp_map
+// keeps (orbx::Staged).  Each layout's stage() goes through Layout::put: a host array is copied into its slot and named on the device, an
+// absent one is passed through.  Host C++ only: tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp and
+// tests/_probe/fuse_host.cpp hold the layouts against their sizes without a GPU.
 #pragma once
 #include <cstring>
 
@@ -50,13 +51,8 @@ struct FrameSlots {
     // the caller's frame `f` of nt features as the kernels read it: copied into the pinned block h and named inside the device block d,
     // or passed through
     Frame stage(uint8_t* h, uint8_t* d, const Frame& f, int nt, const int32_t* d_nt) const {
-        if (!kps.present) return {f.kps_un, f.desc, f.cell_off, f.cell_feat, d_nt, f.cap, f.claimed};
-        std::memcpy(Layout::at(h, kps), f.kps_un, (size_t)nt * sizeof(orbx_keypoint));
-        std::memcpy(Layout::at(h, desc), f.desc, (size_t)nt * 32);
-        std::memcpy(Layout::at(h, cell_off), f.cell_off, (size_t)(ORBF_GRID_CELLS + 1) * 4);
-        std::memcpy(Layout::at(h, cell_feat), f.cell_feat, (size_t)nt * 4);
-        if (claimed.present) std::memcpy(Layout::at(h, claimed), f.claimed, (size_t)nt);
-        return {Layout::at(d, kps), Layout::at(d, desc), Layout::at(d, cell_off), Layout::at(d, cell_feat), d_nt, f.cap, Layout::at(d, claimed)};
+        return {Layout::put(h, d, kps, f.kps_un, nt), Layout::put(h, d, desc, f.desc, (size_t)nt * 32), Layout::put(h, d, cell_off, f.cell_off, ORBF_GRID_CELLS + 1),
+                Layout::put(h, d, cell_feat, f.cell_feat, nt), d_nt, f.cap, Layout::put(h, d, claimed, f.claimed, nt)};
     }
 };
 
@@ -154,17 +150,10 @@ struct RefreshBlock {
     // copies the caller's host arrays into the pinned block h and names them inside the device block d; the key frames' features are
     // passed through when they are not part of the block
     void stage(uint8_t* h, uint8_t* d, const RefreshLists& l, const KeyFrames& k, RefreshLists& dl, KeyFrames& dk) const {
-        if (pos.present) std::memcpy(Layout::at(h, pos), l.pos, (size_t)n * 12);
-        std::memcpy(Layout::at(h, obs_off), l.obs_off, ((size_t)n + 1) * 4);
-        if (nobs > 0) std::memcpy(Layout::at(h, obs), l.obs, (size_t)nobs * 8);
-        if (ref.present) std::memcpy(Layout::at(h, ref), l.ref, (size_t)n * 4);
-        if (skip.present) std::memcpy(Layout::at(h, skip), l.skip, (size_t)n);
-        if (kf_ow.present) std::memcpy(Layout::at(h, kf_ow), k.ow, (size_t)nkf * 12);
-        if (kf_bad.present) std::memcpy(Layout::at(h, kf_bad), k.bad, (size_t)nkf);
-        if (kf_kps.present) std::memcpy(Layout::at(h, kf_kps), k.kps, nfeat * sizeof(orbx_keypoint));
-        if (kf_desc.present) std::memcpy(Layout::at(h, kf_desc), k.desc, nfeat * 32);
-        dl = {Layout::at(d, pos), Layout::at(d, obs_off), Layout::at(d, obs), Layout::at(d, ref), Layout::at(d, skip)};
-        dk = {Layout::at(d, kf_ow), Layout::at(d, kf_bad), kf_kps.present ? Layout::at(d, kf_kps) : k.kps, kf_desc.present ? Layout::at(d, kf_desc) : k.desc, k.nkf, k.cap};
+        dl = {Layout::put(h, d, pos, l.pos, (size_t)n * 3), Layout::put(h, d, obs_off, l.obs_off, (size_t)n + 1), Layout::put(h, d, obs, l.obs, (size_t)nobs * 2),
+              Layout::put(h, d, ref, l.ref, n), Layout::put(h, d, skip, l.skip, n)};
+        dk = {Layout::put(h, d, kf_ow, k.ow, (size_t)nkf * 3), Layout::put(h, d, kf_bad, k.bad, nkf), Layout::put(h, d, kf_kps, k.kps, nfeat),
+              Layout::put(h, d, kf_desc, k.desc, nfeat * 32), k.nkf, k.cap};
     }
 };
 
@@ -240,22 +229,11 @@ struct FuseBlock {
     // copies the caller's host arrays into the pinned block h and names everything inside the device block d; key frames that are not part
     // of the block are passed through
     void stage(uint8_t* h, uint8_t* d, const orbp_view* v, const Lists& l, const FuseFrames& k, const orbp_view*& dv, Lists& dl, FuseFrames& dk, FuseOut& dout) const {
-        std::memcpy(Layout::at(h, views), v, (size_t)nviews * sizeof(orbp_view));
-        std::memcpy(Layout::at(h, nlist), l.nlist, (size_t)nviews * 4);
-        if (frame.present) std::memcpy(Layout::at(h, frame), k.frame, (size_t)nviews * 4);
-        std::memcpy(Layout::at(h, nt), k.nt, (size_t)nframes * 4);
-        std::memcpy(Layout::at(h, list), l.list, nent * 4);
-        if (skip.present) std::memcpy(Layout::at(h, skip), l.skip, nent);
-        if (kps.present) {
-            std::memcpy(Layout::at(h, kps), k.kps_un, nfeat * sizeof(orbx_keypoint));
-            std::memcpy(Layout::at(h, desc), k.desc, nfeat * 32);
-            std::memcpy(Layout::at(h, cell_off), k.cell_off, (size_t)nframes * (ORBF_GRID_CELLS + 1) * 4);
-            std::memcpy(Layout::at(h, cell_feat), k.cell_feat, nfeat * 4);
-        }
-        dv = Layout::at(d, views);
-        dl = {Layout::at(d, list), Layout::at(d, nlist), l.lcap, Layout::at(d, skip)};
-        dk = {kps.present ? Layout::at(d, kps) : k.kps_un, kps.present ? Layout::at(d, desc) : k.desc, kps.present ? Layout::at(d, cell_off) : k.cell_off,
-              kps.present ? Layout::at(d, cell_feat) : k.cell_feat, Layout::at(d, nt), k.nframes, k.cap, Layout::at(d, frame)};
+        dv = Layout::put(h, d, views, v, nviews);
+        dl = {Layout::put(h, d, list, l.list, nent), Layout::put(h, d, nlist, l.nlist, nviews), l.lcap, Layout::put(h, d, skip, l.skip, nent)};
+        dk = {Layout::put(h, d, kps, k.kps_un, nfeat), Layout::put(h, d, desc, k.desc, nfeat * 32),
+              Layout::put(h, d, cell_off, k.cell_off, (size_t)nframes * (ORBF_GRID_CELLS + 1)), Layout::put(h, d, cell_feat, k.cell_feat, nfeat),
+              Layout::put(h, d, nt, k.nt, nframes), k.nframes, k.cap, Layout::put(h, d, frame, k.frame, nviews)};
         dout = {Layout::at(d, best_idx), Layout::at(d, best_dist), Layout::at(d, rec)};
     }
 };

@@ -218,7 +218,7 @@ struct orbp_map {
     uint32_t stamp_now = 0;
     orbx::DevBuf geom, desc, d_live, d_tab, scratch;
     orbx::PinnedBuf h_tab;
-    orbx::Block one, put, refresh, fuse;              // the blocks of the one-view calls, of orbp_put, of orbp_refresh and of orbp_fuse
+    orbx::Block block;                                // of the synchronous host forms (orbx::Staged), one at a time under `mu`
     orbx::Stream own;
     orbx::Chain chain;                                // device work on the map is ordered across the callers' streams
     orbx::Event tab_done;
@@ -229,7 +229,10 @@ namespace {
 
 using orbx::DeviceScope;
 using orbx::Layout;
-using Link = orbx::Chain::Link;
+using Call = orbx::Call<orbp_map>;
+using Staged = orbx::Staged<orbp_map>;
+// leaves the entry point with a status that is not ORBX_OK
+#define TRY(call) do { const int rc_ = (call); if (rc_ != ORBX_OK) return rc_; } while (0)
 
 // the slots of a put / erase: range, and for a put no slot twice
 int check_slots(orbp_map* m, const int32_t* slots, int n, bool unique, bool need_live) {
@@ -253,8 +256,7 @@ int upload_slots(orbp_map* m, const int32_t* slots, int n, hipStream_t st) {
     if (m->h_tab.size() < (size_t)n * 4) {
         HIPCHK(m, hipStreamSynchronize(st));
         HIPCHK(m, m->chain.wait());
-        size_t want = std::max<size_t>(4096, m->h_tab.size());
-        while (want < (size_t)n * 4) want *= 2;
+        const size_t want = orbx::doubled(m->h_tab.size(), (size_t)n * 4);
         HIPCHK(m, m->h_tab.ensure(want, hipHostMallocDefault));
         HIPCHK(m, m->d_tab.ensure(want));
     }
@@ -265,11 +267,10 @@ int upload_slots(orbp_map* m, const int32_t* slots, int n, hipStream_t st) {
     return ORBX_OK;
 }
 
-// inside the caller's link of the chain
+// inside the caller's call
 int put_locked(orbp_map* m, const int32_t* slots, int n, const float* d_pos, const float* d_normal, const float* d_min, const float* d_max,
                const uint8_t* d_desc, hipStream_t st) {
-    const int rc = upload_slots(m, slots, n, st);
-    if (rc != ORBX_OK) return rc;
+    TRY(upload_slots(m, slots, n, st));
     orbp::k_put<<<(n + orbp::TPB - 1) / orbp::TPB, orbp::TPB, 0, st>>>(n, m->d_tab.as<int32_t>(), d_pos, d_normal, d_min, d_max, d_desc,
                                                                        m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>());
     HIPCHK(m, hipGetLastError());
@@ -278,12 +279,11 @@ int put_locked(orbp_map* m, const int32_t* slots, int n, const float* d_pos, con
     return ORBX_OK;
 }
 
-// Inside the caller's link of the chain: the slot table goes up as for a put, one launch refreshes the slots in place.  The host's
+// Inside the caller's call: the slot table goes up as for a put, one launch refreshes the slots in place.  The host's
 // live flags are the caller's business: orbp_refresh knows the statuses, orbp_refresh_batch_device does not.
 int refresh_locked(orbp_map* m, const int32_t* slots, int n, const orbp::RefreshLists& L, const orbp::KeyFrames& K, const orbp::Factors& F, int what,
                    orbp_refreshed* d_out, hipStream_t st) {
-    const int rc = upload_slots(m, slots, n, st);
-    if (rc != ORBX_OK) return rc;
+    TRY(upload_slots(m, slots, n, st));
     const orbp::Refresh a{n, m->d_tab.as<int32_t>(), L, K, what, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), d_out};
     HIPCHK(m, orbp::launch_refresh(a, F, st));
     return ORBX_OK;
@@ -319,19 +319,6 @@ void launch_project(orbp_map* m, const orbp_view* d_views, int nviews, const orb
     else orbp::k_project<false><<<nviews, orbp::TPB, 0, st>>>(w, F);
 }
 
-// waits for the device work that may still read a handle-owned buffer or block, then grows it
-int grow(orbp_map* m, orbx::DevBuf& buf, size_t bytes) {
-    if (bytes <= buf.size()) return ORBX_OK;
-    HIPCHK(m, m->chain.wait());
-    HIPCHK(m, buf.ensure(bytes));
-    return ORBX_OK;
-}
-int grow(orbp_map* m, orbx::Block& b, size_t host_bytes, size_t dev_bytes) {
-    HIPCHK(m, m->chain.wait());
-    HIPCHK(m, b.ensure(host_bytes, dev_bytes));
-    return ORBX_OK;
-}
-
 // what the source-frame walks need beyond check_walk: a list (entry i is feature i of the source frame) and its key points
 int check_source(const orbp_map* m, const void* d_views, int nviews, const int32_t* d_list, const int32_t* d_nlist, int lcap, int qcap,
                  const void* d_src_kps, const void* d_src_desc) {
@@ -341,16 +328,15 @@ int check_source(const orbp_map* m, const void* d_views, int nviews, const int32
     return ORBX_OK;
 }
 
-// Projection, window search and the result by feature, inside the caller's link of the chain.  src == NULL: the frame mode
+// Projection, window search and the result by feature, inside the caller's call.  src == NULL: the frame mode
 // (d_t2pos NULL, d_rec may be set).
 int track_locked(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const orbp::Lists& lists, const orbp::Source* src,
                  const orbf_bounds* b, const orbs_params& prm, const orbp::Frame& fr, int qcap, const orbp::Queries& q, orbp_record* d_rec,
                  int32_t* d_t2pos, int32_t* d_t2slot, int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, hipStream_t st) {
     launch_project(m, d_views, nviews, F, lists, src, d_rec, q, d_nq, d_overflow, qcap, st);
     HIPCHK(m, hipGetLastError());
-    const int rc = orbs_window_search_batch_device(b, &prm, fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, fr.cap, fr.claimed, q.qxyr, q.qlev, q.qdesc,
-                                                   q.qangle, nullptr, q.nq_clamped, qcap, nviews, q.q2t, q.t2q, nullptr, nullptr, d_nmatches, st);
-    if (rc != ORBX_OK) return rc;
+    TRY(orbs_window_search_batch_device(b, &prm, fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, fr.cap, fr.claimed, q.qxyr, q.qlev, q.qdesc, q.qangle, nullptr,
+                                        q.nq_clamped, qcap, nviews, q.q2t, q.t2q, nullptr, nullptr, d_nmatches, st));
     orbp::k_t2source<<<dim3((fr.cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(q.t2q, q.qpos, lists.list, fr.nt, fr.cap, qcap, lists.lcap,
                                                                                               d_t2pos, d_t2slot);
     HIPCHK(m, hipGetLastError());
@@ -362,21 +348,18 @@ int track_batch(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::F
                 const orbf_bounds* b, const orbs_params& prm, const orbp::Frame& fr, int qcap, orbp_record* d_rec, int32_t* d_t2pos, int32_t* d_t2slot,
                 int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, void* stream) {
     if (orbs_lds_bytes(fr.cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
     Layout L;
     orbp::QuerySlots q;
     q.reserve(L, nviews, fr.cap, qcap, src != nullptr);
-    int rc = grow(m, m->scratch, L.total());
-    if (rc != ORBX_OK) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);
-    rc = track_locked(m, d_views, nviews, F, lists, src, b, prm, fr, qcap, q.at(m->scratch.as()), d_rec, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow, st);
-    if (rc != ORBX_OK) return rc;
-    HIPCHK(m, link.end());
-    return ORBX_OK;
+    if (L.total() > m->scratch.size()) {
+        HIPCHK(m, m->chain.wait());                                    // device work that may still use the scratch
+        HIPCHK(m, m->scratch.ensure(L.total()));
+    }
+    TRY(c.begin());
+    TRY(track_locked(m, d_views, nviews, F, lists, src, b, prm, fr, qcap, q.at(m->scratch.as()), d_rec, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow, c.st));
+    return c.end();
 }
 
 // orbp_track / orbp_track_source after their argument checks: one view through the handle's block (orbp::TrackBlock), synchronous.
@@ -386,46 +369,28 @@ int track_one(orbp_map* m, const orbp_view* view, const orbp::Factors& F, const 
               orbp_record* rec, int32_t* t2pos, int32_t* t2slot, int* nmatches, int* nvisible, void* stream) {
     const int cap = frame.cap, lcap = std::max(nlist, 1);
     if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    Call c(m, stream);
     const bool up_src = src && !src_on_device && nlist > 0;
     const orbp::TrackBlock B(cap, lcap, qcap, {src != nullptr, src || list, skip != nullptr, up_src, up_src && view->mode == ORBP_MODE_LAST_FRAME,
                                               !frame_on_device, frame.claimed != nullptr, t2slot != nullptr, rec != nullptr});
-    const size_t up_bytes = B.L.upload(), io_bytes = up_bytes + B.L.download(), total = B.L.total();
-    if (!m->one.fits(io_bytes, total)) {
-        const int rc = grow(m, m->one, io_bytes + io_bytes / 2, total + total / 2);
-        if (rc != ORBX_OK) return rc;
-    }
-    uint8_t* h = m->one.h.as();
-    uint8_t* d = m->one.d.as();
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    uint8_t* const h = s.h;
+    uint8_t* const d = s.d;
     std::memcpy(Layout::at(h, B.view), view, sizeof(orbp_view));
     Layout::at(h, B.counts)[0] = nt;
     Layout::at(h, B.counts)[1] = nlist;
-    if (list && nlist > 0) std::memcpy(Layout::at(h, B.list), list, (size_t)nlist * 4);
-    if (skip && nlist > 0) std::memcpy(Layout::at(h, B.skip), skip, (size_t)nlist);
-    if (B.src_kps.present) std::memcpy(Layout::at(h, B.src_kps), src->kps, (size_t)nlist * sizeof(orbx_keypoint));
-    if (B.src_desc.present) std::memcpy(Layout::at(h, B.src_desc), src->desc, (size_t)nlist * 32);
     const int32_t* d_counts = Layout::at(d, B.counts);
+    const orbp::Lists dl{s.put(B.list, list, nlist), d_counts + 1, lcap, s.put(B.skip, skip, nlist)};
     const orbp::Frame fr = B.frame.stage(h, d, frame, nt, d_counts);
     // with nlist == 0 nothing is read through the source pointers; the kernel still wants them non-NULL for a last-frame view
-    orbp::Source d_src{};
-    if (src) {
-        d_src.kps = B.src_kps.present ? Layout::at(d, B.src_kps) : (nlist > 0 ? src->kps : reinterpret_cast<const orbx_keypoint*>(d));
-        d_src.desc = B.src_desc.present ? Layout::at(d, B.src_desc) : (nlist > 0 ? src->desc : d);
-    }
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);                                           // from here every way out leaves the copies below behind the chain
-    HIPCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-    int32_t* d_res = Layout::at(d, B.result);                          // nq, overflow, nmatches
-    const int rc = track_locked(m, Layout::at(d, B.view), 1, F, {Layout::at(d, B.list), d_counts + 1, lcap, Layout::at(d, B.skip)}, src ? &d_src : nullptr, b,
-                                prm, fr, qcap, B.q.at(d), Layout::at(d, B.rec), Layout::at(d, B.t2pos), Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1,
-                                st);
-    if (rc != ORBX_OK) return rc;
-    HIPCHK(m, hipMemcpyAsync(h + up_bytes, d + up_bytes, io_bytes - up_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(m, link.end());
-    HIPCHK(m, hipStreamSynchronize(st));
+    orbp::Source d_src{reinterpret_cast<const orbx_keypoint*>(d), d};
+    if (src && nlist > 0) d_src = {s.put(B.src_kps, src->kps, nlist), s.put(B.src_desc, src->desc, (size_t)nlist * 32)};
+    TRY(s.run([&] {
+        int32_t* d_res = Layout::at(d, B.result);                      // nq, overflow, nmatches
+        return track_locked(m, Layout::at(d, B.view), 1, F, dl, src ? &d_src : nullptr, b, prm, fr, qcap, B.q.at(d), Layout::at(d, B.rec), Layout::at(d, B.t2pos),
+                            Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1, c.st);
+    }));
     const int32_t* res = Layout::at(h, B.result);
     if (nvisible) *nvisible = res[0];
     if (res[1]) return ORBX_ERR_CAPACITY;
@@ -476,14 +441,11 @@ int orbp_size(const orbp_map* m) { return m ? m->n_live : 0; }
 
 int orbp_clear(orbp_map* m) {
     if (!m) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = m->own;
-    HIPCHK(m, m->chain.begin(st));
-    HIPCHK(m, hipMemsetAsync(m->d_live.as(), 0, (size_t)m->capacity, st));
-    HIPCHK(m, m->chain.end(st));
-    HIPCHK(m, hipStreamSynchronize(st));
+    Call c(m, nullptr);
+    TRY(c.begin());
+    HIPCHK(m, hipMemsetAsync(m->d_live.as(), 0, (size_t)m->capacity, c.st));
+    TRY(c.end());
+    HIPCHK(m, hipStreamSynchronize(c.st));
     std::fill(m->live.begin(), m->live.end(), 0);
     m->n_live = 0;
     return ORBX_OK;
@@ -494,17 +456,11 @@ int orbp_put_device(orbp_map* m, const int32_t* slots, int n, const float* d_pos
     if (!m || n < 0) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     if (!slots || !d_pos || !d_normal || !d_min_dist || !d_max_dist) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
+    Call c(m, stream);
     if (check_slots(m, slots, n, true, d_desc == nullptr) != ORBX_OK) return ORBX_ERR_ARG;
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);
-    const int rc = put_locked(m, slots, n, d_pos, d_normal, d_min_dist, d_max_dist, d_desc, st);
-    if (rc != ORBX_OK) return rc;
-    HIPCHK(m, link.end());
-    return ORBX_OK;
+    TRY(c.begin());
+    TRY(put_locked(m, slots, n, d_pos, d_normal, d_min_dist, d_max_dist, d_desc, c.st));
+    return c.end();
 }
 
 int orbp_put(orbp_map* m, const int32_t* slots, int n, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
@@ -512,55 +468,31 @@ int orbp_put(orbp_map* m, const int32_t* slots, int n, const float* pos, const f
     if (!m || n < 0) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     if (!slots || !pos || !normal || !min_dist || !max_dist) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
+    Call c(m, nullptr);                                                // always the handle's own stream
     if (check_slots(m, slots, n, true, desc == nullptr) != ORBX_OK) return ORBX_ERR_ARG;
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    // staged through the handle's pinned block (grown by doubling, kept): one copy up, no allocation in the steady state
     Layout L;
     const auto s_pos = L.add<float>((size_t)n * 3), s_nrm = L.add<float>((size_t)n * 3), s_min = L.add<float>(n), s_max = L.add<float>(n);
     const auto s_desc = L.add<uint8_t>((size_t)n * 32, desc != nullptr);
-    const size_t total = L.total();
-    hipStream_t st = m->own;
-    if (!m->put.fits(total, total)) {
-        size_t want = std::max<size_t>(4096, m->put.h.size());
-        while (want < total) want *= 2;
-        const int rc = grow(m, m->put, want, want);
-        if (rc != ORBX_OK) return rc;
-    }
-    uint8_t* h = m->put.h.as();
-    uint8_t* d = m->put.d.as();
-    std::memcpy(Layout::at(h, s_pos), pos, (size_t)n * 12);
-    std::memcpy(Layout::at(h, s_nrm), normal, (size_t)n * 12);
-    std::memcpy(Layout::at(h, s_min), min_dist, (size_t)n * 4);
-    std::memcpy(Layout::at(h, s_max), max_dist, (size_t)n * 4);
-    if (desc) std::memcpy(Layout::at(h, s_desc), desc, (size_t)n * 32);
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);                                           // every way out leaves the copy below behind the chain
-    HIPCHK(m, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
-    const int rc = put_locked(m, slots, n, Layout::at(d, s_pos), Layout::at(d, s_nrm), Layout::at(d, s_min), Layout::at(d, s_max), Layout::at(d, s_desc), st);
-    if (rc != ORBX_OK) return rc;
-    HIPCHK(m, link.end());
-    HIPCHK(m, hipStreamSynchronize(st));
-    return ORBX_OK;
+    L.end_upload();                                                    // nothing comes back
+    Staged s(c, m->block, L);
+    TRY(s.fit());
+    const float *d_pos = s.put(s_pos, pos, (size_t)n * 3), *d_nrm = s.put(s_nrm, normal, (size_t)n * 3), *d_min = s.put(s_min, min_dist, n), *d_max = s.put(s_max, max_dist, n);
+    const uint8_t* d_desc = s.put(s_desc, desc, (size_t)n * 32);
+    return s.run([&] { return put_locked(m, slots, n, d_pos, d_nrm, d_min, d_max, d_desc, c.st); });
 }
 
 int orbp_erase(orbp_map* m, const int32_t* slots, int n) {
     if (!m || n < 0) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     if (!slots) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
+    Call c(m, nullptr);
     if (check_slots(m, slots, n, false, false) != ORBX_OK) return ORBX_ERR_ARG;
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = m->own;
-    HIPCHK(m, m->chain.begin(st));
-    const int rc = upload_slots(m, slots, n, st);
-    if (rc != ORBX_OK) return rc;
-    orbp::k_erase<<<(n + orbp::TPB - 1) / orbp::TPB, orbp::TPB, 0, st>>>(n, m->d_tab.as<int32_t>(), m->d_live.as<uint8_t>());
+    TRY(c.begin());
+    TRY(upload_slots(m, slots, n, c.st));
+    orbp::k_erase<<<(n + orbp::TPB - 1) / orbp::TPB, orbp::TPB, 0, c.st>>>(n, m->d_tab.as<int32_t>(), m->d_live.as<uint8_t>());
     HIPCHK(m, hipGetLastError());
-    HIPCHK(m, m->chain.end(st));
-    HIPCHK(m, hipStreamSynchronize(st));
+    TRY(c.end());
+    HIPCHK(m, hipStreamSynchronize(c.st));
     for (int i = 0; i < n; i++)
         if (m->live[slots[i]]) { m->live[slots[i]] = 0; m->n_live--; }
     return ORBX_OK;
@@ -599,16 +531,11 @@ int orbp_refresh_batch_device(orbp_map* m, const int32_t* slots, int n, const fl
     if (!m || orbp::check_refresh(n, L, K, factors, nlevels, what, true, true) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     if (!slots) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
+    Call c(m, stream);
     if (check_refresh_slots(m, slots, n, d_pos != nullptr, what) != ORBX_OK) return ORBX_ERR_ARG;
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);
-    const int rc = refresh_locked(m, slots, n, L, K, F, what, d_out, st);
-    if (rc != ORBX_OK) return rc;
-    HIPCHK(m, link.end());
+    TRY(c.begin());
+    TRY(refresh_locked(m, slots, n, L, K, F, what, d_out, c.st));
+    TRY(c.end());
     for (int i = 0; i < n; i++)                                        // the statuses stay on the device: orbp.h
         if (!m->live[slots[i]]) { m->live[slots[i]] = 1; m->n_live++; }
     return ORBX_OK;
@@ -624,33 +551,16 @@ int orbp_refresh(orbp_map* m, const int32_t* slots, int n, const float* pos, con
         return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     if (!slots) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
+    Call c(m, stream);
     if (check_refresh_slots(m, slots, n, pos != nullptr, what) != ORBX_OK) return ORBX_ERR_ARG;
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
     const orbp::RefreshBlock B(n, obs_off[n], L, K, kf_on_device == 0);
-    const size_t up_bytes = B.L.upload(), total = B.L.total();
-    if (!m->refresh.fits(total, total)) {
-        size_t want = std::max<size_t>(4096, m->refresh.h.size());
-        while (want < total) want *= 2;
-        const int rc = grow(m, m->refresh, want, want);
-        if (rc != ORBX_OK) return rc;
-    }
-    uint8_t* h = m->refresh.h.as();
-    uint8_t* d = m->refresh.d.as();
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
     orbp::RefreshLists dl;
     orbp::KeyFrames dk;
-    B.stage(h, d, L, K, dl, dk);
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);                                           // every way out leaves the copies below behind the chain
-    HIPCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-    const int rc = refresh_locked(m, slots, n, dl, dk, F, what, Layout::at(d, B.out), st);
-    if (rc != ORBX_OK) return rc;
-    HIPCHK(m, hipMemcpyAsync(h + up_bytes, d + up_bytes, total - up_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(m, link.end());
-    HIPCHK(m, hipStreamSynchronize(st));
-    const orbp_refreshed* res = Layout::at(h, B.out);
+    B.stage(s.h, s.d, L, K, dl, dk);
+    TRY(s.run([&] { return refresh_locked(m, slots, n, dl, dk, F, what, Layout::at(s.d, B.out), c.st); }));
+    const orbp_refreshed* res = Layout::at(s.h, B.out);
     for (int i = 0; i < n; i++)
         if (res[i].status == ORBP_REFRESH_OK && !m->live[slots[i]]) { m->live[slots[i]] = 1; m->n_live++; }
     if (out) std::memcpy(out, res, (size_t)n * sizeof(orbp_refreshed));
@@ -668,16 +578,11 @@ int orbp_fuse_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, co
     if (!m || orbp::check_fuse(d_views, nviews, factors, nlevels, L, b, orb_dist, K, out, true, true) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK)
         return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);
+    Call c(m, stream);
+    TRY(c.begin());
     const orbp::Fuse a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), L, K, *b, orb_dist, out, 0};
-    HIPCHK(m, orbp::launch_fuse(a, nviews, F, st));
-    HIPCHK(m, link.end());
-    return ORBX_OK;
+    HIPCHK(m, orbp::launch_fuse(a, nviews, F, c.st));
+    return c.end();
 }
 
 int orbp_fuse(orbp_map* m, const orbp_view* views, int nviews, const float* factors, int nlevels, const int32_t* list, const int32_t* nlist, int lcap,
@@ -692,41 +597,28 @@ int orbp_fuse(orbp_map* m, const orbp_view* views, int nviews, const float* fact
         fill_factors(factors, nlevels, F) != ORBX_OK)
         return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    Call c(m, stream);
     const orbp::FuseBlock B(nviews, L, K, frames_on_device == 0, rec != nullptr);
-    const size_t up_bytes = B.L.upload(), total = B.L.total();
-    if (!m->fuse.fits(total, total)) {
-        size_t want = std::max<size_t>(4096, m->fuse.h.size());
-        while (want < total) want *= 2;
-        const int rc = grow(m, m->fuse, want, want);
-        if (rc != ORBX_OK) return rc;
-    }
-    uint8_t* h = m->fuse.h.as();
-    uint8_t* d = m->fuse.d.as();
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
     const orbp_view* dv;
     orbp::Lists dl;
     orbp::FuseFrames dk;
     orbp::FuseOut dout;
-    B.stage(h, d, views, L, K, dv, dl, dk, dout);
-    HIPCHK(m, m->chain.begin(st));
-    Link link(m->chain, st);                                           // every way out leaves the copies below behind the chain
-    HIPCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-    const orbp::Fuse a{dv, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), dl, dk, *b, orb_dist, dout, 0};
-    HIPCHK(m, orbp::launch_fuse(a, nviews, F, st));
-    HIPCHK(m, hipMemcpyAsync(h + up_bytes, d + up_bytes, total - up_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(m, link.end());
-    HIPCHK(m, hipStreamSynchronize(st));
+    B.stage(s.h, s.d, views, L, K, dv, dl, dk, dout);
+    TRY(s.run([&]() -> int {
+        const orbp::Fuse a{dv, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), dl, dk, *b, orb_dist, dout, 0};
+        HIPCHK(m, orbp::launch_fuse(a, nviews, F, c.st));
+        return ORBX_OK;
+    }));
     // only what the kernel wrote reaches the caller: entries at i >= nlist[p] stay as they were
     for (int p = 0; p < nviews; p++) {
         const int n = std::min(std::max(nlist[p], 0), lcap);
         const size_t e = (size_t)p * lcap;
         if (n == 0) continue;
-        std::memcpy(best_idx + e, Layout::at(h, B.best_idx) + e, (size_t)n * 4);
-        std::memcpy(best_dist + e, Layout::at(h, B.best_dist) + e, (size_t)n * 4);
-        if (rec) std::memcpy(rec + e, Layout::at(h, B.rec) + e, (size_t)n * sizeof(orbp_fused));
+        std::memcpy(best_idx + e, Layout::at(s.h, B.best_idx) + e, (size_t)n * 4);
+        std::memcpy(best_dist + e, Layout::at(s.h, B.best_dist) + e, (size_t)n * 4);
+        if (rec) std::memcpy(rec + e, Layout::at(s.h, B.rec) + e, (size_t)n * sizeof(orbp_fused));
     }
     return ORBX_OK;
 }
@@ -738,15 +630,11 @@ int orbp_project_batch_device(orbp_map* m, const orbp_view* d_views, int nviews,
     if (check_walk(m, d_views, nviews, d_list, d_nlist, lcap, qcap) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK) return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
     if (!d_qxyr || !d_qlev || !d_qdesc || !d_qpos || !d_nq || !d_overflow) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
-    HIPCHK(m, m->chain.begin(st));
-    launch_project(m, d_views, nviews, F, {d_list, d_nlist, lcap, d_skip}, nullptr, d_rec, {d_qxyr, d_qlev, d_qdesc, d_qpos}, d_nq, d_overflow, qcap, st);
+    Call c(m, stream);
+    TRY(c.begin());
+    launch_project(m, d_views, nviews, F, {d_list, d_nlist, lcap, d_skip}, nullptr, d_rec, {d_qxyr, d_qlev, d_qdesc, d_qpos}, d_nq, d_overflow, qcap, c.st);
     HIPCHK(m, hipGetLastError());
-    HIPCHK(m, m->chain.end(st));
-    return ORBX_OK;
+    return c.end();
 }
 
 int orbp_track_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
@@ -786,17 +674,13 @@ int orbp_project_source_batch_device(orbp_map* m, const orbp_view* d_views, int 
         return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
     if (!d_qxyr || !d_qlev || !d_qdesc || ((uintptr_t)d_qdesc & 15) || !d_qangle || !d_qpos || !d_nq || !d_overflow) return ORBX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(m->mu);
-    DeviceScope ds(m->device);
-    if (!ds.ok) return ORBX_ERR_DEVICE;
-    hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)m->own;
+    Call c(m, stream);
+    TRY(c.begin());
     const orbp::Source src{d_src_kps, d_src_desc};
-    HIPCHK(m, m->chain.begin(st));
     launch_project(m, d_views, nviews, F, {d_list, d_nlist, lcap, d_skip}, &src, nullptr, {d_qxyr, d_qlev, d_qdesc, d_qpos, nullptr, nullptr, nullptr, d_qangle},
-                   d_nq, d_overflow, qcap, st);
+                   d_nq, d_overflow, qcap, c.st);
     HIPCHK(m, hipGetLastError());
-    HIPCHK(m, m->chain.end(st));
-    return ORBX_OK;
+    return c.end();
 }
 
 int orbp_track_source_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,

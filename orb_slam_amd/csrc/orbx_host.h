@@ -1,9 +1,13 @@
 // Host-side owners of the HIP resources behind the C ABI: device and pinned buffers, streams, events, the device scope and event chain of
-// a handle, the layout of the blocks a handle keeps, and the one-shot staging of the synchronous host forms.  Each owner releases what it
-// holds when it goes out of scope, so an early return leaks nothing.
+// a handle, the scope of one call on a handle (Call), the layout of the block a handle keeps (Layout, Block), the path of a synchronous
+// host form through that block (Staged), and the one-shot staging of the host forms without a handle (Staging).  Each owner releases
+// what it holds when it goes out of scope, so an early return leaks nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstring>
+#include <mutex>
+#include <optional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -117,8 +121,8 @@ struct Chain {
         return e;
     }
     hipError_t wait() const { return chained ? hipEventSynchronize(ev) : hipSuccess; }
-    // One piece of work, after begin(): recorded by end(), or when the scope is left early, so that the handle's next call waits for
-    // whatever this one had enqueued (a copy out of a pinned block, say) before it touches the same memory.
+    // One piece of work, after begin(): recorded by end(), or when the scope is left early, so that the stream of the handle's next
+    // call waits for whatever this one had enqueued.  (What the next call's host writes wait for is Block::busy's business.)
     struct Link {
         Link(Chain& c, hipStream_t st) : c_(&c), st_(st) {}
         ~Link() { if (c_) (void)c_->end(st_); }
@@ -148,16 +152,24 @@ class Layout {
     size_t total() const { return total_; }
     // the slot inside a block that starts at `base` (pinned host or device memory)
     template <class T> static T* at(void* base, Slot<T> s) { return s.present ? reinterpret_cast<T*>(static_cast<uint8_t*>(base) + s.off) : nullptr; }
+    // The caller's host array `src` of n elements as the kernels read it: copied into the slot of the pinned block h and named inside the
+    // device block d.  An absent slot passes `src` through: an array the caller does not have (NULL) or keeps on the device.
+    template <class T> static const T* put(void* h, void* d, Slot<T> s, const T* src, size_t n) {
+        if (!s.present) return src;
+        if (n) std::memcpy(at(h, s), src, n * sizeof(T));
+        return at(d, s);
+    }
 
   private:
     size_t total_ = 0, up_ = 0, down_ = 0;
 };
 
 // A pinned block and its device twin, kept by a handle and grown together: a failed grow leaves both empty, so the next call grows
-// again and never pairs a block of the new size with a missing one.
+// again and never pairs a block of the new size with a missing one.  busy: a call left while copies of the block were in flight.
 struct Block {
     PinnedBuf h;
     DevBuf d;
+    bool busy = false;
     bool fits(size_t host_bytes, size_t dev_bytes) const { return host_bytes <= h.size() && dev_bytes <= d.size(); }
     hipError_t ensure(size_t host_bytes, size_t dev_bytes) {
         hipError_t e = h.ensure(host_bytes, hipHostMallocDefault);
@@ -165,6 +177,87 @@ struct Block {
         if (e != hipSuccess) { h.reset(); d.reset(); }
         return e;
     }
+};
+
+// The size a kept buffer of `have` bytes grows to for `need`: doubled from 4096, so a slowly growing need allocates seldom.
+inline size_t doubled(size_t have, size_t need) {
+    size_t want = have > 4096 ? have : 4096;
+    while (want < need) want *= 2;
+    return want;
+}
+
+// One entry point's grip on a handle H (mu, device, own, chain, err): the handle's mutex and its device for the scope, the stream the call
+// runs on (the caller's, or the handle's own), and from begin() on its link of the chain, which every way out of the scope records.
+template <class H>
+class Call {
+    std::lock_guard<std::mutex> lk_;                                    // released last: after the chain is recorded and the device given back
+    DeviceScope ds_;
+
+  public:
+    H* const m;
+    const hipStream_t st;
+    Call(H* h, void* stream) : lk_(h->mu), ds_(h->device), m(h), st(stream ? (hipStream_t)stream : (hipStream_t)h->own) {}
+    bool ok() const { return ds_.ok; }                                  // the device could be selected
+    // `st` waits for the handle's earlier work; an unselectable device is reported here, with nothing enqueued or recorded
+    int begin() {
+        if (!ok()) return ORBX_ERR_DEVICE;
+        HIPCHK(m, m->chain.begin(st));
+        link_.emplace(m->chain, st);
+        return ORBX_OK;
+    }
+    // records the chain
+    int end() {
+        HIPCHK(m, link_->end());
+        return ORBX_OK;
+    }
+
+  private:
+    std::optional<Chain::Link> link_;                                   // left first
+};
+
+// A synchronous host form through the block `b` a handle keeps, laid out by `L`: fit() makes the block fit and hands out h and d, the
+// caller fills the upload span (put()), and run(body) uploads [0, upload()), lets `body` enqueue the kernels, downloads
+// [upload(), upload() + download()), records the chain and waits for the stream.  What lies behind the download span is device memory
+// only.  The forms of a handle share one block: each holds the handle's mutex until it has synchronised, so no two are in flight.  A call
+// that leaves between its upload and its synchronise marks the block busy, and the next fit() waits for the chain (which that call's link
+// recorded) before the host writes into the pinned half again; in the steady state fit() waits for nothing and allocates nothing.
+template <class H>
+class Staged {
+  public:
+    uint8_t* h = nullptr;
+    uint8_t* d = nullptr;
+    Staged(Call<H>& c, Block& b, const Layout& L) : c_(c), b_(b), up_(L.upload()), down_(L.download()), total_(L.total()) {}
+    int fit() {
+        H* m = c_.m;
+        if (!c_.ok()) return ORBX_ERR_DEVICE;
+        const bool grow = !b_.fits(up_ + down_, total_);
+        if (grow || b_.busy) HIPCHK(m, m->chain.wait());                // device work that may still read or write the block
+        b_.busy = false;
+        if (grow) HIPCHK(m, b_.ensure(doubled(b_.h.size(), up_ + down_), doubled(b_.d.size(), total_)));
+        h = b_.h.as();
+        d = b_.d.as();
+        return ORBX_OK;
+    }
+    template <class T> const T* put(Layout::Slot<T> s, const T* src, size_t n) const { return Layout::put(h, d, s, src, n); }
+    // body() returns an ORBX status; anything but ORBX_OK ends the call there, with the chain recorded
+    template <class Body> int run(Body body) {
+        H* m = c_.m;
+        int rc = c_.begin();
+        if (rc != ORBX_OK) return rc;
+        b_.busy = true;
+        HIPCHK(m, hipMemcpyAsync(d, h, up_, hipMemcpyHostToDevice, c_.st));
+        if ((rc = body()) != ORBX_OK) return rc;
+        if (down_) HIPCHK(m, hipMemcpyAsync(h + up_, d + up_, down_, hipMemcpyDeviceToHost, c_.st));
+        if ((rc = c_.end()) != ORBX_OK) return rc;
+        HIPCHK(m, hipStreamSynchronize(c_.st));
+        b_.busy = false;
+        return ORBX_OK;
+    }
+
+  private:
+    Call<H>& c_;
+    Block& b_;
+    const size_t up_, down_, total_;
 };
 
 // One-shot staging of a synchronous host form: the arrays live in ONE device allocation laid out by Layout.  in() / out() reserve an

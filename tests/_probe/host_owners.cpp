@@ -1,7 +1,10 @@
-// orb_slam_amd/csrc/orbx_host.h and orbp_host.h on the CPU against tests/_probe/hip_stub: the staging layout, the layouts of the blocks
-// a map-point table keeps, the device scope and the event chain, and what the owners hold after a failed allocation
+// orb_slam_amd/csrc/orbx_host.h and orbp_host.h on the CPU against tests/_probe/hip_stub: the staging layout, the layouts of the block
+// a map-point table keeps, the device scope and the event chain, what the owners hold after a failed allocation, and the scope of a call
+// on a handle (orbx::Call) with the path of a synchronous host form through the handle's block (orbx::Staged), in the order of their HIP calls
 // (tests/test_host_owners.py builds this under AddressSanitizer, which also reports leaks and double frees).
 #include <cstdio>
+#include <mutex>
+#include <string>
 
 #include "orbp_host.h"
 #include "orbx_host.h"
@@ -18,6 +21,56 @@ static bool spans(const orbp::TrackBlock& B, size_t up, size_t down, size_t tota
 }
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAIL line %d: %s\n", __LINE__, #c); return 1; } } while (0)
+
+namespace {
+// what orbx::Call and orbx::Staged want of a handle
+struct Handle {
+    int device = 0;
+    std::mutex mu;
+    std::string err;
+    Stream own;
+    Chain chain;
+    Block block;
+};
+}  // namespace
+
+static bool all(const uint8_t* p, size_t n, uint8_t v) {
+    for (size_t i = 0; i < n; i++)
+        if (p[i] != v) return false;
+    return true;
+}
+
+// One synchronous host form over `m`'s block as orbp_project.hip writes them: fit, fill the upload span, run a body that stands in for the
+// kernels (it answers 0x22 into the download span and returns body_rc).  Around it every byte of both halves that no copy may touch holds a
+// sentinel.  Returns 1 on a failed check; rc: the call's status; at_fill: the HIP calls up to the first write into the pinned block.
+static int staged_call(Handle& m, const Layout& L, int body_rc, int& rc, std::string& at_fill) {
+    const size_t up = L.upload(), down = L.download(), total = L.total();
+    hip_stub_log.clear();
+    hip_stub_up = hip_stub_down = {};
+    at_fill = "-";
+    Call<Handle> c(&m, nullptr);
+    CHECK(c.st == (hipStream_t)m.own && hip_stub_device == m.device);
+    Staged<Handle> s(c, m.block, L);
+    if ((rc = s.fit()) != ORBX_OK) return 0;
+    at_fill = hip_stub_log;
+    CHECK(s.h == m.block.h.as() && s.d == m.block.d.as() && m.block.fits(up + down, total) && !m.block.busy);
+    const size_t hsize = m.block.h.size(), dsize = m.block.d.size();
+    std::memset(s.h, 0x11, up);
+    std::memset(s.h + up, 0xA5, hsize - up);                          // the download span and the pinned bytes beyond it
+    std::memset(s.d, 0x33, dsize);                                    // the device-only tail among them
+    bool body_ok = false;
+    rc = s.run([&] {
+        body_ok = hip_stub_log.back() == 'u' && all(s.d, up, 0x11) && all(s.d + up, dsize - up, 0x33);      // the upload is [0, up) and is in front
+        std::memset(s.d + up, 0x22, down);
+        return body_rc;
+    });
+    CHECK(body_ok && hip_stub_up.dst == s.d && hip_stub_up.src == s.h && hip_stub_up.bytes == up);
+    CHECK(all(s.h, up, 0x11) && all(s.h + up + down, hsize - up - down, 0xA5) && all(s.d + up + down, dsize - up - down, 0x33));
+    if (rc != ORBX_OK) return 0;
+    if (down) CHECK(hip_stub_down.dst == s.h + up && hip_stub_down.src == s.d + up && hip_stub_down.bytes == down && all(s.h + up, down, 0x22));
+    else CHECK(hip_stub_down.bytes == 0 && hip_stub_log.find('d') == std::string::npos);
+    return 0;
+}
 
 int main() {
     {
@@ -144,6 +197,100 @@ int main() {
             Chain::Link link(c2, nullptr);
             CHECK(link.end() == hipSuccess && c2.chained);
         }
+    }
+    CHECK(hip_stub_live == 0);
+    {
+        // Call: the handle's device for the scope, the chain recorded once on every way out after begin(), the mutex free afterwards
+        Handle m;
+        CHECK(m.own.ensure() == hipSuccess && m.chain.ev.ensure() == hipSuccess);
+        hipStream_t other = nullptr;
+        CHECK(hipStreamCreateWithFlags(&other, hipStreamNonBlocking) == hipSuccess);
+        hip_stub_device = 1;
+        hip_stub_log.clear();
+        {
+            Call<Handle> c(&m, other);                                 // the caller's stream; left without begin(): nothing recorded
+            CHECK(c.ok() && c.st == other && hip_stub_device == 0);
+        }
+        CHECK(hip_stub_device == 1 && hip_stub_log.empty() && !m.chain.chained && m.mu.try_lock());
+        m.mu.unlock();
+        {
+            Call<Handle> c(&m, nullptr);                               // left early after begin()
+            CHECK(c.begin() == ORBX_OK && hip_stub_log.empty());       // nothing to wait for yet
+        }
+        CHECK(hip_stub_log == "r" && m.chain.chained && hip_stub_device == 1 && m.mu.try_lock());
+        m.mu.unlock();
+        {
+            Call<Handle> c(&m, nullptr);
+            CHECK(c.begin() == ORBX_OK && c.end() == ORBX_OK && hip_stub_log == "rsr");
+        }
+        CHECK(hip_stub_log == "rsr");                                   // end() recorded it: leaving does not record again
+        CHECK(hip_stub_device == 1);
+        // a device that cannot be selected: reported by begin() and by fit(), nothing enqueued, recorded or allocated
+        m.device = 7;
+        hip_stub_log.clear();
+        {
+            Call<Handle> c(&m, nullptr);
+            Layout L;
+            L.add<uint8_t>(100);
+            L.end_upload();
+            Staged<Handle> s(c, m.block, L);
+            CHECK(!c.ok() && c.begin() == ORBX_ERR_DEVICE && s.fit() == ORBX_ERR_DEVICE && s.run([] { return (int)ORBX_OK; }) == ORBX_ERR_DEVICE);
+        }
+        CHECK(hip_stub_log.empty() && hip_stub_device == 1 && !m.block.h && !m.block.d && m.mu.try_lock());
+        m.mu.unlock();
+        CHECK(hipStreamDestroy(other) == hipSuccess);
+    }
+    CHECK(hip_stub_live == 0);
+    {
+        // Staged: one block for every form of a handle
+        Handle m;
+        CHECK(m.own.ensure() == hipSuccess && m.chain.ev.ensure() == hipSuccess);
+        const int live0 = hip_stub_live;
+        int rc = 0;
+        std::string at_fill;
+        Layout L;                                                       // 512 up, 256 down, 1024 behind them on the device only
+        L.add<uint8_t>(300); L.end_upload(); L.add<int32_t>(3); L.end_download(); L.add<uint8_t>(1000);
+        CHECK(L.upload() == 512 && L.download() == 256 && L.total() == 1792);
+        // the first call grows the empty block (nothing to wait for: no work on the handle yet), both halves to 4096
+        CHECK(staged_call(m, L, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK);
+        CHECK(at_fill == "mm" && hip_stub_log == "mmudry" && m.block.h.size() == 4096 && m.block.d.size() == 4096 && hip_stub_live == live0 + 2);
+        // the steady state: nothing allocated, no wait on the host; the stream waits for the chain
+        const void *h0 = m.block.h, *d0 = m.block.d;
+        CHECK(staged_call(m, L, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK);
+        CHECK(at_fill.empty() && hip_stub_log == "sudry" && (void*)m.block.h == h0 && (void*)m.block.d == d0 && !m.block.busy);
+        // an empty download span issues no copy (orbp_put)
+        Layout U;
+        U.add<float>(257); U.end_upload();
+        CHECK(U.download() == 0 && staged_call(m, U, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill.empty() && hip_stub_log == "sury");
+        // a device-only tail grows the device half alone, a larger upload both: the host waits for the chain before anything is freed, and
+        // the pinned half is sized to the two spans, the device half to the whole layout
+        Layout T;
+        T.add<uint8_t>(300); T.end_upload(); T.add<int32_t>(3); T.end_download(); T.add<uint8_t>(10000);
+        CHECK(staged_call(m, T, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill == "wfm" && m.block.h.size() == 4096 && m.block.d.size() == 16384);
+        Layout G;
+        G.add<uint8_t>(5000); G.end_upload(); G.add<int32_t>(3); G.end_download(); G.add<uint8_t>(20000);
+        CHECK(staged_call(m, G, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill == "wfmfm" && m.block.h.size() == 8192 && m.block.d.size() == 32768);
+        CHECK(hip_stub_live == live0 + 2);
+        // a small call after the large ones runs in the block as it is
+        CHECK(staged_call(m, L, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill.empty() && m.block.h.size() == 8192 && m.block.d.size() == 32768);
+        // a failed grow (the pinned half grows, the device half fails) leaves both halves empty; the next call grows again
+        Layout H;
+        H.add<uint8_t>(9000); H.end_upload(); H.add<int32_t>(3); H.end_download(); H.add<uint8_t>(40000);
+        hip_stub_fail = 2;
+        m.err.clear();
+        CHECK(staged_call(m, H, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_ERR_DEVICE && !m.err.empty() && at_fill == "-");
+        CHECK(!m.block.h && !m.block.d && m.block.h.size() == 0 && m.block.d.size() == 0 && hip_stub_live == live0 && hip_stub_log == "wfmff");     // waited, then: pinned freed and made, device freed, its allocation fails, pinned freed
+        CHECK(staged_call(m, H, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill == "wmm" && m.block.h.size() == 16384 && m.block.d.size() == 65536);
+        // a body that fails after the upload: the chain is recorded once, nothing comes down, nothing is waited for; the next call waits
+        // for the chain on the host before its first write into the pinned block, the call after that does not
+        CHECK(staged_call(m, L, ORBX_ERR_ARG, rc, at_fill) == 0 && rc == ORBX_ERR_ARG && at_fill.empty() && hip_stub_log == "sur" && m.block.busy);
+        CHECK(staged_call(m, L, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill == "w" && hip_stub_log == "wsudry" && !m.block.busy);
+        CHECK(staged_call(m, L, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill.empty() && hip_stub_log == "sudry");
+        // ... and so does a call that has to grow after a failed one: one wait serves both
+        CHECK(staged_call(m, L, ORBX_ERR_CAPACITY, rc, at_fill) == 0 && rc == ORBX_ERR_CAPACITY && m.block.busy);
+        Layout I;
+        I.add<uint8_t>(20000); I.end_upload();
+        CHECK(staged_call(m, I, ORBX_OK, rc, at_fill) == 0 && rc == ORBX_OK && at_fill == "wfm" && m.block.h.size() == 32768 && m.block.d.size() == 65536);
     }
     CHECK(hip_stub_live == 0);
     std::printf("host owners ok\n");
