@@ -31,7 +31,7 @@ EXPORTS = [
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_download",
     "orbx_stream_create", "orbx_stream_create_priority", "orbx_stream_destroy", "orbx_stream_synchronize", "orbx_event_create", "orbx_event_destroy", "orbx_event_record",
     "orbx_stream_wait_event", "orbx_device_copy_async", "orbx_host_alloc", "orbx_host_free", "orbx_device_upload_async", "orbx_device_download_async", "orbx_debug_set_stop_after", "orbx_debug_set_blur_on_demand", "orbx_debug_level_size", "orbx_debug_fetch",
-    "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
+    "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_eval_blur_window", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
     "orbm_debug_set_match_path",
     "orbm_debug_get_match_path",
 ]
@@ -231,6 +231,7 @@ def lib():
         L.orbx_debug_fetch.restype = cl
         L.orbx_debug_eval_math.argtypes = [ci, vp, vp, vp, vp, ci, ci]
         L.orbx_debug_eval_compass.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci]
+        L.orbx_debug_eval_blur_window.argtypes = [vp, vp, ci, ci, ci, ci]
         L.orbx_debug_nth_element.argtypes = [vp, ci, ci, vp, ci]
         L.orbx_debug_geometry.argtypes = [ctypes.POINTER(Params), ci, ci, vp, ci]
         L.orbx_debug_stage_timing.argtypes = [vp, ci]
@@ -745,6 +746,18 @@ def eval_compass(c, e, w, n, s, t, device=0):
     rc = lib().orbx_debug_eval_compass(*[a.ctypes.data for a in arrs], out.ctypes.data, arrs[0].size, int(t), device)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbx_debug_eval_compass")
+    return out
+
+
+def eval_blur_window(windows, blur_rounding=BLUR_X86_SSE2, general=False, device=0):
+    """k_describe_od's per-key-point blur on (n, 43, 48) uint8 windows -> the (n, 37, 40) blurred regions the taps read (window rows 3 .. 39,
+    columns 4 .. 43), every column in the one rounding mode; general: through the per-lane epilogue of edge windows"""
+    win = np.ascontiguousarray(windows, dtype=np.uint8)
+    assert win.ndim == 3 and win.shape[1:] == (43, 48)
+    out = np.empty((win.shape[0], 37, 40), np.uint8)
+    rc = lib().orbx_debug_eval_blur_window(win.ctypes.data, out.ctypes.data, win.shape[0], int(blur_rounding), int(bool(general)), device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_debug_eval_blur_window")
     return out
 
 

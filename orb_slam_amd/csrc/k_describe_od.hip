@@ -6,8 +6,9 @@
 // k_describe reads two things per keypoint: the 31 x 31 patch of the PLAIN level (IC_Angle) and the 37 x 37 window of the BLURRED level
 // the rotated pattern can reach — the only consumer the blurred plane has.  Here a wave stages ONE 43 x 48-byte window of the plain
 // level per keypoint (rows y-21 .. y+21, 48 bytes from the 4-byte aligned column at or left of x-22: the patch AND everything the 7 x 7
-// filter needs around the 37 x 37 tap window), computes IC_Angle from it, then blurs it IN PLACE with exact int8 matrix products
-// (v_mfma_i32_16x16x64_i8; the arithmetic of k_blur_mfma on window-shaped operands) and takes the 512 taps from the result.  The blurred
+// filter needs around the 37 x 37 tap window), computes IC_Angle from it, then blurs it IN PLACE with exact matrix products (the row pass
+// on v_mfma_i32_16x16x64_i8, the arithmetic of k_blur_mfma on window-shaped operands; the column pass on v_mfma_f32_16x16x32_f16, exact as
+// well: orb_math.h blurf_*) and takes the 512 taps from the result.  The blurred
 // plane, the blur kernel (VGA: 0.49 ms and 2.2 GB per 1024 frames; 1080p: 0.80 ms per 256 frames on the VALU) and the second gather
 // of every keypoint disappear; the windows of a frame cover 1.4 x the pyramid's pixels at VGA / 1000 and 0.58 x at 1080p / 2000.
 //
@@ -19,18 +20,23 @@
 //               The window is then the level's reflect-101 extension at DISTINCT positions: every window takes the same arithmetic.
 //   row pass    Mid[r][c'] = sum_t tap[t] * In[r][c'+1+t]  (c' <-> window column c'+4: outputs start on a dword): per 16-column tile
 //               ct and 16-row tile t one MFMA, A = the window rows (a lane's 16 bytes are one ds_read_b128), B = the banded tap matrix
-//               (a lane constant).  Pixels go in centred (p - 128) and the accumulator starts at 128, so the result is S - 32768 in
-//               signed 16 bits: HI byte signed, LO byte unsigned (centred again) — two int8 operands.
-//   column pass Out[ro][c'] = sum_t tap[t] * Mid[ro+t][c']: the row pass leaves lane (c' % 16, g) with Mid rows 16t+4g+i of column c',
-//               which IS an A operand of this shape when the summed index K is numbered 16g+4t+i (the tap matrix is permuted to match,
-//               a lane constant again): no data moves between the passes.  Two products (HI, LO) per 16 x 16 tile; the result has four
-//               consecutive COLUMNS of one output row per lane: one aligned ds_write_b32 into the window, in place.
+//               (a lane constant).  Pixels go in centred (p - 128) and the accumulator starts at blurf_mid_start(), so the 32-bit result
+//               is 0x0064HHLL with HHLL = S_row: a v_perm_b32 per two elements makes the f16 pair (1024 + LL) of the column pass's LO
+//               operand, another the pair (1024 + HH), which one v_pk_add_f16 turns into the HI operand (orb_math.h blurf_hi / blurf_lo).
+//   column pass Out[ro][c'] = sum_t tap[t] * Mid[ro+t][c'] as a float product: the row pass leaves lane (c' % 16, g) with Mid rows
+//               16t+4g+i of column c' (i = 0 .. 3), whose four register pairs LO01 HI01 LO23 HI23 ARE an A operand of
+//               v_mfma_f32_16x16x32_f16 (lane (m, g) holds K = 8g .. 8g+7) for row tile t: no data moves between the passes.  The tap
+//               matrix (x 2^-8 in the HI slots, x 2^-16 in the LO slots, a lane constant) is numbered to match.  An output row needs two
+//               row tiles, i.e. two chained products per 16 x 16 tile; the accumulator starts at blurf_start() and ends at S / 65536, exactly.
+//               The result has four consecutive COLUMNS of one output row per lane: one aligned ds_write_b32 into the window, in place.
 //   rounding    (S + 0x8000) >> 16 half-up or ties-to-even by ABSOLUTE column (x < w & ~3: OpenCV's SSE2 column filter), saturated —
-//               orb_math.h blur_round, as k_blur / k_blur_mfma.
+//               orb_math.h blur_round, as k_blur / k_blur_mfma: here round-to-nearest-even resp. floor(v + 0.5) of the float
+//               (blurf_round), then v_cvt_pk_u8_f32, which saturates and puts the byte into the output dword.
 //   H4          taps up to 2 px outside the level read the UNBLURRED reflect-101 border in the reference.  Outputs at
 //               out-of-level positions are simply not written: the window keeps the plain reflected pixel there.
 //   tiles       two 16-wide tiles per axis per window; the last 8 columns and 5 rows of two windows share one tile (see the blur below).
-// 20 MFMAs and ~150 VALU instructions per keypoint for the blur; a wave owns four keypoints.
+// 20 MFMAs (7.5 int8, 12.5 f16) and ~87 VALU instructions per keypoint for the blur (listing, fast epilogue: 170 per pair + 8 for the corner);
+// a wave owns four keypoints.
 #include <algorithm>
 #include <type_traits>
 
@@ -60,8 +66,9 @@ struct OdTables {
     float pat[256][4];             // test t: x0, y0, x1, y1
     uint32_t trow[3][64][4];       // row pass, lane: K = 16 g + 4 v + byte; [ct < 2]: window column K, output column c' = 16 ct + n;
                                    // [2] (PCOL): K block 2 = the first window's columns 32 .. 47 -> c' = 32 + n (n < 8), block 3 = the second's -> c' = 24 + n (n >= 8)
-    uint32_t tcol[3][64][4];       // column pass, lane: K = 16 g + 4 v + byte <-> Mid row 16 v + 4 g + byte; [rt < 2]: output row ro = 16 rt + n;
-                                   // [2] (PROW, CORNER): register 2 -> ro = 32 + n (n < 5), register 3 = the other window's -> ro = 24 + n (8 <= n < 13)
+    uint32_t tcol[4][64][4];       // column pass (f16 pairs), lane (n, g), register v, half h: K = 8 g + 2 v + h <-> LO (v even) / HI (v odd) of Mid row
+                                   // 16 t + 4 g + 2 (v / 2) + h of the product's row tile t; output row ro = 16 rt + n: [0] t = rt, [1] t = rt + 1;
+                                   // (PROW, CORNER) ro = 32 + (n & 7), t = 2: [2] the first window's (n < 5), [3] the second's (8 <= n < 13)
 };
 constexpr uint32_t c_pattern_host[256] = {
 #include "orb_pattern_packed.inc"
@@ -85,23 +92,176 @@ constexpr OdTables make_od_tables() {
         for (int l = 0; l < 64; l++)
             for (int v = 0; v < 4; v++) {
                 const int n = l & 15, g = l >> 4;
-                if (c < 2) {
-                    T.trow[c][l][v] = od_taps4(16 * g + 4 * v - (16 * c + n) - 1);
-                    T.tcol[c][l][v] = od_taps4(16 * v + 4 * g - (16 * c + n));
-                } else {
-                    T.trow[c][l][v] = g == 2 && n < 8 ? od_taps4(4 * v - n - 1) : g == 3 && n >= 8 ? od_taps4(4 * v - (n - 8) - 1) : 0u;
-                    T.tcol[c][l][v] = v == 2 && n < 5 ? od_taps4(4 * g - n) : v == 3 && n >= 8 && n < 13 ? od_taps4(4 * g - (n - 8)) : 0u;
+                if (c < 2) T.trow[c][l][v] = od_taps4(16 * g + 4 * v - (16 * c + n) - 1);
+                else T.trow[c][l][v] = g == 2 && n < 8 ? od_taps4(4 * v - n - 1) : g == 3 && n >= 8 ? od_taps4(4 * v - (n - 8) - 1) : 0u;
+            }
+    for (int c = 0; c < 4; c++)
+        for (int l = 0; l < 64; l++)
+            for (int v = 0; v < 4; v++) {
+                const int n = l & 15, g = l >> 4;
+                uint32_t word = 0;
+                for (int h = 0; h < 2; h++) {
+                    const int row = 4 * g + 2 * (v >> 1) + h;                   // Mid row inside the product's row tile
+                    const int t = c == 0 ? row - n : c == 1 ? 16 + row - n : c == 2 ? (n < 5 ? row - n : -1) : (n >= 8 && n < 13 ? row - (n - 8) : -1);
+                    word |= f16_bits_scaled(blur_tap(t), (v & 1) ? 8 : 16) << (16 * h);      // blurf_tap_hi / blurf_tap_lo
                 }
+                T.tcol[c][l][v] = word;
             }
     return T;
 }
 static __device__ __constant__ OdTables c_od = make_od_tables();
+
+typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+// v_cvt_pk_u8_f32 rounds to nearest even and saturates to 0 .. 255 (profiles/describe_od_f16_probe.txt (c)); were it otherwise, a v_rndne_f32 goes in front
+constexpr bool OD_CVT_RNE = true;
+constexpr int OD_GEN = 0, OD_EVEN = 1, OD_UP = 2;           // the epilogue's forms: per-lane tie mode and H4 merge; ties to even everywhere; half up everywhere
+
+// ---- the blur of a wave's four windows in place, two windows (a pair: slots 2 p, 2 p + 1) at a time, the whole wave on each.
+// win0: the wave's OD_KPW windows (+ OD_TAIL readable bytes behind the last); nlive: 1 .. 4 of them are in use (wave-uniform); per window
+// (wave-uniform) w0 .. w3: xs / yq = level column of its byte 0 / level row of its row 21, tw = its tie mode where that is uniform (1: ties to even),
+// gen = it takes the per-lane epilogue — an edge window (H4 merge against Lw x Lh), or one whose outputs straddle Lwvec (ties-to-even
+// columns x < Lwvec, half up beyond).  Trow / Tcol: the lane's rows of c_od.trow / c_od.tcol[0 .. 1]; tprow: the lane's row of c_od.tcol[2] in
+// LDS, that of c_od.tcol[3] 64 entries behind it (five uses per wave: read where they are used, they would cost the kernel its fourth wave per SIMD).
+// Output column c' <-> window column c' + 4, output row ro <-> window row ro + 3; the taps read c' <= 39, ro <= 36.  Tiles:
+//   OWN     c' 16 ct .. +15, ro 16 rt .. +15 (ct, rt < 2) of one window: 4 per window; the column pass's two products take the row pass's row
+//           tiles rt and rt + 1
+//   PROW    c' 16 ct .. +15, ro 32 .. 36 of BOTH windows of a pair: the first product takes the first window's row tile 2 (Mid rows 32 .. 47)
+//           with taps on N < 5 <-> its row 32 + N, the second the second window's with taps on N = 8 .. 12 <-> its row 32 + N - 8
+//           (N = 5 .. 7, 13 .. 15: zero taps, stored to rows 37 .. 39, which nothing reads once the pair's operands are in registers)
+//   PCOL    c' 32 .. 39 of both windows of a pair, ro 16 rt .. +15: the row pass's K block 2 is the first window's bytes 32 .. 47 (as
+//           always) and block 3 the second window's (the first window's operand read fetches them there; the column tiles of one
+//           window have zero taps on block 3); M < 8 <-> the first window's column 32 + M, M >= 8 <-> the second's column 32 + M - 8
+//   CORNER  c' 32 .. 39, ro 32 .. 36 of all four windows: PROW's two products on PCOL's row tile 2 of pair 1 and of pair 0
+// Per four windows 30 row-pass and 50 column-pass MFMAs and 25 epilogues instead of 36, 72 and 36 (three 16 x 16 tiles per axis, the third
+// overlapping the second).  Every output the taps read is written exactly once; per pair, both windows' operands are read before the first store.
+struct OdWin { int xs, yq; uint32_t tw; bool gen; };      // (scalars, not arrays: an array reference indexed by a lane value would live in scratch)
+__device__ __forceinline__ void od_blur_windows(uint8_t* win0, int lane, int nlive, OdWin w0, OdWin w1, OdWin w2, OdWin w3, int Lw, int Lh, int Lwvec, const v4i (&Trow)[3], const v4i (&Tcol)[2], const v4i* tprow) {
+    const int n16 = lane & 15, g4 = lane >> 4;               // the MFMA's view of the lane: row / column lane % 16, K block lane / 16
+    const unsigned a_off = (unsigned)(n16 * OD_PITCH + 16 * g4);                                             // the lane's 16 operand bytes in a row tile
+    const unsigned a_offp = g4 == 3 ? (unsigned)(OD_WIN_BYTES + n16 * OD_PITCH + 32) : a_off;               // (first window of a pair) block 3: the second's bytes 32 ..
+    const unsigned o_own = (unsigned)((n16 + 3) * OD_PITCH + 4 + 4 * g4);                                    // OWN (0, 0)
+    const unsigned o_prow = (unsigned)((n16 >= 8 ? OD_WIN_BYTES : 0) + ((n16 & 7) + 35) * OD_PITCH + 4 + 4 * g4);          // PROW of column tile 0
+    const unsigned o_pcol = (unsigned)((g4 >= 2 ? OD_WIN_BYTES : 0) + (n16 + 3) * OD_PITCH + 36 + 4 * (g4 & 1));          // PCOL of row tile 0
+    const unsigned o_corner = (unsigned)((n16 < 8 ? 2 : 0) * OD_WIN_BYTES + (g4 >= 2 ? OD_WIN_BYTES : 0) + ((n16 & 7) + 35) * OD_PITCH + 36 + 4 * (g4 & 1));
+    const v4i cmid = {blurf_mid_start(), blurf_mid_start(), blurf_mid_start(), blurf_mid_start()};
+    const h2v unbias = {(_Float16)-blurf_lo_bias(), (_Float16)-blurf_lo_bias()};
+    // row pass of one column tile: z[t] = 0x0064HHLL for Mid rows 16 t + 4 g + i, made into the column pass's operand of row tile t: the f16 pairs
+    // LO01, HI01, LO23, HI23 (LO = 0x64LL = 1024 + LL as it stands, HI = 0x64HH - 1024)
+    auto row_pass = [&](const v4i (&A)[3], const v4i& T, v4i (&M)[3]) {
+        v4i z[3];
+#pragma unroll
+        for (int t = 0; t < 3; t++) z[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], T, cmid, 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < 3; t++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t z0 = (uint32_t)z[t][2 * h], z1 = (uint32_t)z[t][2 * h + 1];
+                M[t][2 * h] = (int)__builtin_amdgcn_perm(z1, z0, 0x06040200u);                                // LL0 64 LL1 64
+                M[t][2 * h + 1] = __builtin_bit_cast(int, __builtin_bit_cast(h2v, __builtin_amdgcn_perm(z1, z0, 0x06050201u)) + unbias);      // HH0 64 HH1 64, - 1024 each
+            }
+    };
+    // column pass of one tile (row tiles Ma, Mb against the tap operands Ta, Tb) + rounding + saturation + the aligned store.  The lane's dword is
+    // output columns cb .. cb + 3 of output row ro of the window at column xs_l / row yq_l (GEN only: per-lane tie mode and H4 merge; otherwise the
+    // pair's uniform tie mode, whose half-up form starts the accumulator 0.5 higher and floors).  MODE: OD_GEN, OD_EVEN, OD_UP.
+    auto epilogue = [&](auto MODE, const v4i& Ma, const v4i& Mb, const v4i& Ta, const v4i& Tb, uint8_t* dst, int xs_l, int yq_l, int cb, int ro) {
+        constexpr bool gen = decltype(MODE)::value == OD_GEN, twu = decltype(MODE)::value == OD_EVEN;
+        constexpr float st = (gen || twu) ? blurf_start() : blurf_start() + 0.5f;
+        f4v acc = {st, st, st, st};
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8v, Ma), __builtin_bit_cast(h8v, Ta), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8v, Mb), __builtin_bit_cast(h8v, Tb), acc, 0, 0, 0);
+        float v[4] = {acc[0], acc[1], acc[2], acc[3]};
+        uint32_t keep = 0;
+        if (gen) {
+            const int X0 = xs_l + 4 + cb;                    // level column of the lane's first output byte (a multiple of 4)
+            const bool te = X0 < Lwvec;
+            uint32_t keepc = 0;                              // bytes whose column lies outside the level
+#pragma unroll
+            for (int bb = 0; bb < 4; bb++) keepc |= ((unsigned)(X0 + bb) < (unsigned)Lw ? 0u : 0xFFu) << (8 * bb);
+            keep = (unsigned)(yq_l - 18 + ro) < (unsigned)Lh ? keepc : 0xFFFFFFFFu;
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = te ? __builtin_rintf(v[i]) : __builtin_floorf(v[i] + 0.5f);       // (blurf_round)
+        } else if (!twu) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = __builtin_floorf(v[i]);
+        } else if (!OD_CVT_RNE) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = __builtin_rintf(v[i]);
+        }
+        uint32_t o = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) o = __builtin_amdgcn_cvt_pk_u8_f32(v[i], (uint32_t)i, o);      // rounds (an integer stays), saturates, packs byte i
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+        if (gen) o = (o & ~keep) | (*d & keep);              // out-of-level positions keep the plain reflected pixel (H4)
+        *d = o;
+    };
+    v4i mc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // the corner's operands: row tile 2 of each pair's PCOL row pass (Mid rows 32 .. 47)
+    // (the pair's wave-uniform values come in as scalars: the per-window arrays stay unindexed by the loop counter, i.e. out of scratch)
+    auto blur_pair = [&](auto GEN, int p, int xs0, int yq0, int xs1, int yq1) {
+        uint8_t* W = win0 + 2 * p * OD_WIN_BYTES;
+        v4i A0[3], A1[3];
+        {
+            const unsigned r0 = (unsigned)(uintptr_t)(lptr_t)(W + a_offp), r1 = (unsigned)(uintptr_t)(lptr_t)(W + OD_WIN_BYTES + a_off);
+            asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:768\n\tds_read_b128 %2, %6 offset:1536\n\t"
+                         "ds_read_b128 %3, %7\n\tds_read_b128 %4, %7 offset:768\n\tds_read_b128 %5, %7 offset:1536\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(A0[0]), "=&v"(A0[1]), "=&v"(A0[2]), "=&v"(A1[0]), "=&v"(A1[1]), "=&v"(A1[2]) : "v"(r0), "v"(r1) : "memory");
+        }
+#pragma unroll
+        for (int t = 0; t < 3; t++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) { A0[t][e] = (int)((uint32_t)A0[t][e] ^ 0x80808080u); A1[t][e] = (int)((uint32_t)A1[t][e] ^ 0x80808080u); }
+        const int xs_r = n16 >= 8 ? xs1 : xs0, yq_r = n16 >= 8 ? yq1 : yq0;       // (GEN) PROW lanes' window
+        const int xs_c = g4 >= 2 ? xs1 : xs0, yq_c = g4 >= 2 ? yq1 : yq0;         // (GEN) PCOL lanes' window
+        {
+            v4i MP[3];
+            row_pass(A0, Trow[2], MP);
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++)
+                epilogue(GEN, MP[rt], MP[rt + 1], Tcol[0], Tcol[1], W + o_pcol + 16 * rt * OD_PITCH, xs_c, yq_c, 32 + 4 * (g4 & 1), 16 * rt + n16);
+            if (p == 0) { mc[0] = MP[2]; mc[1] = MP[2]; }    // (pair 1 idle: its corner lanes get pair 0's rows)
+            else mc[1] = MP[2];
+        }
+#pragma unroll
+        for (int ct = 0; ct < 2; ct++) {
+            v4i M0[3], M1[3];                                // (one window after the other: only row tile 2 of the first outlives its own epilogues)
+            row_pass(A0, Trow[ct], M0);
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++)
+                epilogue(GEN, M0[rt], M0[rt + 1], Tcol[0], Tcol[1], W + o_own + (16 * rt * OD_PITCH + 16 * ct), xs0, yq0, 16 * ct + 4 * g4, 16 * rt + n16);
+            row_pass(A1, Trow[ct], M1);
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++)
+                epilogue(GEN, M1[rt], M1[rt + 1], Tcol[0], Tcol[1], W + OD_WIN_BYTES + o_own + (16 * rt * OD_PITCH + 16 * ct), xs1, yq1, 16 * ct + 4 * g4, 16 * rt + n16);
+            epilogue(GEN, M0[2], M1[2], tprow[0], tprow[64], W + o_prow + 16 * ct, xs_r, yq_r, 16 * ct + 4 * g4, 32 + (n16 & 7));
+        }
+    };
+#pragma unroll 1
+    for (int p = 0; p < 2; p++) {
+        if (p > 0 && nlive <= 2) continue;                   // wave-uniform
+        const int xs0 = p ? w2.xs : w0.xs, yq0 = p ? w2.yq : w0.yq, xs1 = p ? w3.xs : w1.xs, yq1 = p ? w3.yq : w1.yq;
+        const uint32_t tw0 = p ? w2.tw : w0.tw, tw1 = p ? w3.tw : w1.tw;
+        if ((p ? w2.gen || w3.gen : w0.gen || w1.gen) || tw0 != tw1) blur_pair(std::integral_constant<int, OD_GEN>{}, p, xs0, yq0, xs1, yq1);
+        else if (tw0) blur_pair(std::integral_constant<int, OD_EVEN>{}, p, xs0, yq0, xs1, yq1);
+        else blur_pair(std::integral_constant<int, OD_UP>{}, p, xs0, yq0, xs1, yq1);
+    }
+    {
+        const bool gen = w0.gen || w1.gen || w2.gen || w3.gen || w0.tw != w1.tw || w0.tw != w2.tw || w0.tw != w3.tw;
+        const int wsc = (n16 < 8 ? 2 : 0) + (g4 >= 2 ? 1 : 0);
+        const int xs_k = wsc == 0 ? w0.xs : wsc == 1 ? w1.xs : wsc == 2 ? w2.xs : w3.xs;
+        const int yq_k = wsc == 0 ? w0.yq : wsc == 1 ? w1.yq : wsc == 2 ? w2.yq : w3.yq;
+        if (gen) epilogue(std::integral_constant<int, OD_GEN>{}, mc[1], mc[0], tprow[0], tprow[64], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7));
+        else if (w0.tw) epilogue(std::integral_constant<int, OD_EVEN>{}, mc[1], mc[0], tprow[0], tprow[64], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7));
+        else epilogue(std::integral_constant<int, OD_UP>{}, mc[1], mc[0], tprow[0], tprow[64], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7));
+    }
+}
 
 template <bool FMA, bool GATHER>
 __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     __shared__ __attribute__((aligned(16))) float s_pat[256 * 4];       // test t: x0, y0, x1, y1 as floats (one ds_read_b128 = the two points as register pairs)
     __shared__ __attribute__((aligned(16))) uint32_t s_mask[256];       // circle byte masks of the 31 x 8 patch dwords (slots 248.. = 0)
     __shared__ __attribute__((aligned(16))) uint8_t s_win[OD_WAVES * OD_KPW * OD_WIN_BYTES + OD_TAIL];
+    __shared__ __attribute__((aligned(16))) v4i s_tprow[2 * 64];        // c_od.tcol[2 .. 3] (with it 40,704 bytes: four workgroups per CU still fit 160 KB)
     const DevGeom& g = b.g;
     int frame, wgi;
     if (!frame_item(b, blockIdx.x, (g.nquads + OD_WAVES - 1) / OD_WAVES, frame, wgi)) return;
@@ -109,6 +269,7 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     const int grp = lane >> 4, li = lane & 15;
     const float4 pat_first = *reinterpret_cast<const float4*>(c_od.pat[tid & 255]);      // requested first: loads return in order, the tables are built while the key points are on their way
     const uint32_t mask_first = c_od.mask[tid & 255];
+    const uint2 tprow_first = reinterpret_cast<const uint2*>(c_od.tcol[2])[tid & 255];
     const int32_t* counts = b.level_count + frame * MAX_LEVELS;
     const int quad = wgi * OD_WAVES + wave_id();
     const bool live = quad < g.nquads;
@@ -146,6 +307,7 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     static_assert(OD_WAVES * 64 == 256, "one table entry per thread");
     reinterpret_cast<float4*>(s_pat)[tid] = pat_first;
     s_mask[tid] = mask_first;
+    reinterpret_cast<uint2*>(s_tprow)[tid] = tprow_first;
     int out_base = 0, total = 0, cnt = 0;
     for (int l = 0; l < g.nlevels; l++) {
         int c = 0;
@@ -226,14 +388,12 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
     // ---- lane constants of the two passes (independent of the keypoint)
-    const int n16 = li, g4 = grp;                            // the MFMA's view of the lane: row / column lane % 16, K block lane / 16
     // [0], [1]: the 16-wide column / row tiles of one window; [2]: the paired tiles of the last 8 columns / 5 rows (blur below)
-    v4i Trow[3], Tcol[3];
+    v4i Trow[3], Tcol[2];
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        Trow[c] = *reinterpret_cast<const v4i*>(c_od.trow[c][lane]);
-        Tcol[c] = *reinterpret_cast<const v4i*>(c_od.tcol[c][lane]);
-    }
+    for (int c = 0; c < 3; c++) Trow[c] = *reinterpret_cast<const v4i*>(c_od.trow[c][lane]);
+#pragma unroll
+    for (int c = 0; c < 2; c++) Tcol[c] = *reinterpret_cast<const v4i*>(c_od.tcol[c][lane]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the windows have landed
     wave_lds_fence();
 
@@ -318,25 +478,7 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
     const float angle = fast_atan2_deg((float)m01, (float)m10);
     wave_lds_fence();                                          // every patch read is done before the windows are overwritten
 
-    // ---- the blur, two windows (a pair: slots 2 p, 2 p + 1) at a time, the whole wave on each
-    // Output column c' <-> window column c' + 4, output row ro <-> window row ro + 3; the taps read c' <= 39, ro <= 36.  Tiles:
-    //   OWN     c' 16 ct .. +15, ro 16 rt .. +15 (ct, rt < 2) of one window: 4 per window
-    //   PROW    c' 16 ct .. +15, ro 32 .. 36 of BOTH windows of a pair: the column pass's A carries the first window's Mid rows 32 .. 47 in
-    //           register 2 (as always) and the second window's in register 3 (whose K slots are empty in every other tile); N < 8 <-> the
-    //           first window's row 32 + N, N >= 8 <-> the second's row 32 + N - 8 (N = 5 .. 7, 13 .. 15: zero taps, stored to rows 37 .. 39,
-    //           which nothing reads once the pair's operands are in registers)
-    //   PCOL    c' 32 .. 39 of both windows of a pair, ro 16 rt .. +15: the row pass's K block 2 is the first window's bytes 32 .. 47 (as
-    //           always) and block 3 the second window's (the first window's operand read fetches them there; the column tiles of one
-    //           window have zero taps on block 3); M < 8 <-> the first window's column 32 + M, M >= 8 <-> the second's column 32 + M - 8
-    //   CORNER  c' 32 .. 39, ro 32 .. 36 of all four windows: PCOL's rows 32 .. 47 of pair 1 in register 2, of pair 0 in register 3
-    // Per four windows 80 MFMAs and 25 epilogues instead of 108 and 36 (three 16 x 16 tiles per axis, the third overlapping the second).
-    // Every output the taps read is written exactly once; per pair, both windows' operands are read before the first store.
-    const unsigned a_off = (unsigned)(n16 * OD_PITCH + 16 * g4);                                             // the lane's 16 operand bytes in a row tile
-    const unsigned a_offp = g4 == 3 ? (unsigned)(OD_WIN_BYTES + n16 * OD_PITCH + 32) : a_off;               // (first window of a pair) block 3: the second's bytes 32 ..
-    const unsigned o_own = (unsigned)((n16 + 3) * OD_PITCH + 4 + 4 * g4);                                    // OWN (0, 0)
-    const unsigned o_prow = (unsigned)((n16 >= 8 ? OD_WIN_BYTES : 0) + ((n16 & 7) + 35) * OD_PITCH + 4 + 4 * g4);          // PROW of column tile 0
-    const unsigned o_pcol = (unsigned)((g4 >= 2 ? OD_WIN_BYTES : 0) + (n16 + 3) * OD_PITCH + 36 + 4 * (g4 & 1));          // PCOL of row tile 0
-    const unsigned o_corner = (unsigned)((n16 < 8 ? 2 : 0) * OD_WIN_BYTES + (g4 >= 2 ? OD_WIN_BYTES : 0) + ((n16 & 7) + 35) * OD_PITCH + 36 + 4 * (g4 & 1));
+    // ---- the blur of the wave's windows (od_blur_windows)
     // per window (wave-uniform): where it lies, and whether its tiles take the per-lane epilogue — an edge window (H4 merge), or one whose
     // outputs straddle blur_wvec (ties-to-even columns x < wvec, half up beyond).  Idle slots copy the tie mode of the slot before them.
     int xsw[OD_KPW], yqw[OD_KPW];
@@ -352,117 +494,8 @@ __device__ __forceinline__ void k_describe_od_body(const Batch& b) {
         tww[q] = liveq ? (lo ? 1u : 0u) : tww[q > 0 ? q - 1 : 0];
         genw[q] = liveq && (((fixmask >> (4 + q)) & 1u) || lo != hi);
     }
-    constexpr uint32_t CADD = 257 * 32896 + 0x7FFF;           // the centring offsets + the rounding constant (+ 1 more where half up)
-    const v4i c128 = {128, 128, 128, 128}, zero = {0, 0, 0, 0};
-    // row pass of one column tile: z[t] = S - 32768 for Mid rows 16 t + 4 g + i, split into the column pass's two int8 operands (registers 0 .. 2;
-    // the caller sets register 3: the other window's register 2, or anything where its taps are zero).
-    auto row_pass = [&](const v4i (&A)[3], const v4i& T, v4i& HI, v4i& LO) {
-        v4i z[3];
-#pragma unroll
-        for (int t = 0; t < 3; t++) z[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], T, c128, 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 3; t++) {
-            const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)z[t][1], (uint32_t)z[t][0], 0x05010400u);      // lo0 lo1 hi0 hi1
-            const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)z[t][3], (uint32_t)z[t][2], 0x05010400u);
-            LO[t] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
-            HI[t] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
-        }
-    };
-    const uint32_t c255 = 255;
-    // column pass of one tile + rounding + saturation + the aligned store.  The lane's dword is output columns cb .. cb + 3 of output row ro
-    // of the window at column xs_l / row yq_l (GEN only: per-lane tie mode and H4 merge; otherwise the pair's uniform tie mode `twu`).
-    auto epilogue = [&](auto GEN, const v4i& HI, const v4i& LO, const v4i& T, uint8_t* dst, int xs_l, int yq_l, int cb, int ro, uint32_t twu) {
-        constexpr bool gen = decltype(GEN)::value;
-        uint32_t tw = twu, keep = 0;
-        if (gen) {
-            const int X0 = xs_l + 4 + cb;                    // level column of the lane's first output byte (a multiple of 4)
-            tw = X0 < L.wvec ? 1u : 0u;
-            uint32_t keepc = 0;                              // bytes whose column lies outside the level
-#pragma unroll
-            for (int bb = 0; bb < 4; bb++) keepc |= ((unsigned)(X0 + bb) < (unsigned)L.w ? 0u : 0xFFu) << (8 * bb);
-            keep = (unsigned)(yq_l - 18 + ro) < (unsigned)L.h ? keepc : 0xFFFFFFFFu;
-        }
-        const uint32_t cadd = CADD + (tw ^ 1u);
-        v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(HI, T, zero, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc[i] = (int)(((uint32_t)acc[i] << 8) + cadd);
-        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(LO, T, acc, 0, 0, 0);
-        uint32_t q[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t t = (uint32_t)acc[i];
-            q[i] = t + ((t >> 16) & tw);                     // + bit 16 on ties-to-even columns (v_and_b32_sdwa + v_add)
-        }
-        // saturate the high halves and pack them: one SDWA min per byte (WORD_1 in, BYTE_i out, the other bytes kept)
-        uint32_t o;
-        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD" : "=v"(o) : "v"(q[0]), "v"(c255));
-        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:DWORD" : "+v"(o) : "v"(q[1]), "v"(c255));
-        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:DWORD" : "+v"(o) : "v"(q[2]), "v"(c255));
-        asm("v_min_u16_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:DWORD" : "+v"(o) : "v"(q[3]), "v"(c255));
-        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
-        if (gen) o = (o & ~keep) | (*d & keep);              // out-of-level positions keep the plain reflected pixel (H4)
-        *d = o;
-    };
-    int hc[2] = {0, 0}, lc[2] = {0, 0};                      // the corner's operands: register 2 of each pair's PCOL row pass (Mid rows 32 .. 47)
-    // (the pair's wave-uniform values come in as scalars: the per-window arrays stay unindexed by the loop counter, i.e. out of scratch)
-    auto blur_pair = [&](auto GEN, int p, int xs0, int yq0, int xs1, int yq1, uint32_t twu) {
-        uint8_t* W = win0 + 2 * p * OD_WIN_BYTES;
-        v4i A0[3], A1[3];
-        {
-            const unsigned r0 = (unsigned)(uintptr_t)(lptr_t)(W + a_offp), r1 = (unsigned)(uintptr_t)(lptr_t)(W + OD_WIN_BYTES + a_off);
-            asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:768\n\tds_read_b128 %2, %6 offset:1536\n\t"
-                         "ds_read_b128 %3, %7\n\tds_read_b128 %4, %7 offset:768\n\tds_read_b128 %5, %7 offset:1536\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&v"(A0[0]), "=&v"(A0[1]), "=&v"(A0[2]), "=&v"(A1[0]), "=&v"(A1[1]), "=&v"(A1[2]) : "v"(r0), "v"(r1) : "memory");
-        }
-#pragma unroll
-        for (int t = 0; t < 3; t++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) { A0[t][e] = (int)((uint32_t)A0[t][e] ^ 0x80808080u); A1[t][e] = (int)((uint32_t)A1[t][e] ^ 0x80808080u); }
-        const int xs_r = n16 >= 8 ? xs1 : xs0, yq_r = n16 >= 8 ? yq1 : yq0;       // (GEN) PROW lanes' window
-        const int xs_c = g4 >= 2 ? xs1 : xs0, yq_c = g4 >= 2 ? yq1 : yq0;         // (GEN) PCOL lanes' window
-        {
-            v4i HP, LP;
-            row_pass(A0, Trow[2], HP, LP);
-            HP[3] = HP[2]; LP[3] = LP[2];                    // (zero taps in PCOL)
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++)
-                epilogue(GEN, HP, LP, Tcol[rt], W + o_pcol + 16 * rt * OD_PITCH, xs_c, yq_c, 32 + 4 * (g4 & 1), 16 * rt + n16, twu);
-            if (p == 0) { hc[0] = HP[2]; lc[0] = LP[2]; hc[1] = HP[2]; lc[1] = LP[2]; }      // (pair 1 idle: its corner lanes get pair 0's rows)
-            else { hc[1] = HP[2]; lc[1] = LP[2]; }
-        }
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++) {
-            v4i H0, L0, H1, L1;
-            row_pass(A0, Trow[ct], H0, L0);
-            row_pass(A1, Trow[ct], H1, L1);
-            H0[3] = H1[2]; L0[3] = L1[2];                    // (PROW's second window; zero taps in OWN)
-            H1[3] = H1[2]; L1[3] = L1[2];
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) {
-                epilogue(GEN, H0, L0, Tcol[rt], W + o_own + (16 * rt * OD_PITCH + 16 * ct), xs0, yq0, 16 * ct + 4 * g4, 16 * rt + n16, twu);
-                epilogue(GEN, H1, L1, Tcol[rt], W + OD_WIN_BYTES + o_own + (16 * rt * OD_PITCH + 16 * ct), xs1, yq1, 16 * ct + 4 * g4, 16 * rt + n16, twu);
-            }
-            epilogue(GEN, H0, L0, Tcol[2], W + o_prow + 16 * ct, xs_r, yq_r, 16 * ct + 4 * g4, 32 + (n16 & 7), twu);
-        }
-    };
-    const int nlive = min(cnt - k0, OD_KPW);                 // (wave-uniform) 1 .. 4
-#pragma unroll 1
-    for (int p = 0; p < 2; p++) {
-        if (p > 0 && nlive <= 2) continue;                   // wave-uniform
-        const int xs0 = p ? xsw[2] : xsw[0], yq0 = p ? yqw[2] : yqw[0], xs1 = p ? xsw[3] : xsw[1], yq1 = p ? yqw[3] : yqw[1];
-        const uint32_t tw0 = p ? tww[2] : tww[0], tw1 = p ? tww[3] : tww[1];
-        if ((p ? genw[2] || genw[3] : genw[0] || genw[1]) || tw0 != tw1) blur_pair(std::true_type{}, p, xs0, yq0, xs1, yq1, tw0);
-        else blur_pair(std::false_type{}, p, xs0, yq0, xs1, yq1, tw0);
-    }
-    {
-        const bool gen = genw[0] || genw[1] || genw[2] || genw[3] || tww[0] != tww[1] || tww[0] != tww[2] || tww[0] != tww[3];
-        const int wsc = (n16 < 8 ? 2 : 0) + (g4 >= 2 ? 1 : 0);
-        const int xs_k = wsc == 0 ? xsw[0] : wsc == 1 ? xsw[1] : wsc == 2 ? xsw[2] : xsw[3];
-        const int yq_k = wsc == 0 ? yqw[0] : wsc == 1 ? yqw[1] : wsc == 2 ? yqw[2] : yqw[3];
-        const v4i HC = {hc[1], hc[1], hc[1], hc[0]}, LC = {lc[1], lc[1], lc[1], lc[0]};      // (registers 0, 1: zero taps)
-        if (gen) epilogue(std::true_type{}, HC, LC, Tcol[2], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7), tww[0]);
-        else epilogue(std::false_type{}, HC, LC, Tcol[2], win0 + o_corner, xs_k, yq_k, 32 + 4 * (g4 & 1), 32 + (n16 & 7), tww[0]);
-    }
+    od_blur_windows(win0, lane, min(cnt - k0, OD_KPW), OdWin{xsw[0], yqw[0], tww[0], genw[0]}, OdWin{xsw[1], yqw[1], tww[1], genw[1]},
+                    OdWin{xsw[2], yqw[2], tww[2], genw[2]}, OdWin{xsw[3], yqw[3], tww[3], genw[3]}, L.w, L.h, L.wvec, Trow, Tcol, s_tprow + lane);
     wave_lds_fence();
 
     // ---- rotated BRIEF on the blurred window (:154-194)
@@ -558,6 +591,36 @@ int launch_describe_od(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const dim3 grid(frame_item_blocks(b, (g.nquads + OD_WAVES - 1) / OD_WAVES)), block(OD_WAVES * 64);
     if (g.fp_contract) hipLaunchKernelGGL(b.img_tab ? k_describe_od_gather<true> : k_describe_od<true>, grid, block, 0, stream, b);
     else hipLaunchKernelGGL(b.img_tab ? k_describe_od_gather<false> : k_describe_od<false>, grid, block, 0, stream, b);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+// orbx_debug_eval_blur_window: od_blur_windows on caller-supplied windows, four per wave as in the kernel.  The windows lie at level column 0 /
+// row 18 of a level far larger than they are: nothing is outside it, and the general (per-lane) epilogue sees the one tie mode everywhere.
+__global__ __launch_bounds__(64) void k_eval_blur_window(const uint32_t* win, uint8_t* out, int n, int ties_even, int general) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_w[(OD_KPW * OD_WIN_BYTES + OD_TAIL) / 4];
+    const int lane = threadIdx.x, q0 = blockIdx.x * OD_KPW, nlive = min(n - q0, OD_KPW);
+    for (int i = lane; i < (OD_KPW * OD_WIN_BYTES + OD_TAIL) / 4; i += 64)
+        s_w[i] = i < nlive * (OD_WIN_BYTES / 4) ? win[(size_t)q0 * (OD_WIN_BYTES / 4) + i] : 0u;
+    __shared__ __attribute__((aligned(16))) v4i s_tprow[2 * 64];
+    v4i Trow[3], Tcol[2];
+#pragma unroll
+    for (int c = 0; c < 3; c++) Trow[c] = *reinterpret_cast<const v4i*>(c_od.trow[c][lane]);
+#pragma unroll
+    for (int c = 0; c < 2; c++) { Tcol[c] = *reinterpret_cast<const v4i*>(c_od.tcol[c][lane]); s_tprow[64 * c + lane] = *reinterpret_cast<const v4i*>(c_od.tcol[2 + c][lane]); }
+    wave_lds_fence();
+    const int big = 1 << 20;
+    const OdWin w = {0, 18, ties_even ? 1u : 0u, general != 0};
+    uint8_t* W = reinterpret_cast<uint8_t*>(s_w);
+    od_blur_windows(W, lane, nlive, w, w, w, w, big, big, ties_even ? big : 0, Trow, Tcol, s_tprow + lane);
+    wave_lds_fence();
+    for (int i = lane; i < nlive * (37 * 40); i += 64) {
+        const int q = i / (37 * 40), r = (i - q * (37 * 40)) / 40, c = i % 40;
+        out[(size_t)q0 * (37 * 40) + i] = W[q * OD_WIN_BYTES + (r + 3) * OD_PITCH + c + 4];
+    }
+}
+int launch_eval_blur_window(const uint8_t* win, uint8_t* out, int n, int ties_even, int general) {
+    static_assert(OD_WIN_BYTES % 4 == 0 && OD_TAIL % 4 == 0, "the windows are copied by dwords");
+    hipLaunchKernelGGL(k_eval_blur_window, dim3((n + OD_KPW - 1) / OD_KPW), dim3(64), 0, 0, reinterpret_cast<const uint32_t*>(win), out, n, ties_even, general);
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 

@@ -195,6 +195,47 @@ ORBX_HD int blur_round(int sum, int ties_even) {
     return q > 255 ? 255 : q;
 }
 
+// ---- the blur's column pass as a float matrix product (k_describe_od.hip: v_mfma_f32_16x16x32_f16) -----------------
+// The row pass leaves Mid = S_row = sum of tap * pixel, 0 .. 65535 (the taps sum to 257).  The column sum S = sum of tap * Mid has up to 25 bits
+// and the int8 matrix product cannot carry the x 256 between Mid's two bytes; a float product can.  Per Mid element two f16 operands:
+//   HI = Mid >> 8                 0 .. 255, exact in f16; it meets the tap scaled by 2^-8
+//   LO = 1024 + (Mid & 255)       exact in f16 too, and its bit pattern is 0x6400 | (Mid & 255): a byte move, no conversion; tap scaled by 2^-16
+// The 1024 of every LO slot is taken off again by the accumulator's start value, -1024 * 257 / 65536 (each output meets every tap once).
+// Every product is an integer multiple of 2^-16 and every partial sum, in ANY order of the slots, lies in [start, S / 65536]: below 256 such
+// a number has at most 24 significant bits, so float accumulation is exact and the result IS S / 65536 whenever that is below 256.  From
+// 256 on (S up to 257 * 65535: 256.996) a sum may round to a multiple of 2^-15, and stays >= 255.5 because 255.5 is one: the output
+// saturates either way.  blur_round's two modes are then round-to-nearest-even of that float, or floor(v + 0.5) (v + 0.5 is exact below 256),
+// saturated.  tests/test_blur_f16_host.py runs structured, random and constructed-tie columns in random slot orders.
+ORBX_HD constexpr int blur_tap(int t) { return t == 0 || t == 6 ? ORBX_G0 : t == 1 || t == 5 ? ORBX_G1 : t == 2 || t == 4 ? ORBX_G2 : t == 3 ? ORBX_G3 : 0; }
+ORBX_HD constexpr int blur_tap_sum() { return blur_tap(0) + blur_tap(1) + blur_tap(2) + blur_tap(3) + blur_tap(4) + blur_tap(5) + blur_tap(6); }
+ORBX_HD constexpr int blurf_lo_bias() { return 1024; }                                   // f16 1024.0 = 0x6400, ulp 1 up to 2047
+ORBX_HD constexpr int blurf_hi(int mid) { return mid >> 8; }
+ORBX_HD constexpr int blurf_lo(int mid) { return blurf_lo_bias() + (mid & 255); }
+ORBX_HD constexpr float blurf_tap_hi(int t) { return (float)blur_tap(t) / 256.f; }
+ORBX_HD constexpr float blurf_tap_lo(int t) { return (float)blur_tap(t) / 65536.f; }
+ORBX_HD constexpr float blurf_start() { return -(float)(blurf_lo_bias() * blur_tap_sum()) / 65536.f; }
+// the row pass's accumulator start that makes its int32 result 0x0064HHLL: pixels go in centred (p - 128), and byte 2 is the high byte of
+// every f16 operand whose low byte is LL or HH (0x64HH = 1024 + HI: the kernel takes the 1024 off again with one packed f16 add)
+ORBX_HD constexpr int blurf_mid_start() { return 128 * blur_tap_sum() + (0x64 << 16); }
+// bit pattern of the f16 value v * 2^-shift for an integer 0 <= v < 2048 whose scaled value is a normal f16 number (0 for v = 0)
+ORBX_HD constexpr uint32_t f16_bits_scaled(int v, int shift) {
+    if (v <= 0) return 0u;
+    int p = 0;
+    while ((v >> p) > 1) p++;
+    return (uint32_t)(p - shift + 15) << 10 | (((uint32_t)v << (10 - p)) & 0x3FFu);
+}
+// one output: mid[t] = the seven Mid values under the taps; the float the matrix product leaves (HI slots first here; any order gives the same)
+ORBX_HD float blurf_column(const int mid[7]) {
+    float acc = blurf_start();
+    for (int t = 0; t < 7; t++) acc = acc + (float)blurf_hi(mid[t]) * blurf_tap_hi(t);
+    for (int t = 0; t < 7; t++) acc = acc + (float)blurf_lo(mid[t]) * blurf_tap_lo(t);
+    return acc;
+}
+ORBX_HD int blurf_round(float v, int ties_even) {
+    const float r = ties_even ? rintf(v) : floorf(v + 0.5f);
+    return r > 255.f ? 255 : r < 0.f ? 0 : (int)r;
+}
+
 // ---- 256-bit Hamming distance (host form; kernels use v_bcnt directly) -------------------------
 ORBX_HD int hamming256_words(const uint32_t* a, const uint32_t* b) {
     int dist = 0;

@@ -10,6 +10,7 @@
 namespace orbx {
 int launch_eval_math(int kind, const float* in0, const float* in1, float* out0, float* out1, int n);
 int launch_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t);
+int launch_eval_blur_window(const uint8_t* win, uint8_t* out, int n, int ties_even, int general);
 void stage_timer_collect(StageTimer& t);
 int launch_debug_nth(const float* d_resp, int n, int nth, int* d_out);
 int launch_ingest(uint8_t* d_dst, const uint8_t* mapped_src, size_t bytes, hipStream_t stream);
@@ -860,6 +861,20 @@ int orbx_debug_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t
     const int rc = launch_eval_compass(s[ic], s[ie], s[iw], s[in_], s[is], s[o], n, t);
     if (rc != ORBX_OK) return rc;
     HIPTRY(s.get(out, o, n));
+    return ORBX_OK;
+}
+
+int orbx_debug_eval_blur_window(const uint8_t* windows, uint8_t* out, int n, int rounding, int general, int device) {
+    if (n <= 0) return ORBX_OK;
+    if (!windows || !out || (rounding != ORBX_BLUR_X86_SSE2 && rounding != ORBX_BLUR_HALF_UP)) return ORBX_ERR_ARG;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto iw = s.in(windows, (size_t)n * 43 * 48);
+    const auto o = s.out<uint8_t>((size_t)n * 37 * 40);
+    HIPTRY(s.alloc());
+    const int rc = launch_eval_blur_window(s[iw], s[o], n, rounding == ORBX_BLUR_X86_SSE2, general);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(out, o, (size_t)n * 37 * 40));
     return ORBX_OK;
 }
 
