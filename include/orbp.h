@@ -24,6 +24,14 @@
  *   orbp_fuse[_batch_device]     <- the search of int ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>&, float th)   src/ORBmatcher.cc:1016-1134
  *                                   for every call LocalMapping::SearchInNeighbors makes (src/LocalMapping.cc:373-450; ORBP_MODE_FUSE);
  *                                   Replace / AddObservation / AddMapPoint stay with the caller
+ *                                   and, through views made by orbp_view_from_sim3, the search of
+ *                                   int ORBmatcher::Fuse(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, float th)   src/ORBmatcher.cc:1136-1265
+ *                                   for every call of LoopClosing::SearchAndFuse (src/LoopClosing.cc:557-570)
+ *   orbp_view_from_sim3          <- the decomposition of Scw                                      src/ORBmatcher.cc:298-302 (= :1145-1149)
+ *   orbp_loop_project_batch_device, orbp_loop_search[_batch_device]
+ *                                <- int ORBmatcher::SearchByProjection(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, vector<MapPoint*>& vpMatched, int th)
+ *                                   src/ORBmatcher.cc:286-407 (LoopClosing::ComputeSim3, src/LoopClosing.cc:370; ORBP_MODE_LOOP)
+ *                                   (projection + orbs_window_search_batch_device with ORBS_RULE_BEST, TH_LOW, no rotation check)
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -67,6 +75,21 @@
  *   the lowest index); no cell window or no feature kept -> ORBP_FUSE_EMPTY;
  *   best distance <= orb_dist -> ORBP_FUSE_FUSED with that feature, else ORBP_FUSE_FAR and no feature.
  * Nothing is claimed and there is no ratio, second distance or rotation check: every entry is on its own.
+ * The Scw overload of Fuse (src/ORBmatcher.cc:1160-1245) is this text word for word over the view of orbp_view_from_sim3 (its `1.0/z`, a float
+ * division too, rounds as 1.0f / PcZ does), so LoopClosing::SearchAndFuse is orbp_fuse as it stands: one ORBP_MODE_FUSE view per corrected key
+ * frame, every list the loop map points, all views in one launch.
+ *
+ * Arithmetic of orbp_view_from_sim3 (src/ORBmatcher.cc:298-302 = :1145-1149), Scw = [sR | st] being rows 0..2 of the 4 x 4 matrix:
+ *   scw = (float)sqrt(sum of (double)sR[0][k]*(double)sR[0][k]), a double sum from 0.0 in index order (`sRcw.row(0).dot(sRcw.row(0))`);
+ *   Rcw[i] = (float)((double)sR[i] / (double)scw), tcw[i] = (float)((double)st[i] / (double)scw) (`Mat / double`);
+ *   Ow[c] = ((0.0f + (-Rcw[0][c])*tcw[0]) + (-Rcw[1][c])*tcw[1]) + (-Rcw[2][c])*tcw[2] in float (`-Rcw.t()*tcw`: the product of the negated transpose).
+ *
+ * Arithmetic of ORBP_MODE_LOOP (src/ORBmatcher.cc:311-363), per list entry: the steps of ORBP_MODE_FUSE above, word for word, up to and including
+ * radius = th * factors[level], with the same statuses for the five rejections (the reference's `int th` enters as the float view.th).  An entry
+ * that passes them all has the status ORBP_LOOP_QUERY and becomes a query: window (u, v, radius), levels [level - 1, level], the table's
+ * descriptor, no angle.  The queries of a view are searched IN LIST ORDER by orbs_window_search_batch_device with ORBS_RULE_BEST, th = orb_dist
+ * (TH_LOW in the reference, accepted when <=), no rotation check and d_claimed = `vpMatched[idx] != NULL` on entry: a match takes its feature,
+ * and later entries pass that feature over (:378, :398-402).
  *
  * ONE DELIBERATE DEVIATION.  Where the reference leaves u or v NaN (PcZ == 0 together with PcX == 0 or PcY == 0: a point at
  * the camera centre) all its comparisons fail, the point passes with a NaN window and GetFeaturesInArea converts NaN to
@@ -98,8 +121,10 @@ extern "C" {
 #define ORBP_MODE_FRAME 0             /* Frame::isInFrustum */
 #define ORBP_MODE_LAST_FRAME 1        /* orbp_*_source*: the list is the last frame's features (motion-model tracking) */
 #define ORBP_MODE_KEYFRAME 2          /* orbp_*_source*: the list is a key frame's features (relocalisation) */
-#define ORBP_MODE_FUSE 3              /* orbp_fuse*: map points into key frames (LocalMapping's Fuse).  To orbp_project* / orbp_track* it is an unknown
-                                         mode; the loop-closing projections (the Scw overload of Fuse, SearchBySim3) have no mode */
+#define ORBP_MODE_FUSE 3              /* orbp_fuse*: map points into key frames (LocalMapping's Fuse, and the Scw overload of LoopClosing's through
+                                         orbp_view_from_sim3).  To orbp_project* / orbp_track* it is an unknown mode */
+#define ORBP_MODE_LOOP 4              /* orbp_loop_*: the loop map points into one key frame through a similarity (LoopClosing's SearchByProjection).  To
+                                         every other entry point it is an unknown mode; SearchBySim3 has no mode */
 
 typedef struct orbp_map orbp_map;
 
@@ -126,7 +151,7 @@ typedef struct orbp_record {
 } orbp_record;
 
 /* ORBX_ERR_ARG for capacity outside [1, ORBP_MAX_CAPACITY] or a NULL `out`; ORBX_ERR_DEVICE without a usable GPU.
- * Device memory: 65 bytes per slot; the scratch of orbp_track* and the blocks of orbp_refresh and orbp_fuse are allocated on first use and kept. */
+ * Device memory: 65 bytes per slot; the scratch of orbp_track* and orbp_loop_* and the blocks of orbp_refresh and orbp_fuse are allocated on first use and kept. */
 int orbp_create(int capacity, int device, orbp_map** out);
 void orbp_destroy(orbp_map* map);
 int orbp_capacity(const orbp_map* map);
@@ -375,6 +400,61 @@ int orbp_fuse(orbp_map* map, const orbp_view* views, int nviews, const float* fa
               int lcap, const uint8_t* skip, const orbf_bounds* b, int orb_dist, const orbx_keypoint* kps_un, const uint8_t* desc,
               const int32_t* cell_off, const int32_t* cell_feat, const int32_t* nt, int nframes, int cap, int frames_on_device,
               const int32_t* frame, int32_t* best_idx, int32_t* best_dist, orbp_fused* rec, void* stream);
+
+/* ---- Loop closing.  orbp_view_from_sim3 fills Rcw, tcw and Ow of *view from rows 0..2 of the 4 x 4 float Scw (row major, [sR | st]) by the
+ * arithmetic at the top of this file and leaves every other field alone.  ORBX_ERR_ARG for a NULL pointer or an scw that is zero or not
+ * finite (the view is then untouched).  Host only: needs no GPU. */
+int orbp_view_from_sim3(const float Scw[12], orbp_view* view);
+
+/* The status of a list entry that passed every test of ORBP_MODE_LOOP, whether or not qcap left room for it as a query; the rejections are
+ * ORBP_FUSE_SKIPPED, _DEPTH, _IMAGE, _DISTANCE and _ANGLE, and the record's u, v and level are filled as for those. */
+#define ORBP_LOOP_QUERY 8
+
+/* The projection of ORBP_MODE_LOOP for nviews views, flat over (view, 256-entry tile) in two launches: every entry is tested on its own, then
+ * the entries that passed are compacted in list order behind the counts of the tiles in front of them.  All arrays are device buffers except
+ * `factors`.  View p walks the slots d_list[p*lcap + i], i < d_nlist[p] (clamped to [0, lcap]); d_skip (may be NULL) passes an entry over
+ * (isBad() || spAlreadyFound.count(pMP)), as does a slot that is out of range or free.
+ *   d_rec (may be NULL): the record of every entry i < d_nlist[p] at p*lcap + i (entries behind the list are not written).
+ *   d_qxyr[3*qcap], d_qlev[2*qcap], d_qdesc[32*qcap] (16-byte aligned), d_qpos[qcap] per view: the queries in list order, in the layout
+ *       orbs_window_search_batch_device reads, and the list position of each.
+ *   d_nq[p]: always the true count of entries that passed; when it exceeds qcap only the first qcap queries are written and d_overflow[p] = 1
+ *       (else 0).  A view whose mode is not ORBP_MODE_LOOP sees nothing: d_nq[p] = 0, d_overflow[p] = ORBX_ERR_ARG, its records ORBP_FUSE_SKIPPED.
+ * ORBX_ERR_ARG before anything touches the GPU for nviews outside [0, ORBP_MAX_VIEWS], lcap < 1, qcap < 1, nviews * lcap >= 2^31, nlevels
+ * outside [1, ORBS_MAX_LEVELS], a NULL required array, d_qdesc not 16-byte aligned, another array not 4-byte aligned.  Asynchronous on
+ * `stream` (NULL: the map's own) inside the handle's event chain.  The per-tile counts (and the records, without d_rec) live in the handle's
+ * scratch, which grows on the first call of a size (synchronously, after a wait for the chain) and is kept. */
+int orbp_loop_project_batch_device(orbp_map* map, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                                   const int32_t* d_nlist, int lcap, const uint8_t* d_skip, orbp_fused* d_rec, float* d_qxyr, int32_t* d_qlev,
+                                   uint8_t* d_qdesc, int32_t* d_qpos, int32_t* d_nq, int32_t* d_overflow, int qcap, void* stream);
+
+/* Projection, then on the same stream the window search (ORBS_RULE_BEST, th = orb_dist, no rotation check) and the result by feature.  View p
+ * searches key frame d_frame[p] (d_frame == NULL: key frame p) of the nframes key frames in the batch layout of orbp_fuse_batch_device;
+ * d_claimed (may be NULL) is per VIEW: d_claimed[p*cap + idx] != 0 when vpMatched[idx] is set on entry.  Outputs: d_t2pos[p*cap + idx] the list
+ * position of the entry matched to feature idx in this call (-1 none, also for a feature claimed on entry or at or behind the key frame's
+ * count; vpMatched[idx] = vpPoints[that]), d_t2slot (may be NULL) its map slot, d_nmatches[p] the reference's return value, d_nq / d_overflow
+ * / d_rec (may be NULL) as above (a view with d_overflow[p] == 1 was searched with its first qcap queries only).  A view whose mode is not
+ * ORBP_MODE_LOOP or whose key frame is outside [0, nframes) sees nothing: d_nq[p] = 0, d_overflow[p] = ORBX_ERR_ARG, no match.
+ * With d_frame (or more views than key frames) the rows are gathered per view into the handle's scratch first: a caller with one view passes
+ * the row's own addresses and nframes = 1 instead.
+ * ORBX_ERR_ARG as above and for cap outside [1, ORBF_MAX_FEATURES], qcap > ORBF_MAX_FEATURES, nframes < 1, nframes * cap >= 2^31, orb_dist outside [0, 256], d_desc not 16-byte aligned; ORBX_ERR_CAPACITY when the search does not fit the LDS
+ * (orbs_lds_bytes(cap, qcap)).  Scratch as above. */
+int orbp_loop_search_batch_device(orbp_map* map, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                                  const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const orbf_bounds* b, int orb_dist,
+                                  const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat,
+                                  const int32_t* d_nt, int nframes, int cap, const int32_t* d_frame, const uint8_t* d_claimed, int qcap,
+                                  orbp_fused* d_rec, int32_t* d_t2pos, int32_t* d_t2slot, int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow,
+                                  void* stream);
+
+/* One view, synchronous: the latency form, one pinned block up and one down.  view, factors, list / skip (nlist entries), rec[nlist] (may be
+ * NULL), t2pos[nt], t2slot[nt] (may be NULL), *nmatches and *nvisible (may be NULL) are HOST memory.  The key frame (kps_un[nt], desc[32*nt],
+ * cell_off[ORBF_GRID_CELLS+1], cell_feat[nt]) is host memory, or device memory when frame_on_device != 0 (a row of a resident store: desc
+ * 16-byte aligned); claimed[nt] (may be NULL) is host memory either way: it is this call's vpMatched.  ORBX_ERR_ARG for a view whose mode is
+ * not ORBP_MODE_LOOP; ORBX_ERR_CAPACITY when more than qcap entries pass (*nvisible then holds the count; nothing else is written).
+ * stream NULL: the map's own stream. */
+int orbp_loop_search(orbp_map* map, const orbp_view* view, const float* factors, int nlevels, const int32_t* list, int nlist, const uint8_t* skip,
+                     const orbf_bounds* b, int orb_dist, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
+                     const int32_t* cell_feat, const uint8_t* claimed, int nt, int frame_on_device, int qcap, orbp_fused* rec, int32_t* t2pos,
+                     int32_t* t2slot, int* nmatches, int* nvisible, void* stream);
 
 #ifdef __cplusplus
 }

@@ -57,14 +57,15 @@ EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_b
 EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
              "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
              "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh", "orbp_fuse_batch_device",
-             "orbp_fuse"]
+             "orbp_fuse", "orbp_view_from_sim3", "orbp_loop_project_batch_device", "orbp_loop_search_batch_device", "orbp_loop_search"]
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
 # orbp_view.mode
-MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE = 0, 1, 2, 3
+MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP = 0, 1, 2, 3, 4
 # orbp_fused.status
 (FUSE_FUSED, FUSE_SKIPPED, FUSE_DEPTH, FUSE_IMAGE, FUSE_DISTANCE, FUSE_ANGLE, FUSE_EMPTY, FUSE_FAR) = range(8)
+LOOP_QUERY = 8              # orbp_loop_*: the entry passed every test and is a query
 # orbp_refresh*: `what` bits and orbp_refreshed.status
 REFRESH_NORMAL_DEPTH, REFRESH_DESCRIPTOR = 1, 2
 (REFRESH_OK, REFRESH_SKIPPED, REFRESH_EMPTY, REFRESH_BAD_INDEX, REFRESH_BAD_OCTAVE, REFRESH_NONFINITE) = range(6)
@@ -129,6 +130,22 @@ class View(ctypes.Structure):
         v.min_x, v.max_x, v.min_y, v.max_y = int(min_x), int(max_x), int(min_y), int(max_y)
         v.view_cos_limit, v.th, v.mode, v.reserved = float(view_cos_limit), float(th), 0, 0
         return v
+
+
+def view_from_sim3(Scw, view):
+    """orbp_view_from_sim3: Rcw, tcw and Ow of `view` (a View, or a VIEW_DTYPE array of one record) from the similarity Scw (4 x 4 or its rows
+    0..2, float32); every other field stays.  Host arithmetic: needs no GPU.  Raises OrbxError(ORBX_ERR_ARG) for a zero or non-finite scale."""
+    S = np.ascontiguousarray(np.asarray(Scw, dtype=np.float32).reshape(-1)[:12])
+    assert S.size == 12
+    if isinstance(view, np.ndarray):
+        assert view.dtype == VIEW_DTYPE and view.size == 1 and view.flags.c_contiguous
+        ptr = view.ctypes.data
+    else:
+        ptr = ctypes.addressof(view)
+    rc = lib().orbp_view_from_sim3(S.ctypes.data, ptr)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbp_view_from_sim3")
+    return view
 
 
 class TriCamera(ctypes.Structure):
@@ -295,6 +312,10 @@ def lib():
         L.orbp_refresh.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, vp]
         L.orbp_fuse_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.orbp_fuse.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]
+        L.orbp_view_from_sim3.argtypes = [vp, vp]
+        L.orbp_loop_project_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.orbp_loop_search_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.orbp_loop_search.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
         L.orbp_project_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_track_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
                                                      vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
@@ -1381,3 +1402,66 @@ class MapPointTable:
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_track_source (nvisible=%d)" % nv.value)
         return dict(t2pos=t2pos[:nt], t2slot=t2slot[:nt], nmatches=nm.value, nvisible=nv.value)
+
+    def loop_project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
+                                  d_overflow, qcap, stream=0):
+        """the queries of loop closing's SearchByProjection(pKF, Scw, ...) (view.mode = MODE_LOOP), compacted in list order: device pointers
+        as ints (0 = NULL: d_skip, d_rec); d_rec is FUSED_DTYPE"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_loop_project_batch_device(self.h, d_views or None, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap,
+                                                  d_skip or None, d_rec or None, d_qxyr or None, d_qlev or None, d_qdesc or None, d_qpos or None,
+                                                  d_nq or None, d_overflow or None, qcap, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_loop_project_batch_device")
+
+    def loop_search_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, bounds, orb_dist, d_kps_un, d_desc, d_cell_off,
+                                 d_cell_feat, d_nt, nframes, cap, d_frame, d_claimed, qcap, d_rec, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow,
+                                 stream=0):
+        """projection, in-order window search (RULE_BEST, orb_dist, no rotation check) and the result by feature; the key frames in the batch
+        layout, view p searching row d_frame[p] (0: row p); d_claimed per view"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_loop_search_batch_device(self.h, d_views or None, nviews, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap,
+                                                 d_skip or None, ctypes.addressof(bounds), orb_dist, d_kps_un or None, d_desc or None, d_cell_off or None,
+                                                 d_cell_feat or None, d_nt or None, nframes, cap, d_frame or None, d_claimed or None, qcap, d_rec or None,
+                                                 d_t2pos or None, d_t2slot or None, d_nmatches or None, d_nq or None, d_overflow or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_loop_search_batch_device")
+
+    def loop_search(self, view, factors, list, skip, bounds, orb_dist, kps_un, desc, cell_off, cell_feat, claimed=None, nt=None, qcap=None,
+                    want_records=True):
+        """One view (the latency form): -> dict(t2pos, t2slot, nmatches, nvisible, rec).  view: a View or one VIEW_DTYPE record; list / skip /
+        claimed: host arrays.  The key frame (kps_un, desc, cell_off, cell_feat) is host arrays, or device pointers as ints (nt must then be
+        given).  Raises OrbxError(ORBX_ERR_CAPACITY) when more than qcap entries pass (e.nvisible holds the count)."""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        list = np.ascontiguousarray(list, dtype=np.int32)
+        nlist = len(list)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            assert len(skip) == nlist
+        frame_dev = isinstance(kps_un, int)
+        if not frame_dev:
+            kps_un = np.ascontiguousarray(kps_un)
+            nt = len(kps_un)
+            desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(nt, 32)
+            cell_off = np.ascontiguousarray(cell_off, dtype=np.int32)
+            cell_feat = np.ascontiguousarray(cell_feat, dtype=np.int32)
+            assert kps_un.dtype.itemsize == 28 and len(cell_off) == GRID_CELLS + 1
+        if claimed is not None:
+            claimed = np.ascontiguousarray(claimed, dtype=np.uint8)
+            assert len(claimed) == nt
+        if isinstance(view, np.ndarray):
+            view = np.ascontiguousarray(view, dtype=VIEW_DTYPE).reshape(-1)[:1]
+        qcap = qcap or max(1, min(nlist, 8192))
+        rec = np.zeros(max(nlist, 1), FUSED_DTYPE) if want_records else None
+        t2pos = np.full(max(nt, 1), -1, np.int32)
+        t2slot = np.full(max(nt, 1), -1, np.int32)
+        nm, nv = ctypes.c_int(), ctypes.c_int()
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        rc = lib().orbp_loop_search(self.h, ptr(view) if isinstance(view, np.ndarray) else ctypes.addressof(view), f.ctypes.data, len(f), ptr(list), nlist,
+                                    ptr(skip), ctypes.addressof(bounds), orb_dist, ptr(kps_un), ptr(desc), ptr(cell_off), ptr(cell_feat), ptr(claimed), nt,
+                                    1 if frame_dev else 0, qcap, ptr(rec), ptr(t2pos), ptr(t2slot), ctypes.byref(nm), ctypes.byref(nv), None)
+        if rc != ORBX_OK:
+            e = OrbxError(rc, "orbp_loop_search (nvisible=%d)" % nv.value)
+            e.nvisible = nv.value
+            raise e
+        return dict(t2pos=t2pos[:nt], t2slot=t2slot[:nt], nmatches=nm.value, nvisible=nv.value, rec=rec[:nlist] if rec is not None else None)

@@ -12,12 +12,18 @@
 // Fuse / FuseInNeighbors (LocalMapPointsFuse.cc) replace ORBmatcher::Fuse(pKF, vpMapPoints, th) as LocalMapping::SearchInNeighbors calls it: the
 // search of every target key frame is one orbp_fuse over the same resident key frames, whose rows then carry their grid too; Replace /
 // AddObservation / AddMapPoint stay the reference's in-order loop on the host.
+// SearchByProjection(pKF, Scw, ...) / SearchAndFuse (LocalMapPointsLoop.cc) replace the two searches LoopClosing makes once a Sim3 is accepted:
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) as one orbp_loop_search against pKF's resident row, and the loop of
+// LoopClosing::SearchAndFuse as one orbp_fuse over every corrected key frame, followed by the reference's in-order loop on the host.  Both read
+// the points' positions from the mirror: a caller who moved points (CorrectLoop does, before it fuses) must Put them first, or construct
+// with refresh_every_call.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
 #include <cstdint>
 #include <set>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "orbp.h"
@@ -82,6 +88,20 @@ public:
     // receives the return value of each of the vpTargetKFs.size() + 1 Fuse calls this replaces.
     void FuseInNeighbors(KeyFrame* pCurrent, const std::vector<KeyFrame*>& vpTargetKFs, float th = 2.5, std::vector<int>* nFused = 0);
 
+    // int ORBmatcher::SearchByProjection(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, vector<MapPoint*>& vpMatched, int th)
+    // (src/ORBmatcher.cc:286-407, called at src/LoopClosing.cc:370) with the reference's signature and effects (LocalMapPointsLoop.cc; links only
+    // when that file, LocalMapPointsFuse.cc and LocalMapPointsRefresh.cc are built in).  Points that are bad or already in vpMatched are passed
+    // over, features with vpMatched[idx] != NULL are never matched, vpMatched[idx] receives the matched points; returns the reference's return
+    // value.  pKF's features and grid come from the resident key-frame store.  At most ORBF_MAX_FEATURES listed points may pass the tests.
+    int SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th);
+    // The loop of LoopClosing::SearchAndFuse (src/LoopClosing.cc:557-570): ORBmatcher::Fuse(pKF, Scw, vpLoopMapPoints, th) for every corrected key
+    // frame.  vCorrectedScw: CorrectedPosesMap in its iteration order, with Converter::toCvMat applied.  One orbp_fuse searches every key frame
+    // (nothing in Fuse claims a feature, so an entry's search does not depend on what earlier entries or key frames did); then lines :1152-1261 run
+    // per key frame, in order: spAlreadyFound = pKF->GetMapPoints() as the key frame's turn begins, isBad() as of each iteration, and
+    // pMPinKF->Replace(pMP), or AddObservation + AddMapPoint, as the reference does.  nFused (may be NULL) receives each call's return value.
+    void SearchAndFuse(const std::vector<std::pair<KeyFrame*, cv::Mat> >& vCorrectedScw, const std::vector<MapPoint*>& vpLoopMapPoints, float th = 4,
+                       std::vector<int>* nFused = 0);
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
@@ -111,8 +131,9 @@ private:
     void growKeyFrames(int rows, int feats);
     void residentForFuse(const std::vector<KeyFrame*>& kfs);
     // best_idx of orbp_fuse for views[p] = (targets[p], *lists[p]) -> best[p][i]
+    // vScw (may be NULL): the views are the decompositions of these similarities (SearchAndFuse)
     void searchFuse(const std::vector<KeyFrame*>& targets, const std::vector<const std::vector<MapPoint*>*>& lists, float th,
-                    std::vector<std::vector<int32_t> >& best);
+                    std::vector<std::vector<int32_t> >& best, const std::vector<cv::Mat>* vScw = 0);
     std::unordered_map<KeyFrame*, int> kf_row_;
     std::vector<KeyFrame*> kf_owner_;            // per row; NULL = free
     std::vector<int32_t> kf_free_;

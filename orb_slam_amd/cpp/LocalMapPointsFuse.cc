@@ -90,8 +90,11 @@ void LocalMapPoints::residentForFuse(const std::vector<KeyFrame*>& kfs) {
     }
 }
 
+// vScw (loop closing, LocalMapPointsLoop.cc): view p is the decomposition of (*vScw)[p] instead of the key frame's own pose, and a point that is
+// in the key frame is searched like any other: that overload passes over the members of pKF->GetMapPoints(), which its caller reads when the
+// key frame's turn comes
 void LocalMapPoints::searchFuse(const std::vector<KeyFrame*>& targets, const std::vector<const std::vector<MapPoint*>*>& lists, float th,
-                                std::vector<std::vector<int32_t> >& best) {
+                                std::vector<std::vector<int32_t> >& best, const std::vector<cv::Mat>* vScw) {
     const int nviews = (int)targets.size();
     best.assign(nviews, std::vector<int32_t>());
     if (nviews == 0) return;
@@ -105,7 +108,7 @@ void LocalMapPoints::searchFuse(const std::vector<KeyFrame*>& targets, const std
         for (size_t i = 0; i < v.size(); i++) {
             MapPoint* pMP = v[i];
             // what the loop would pass over already is not searched: both conditions can only turn ON later, and the loop asks again
-            if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(targets[p])) continue;
+            if (!pMP || pMP->isBad() || (!vScw && pMP->IsInKeyFrame(targets[p]))) continue;
             std::unordered_map<MapPoint*, int>::iterator it = slot_.find(pMP);
             if (it == slot_.end() || refresh_) Put(pMP);
             list[p * lcap + i] = it == slot_.end() ? slot_[pMP] : it->second;
@@ -120,11 +123,19 @@ void LocalMapPoints::searchFuse(const std::vector<KeyFrame*>& targets, const std
         KeyFrame* pKF = targets[p];
         orbp_view& V = views[p];
         std::memset(&V, 0, sizeof(V));
-        const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) V.Rcw[r * 3 + c] = Rcw.at<float>(r, c);
-            V.tcw[r] = tcw.at<float>(r);
-            V.Ow[r] = Ow.at<float>(r);
+        if (vScw) {
+            float S[12];
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 4; c++) S[r * 4 + c] = (*vScw)[p].at<float>(r, c);
+            const int rc = orbp_view_from_sim3(S, &V);
+            if (rc != ORBX_OK) fail("orbp_view_from_sim3", rc);
+        } else {
+            const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) V.Rcw[r * 3 + c] = Rcw.at<float>(r, c);
+                V.tcw[r] = tcw.at<float>(r);
+                V.Ow[r] = Ow.at<float>(r);
+            }
         }
         V.fx = pKF->fx; V.fy = pKF->fy; V.cx = pKF->cx; V.cy = pKF->cy;
         V.min_x = b.min_x; V.max_x = b.max_x; V.min_y = b.min_y; V.max_y = b.max_y;

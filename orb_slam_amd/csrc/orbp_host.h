@@ -1,8 +1,9 @@
 // The argument groups of the map-point walk (orbp_project.hip) and the layouts its synchronous host forms give the one block an orbp_map
 // keeps (orbx::Staged).  Each layout's stage() goes through Layout::put: a host array is copied into its slot and named on the device, an
-// absent one is passed through.  Host C++ only: tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp and
-// tests/_probe/fuse_host.cpp hold the layouts against their sizes without a GPU.
+// absent one is passed through.  Host C++ only: tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp,
+// tests/_probe/fuse_host.cpp and tests/_probe/loop_host.cpp hold the layouts against their sizes without a GPU.
 #pragma once
+#include <cmath>
 #include <cstring>
 
 #include "orbp.h"
@@ -235,6 +236,158 @@ struct FuseBlock {
               Layout::put(h, d, cell_off, k.cell_off, (size_t)nframes * (ORBF_GRID_CELLS + 1)), Layout::put(h, d, cell_feat, k.cell_feat, nfeat),
               Layout::put(h, d, nt, k.nt, nframes), k.nframes, k.cap, Layout::put(h, d, frame, k.frame, nviews)};
         dout = {Layout::at(d, best_idx), Layout::at(d, best_dist), Layout::at(d, rec)};
+    }
+};
+
+// ---- loop closing: ORBP_MODE_LOOP (orbp_loop.hip) and the view of a similarity
+
+// orbp_view_from_sim3: the arithmetic include/orbp.h states, every step a single IEEE operation (the build has -ffp-contract=off)
+inline int view_from_sim3(const float* Scw, orbp_view* view) {
+    if (!Scw || !view) return ORBX_ERR_ARG;
+    double s2 = 0.0;
+    for (int k = 0; k < 3; k++) s2 = s2 + (double)Scw[k] * (double)Scw[k];
+    const float scw = (float)std::sqrt(s2);
+    if (!(scw > 0.0f) || !std::isfinite(scw)) return ORBX_ERR_ARG;
+    float R[9], t[3];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) R[r * 3 + c] = (float)((double)Scw[r * 4 + c] / (double)scw);
+        t[r] = (float)((double)Scw[r * 4 + 3] / (double)scw);
+    }
+    for (int c = 0; c < 3; c++) {
+        float s = 0.0f;
+        for (int k = 0; k < 3; k++) s = s + (-R[k * 3 + c]) * t[k];
+        view->Ow[c] = s;
+    }
+    std::memcpy(view->Rcw, R, sizeof(R));
+    std::memcpy(view->tcw, t, sizeof(t));
+    return ORBX_OK;
+}
+
+constexpr int LOOP_TILE = 256;                         // entries of one workgroup of the loop projection
+inline int loop_tiles(int lcap) { return (lcap + LOOP_TILE - 1) / LOOP_TILE; }
+
+// What the two kernels of the loop projection read and write; p0: the first view of the launch.  nframes == 0: the projection alone, no key
+// frame to be in range.  rec is never null here: the caller's array or the handle's scratch.  tile_count: the passing entries of every
+// (view, tile), loop_tiles(lcap) words per view.  Of Q the kernels write qxyr, qlev, qdesc, qpos and nq_clamped (may be null).
+struct Loop {
+    const orbp_view* views;
+    int capacity;                                      // the table
+    const float* geom;
+    const uint8_t* tdesc;
+    const uint8_t* live;
+    Lists L;
+    const int32_t* frame;
+    int nframes;
+    orbp_fused* rec;
+    int32_t* tile_count;
+    Queries Q;
+    int32_t* nq;
+    int32_t* overflow;
+    int qcap;
+    int p0;
+};
+hipError_t launch_loop_project(const Loop& a, int nviews, const Factors& F, hipStream_t st);
+
+// The rows K.frame names (null: row p), copied per view into the layout orbs_window_search_batch_device reads (problem p = view p); a row out
+// of range becomes an empty frame.
+struct LoopGather {
+    FuseFrames K;
+    orbx_keypoint* kps;
+    uint8_t* desc;
+    int32_t* cell_off;
+    int32_t* cell_feat;
+    int32_t* nt;
+    int p0;
+};
+hipError_t launch_loop_gather(const LoopGather& g, int nviews, hipStream_t st);
+
+struct LoopQueries { float* qxyr; int32_t* qlev; uint8_t* qdesc; int32_t* qpos; };
+struct LoopOut { orbp_fused* rec; int32_t* t2pos; int32_t* t2slot; int32_t* nmatches; int32_t* nq; int32_t* overflow; };
+
+// The arguments of orbp_loop_project_batch_device that do not need the handle (all arrays are device memory: presence and alignment).
+inline int check_loop_project(const orbp_view* d_views, int nviews, const float* factors, int nlevels, const Lists& L, const orbp_fused* d_rec,
+                              const LoopQueries& q, const int32_t* d_nq, const int32_t* d_overflow, int qcap) {
+    if (nviews < 0 || nviews > ORBP_MAX_VIEWS || L.lcap < 1 || qcap < 1 || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
+    if ((long long)nviews * L.lcap >= (1ll << 31)) return ORBX_ERR_ARG;                               // the records are indexed p*lcap + i
+    if (nviews == 0) return ORBX_OK;
+    if (!d_views || !L.list || !L.nlist || !q.qxyr || !q.qlev || !q.qdesc || !q.qpos || !d_nq || !d_overflow) return ORBX_ERR_ARG;
+    if ((uintptr_t)q.qdesc & 15) return ORBX_ERR_ARG;
+    const uintptr_t words = (uintptr_t)d_views | (uintptr_t)L.list | (uintptr_t)L.nlist | (uintptr_t)d_rec | (uintptr_t)q.qxyr | (uintptr_t)q.qlev |
+                            (uintptr_t)q.qpos | (uintptr_t)d_nq | (uintptr_t)d_overflow;
+    return (words & 3) ? ORBX_ERR_ARG : ORBX_OK;
+}
+
+// The arguments of orbp_loop_search_batch_device that do not need the handle (device memory: presence and alignment; a view's mode and row are
+// reported per view by the kernels).  The LDS limit of the search comes after them.
+inline int check_loop_search(const orbp_view* d_views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
+                             const FuseFrames& K, int qcap, const LoopOut& out) {
+    if (nviews < 0 || nviews > ORBP_MAX_VIEWS || L.lcap < 1 || qcap < 1 || qcap > ORBF_MAX_FEATURES || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS)
+        return ORBX_ERR_ARG;
+    if (!b || orb_dist < 0 || orb_dist > 256) return ORBX_ERR_ARG;
+    if (K.cap < 1 || K.cap > ORBF_MAX_FEATURES || K.nframes < 1 || (long long)K.nframes * K.cap >= (1ll << 31)) return ORBX_ERR_ARG;
+    if ((long long)nviews * L.lcap >= (1ll << 31)) return ORBX_ERR_ARG;                               // nviews * cap stays below 2^30
+    if (nviews == 0) return ORBX_OK;
+    if (!d_views || !L.list || !L.nlist || !K.kps_un || !K.desc || !K.cell_off || !K.cell_feat || !K.nt || !out.t2pos || !out.nmatches || !out.nq || !out.overflow)
+        return ORBX_ERR_ARG;
+    if (((uintptr_t)K.desc & 15) || (((uintptr_t)K.kps_un | (uintptr_t)K.cell_off | (uintptr_t)K.cell_feat) & 3)) return ORBX_ERR_ARG;
+    const uintptr_t words = (uintptr_t)d_views | (uintptr_t)L.list | (uintptr_t)L.nlist | (uintptr_t)K.nt | (uintptr_t)K.frame | (uintptr_t)out.rec |
+                            (uintptr_t)out.t2pos | (uintptr_t)out.t2slot | (uintptr_t)out.nmatches | (uintptr_t)out.nq | (uintptr_t)out.overflow;
+    return (words & 3) ? ORBX_ERR_ARG : ORBX_OK;
+}
+
+// The arguments of orbp_loop_search (one view, host memory; the key frame on the device when frame_device)
+inline int check_loop_one(const orbp_view* view, const float* factors, int nlevels, const int32_t* list, int nlist, const orbf_bounds* b, int orb_dist,
+                          const Frame& fr, int nt, bool frame_device, int qcap, const int32_t* t2pos, const int* nmatches) {
+    if (!view || !b || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS || nlist < 0 || nt < 0 || nt > ORBF_MAX_FEATURES || qcap < 1 ||
+        qcap > ORBF_MAX_FEATURES)
+        return ORBX_ERR_ARG;
+    if (orb_dist < 0 || orb_dist > 256 || view->mode != ORBP_MODE_LOOP) return ORBX_ERR_ARG;
+    if (nlist > 0 && !list) return ORBX_ERR_ARG;
+    if (!nmatches || !fr.cell_off || (nt > 0 && (!fr.kps_un || !fr.desc || !fr.cell_feat || !t2pos))) return ORBX_ERR_ARG;
+    if (frame_device && (((uintptr_t)fr.desc & 15) || (((uintptr_t)fr.kps_un | (uintptr_t)fr.cell_off | (uintptr_t)fr.cell_feat) & 3))) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// What the loop projection and search keep on the device between their launches, carved from the handle's scratch (batch forms) or from the
+// tail of the one-view block: the queries, the per-tile counts, the records when the caller wants none, and the gathered rows.
+struct LoopSlots {
+    QuerySlots q;
+    Layout::Slot<int32_t> tile_count, g_cell_off, g_cell_feat, g_nt;
+    Layout::Slot<orbp_fused> rec;
+    Layout::Slot<orbx_keypoint> g_kps;
+    Layout::Slot<uint8_t> g_desc;
+    // search: the search's tables beside the queries (cap: the key frames'); else the caller owns the query arrays
+    void reserve(Layout& L, int nviews, int lcap, int cap, int qcap, bool search, bool with_rec, bool gather) {
+        if (search) q.reserve(L, nviews, cap, qcap, false);
+        tile_count = L.add<int32_t>((size_t)nviews * loop_tiles(lcap));
+        rec = L.add<orbp_fused>((size_t)nviews * lcap, with_rec);
+        const size_t nfeat = (size_t)nviews * cap;
+        g_kps = L.add<orbx_keypoint>(nfeat, gather); g_desc = L.add<uint8_t>(nfeat * 32, gather);
+        g_cell_off = L.add<int32_t>((size_t)nviews * (ORBF_GRID_CELLS + 1), gather); g_cell_feat = L.add<int32_t>(nfeat, gather); g_nt = L.add<int32_t>(nviews, gather);
+    }
+};
+
+// The block of orbp_loop_search, one pinned copy up and one down:
+//   up    [view | nt, nlist | list | skip | claimed | frame]     (absent: what the caller does not pass, and the key frame when it is on the device)
+//   down  [nq, overflow, nmatches | t2pos | t2slot | rec]        (absent: t2slot and rec when the caller wants none)
+// and behind them, on the device only, the queries, the per-tile counts and the records nobody asked for.
+struct LoopBlock {
+    struct Flags { bool skip, claimed, frame, t2slot, rec; };
+    Layout L;
+    Layout::Slot<orbp_view> view;
+    Layout::Slot<int32_t> counts, list, result, t2pos, t2slot;
+    Layout::Slot<uint8_t> skip, claimed;
+    Layout::Slot<orbp_fused> rec;
+    FrameSlots frame;
+    LoopSlots dev;
+    LoopBlock(int cap, int lcap, int qcap, const Flags& f) {
+        view = L.add<orbp_view>(1); counts = L.add<int32_t>(2); list = L.add<int32_t>(lcap); skip = L.add<uint8_t>(lcap, f.skip);
+        claimed = L.add<uint8_t>(cap, f.claimed);
+        frame.reserve(L, cap, f.frame, false);
+        L.end_upload();
+        result = L.add<int32_t>(3); t2pos = L.add<int32_t>(cap); t2slot = L.add<int32_t>(cap, f.t2slot); rec = L.add<orbp_fused>(lcap, f.rec);
+        L.end_download();
+        dev.reserve(L, 1, lcap, cap, qcap, true, !f.rec, false);
     }
 };
 

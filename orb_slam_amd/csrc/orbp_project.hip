@@ -21,7 +21,8 @@
 //              list's and overlap the dependent list -> live -> geometry chain that bounds the stage.
 //   (k_refresh, the refresh of slots from their observations, is orbp_refresh.hip; its host side is refresh_locked below.)
 //   (k_fuse, the search of LocalMapping's Fuse over (view, entry), is orbp_fuse.hip; its host side is orbp_fuse* below.)
-//   k_t2source orbp_track*: turns the search's feature -> query table into feature -> list position (the source feature index of
+//   (k_loop_test / k_loop_pack, the flat projection of loop closing's search, are orbp_loop.hip; their host side is orbp_loop_* below.)
+//   k_t2source orbp_track*, orbp_loop_search*: turns the search's feature -> query table into feature -> list position (the source feature index of
 //              orbp_track_source*) and feature -> map slot through the list positions the projection left (d_qpos); features
 //              without a match, or beyond the frame's count, get -1.  Either output may be absent, and so may the list (identity).
 // With one workgroup per view the one-view call walks its list as a serial chain of 256-entry tiles (two barriers and a dependent
@@ -401,6 +402,39 @@ int track_one(orbp_map* m, const orbp_view* view, const orbp::Factors& F, const 
     return ORBX_OK;
 }
 
+// The device side of orbp_loop_search*, inside the caller's call: the gather of the views' rows (gather slots present), the flat projection,
+// the in-order window search and the result by feature.  K: the key frames as the caller laid them out; claimed: per view.
+int loop_locked(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const orbp::Lists& lists, const orbf_bounds* b, int orb_dist,
+                const orbp::FuseFrames& K, const uint8_t* d_claimed, int qcap, const orbp::LoopSlots& S, void* scratch, const orbp::LoopOut& out, hipStream_t st) {
+    const orbp::Queries q = S.q.at(scratch);
+    orbp::Frame fr{K.kps_un, K.desc, K.cell_off, K.cell_feat, K.nt, K.cap, d_claimed};
+    if (S.g_kps.present) {
+        const orbp::LoopGather g{K, Layout::at(scratch, S.g_kps), Layout::at(scratch, S.g_desc), Layout::at(scratch, S.g_cell_off), Layout::at(scratch, S.g_cell_feat),
+                                 Layout::at(scratch, S.g_nt), 0};
+        HIPCHK(m, orbp::launch_loop_gather(g, nviews, st));
+        fr = {g.kps, g.desc, g.cell_off, g.cell_feat, g.nt, K.cap, d_claimed};
+    }
+    const orbp::Loop a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), lists, K.frame, K.nframes,
+                       out.rec ? out.rec : Layout::at(scratch, S.rec), Layout::at(scratch, S.tile_count), q, out.nq, out.overflow, qcap, 0};
+    HIPCHK(m, orbp::launch_loop_project(a, nviews, F, st));
+    const orbs_params prm{ORBS_RULE_BEST, orb_dist, 0.0f, 0};
+    TRY(orbs_window_search_batch_device(b, &prm, fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, fr.cap, fr.claimed, q.qxyr, q.qlev, q.qdesc, nullptr, nullptr,
+                                        q.nq_clamped, qcap, nviews, q.q2t, q.t2q, nullptr, nullptr, out.nmatches, st));
+    orbp::k_t2source<<<dim3((fr.cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(q.t2q, q.qpos, lists.list, fr.nt, fr.cap, qcap, lists.lcap, out.t2pos,
+                                                                                              out.t2slot);
+    HIPCHK(m, hipGetLastError());
+    return ORBX_OK;
+}
+
+// the handle's scratch holds `L`: grown synchronously on the first call of a size, after the device work that may still use it
+int fit_scratch(orbp_map* m, const Layout& L) {
+    if (L.total() > m->scratch.size()) {
+        HIPCHK(m, m->chain.wait());
+        HIPCHK(m, m->scratch.ensure(L.total()));
+    }
+    return ORBX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -717,6 +751,94 @@ int orbp_track_source(orbp_map* m, const orbp_view* view, const float* factors, 
     const orbp::Source src{src_kps, src_desc};
     return track_one(m, view, F, list, nlist, skip, &src, src_on_device != 0, b, *prm, {kps_un, desc, cell_off, cell_feat, nullptr, std::max(nt, 1), claimed},
                      nt, frame_on_device != 0, qcap, nullptr, t2pos, t2slot, nmatches, nvisible, stream);
+}
+
+int orbp_view_from_sim3(const float* Scw, orbp_view* view) { return orbp::view_from_sim3(Scw, view); }
+
+int orbp_loop_project_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                                   const int32_t* d_nlist, int lcap, const uint8_t* d_skip, orbp_fused* d_rec, float* d_qxyr, int32_t* d_qlev,
+                                   uint8_t* d_qdesc, int32_t* d_qpos, int32_t* d_nq, int32_t* d_overflow, int qcap, void* stream) {
+    const orbp::Lists L{d_list, d_nlist, lcap, d_skip};
+    orbp::Factors F;
+    if (!m || orbp::check_loop_project(d_views, nviews, factors, nlevels, L, d_rec, {d_qxyr, d_qlev, d_qdesc, d_qpos}, d_nq, d_overflow, qcap) != ORBX_OK ||
+        fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    Layout lay;
+    orbp::LoopSlots S;
+    S.reserve(lay, nviews, lcap, 1, qcap, false, d_rec == nullptr, false);
+    TRY(fit_scratch(m, lay));
+    TRY(c.begin());
+    void* scratch = m->scratch.as();
+    const orbp::Loop a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), L, nullptr, 0,
+                       d_rec ? d_rec : Layout::at(scratch, S.rec), Layout::at(scratch, S.tile_count), {d_qxyr, d_qlev, d_qdesc, d_qpos}, d_nq, d_overflow, qcap, 0};
+    HIPCHK(m, orbp::launch_loop_project(a, nviews, F, c.st));
+    return c.end();
+}
+
+int orbp_loop_search_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
+                                  const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const orbf_bounds* b, int orb_dist, const orbx_keypoint* d_kps_un,
+                                  const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat, const int32_t* d_nt, int nframes, int cap,
+                                  const int32_t* d_frame, const uint8_t* d_claimed, int qcap, orbp_fused* d_rec, int32_t* d_t2pos, int32_t* d_t2slot,
+                                  int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, void* stream) {
+    const orbp::Lists L{d_list, d_nlist, lcap, d_skip};
+    const orbp::FuseFrames K{d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt, nframes, cap, d_frame};
+    const orbp::LoopOut out{d_rec, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow};
+    orbp::Factors F;
+    if (!m || orbp::check_loop_search(d_views, nviews, factors, nlevels, L, b, orb_dist, K, qcap, out) != ORBX_OK || fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (nviews == 0) return ORBX_OK;
+    if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    Layout lay;
+    orbp::LoopSlots S;
+    S.reserve(lay, nviews, lcap, cap, qcap, true, d_rec == nullptr, d_frame != nullptr || nviews > nframes);
+    TRY(fit_scratch(m, lay));
+    TRY(c.begin());
+    TRY(loop_locked(m, d_views, nviews, F, L, b, orb_dist, K, d_claimed, qcap, S, m->scratch.as(), out, c.st));
+    return c.end();
+}
+
+int orbp_loop_search(orbp_map* m, const orbp_view* view, const float* factors, int nlevels, const int32_t* list, int nlist, const uint8_t* skip,
+                     const orbf_bounds* b, int orb_dist, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off, const int32_t* cell_feat,
+                     const uint8_t* claimed, int nt, int frame_on_device, int qcap, orbp_fused* rec, int32_t* t2pos, int32_t* t2slot, int* nmatches,
+                     int* nvisible, void* stream) {
+    const int cap = std::max(nt, 1), lcap = std::max(nlist, 1);
+    const orbp::Frame frame{kps_un, desc, cell_off, cell_feat, nullptr, cap, nullptr};
+    orbp::Factors F;
+    if (!m || orbp::check_loop_one(view, factors, nlevels, list, nlist, b, orb_dist, frame, nt, frame_on_device != 0, qcap, t2pos, nmatches) != ORBX_OK ||
+        fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
+    Call c(m, stream);
+    const orbp::LoopBlock B(cap, lcap, qcap, {skip != nullptr, claimed != nullptr, frame_on_device == 0, t2slot != nullptr, rec != nullptr});
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    uint8_t* const d = s.d;
+    std::memcpy(Layout::at(s.h, B.view), view, sizeof(orbp_view));
+    Layout::at(s.h, B.counts)[0] = nt;
+    Layout::at(s.h, B.counts)[1] = nlist;
+    const int32_t* d_counts = Layout::at(d, B.counts);
+    const orbp::Lists dl{s.put(B.list, list, nlist), d_counts + 1, lcap, s.put(B.skip, skip, nlist)};
+    const orbp::Frame fr = B.frame.stage(s.h, d, frame, nt, d_counts);
+    const orbp::FuseFrames K{fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, d_counts, 1, cap, nullptr};
+    const uint8_t* d_claimed = s.put(B.claimed, claimed, nt);
+    TRY(s.run([&] {
+        int32_t* d_res = Layout::at(d, B.result);                      // nq, overflow, nmatches
+        return loop_locked(m, Layout::at(d, B.view), 1, F, dl, b, orb_dist, K, d_claimed, qcap, B.dev, d,
+                           {Layout::at(d, B.rec), Layout::at(d, B.t2pos), Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1}, c.st);
+    }));
+    const int32_t* res = Layout::at(s.h, B.result);
+    if (nvisible) *nvisible = res[0];
+    if (res[1]) return ORBX_ERR_CAPACITY;
+    *nmatches = res[2];
+    if (nt > 0) std::memcpy(t2pos, Layout::at(s.h, B.t2pos), (size_t)nt * 4);
+    if (nt > 0 && t2slot) std::memcpy(t2slot, Layout::at(s.h, B.t2slot), (size_t)nt * 4);
+    if (rec && nlist > 0) std::memcpy(rec, Layout::at(s.h, B.rec), (size_t)nlist * sizeof(orbp_fused));
+    return ORBX_OK;
 }
 
 }  // extern "C"

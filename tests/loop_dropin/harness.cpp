@@ -1,0 +1,232 @@
+// Drives ORB_SLAM::LocalMapPoints::SearchByProjection(pKF, Scw, ...) / SearchAndFuse (orb_slam_amd/cpp/LocalMapPointsLoop.cc, over the stand-in
+// KeyFrame.h of this directory, the MapPoint.h of tests/fuse_dropin and the Frame.h of tests/mappoints_dropin) through a script, and on request
+// runs the reference's own lines (src/ORBmatcher.cc:398-402, :1152-1261 inside the loop of src/LoopClosing.cc:557-570) over search results the
+// script supplies instead; tests/test_gpu_loop_dropin.py builds two identical object graphs that way and compares what is left of them.
+// Floats travel as the hex of their bit pattern.
+//
+//   harness SCRIPT
+//
+// Script lines (cam, factors, new, mp, bad, kfs, kf, unlink and table as tests/fuse_dropin/harness.cpp):
+//   loopsearch K S(12) TH N id ... M mid ...   LocalMapPoints::SearchByProjection(&kf[K], Scw, points, vpMatched, TH) with vpMatched given per
+//                                           feature (-1 none); prints "S ret" and "M id ..." (vpMatched afterwards)
+//   refloopsearch K N id ... M mid ...      the reference's lines :398-402 with table K (point id -> feature) in place of the search, in list order
+//   loopfuse TH NK {k S(12)} N id ...       LocalMapPoints::SearchAndFuse over the NK key frames in the order given, then the dump
+//   refloopfuse NK k ... N id ...           the reference's lines per key frame, in order, with the tables in place of the search, then the dump
+// The dump: "N nFused ..." per Fuse call, "R replaced", per key frame "K k mpid ..." (one per feature, -1 none), per map point
+// "P id bad nobs k:idx ...".
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <set>
+#include <sstream>
+#include <string>
+
+#include "Frame.h"
+#include "KeyFrame.h"
+#include "LocalMapPoints.h"
+#include "MapPoint.h"
+
+namespace ORB_SLAM {
+float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
+int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
+float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
+int MapPoint::nReplaced = 0;
+}
+using namespace ORB_SLAM;
+
+namespace {
+
+float rdf(std::istringstream& in) {
+    std::string h;
+    in >> h;
+    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+void rddesc(std::istringstream& in, unsigned char* d) {
+    std::string h;
+    in >> h;
+    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
+}
+
+typedef std::map<long, std::unique_ptr<MapPoint> > Points;
+typedef std::map<int, std::map<long, int> > Tables;
+
+// src/ORBmatcher.cc:1152-1261 with the search replaced by the table of (point, key frame)
+int refLoopFuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpPoints, const std::map<long, int>& table) {
+    std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();
+    int nFused = 0;
+    for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+        MapPoint* pMP = vpPoints[iMP];
+        if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
+        const std::map<long, int>::const_iterator it = table.find((long)pMP->mnId);
+        if (it == table.end()) continue;
+        const int bestIdx = it->second;
+        MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
+        if (pMPinKF) {
+            if (!pMPinKF->isBad()) pMPinKF->Replace(pMP);
+        } else {
+            pMP->AddObservation(pKF, bestIdx);
+            pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused++;
+    }
+    return nFused;
+}
+
+cv::Mat rdsim(std::istringstream& in) {
+    cv::Mat S(4, 4, CV_32F);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) S.at<float>(r, c) = rdf(in);
+    S.at<float>(3, 0) = S.at<float>(3, 1) = S.at<float>(3, 2) = 0.0f;
+    S.at<float>(3, 3) = 1.0f;
+    return S;
+}
+
+void dump(const std::vector<int>& nFused, std::vector<KeyFrame>& kfs, Points& mps) {
+    printf("N");
+    for (int n : nFused) printf(" %d", n);
+    printf("\nR %d\n", MapPoint::nReplaced);
+    for (size_t k = 0; k < kfs.size(); k++) {
+        printf("K %zu", k);
+        for (MapPoint* m : kfs[k].mvpMapPoints) printf(" %ld", m ? (long)m->mnId : -1L);
+        printf("\n");
+    }
+    for (Points::iterator it = mps.begin(); it != mps.end(); ++it) {
+        MapPoint& m = *it->second;
+        printf("P %ld %d %zu", it->first, m.mbBad ? 1 : 0, m.mObservations.size());
+        for (std::map<KeyFrame*, std::size_t>::iterator o = m.mObservations.begin(); o != m.mObservations.end(); ++o)
+            printf(" %ld:%zu", (long)(o->first - kfs.data()), o->second);
+        printf("\n");
+    }
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream f(argv[1]);
+    std::string line;
+    Points mps;
+    Tables tables;
+    std::vector<KeyFrame> kfs;
+    std::unique_ptr<LocalMapPoints> L;
+    std::vector<float> factors;
+    while (std::getline(f, line)) {
+        std::istringstream in(line);
+        std::string op;
+        if (!(in >> op)) continue;
+        if (op == "cam") {
+            Frame::fx = rdf(in); Frame::fy = rdf(in); Frame::cx = rdf(in); Frame::cy = rdf(in);
+            in >> Frame::mnMinX >> Frame::mnMaxX >> Frame::mnMinY >> Frame::mnMaxY;
+            Frame::mfGridElementWidthInv = rdf(in); Frame::mfGridElementHeightInv = rdf(in);
+        } else if (op == "factors") {
+            int n; in >> n;
+            factors.resize(n);
+            for (int i = 0; i < n; i++) factors[i] = rdf(in);
+        } else if (op == "new") {
+            int refresh, cap; in >> refresh >> cap;
+            L.reset(new LocalMapPoints(0.8f, refresh != 0, cap));
+        } else if (op == "mp") {
+            long id; in >> id;
+            if (!mps.count(id)) { mps[id].reset(new MapPoint); mps[id]->mnId = id; }
+            MapPoint& m = *mps[id];
+            for (int k = 0; k < 3; k++) m.mWorldPos.at<float>(k) = rdf(in);
+            for (int k = 0; k < 3; k++) m.mNormalVector.at<float>(k) = rdf(in);
+            m.mfMinDistance = rdf(in); m.mfMaxDistance = rdf(in);
+            rddesc(in, m.mDescriptor.ptr<unsigned char>(0));
+        } else if (op == "bad") { long id; int v; in >> id >> v; mps.at(id)->mbBad = v != 0;
+        } else if (op == "kfs") {
+            int n; in >> n;
+            kfs.assign(n, KeyFrame());
+        } else if (op == "kf") {
+            int k, n; in >> k;
+            KeyFrame& K = kfs.at(k);
+            K.mnId = k;
+            K.fx = Frame::fx; K.fy = Frame::fy; K.cx = Frame::cx; K.cy = Frame::cy;
+            K.mfGridElementWidthInv = Frame::mfGridElementWidthInv; K.mfGridElementHeightInv = Frame::mfGridElementHeightInv;
+            K.Rcw = cv::Mat(3, 3, CV_32F); K.tcw = cv::Mat(3, 1, CV_32F); K.Ow = cv::Mat(3, 1, CV_32F);
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) K.Rcw.at<float>(r, c) = rdf(in);
+            for (int r = 0; r < 3; r++) K.tcw.at<float>(r) = rdf(in);
+            for (int r = 0; r < 3; r++) {                              // Ow = -Rcw.t() * tcw: a float sum per row started from 0
+                float s = 0.0f;
+                for (int c = 0; c < 3; c++) s += -K.Rcw.at<float>(c, r) * K.tcw.at<float>(c);
+                K.Ow.at<float>(r) = s;
+            }
+            in >> n;
+            K.mvScaleFactors = factors;
+            K.mvKeysUn.assign(n, cv::KeyPoint());
+            K.mvpMapPoints.assign(n, nullptr);
+            K.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                cv::KeyPoint& kp = K.mvKeysUn[i];
+                kp.pt.x = rdf(kin); kp.pt.y = rdf(kin);
+                kin >> kp.octave;
+                rddesc(kin, K.mDescriptors.ptr<unsigned char>(i));
+                long id; kin >> id;
+                if (id >= 0) { K.mvpMapPoints[i] = mps.at(id).get(); mps.at(id)->mObservations[&K] = (size_t)i; }
+            }
+        } else if (op == "unlink") { long id; int k; in >> id >> k; mps.at(id)->mObservations.erase(&kfs.at(k));
+        } else if (op == "table") {
+            int k, n; in >> k >> n;
+            for (int i = 0; i < n; i++) { long id; int idx; in >> id >> idx; tables[k][id] = idx; }
+        } else if (op == "loopsearch" || op == "refloopsearch") {
+            int k, n, m; in >> k;
+            KeyFrame* pKF = &kfs.at(k);
+            cv::Mat Scw;
+            int th = 0;
+            if (op == "loopsearch") { Scw = rdsim(in); in >> th; }
+            in >> n;
+            std::vector<MapPoint*> pts(n);
+            for (int i = 0; i < n; i++) { long id; in >> id; pts[i] = mps.at(id).get(); }
+            std::string tag; in >> tag >> m;
+            std::vector<MapPoint*> matched(m);
+            for (int i = 0; i < m; i++) { long id; in >> id; matched[i] = id < 0 ? nullptr : mps.at(id).get(); }
+            int ret = 0;
+            if (op == "loopsearch") {
+                ret = L->SearchByProjection(pKF, Scw, pts, matched, th);
+            } else {
+                const std::map<long, int>& table = tables[k];
+                for (MapPoint* pMP : pts) {
+                    const std::map<long, int>::const_iterator it = table.find((long)pMP->mnId);
+                    if (it == table.end()) continue;
+                    matched[it->second] = pMP;
+                    ret++;
+                }
+            }
+            printf("S %d\nM", ret);
+            for (MapPoint* p : matched) printf(" %ld", p ? (long)p->mnId : -1L);
+            printf("\n");
+        } else if (op == "loopfuse" || op == "refloopfuse") {
+            float th = 0.f;
+            int nk, n;
+            if (op == "loopfuse") th = rdf(in);
+            in >> nk;
+            std::vector<std::pair<KeyFrame*, cv::Mat> > corrected(nk);
+            for (int i = 0; i < nk; i++) {
+                int k; in >> k;
+                corrected[i].first = &kfs.at(k);
+                if (op == "loopfuse") corrected[i].second = rdsim(in);
+            }
+            in >> n;
+            std::vector<MapPoint*> pts(n);
+            for (int i = 0; i < n; i++) { long id; in >> id; pts[i] = mps.at(id).get(); }
+            std::vector<int> nFused;
+            if (op == "loopfuse") L->SearchAndFuse(corrected, pts, th, &nFused);
+            else
+                for (int i = 0; i < nk; i++) nFused.push_back(refLoopFuse(corrected[i].first, pts, tables[(int)corrected[i].first->mnId]));
+            dump(nFused, kfs, mps);
+        } else {
+            fprintf(stderr, "unknown script line: %s\n", line.c_str());
+            return 2;
+        }
+    }
+    return 0;
+}
