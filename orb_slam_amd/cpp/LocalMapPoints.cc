@@ -17,11 +17,9 @@
 
 namespace ORB_SLAM {
 
-namespace {
-void fail(const char* what, int rc) {
+void LocalMapPoints::fail(const char* what, int rc) {
     throw std::runtime_error(std::string("ORB_SLAM::LocalMapPoints: ") + what + " failed with status " + std::to_string(rc));
 }
-}  // namespace
 
 LocalMapPoints::LocalMapPoints(float nnratio, bool refresh_every_call, int capacity, int device)
     : ratio_(nnratio), refresh_(refresh_every_call), capacity_(std::max(capacity, 1)), device_(device) {
@@ -84,6 +82,13 @@ void LocalMapPoints::Put(MapPoint* pMP) {
         owner_[slot] = pMP;
     }
     mirror(slot, pMP);
+}
+
+int LocalMapPoints::slotOf(MapPoint* pMP) {
+    std::unordered_map<MapPoint*, int>::iterator it = slot_.find(pMP);
+    if (it != slot_.end() && !refresh_) return it->second;
+    Put(pMP);
+    return slot_[pMP];
 }
 
 void LocalMapPoints::Forget(MapPoint* pMP) {
@@ -156,9 +161,7 @@ int LocalMapPoints::SearchReferencePointsInFrustum(Frame& F, const std::vector<M
     for (int i = 0; i < n; i++) {
         MapPoint* pMP = vpLocalMapPoints[i];
         if (pMP->mnLastFrameSeen == F.mnId || pMP->isBad()) continue;             // :704-707
-        std::unordered_map<MapPoint*, int>::iterator it = slot_.find(pMP);
-        if (it == slot_.end() || refresh_) Put(pMP);
-        list_[i] = it == slot_.end() ? slot_[pMP] : it->second;
+        list_[i] = slotOf(pMP);
         skip_[i] = 0;
     }
     flush();

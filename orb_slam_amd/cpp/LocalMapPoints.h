@@ -106,10 +106,14 @@ public:
     int capacity() const { return capacity_; }
 
 private:
+    // throws std::runtime_error: `what` failed with status rc
+    static void fail(const char* what, int rc);
     void flush();
     void grow();
     void mirror(int slot, MapPoint* pMP);
     void viewOf(Frame& F, orbp_view& V, orbf_bounds& b);
+    // the slot of pMP for a search's list: Put first when it is new, or when every call refreshes
+    int slotOf(MapPoint* pMP);
     // vpSource[i]: the map point of source feature i (NULL: none); skip_ is filled by the caller
     int searchSource(Frame& CurrentFrame, int mode, const std::vector<MapPoint*>& vpSource, const cv::KeyPoint* srcKeys,
                      const unsigned char* srcDesc, float th, int ORBdist, bool checkOrientation);
@@ -130,6 +134,8 @@ private:
     int keyFrameRow(KeyFrame* pKF);
     void growKeyFrames(int rows, int feats);
     void residentForFuse(const std::vector<KeyFrame*>& kfs);
+    // the view of pKF's camera inside the bounds b (LocalMapPointsFuse.cc): its own pose, or (Scw != NULL) the decomposition of a similarity
+    orbp_view keyFrameView(KeyFrame* pKF, const cv::Mat* Scw, const orbf_bounds& b, float th, int mode);
     // best_idx of orbp_fuse for views[p] = (targets[p], *lists[p]) -> best[p][i]
     // vScw (may be NULL): the views are the decompositions of these similarities (SearchAndFuse)
     void searchFuse(const std::vector<KeyFrame*>& targets, const std::vector<const std::vector<MapPoint*>*>& lists, float th,

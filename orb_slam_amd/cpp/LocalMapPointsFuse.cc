@@ -4,8 +4,6 @@
 // searches need not have; it needs LocalMapPointsRefresh.cc (the key-frame store) built in.
 #include <algorithm>
 #include <cstring>
-#include <stdexcept>
-#include <string>
 
 #include "LocalMapPoints.h"
 #include "KeyFrame.h"
@@ -21,10 +19,6 @@
 namespace ORB_SLAM {
 
 namespace {
-void fail(const char* what, int rc) {
-    throw std::runtime_error(std::string("ORB_SLAM::LocalMapPoints: ") + what + " failed with status " + std::to_string(rc));
-}
-
 // the loop of src/ORBmatcher.cc:1033-1131 over a search that is already done: isBad() and IsInKeyFrame() are read as of NOW, because a
 // Replace or an AddMapPoint of an earlier iteration (or of an earlier key frame's loop) changes them
 int fuseLoop(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const std::vector<int32_t>& best) {
@@ -90,6 +84,30 @@ void LocalMapPoints::residentForFuse(const std::vector<KeyFrame*>& kfs) {
     }
 }
 
+orbp_view LocalMapPoints::keyFrameView(KeyFrame* pKF, const cv::Mat* Scw, const orbf_bounds& b, float th, int mode) {
+    orbp_view V;
+    std::memset(&V, 0, sizeof(V));
+    if (Scw) {
+        float S[12];
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) S[r * 4 + c] = Scw->at<float>(r, c);
+        const int rc = orbp_view_from_sim3(S, &V);
+        if (rc != ORBX_OK) fail("orbp_view_from_sim3", rc);
+    } else {
+        const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) V.Rcw[r * 3 + c] = Rcw.at<float>(r, c);
+            V.tcw[r] = tcw.at<float>(r);
+            V.Ow[r] = Ow.at<float>(r);
+        }
+    }
+    V.fx = pKF->fx; V.fy = pKF->fy; V.cx = pKF->cx; V.cy = pKF->cy;
+    V.min_x = b.min_x; V.max_x = b.max_x; V.min_y = b.min_y; V.max_y = b.max_y;
+    V.th = th;
+    V.mode = mode;
+    return V;
+}
+
 // vScw (loop closing, LocalMapPointsLoop.cc): view p is the decomposition of (*vScw)[p] instead of the key frame's own pose, and a point that is
 // in the key frame is searched like any other: that overload passes over the members of pKF->GetMapPoints(), which its caller reads when the
 // key frame's turn comes
@@ -109,9 +127,7 @@ void LocalMapPoints::searchFuse(const std::vector<KeyFrame*>& targets, const std
             MapPoint* pMP = v[i];
             // what the loop would pass over already is not searched: both conditions can only turn ON later, and the loop asks again
             if (!pMP || pMP->isBad() || (!vScw && pMP->IsInKeyFrame(targets[p]))) continue;
-            std::unordered_map<MapPoint*, int>::iterator it = slot_.find(pMP);
-            if (it == slot_.end() || refresh_) Put(pMP);
-            list[p * lcap + i] = it == slot_.end() ? slot_[pMP] : it->second;
+            list[p * lcap + i] = slotOf(pMP);
             skip[p * lcap + i] = 0;
         }
     }
@@ -120,28 +136,8 @@ void LocalMapPoints::searchFuse(const std::vector<KeyFrame*>& targets, const std
     std::vector<orbp_view> views(nviews);
     const orbf_bounds b = orbm_access::CameraBounds();
     for (int p = 0; p < nviews; p++) {
-        KeyFrame* pKF = targets[p];
-        orbp_view& V = views[p];
-        std::memset(&V, 0, sizeof(V));
-        if (vScw) {
-            float S[12];
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 4; c++) S[r * 4 + c] = (*vScw)[p].at<float>(r, c);
-            const int rc = orbp_view_from_sim3(S, &V);
-            if (rc != ORBX_OK) fail("orbp_view_from_sim3", rc);
-        } else {
-            const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) V.Rcw[r * 3 + c] = Rcw.at<float>(r, c);
-                V.tcw[r] = tcw.at<float>(r);
-                V.Ow[r] = Ow.at<float>(r);
-            }
-        }
-        V.fx = pKF->fx; V.fy = pKF->fy; V.cx = pKF->cx; V.cy = pKF->cy;
-        V.min_x = b.min_x; V.max_x = b.max_x; V.min_y = b.min_y; V.max_y = b.max_y;
-        V.th = th;
-        V.mode = ORBP_MODE_FUSE;
-        frame[p] = kf_row_[pKF];
+        views[p] = keyFrameView(targets[p], vScw ? &(*vScw)[p] : 0, b, th, ORBP_MODE_FUSE);
+        frame[p] = kf_row_[targets[p]];
     }
     const std::vector<float> factors = targets[0]->GetScaleFactors();
     const int rc = orbp_fuse(map_, views.data(), nviews, factors.data(), targets[0]->GetScaleLevels(), list.data(), nlist.data(), (int)lcap, skip.data(), &b,

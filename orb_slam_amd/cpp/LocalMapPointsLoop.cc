@@ -5,8 +5,6 @@
 #include <algorithm>
 #include <cstring>
 #include <set>
-#include <stdexcept>
-#include <string>
 
 #include "LocalMapPoints.h"
 #include "KeyFrame.h"
@@ -22,10 +20,6 @@
 namespace ORB_SLAM {
 
 namespace {
-void fail(const char* what, int rc) {
-    throw std::runtime_error(std::string("ORB_SLAM::LocalMapPoints: ") + what + " failed with status " + std::to_string(rc));
-}
-
 // src/ORBmatcher.cc:1152-1261 over a search that is already done: the key frame's points are read as its turn begins, isBad() as of each
 // iteration, because a Replace of an earlier iteration (or of an earlier key frame's turn) changes both
 int loopFuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpPoints, const std::vector<int32_t>& best) {
@@ -58,9 +52,7 @@ int LocalMapPoints::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::ve
     for (int i = 0; i < n; i++) {
         MapPoint* pMP = vpPoints[i];
         if (!pMP || pMP->isBad() || spAlreadyFound.count(pMP)) continue;
-        std::unordered_map<MapPoint*, int>::iterator it = slot_.find(pMP);
-        if (it == slot_.end() || refresh_) Put(pMP);
-        list_[i] = it == slot_.end() ? slot_[pMP] : it->second;
+        list_[i] = slotOf(pMP);
         skip_[i] = 0;
     }
     flush();                                                                     // a table that grew keeps its slots
@@ -68,18 +60,8 @@ int LocalMapPoints::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::ve
     const int row = kf_row_[pKF], nt = kf_nt_[row];
     if ((int)vpMatched.size() < nt) fail("SearchByProjection (vpMatched is shorter than the key frame)", ORBX_ERR_ARG);
 
-    orbp_view V;
-    std::memset(&V, 0, sizeof(V));
-    float S[12];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 4; c++) S[r * 4 + c] = Scw.at<float>(r, c);
-    int rc = orbp_view_from_sim3(S, &V);
-    if (rc != ORBX_OK) fail("orbp_view_from_sim3", rc);
     const orbf_bounds b = orbm_access::CameraBounds();
-    V.fx = pKF->fx; V.fy = pKF->fy; V.cx = pKF->cx; V.cy = pKF->cy;
-    V.min_x = b.min_x; V.max_x = b.max_x; V.min_y = b.min_y; V.max_y = b.max_y;
-    V.th = (float)th;
-    V.mode = ORBP_MODE_LOOP;
+    const orbp_view V = keyFrameView(pKF, &Scw, b, (float)th, ORBP_MODE_LOOP);
 
     claimed_.assign(std::max(nt, 1), 0);
     for (int idx = 0; idx < nt; idx++) claimed_[idx] = vpMatched[idx] ? 1 : 0;
@@ -87,10 +69,10 @@ int LocalMapPoints::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::ve
     const std::vector<float> factors = pKF->GetScaleFactors();
     int nmatches = 0, nvisible = 0;
     // pKF's row of the store, in place
-    rc = orbp_loop_search(map_, &V, factors.data(), pKF->GetScaleLevels(), list_.data(), n, skip_.data(), &b, ORBS_TH_LOW,
-                          static_cast<const orbx_keypoint*>(d_kf_kps_) + (size_t)row * feat_cap_, static_cast<const uint8_t*>(d_kf_desc_) + (size_t)row * feat_cap_ * 32,
-                          static_cast<const int32_t*>(d_kf_cell_off_) + (size_t)row * (ORBF_GRID_CELLS + 1), static_cast<const int32_t*>(d_kf_cell_feat_) + (size_t)row * feat_cap_,
-                          claimed_.data(), nt, 1, std::min(std::max(n, 1), ORBF_MAX_FEATURES), nullptr, t2pos_.data(), nullptr, &nmatches, &nvisible, nullptr);
+    const int rc = orbp_loop_search(map_, &V, factors.data(), pKF->GetScaleLevels(), list_.data(), n, skip_.data(), &b, ORBS_TH_LOW,
+                                    static_cast<const orbx_keypoint*>(d_kf_kps_) + (size_t)row * feat_cap_, static_cast<const uint8_t*>(d_kf_desc_) + (size_t)row * feat_cap_ * 32,
+                                    static_cast<const int32_t*>(d_kf_cell_off_) + (size_t)row * (ORBF_GRID_CELLS + 1), static_cast<const int32_t*>(d_kf_cell_feat_) + (size_t)row * feat_cap_,
+                                    claimed_.data(), nt, 1, std::min(std::max(n, 1), ORBF_MAX_FEATURES), nullptr, t2pos_.data(), nullptr, &nmatches, &nvisible, nullptr);
     if (rc != ORBX_OK) fail("orbp_loop_search", rc);
     for (int idx = 0; idx < nt; idx++)
         if (t2pos_[idx] >= 0) vpMatched[idx] = vpPoints[t2pos_[idx]];

@@ -4,20 +4,12 @@
 #include <algorithm>
 #include <cstring>
 #include <map>
-#include <stdexcept>
-#include <string>
 
 #include "LocalMapPoints.h"
 #include "KeyFrame.h"
 #include "orbx.h"
 
 namespace ORB_SLAM {
-
-namespace {
-void fail(const char* what, int rc) {
-    throw std::runtime_error(std::string("ORB_SLAM::LocalMapPoints: ") + what + " failed with status " + std::to_string(rc));
-}
-}  // namespace
 
 // A store of `rows` key frames of `feats` features.  The old one is dropped whole: every row is uploaded again when it is next needed.
 void LocalMapPoints::growKeyFrames(int rows, int feats) {

@@ -2,8 +2,6 @@
 // it names Frame::mvKeys / mvbOutlier and KeyFrame's accessors, which a build that only wants SearchReferencePointsInFrustum need not have.
 #include <algorithm>
 #include <cstring>
-#include <stdexcept>
-#include <string>
 
 #include "LocalMapPoints.h"
 #include "KeyFrame.h"
@@ -20,8 +18,7 @@ int LocalMapPoints::searchSource(Frame& C, int mode, const std::vector<MapPoint*
     for (int i = 0; i < n; i++) {
         MapPoint* pMP = vpSource[i];
         if (!pMP || skip_[i]) continue;
-        if (refresh_ || !slot_.count(pMP)) Put(pMP);
-        list_[i] = slot_[pMP];
+        list_[i] = slotOf(pMP);
     }
     flush();
     orbp_view V;
@@ -42,8 +39,7 @@ int LocalMapPoints::searchSource(Frame& C, int mode, const std::vector<MapPoint*
                                      reinterpret_cast<const orbx_keypoint*>(srcKeys), srcDesc, 0, &b, &prm,
                                      reinterpret_cast<const orbx_keypoint*>(C.mvKeysUn.data()), C.mDescriptors.ptr<unsigned char>(0), cell_off_.data(),
                                      cell_feat_.data(), claimed_.data(), nt, 0, qcap, t2pos_.data(), nullptr, &nmatches, &nvisible, nullptr);
-    if (rc != ORBX_OK)
-        throw std::runtime_error("ORB_SLAM::LocalMapPoints: orbp_track_source failed with status " + std::to_string(rc));
+    if (rc != ORBX_OK) fail("orbp_track_source", rc);
     for (int idx = 0; idx < nt; idx++)
         if (t2pos_[idx] >= 0) C.mvpMapPoints[idx] = vpSource[t2pos_[idx]];         // src/ORBmatcher.cc:1578, :1703
     return nmatches;

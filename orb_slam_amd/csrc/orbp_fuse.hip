@@ -6,7 +6,7 @@
 // k_fuse: a flat grid over (view, list entry), one lane per entry, 256 lanes per workgroup.  Nothing couples two entries: no claim, no
 //   second distance, no ratio, no rotation histogram, no order.  So there is no compaction, no per-problem staging and no commit, and a long
 //   list of one view spreads over as many workgroups as it has tiles (the one-workgroup walk of k_project is a serial chain of tiles there).
-//   A lane projects its point (the helpers of orbp_device.h, shared with k_project), runs the five tests, opens the cell window
+//   A lane runs the five tests on its point (orbp::entry_test of orbp_device.h, the statement k_loop_test shares), opens the cell window
 //   (orbf::window_cells) and scans it column by column: the cells of one grid column are neighbours in the CSR, so a column is one run
 //   cell_off[ix*48 + y0] .. cell_off[ix*48 + y1 + 1] in the reference's order.  The point's descriptor sits in eight registers, a candidate's
 //   arrives as two 16-byte loads; a strictly smaller distance replaces the best.
@@ -30,11 +30,10 @@ __global__ __launch_bounds__(FU_TPB) void k_fuse(Fuse a, Factors F) {
     __shared__ orbp_view V;
     const int p = a.p0 + (int)blockIdx.y, tid = threadIdx.x;
     const Lists& L = a.L;
-    int n = L.nlist[p];
-    n = n < 0 ? 0 : (n > L.lcap ? L.lcap : n);
+    const int n = clamped_count(L, p);
     const int i0 = (int)blockIdx.x * FU_TPB;
     if (i0 >= n) return;                                               // uniform: before the barrier
-    if (tid < (int)(sizeof(orbp_view) / 4)) reinterpret_cast<uint32_t*>(&V)[tid] = reinterpret_cast<const uint32_t*>(a.views + p)[tid];
+    stage_view(V, a.views, p);
     __syncthreads();
     const int i = i0 + tid;
     if (i >= n) return;
@@ -47,27 +46,11 @@ __global__ __launch_bounds__(FU_TPB) void k_fuse(Fuse a, Factors F) {
     do {
         if (!known || (L.skip && L.skip[e])) break;
         const int slot = L.list[e];
-        if (slot < 0 || slot >= a.capacity || !a.live[slot]) break;
-        const float4* g = reinterpret_cast<const float4*>(a.geom) + (size_t)slot * 2;
-        const float4 g0 = g[0], g1 = g[1];
-        const float P[3] = {g0.x, g0.y, g0.z}, Pn[3] = {g0.w, g1.x, g1.y};
-        const float dmin = g1.z, dmax = g1.w;
-        float Pc[3];
-        to_camera(V, P, Pc);
-        if (Pc[2] < 0.0f) { status = ORBP_FUSE_DEPTH; break; }
-        const float invz = 1.0f / Pc[2];
-        const float x = Pc[0] * invz, y = Pc[1] * invz;
-        u = V.fx * x + V.cx;
-        v = V.fy * y + V.cy;
-        if (!(u >= (float)V.min_x && u < (float)V.max_x && v >= (float)V.min_y && v < (float)V.max_y)) { status = ORBP_FUSE_IMAGE; break; }
-        double PO[3], dot = 0.0;
-        const float dist = centre_distance(V, P, PO);
-        if (dist < dmin || dist > dmax) { status = ORBP_FUSE_DISTANCE; break; }
-        for (int k = 0; k < 3; k++) dot = dot + PO[k] * (double)Pn[k];
-        if (dot < 0.5 * (double)dist) { status = ORBP_FUSE_ANGLE; break; }
-        level = level_of(F, dist / dmin);
+        if (slot < 0 || slot >= a.T.capacity || !a.T.live[slot]) break;
+        const float4* g = reinterpret_cast<const float4*>(a.T.geom) + (size_t)slot * 2;
+        status = entry_test(V, F, g[0], g[1], ORBP_FUSE_EMPTY, u, v, level);
+        if (status != ORBP_FUSE_EMPTY) break;
         const float radius = V.th * F.f[level];
-        status = ORBP_FUSE_EMPTY;
         int x0, x1, y0, y1;
         if (!orbf::window_cells(a.b, u, v, radius, &x0, &x1, &y0, &y1)) break;
         int nt = a.K.nt[fr];
@@ -77,7 +60,7 @@ __global__ __launch_bounds__(FU_TPB) void k_fuse(Fuse a, Factors F) {
         const int32_t* feat = a.K.cell_feat + fb;
         const orbx_keypoint* kps = a.K.kps_un + fb;
         const uint4* kd = reinterpret_cast<const uint4*>(a.K.desc) + fb * 2;
-        const uint4* td = reinterpret_cast<const uint4*>(a.tdesc) + (size_t)slot * 2;
+        const uint4* td = reinterpret_cast<const uint4*>(a.T.tdesc) + (size_t)slot * 2;
         const uint4 qa = td[0], qb = td[1];
         const uint32_t q0 = qa.x, q1 = qa.y, q2 = qa.z, q3 = qa.w, q4 = qb.x, q5 = qb.y, q6 = qb.z, q7 = qb.w;
         for (int ix = x0; ix <= x1; ix++) {
@@ -108,18 +91,14 @@ __global__ __launch_bounds__(FU_TPB) void k_fuse(Fuse a, Factors F) {
     }
 }
 
-// gridDim.y holds at most 65535 views: ORBP_MAX_VIEWS takes a second launch
 hipError_t launch_fuse(const Fuse& a, int nviews, const Factors& F, hipStream_t st) {
     const int tiles = (a.L.lcap + FU_TPB - 1) / FU_TPB;
-    for (int p0 = 0; p0 < nviews; p0 += 65535) {
+    return for_view_chunks(nviews, [&](int p0, int np) {
         Fuse b = a;
         b.p0 = p0;
-        const int np = nviews - p0 < 65535 ? nviews - p0 : 65535;
         k_fuse<<<dim3(tiles, np), FU_TPB, 0, st>>>(b, F);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 }  // namespace orbp

@@ -1,7 +1,9 @@
-// The argument groups of the map-point walk (orbp_project.hip) and the layouts its synchronous host forms give the one block an orbp_map
-// keeps (orbx::Staged).  Each layout's stage() goes through Layout::put: a host array is copied into its slot and named on the device, an
-// absent one is passed through.  Host C++ only: tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp,
-// tests/_probe/fuse_host.cpp and tests/_probe/loop_host.cpp hold the layouts against their sizes without a GPU.
+// The argument groups of the map-point table's entry points (orbp_project.hip), the clauses their argument checks are composed of, and the
+// layouts the synchronous host forms give the one block an orbp_map keeps (orbx::Staged): OneView, the shared form of the one-view calls
+// (orbp_track, orbp_track_source: TrackBlock; orbp_loop_search: LoopBlock), RefreshBlock and FuseBlock.  Each layout's stage() goes through
+// Layout::put: a host array is copied into its slot and named on the device, an absent one is passed through.  Host C++ only:
+// tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp, tests/_probe/fuse_host.cpp and tests/_probe/loop_host.cpp hold the checks
+// and the layouts against their sizes without a GPU.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -14,6 +16,8 @@ namespace orbp {
 
 using orbx::Layout;
 
+// the table as the kernels read it: geom, tdesc and live per slot
+struct Table { int capacity; const float* geom; const uint8_t* tdesc; const uint8_t* live; };
 // the lists the views walk (list == NULL: the identity list, frame mode only)
 struct Lists { const int32_t* list; const int32_t* nlist; int lcap; const uint8_t* skip; };
 // the source frames of the last-frame / key-frame modes, entry i of a list being feature i
@@ -40,14 +44,16 @@ struct QuerySlots {
     }
 };
 
-// One frame of `cap` features in the upload span of a one-view call; absent when the caller's frame is on the device already
+// One frame of `cap` features in the upload span of a one-view call; absent when the caller's frame is on the device already.  The
+// claimed flags have a flag of their own: they go up when they are a host array, which is not the same as "the frame goes up"
+// (orbp_track's follow the frame's residence, orbp_loop_search's are a host array beside a resident key frame too).
 struct FrameSlots {
     Layout::Slot<orbx_keypoint> kps;
     Layout::Slot<uint8_t> desc, claimed;
     Layout::Slot<int32_t> cell_off, cell_feat;
-    void reserve(Layout& L, int cap, bool upload, bool with_claimed) {
+    void reserve(Layout& L, int cap, bool upload, bool claimed_host) {
         kps = L.add<orbx_keypoint>(cap, upload); desc = L.add<uint8_t>((size_t)cap * 32, upload); cell_off = L.add<int32_t>(ORBF_GRID_CELLS + 1, upload);
-        cell_feat = L.add<int32_t>(cap, upload); claimed = L.add<uint8_t>(cap, upload && with_claimed);
+        cell_feat = L.add<int32_t>(cap, upload); claimed = L.add<uint8_t>(cap, claimed_host);
     }
     // the caller's frame `f` of nt features as the kernels read it: copied into the pinned block h and named inside the device block d,
     // or passed through
@@ -57,27 +63,69 @@ struct FrameSlots {
     }
 };
 
-// The block of orbp_track / orbp_track_source, one pinned copy up and one down:
-//   up    [view | nt, nlist | list | skip | source key points, descriptors | frame]     (what the caller keeps on the device is absent)
-//   down  [nq, overflow, nmatches | t2pos | t2slot | rec]
-// and behind them, on the device only, the queries.
-struct TrackBlock {
-    struct Flags { bool source, list, skip, src_kps, src_desc, frame, claimed, t2slot, rec; };    // source: t2pos and the queries' angles
+// what the caller of a one-view form hands in and wants back, beyond its records; frame.cap = max(nt, 1), frame.nt unused
+struct OneViewCall { const orbp_view* view; const int32_t* list; int nlist; const uint8_t* skip; Frame frame; int nt; int32_t* t2pos; int32_t* t2slot; int* nmatches; int* nvisible; };
+
+// The block of a one-view synchronous form, one pinned copy up and one down; Rec: the form's record type.
+//   up    [view | nt, nlist | list | skip | frame, claimed | the form's own]     (absent: what the caller does not pass or keeps on the device)
+//   down  [nq, overflow, nmatches | t2pos | t2slot | rec]                        (absent: what the caller does not want)
+// and behind them, on the device only, what the form keeps between its launches.  A form reserves in this order: up(), its own upload
+// slots, down(), its device-only tail.
+template <class Rec>
+struct OneView {
+    struct Flags { bool list, skip, frame, claimed_host, t2pos, t2slot, rec; };    // claimed_host: the flags are a host array (FrameSlots)
     Layout L;
     Layout::Slot<orbp_view> view;
     Layout::Slot<int32_t> counts, list, result, t2pos, t2slot;
-    Layout::Slot<uint8_t> skip, src_desc;
-    Layout::Slot<orbx_keypoint> src_kps;
-    Layout::Slot<orbp_record> rec;
+    Layout::Slot<uint8_t> skip;
+    Layout::Slot<Rec> rec;
     FrameSlots frame;
+    int cap = 1, lcap = 1;
+    Flags flags{};
+    void up(int cap_, int lcap_, const Flags& f) {
+        cap = cap_; lcap = lcap_; flags = f;
+        view = L.add<orbp_view>(1); counts = L.add<int32_t>(2); list = L.add<int32_t>(lcap, f.list); skip = L.add<uint8_t>(lcap, f.skip);
+        frame.reserve(L, cap, f.frame, f.claimed_host);
+    }
+    void down() {
+        const Flags& f = flags;
+        L.end_upload();
+        result = L.add<int32_t>(3); t2pos = L.add<int32_t>(cap, f.t2pos); t2slot = L.add<int32_t>(cap, f.t2slot); rec = L.add<Rec>(lcap, f.rec);
+        L.end_download();
+    }
+    // fills the shared upload slots of the pinned block h and names lists and frame inside the device block d
+    void stage(uint8_t* h, uint8_t* d, const OneViewCall& c, Lists& dl, Frame& fr) const {
+        std::memcpy(Layout::at(h, view), c.view, sizeof(orbp_view));
+        Layout::at(h, counts)[0] = c.nt;
+        Layout::at(h, counts)[1] = c.nlist;
+        const int32_t* d_counts = Layout::at(d, counts);
+        dl = {Layout::put(h, d, list, c.list, c.nlist), d_counts + 1, lcap, Layout::put(h, d, skip, c.skip, c.nlist)};
+        fr = frame.stage(h, d, c.frame, c.nt, d_counts);
+    }
+    // the download span of the pinned block h (result: nq, overflow, nmatches) into the caller's arrays; *nvisible also when the queries overflowed
+    int unpack(uint8_t* h, const OneViewCall& c, Rec* out_rec) const {
+        const int32_t* res = Layout::at(h, result);
+        if (c.nvisible) *c.nvisible = res[0];
+        if (res[1]) return ORBX_ERR_CAPACITY;
+        *c.nmatches = res[2];
+        if (c.nt > 0 && c.t2pos) std::memcpy(c.t2pos, Layout::at(h, t2pos), (size_t)c.nt * 4);
+        if (c.nt > 0 && c.t2slot) std::memcpy(c.t2slot, Layout::at(h, t2slot), (size_t)c.nt * 4);
+        if (out_rec && c.nlist > 0) std::memcpy(out_rec, Layout::at(h, rec), (size_t)c.nlist * sizeof(Rec));
+        return ORBX_OK;
+    }
+};
+
+// orbp_track / orbp_track_source: OneView, the source frame's key points and descriptors in the upload span, the queries behind the download
+// span.  claimed: the caller passes the flags, which follow the frame's residence (on the device with it: a pointer passed through).
+struct TrackBlock : OneView<orbp_record> {
+    struct Flags { bool source, list, skip, src_kps, src_desc, frame, claimed, t2slot, rec; };    // source: t2pos and the queries' angles
+    Layout::Slot<uint8_t> src_desc;
+    Layout::Slot<orbx_keypoint> src_kps;
     QuerySlots q;
     TrackBlock(int cap, int lcap, int qcap, const Flags& f) {
-        view = L.add<orbp_view>(1); counts = L.add<int32_t>(2); list = L.add<int32_t>(lcap, f.list); skip = L.add<uint8_t>(lcap, f.skip);
+        up(cap, lcap, {f.list, f.skip, f.frame, f.frame && f.claimed, f.source, f.t2slot, f.rec});
         src_kps = L.add<orbx_keypoint>(lcap, f.src_kps); src_desc = L.add<uint8_t>((size_t)lcap * 32, f.src_desc);
-        frame.reserve(L, cap, f.frame, f.claimed);
-        L.end_upload();
-        result = L.add<int32_t>(3); t2pos = L.add<int32_t>(cap, f.source); t2slot = L.add<int32_t>(cap, f.t2slot); rec = L.add<orbp_record>(lcap, f.rec);
-        L.end_download();
+        down();
         q.reserve(L, 1, cap, qcap, f.source);
     }
 };
@@ -166,10 +214,7 @@ struct FuseOut { int32_t* best_idx; int32_t* best_dist; orbp_fused* rec; };
 // what the fuse kernel reads and writes (orbp_fuse.hip); p0: the first view of the launch
 struct Fuse {
     const orbp_view* views;
-    int capacity;                                      // the table
-    const float* geom;
-    const uint8_t* tdesc;
-    const uint8_t* live;
+    Table T;
     Lists L;
     FuseFrames K;
     orbf_bounds b;
@@ -179,27 +224,54 @@ struct Fuse {
 };
 hipError_t launch_fuse(const Fuse& a, int nviews, const Factors& F, hipStream_t st);
 
+// gridDim.y holds at most 65535 views, so ORBP_MAX_VIEWS takes a second launch: launch(p0, np) for every chunk of views, up to the first
+// HIP error
+template <class Launch>
+hipError_t for_view_chunks(int nviews, Launch launch) {
+    for (int p0 = 0; p0 < nviews; p0 += 65535) {
+        const hipError_t e = launch(p0, nviews - p0 < 65535 ? nviews - p0 : 65535);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ---- the clauses the argument checks are composed of; each returns true when the arguments pass
+
+// the number of views and the stride of their lists
+inline bool views_ok(int nviews, int lcap) { return nviews >= 0 && nviews <= ORBP_MAX_VIEWS && lcap >= 1; }
+// the scale table
+inline bool factors_ok(const float* factors, int nlevels) { return factors && nlevels >= 1 && nlevels <= ORBS_MAX_LEVELS; }
+// both for the flat kernels, whose entries and records are indexed p*lcap + i in an int
+inline bool flat_views_ok(int nviews, int lcap, const float* factors, int nlevels) {
+    return views_ok(nviews, lcap) && factors_ok(factors, nlevels) && (long long)nviews * lcap < (1ll << 31);
+}
+// the key frames of a search, their grid's bounds and the distance that accepts a match: the sizes ...
+inline bool keyframes_ok(const orbf_bounds* b, int orb_dist, const FuseFrames& K) {
+    return b && orb_dist >= 0 && orb_dist <= 256 && K.cap >= 1 && K.cap <= ORBF_MAX_FEATURES && K.nframes >= 1 && (long long)K.nframes * K.cap < (1ll << 31);
+}
+// ... and the arrays
+inline bool keyframes_present(const FuseFrames& K) { return K.kps_un && K.desc && K.cell_off && K.cell_feat && K.nt; }
+// a frame that is read in place on the device: its descriptors in 16-byte pieces
+inline bool frame_aligned(const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off, const int32_t* cell_feat) {
+    return !((uintptr_t)desc & 15) && !(((uintptr_t)kps_un | (uintptr_t)cell_off | (uintptr_t)cell_feat) & 3);
+}
+// every pointer is 4-byte aligned (a null one is)
+template <class... P>
+bool words_aligned(const P*... p) { return (((uintptr_t)p | ...) & 3) == 0; }
+
 // The arguments of orbp_fuse* that do not need the handle.  on_device: views, lists and outputs are device memory (orbp_fuse_batch_device),
 // so only their presence and alignment can be checked; else the views' modes and rows are walked.  frames_device: the key frames are device
-// addresses, their descriptors read in 16-byte pieces (host arrays are copied into aligned slots).
+// addresses, read in place (host arrays are copied into aligned slots).
 inline int check_fuse(const orbp_view* views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
                       const FuseFrames& K, const FuseOut& out, bool on_device, bool frames_device) {
-    if (nviews < 0 || nviews > ORBP_MAX_VIEWS || L.lcap < 1 || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
-    if (!b || orb_dist < 0 || orb_dist > 256) return ORBX_ERR_ARG;
-    if (K.cap < 1 || K.cap > ORBF_MAX_FEATURES || K.nframes < 1 || (long long)K.nframes * K.cap >= (1ll << 31)) return ORBX_ERR_ARG;
-    if ((long long)nviews * L.lcap >= (1ll << 31)) return ORBX_ERR_ARG;                               // the outputs are indexed p*lcap + i
+    if (!flat_views_ok(nviews, L.lcap, factors, nlevels) || !keyframes_ok(b, orb_dist, K)) return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
-    if (!views || !L.list || !L.nlist || !K.kps_un || !K.desc || !K.cell_off || !K.cell_feat || !K.nt || !out.best_idx || !out.best_dist) return ORBX_ERR_ARG;
-    if (frames_device && (((uintptr_t)K.desc & 15) || (((uintptr_t)K.kps_un | (uintptr_t)K.cell_off | (uintptr_t)K.cell_feat) & 3))) return ORBX_ERR_ARG;
-    if (on_device) {
-        const uintptr_t words = (uintptr_t)views | (uintptr_t)L.list | (uintptr_t)L.nlist | (uintptr_t)K.nt | (uintptr_t)K.frame | (uintptr_t)out.best_idx |
-                                (uintptr_t)out.best_dist | (uintptr_t)out.rec;
-        if (words & 3) return ORBX_ERR_ARG;
-    } else {
-        for (int p = 0; p < nviews; p++) {
-            const int f = K.frame ? K.frame[p] : p;
-            if (views[p].mode != ORBP_MODE_FUSE || f < 0 || f >= K.nframes) return ORBX_ERR_ARG;
-        }
+    if (!views || !L.list || !L.nlist || !keyframes_present(K) || !out.best_idx || !out.best_dist) return ORBX_ERR_ARG;
+    if (frames_device && !frame_aligned(K.kps_un, K.desc, K.cell_off, K.cell_feat)) return ORBX_ERR_ARG;
+    if (on_device) return words_aligned(views, L.list, L.nlist, K.nt, K.frame, out.best_idx, out.best_dist, out.rec) ? ORBX_OK : ORBX_ERR_ARG;
+    for (int p = 0; p < nviews; p++) {
+        const int f = K.frame ? K.frame[p] : p;
+        if (views[p].mode != ORBP_MODE_FUSE || f < 0 || f >= K.nframes) return ORBX_ERR_ARG;
     }
     return ORBX_OK;
 }
@@ -271,10 +343,7 @@ inline int loop_tiles(int lcap) { return (lcap + LOOP_TILE - 1) / LOOP_TILE; }
 // (view, tile), loop_tiles(lcap) words per view.  Of Q the kernels write qxyr, qlev, qdesc, qpos and nq_clamped (may be null).
 struct Loop {
     const orbp_view* views;
-    int capacity;                                      // the table
-    const float* geom;
-    const uint8_t* tdesc;
-    const uint8_t* live;
+    Table T;
     Lists L;
     const int32_t* frame;
     int nframes;
@@ -301,50 +370,39 @@ struct LoopGather {
 };
 hipError_t launch_loop_gather(const LoopGather& g, int nviews, hipStream_t st);
 
-struct LoopQueries { float* qxyr; int32_t* qlev; uint8_t* qdesc; int32_t* qpos; };
 struct LoopOut { orbp_fused* rec; int32_t* t2pos; int32_t* t2slot; int32_t* nmatches; int32_t* nq; int32_t* overflow; };
 
-// The arguments of orbp_loop_project_batch_device that do not need the handle (all arrays are device memory: presence and alignment).
+// The arguments of orbp_loop_project_batch_device that do not need the handle (all arrays are device memory: presence and alignment); of q
+// the four arrays the projection writes.
 inline int check_loop_project(const orbp_view* d_views, int nviews, const float* factors, int nlevels, const Lists& L, const orbp_fused* d_rec,
-                              const LoopQueries& q, const int32_t* d_nq, const int32_t* d_overflow, int qcap) {
-    if (nviews < 0 || nviews > ORBP_MAX_VIEWS || L.lcap < 1 || qcap < 1 || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
-    if ((long long)nviews * L.lcap >= (1ll << 31)) return ORBX_ERR_ARG;                               // the records are indexed p*lcap + i
+                              const Queries& q, const int32_t* d_nq, const int32_t* d_overflow, int qcap) {
+    if (!flat_views_ok(nviews, L.lcap, factors, nlevels) || qcap < 1) return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
     if (!d_views || !L.list || !L.nlist || !q.qxyr || !q.qlev || !q.qdesc || !q.qpos || !d_nq || !d_overflow) return ORBX_ERR_ARG;
     if ((uintptr_t)q.qdesc & 15) return ORBX_ERR_ARG;
-    const uintptr_t words = (uintptr_t)d_views | (uintptr_t)L.list | (uintptr_t)L.nlist | (uintptr_t)d_rec | (uintptr_t)q.qxyr | (uintptr_t)q.qlev |
-                            (uintptr_t)q.qpos | (uintptr_t)d_nq | (uintptr_t)d_overflow;
-    return (words & 3) ? ORBX_ERR_ARG : ORBX_OK;
+    return words_aligned(d_views, L.list, L.nlist, d_rec, q.qxyr, q.qlev, q.qpos, d_nq, d_overflow) ? ORBX_OK : ORBX_ERR_ARG;
 }
 
 // The arguments of orbp_loop_search_batch_device that do not need the handle (device memory: presence and alignment; a view's mode and row are
 // reported per view by the kernels).  The LDS limit of the search comes after them.
 inline int check_loop_search(const orbp_view* d_views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
                              const FuseFrames& K, int qcap, const LoopOut& out) {
-    if (nviews < 0 || nviews > ORBP_MAX_VIEWS || L.lcap < 1 || qcap < 1 || qcap > ORBF_MAX_FEATURES || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS)
-        return ORBX_ERR_ARG;
-    if (!b || orb_dist < 0 || orb_dist > 256) return ORBX_ERR_ARG;
-    if (K.cap < 1 || K.cap > ORBF_MAX_FEATURES || K.nframes < 1 || (long long)K.nframes * K.cap >= (1ll << 31)) return ORBX_ERR_ARG;
-    if ((long long)nviews * L.lcap >= (1ll << 31)) return ORBX_ERR_ARG;                               // nviews * cap stays below 2^30
+    if (!flat_views_ok(nviews, L.lcap, factors, nlevels) || qcap < 1 || qcap > ORBF_MAX_FEATURES || !keyframes_ok(b, orb_dist, K)) return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
-    if (!d_views || !L.list || !L.nlist || !K.kps_un || !K.desc || !K.cell_off || !K.cell_feat || !K.nt || !out.t2pos || !out.nmatches || !out.nq || !out.overflow)
-        return ORBX_ERR_ARG;
-    if (((uintptr_t)K.desc & 15) || (((uintptr_t)K.kps_un | (uintptr_t)K.cell_off | (uintptr_t)K.cell_feat) & 3)) return ORBX_ERR_ARG;
-    const uintptr_t words = (uintptr_t)d_views | (uintptr_t)L.list | (uintptr_t)L.nlist | (uintptr_t)K.nt | (uintptr_t)K.frame | (uintptr_t)out.rec |
-                            (uintptr_t)out.t2pos | (uintptr_t)out.t2slot | (uintptr_t)out.nmatches | (uintptr_t)out.nq | (uintptr_t)out.overflow;
-    return (words & 3) ? ORBX_ERR_ARG : ORBX_OK;
+    if (!d_views || !L.list || !L.nlist || !keyframes_present(K) || !out.t2pos || !out.nmatches || !out.nq || !out.overflow) return ORBX_ERR_ARG;
+    if (!frame_aligned(K.kps_un, K.desc, K.cell_off, K.cell_feat)) return ORBX_ERR_ARG;
+    return words_aligned(d_views, L.list, L.nlist, K.nt, K.frame, out.rec, out.t2pos, out.t2slot, out.nmatches, out.nq, out.overflow) ? ORBX_OK : ORBX_ERR_ARG;
 }
 
 // The arguments of orbp_loop_search (one view, host memory; the key frame on the device when frame_device)
 inline int check_loop_one(const orbp_view* view, const float* factors, int nlevels, const int32_t* list, int nlist, const orbf_bounds* b, int orb_dist,
                           const Frame& fr, int nt, bool frame_device, int qcap, const int32_t* t2pos, const int* nmatches) {
-    if (!view || !b || !factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS || nlist < 0 || nt < 0 || nt > ORBF_MAX_FEATURES || qcap < 1 ||
-        qcap > ORBF_MAX_FEATURES)
+    if (!view || !factors_ok(factors, nlevels) || nlist < 0 || nt < 0 || nt > ORBF_MAX_FEATURES || qcap < 1 || qcap > ORBF_MAX_FEATURES)
         return ORBX_ERR_ARG;
-    if (orb_dist < 0 || orb_dist > 256 || view->mode != ORBP_MODE_LOOP) return ORBX_ERR_ARG;
+    if (!b || orb_dist < 0 || orb_dist > 256 || view->mode != ORBP_MODE_LOOP) return ORBX_ERR_ARG;
     if (nlist > 0 && !list) return ORBX_ERR_ARG;
     if (!nmatches || !fr.cell_off || (nt > 0 && (!fr.kps_un || !fr.desc || !fr.cell_feat || !t2pos))) return ORBX_ERR_ARG;
-    if (frame_device && (((uintptr_t)fr.desc & 15) || (((uintptr_t)fr.kps_un | (uintptr_t)fr.cell_off | (uintptr_t)fr.cell_feat) & 3))) return ORBX_ERR_ARG;
+    if (frame_device && !frame_aligned(fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat)) return ORBX_ERR_ARG;
     return ORBX_OK;
 }
 
@@ -367,26 +425,14 @@ struct LoopSlots {
     }
 };
 
-// The block of orbp_loop_search, one pinned copy up and one down:
-//   up    [view | nt, nlist | list | skip | claimed | frame]     (absent: what the caller does not pass, and the key frame when it is on the device)
-//   down  [nq, overflow, nmatches | t2pos | t2slot | rec]        (absent: t2slot and rec when the caller wants none)
-// and behind them, on the device only, the queries, the per-tile counts and the records nobody asked for.
-struct LoopBlock {
+// orbp_loop_search: OneView with the list and t2pos always there, and behind the download span the queries, the per-tile counts and the
+// records nobody asked for.  claimed: the caller passes the flags, always a host array, also beside a key frame that is resident.
+struct LoopBlock : OneView<orbp_fused> {
     struct Flags { bool skip, claimed, frame, t2slot, rec; };
-    Layout L;
-    Layout::Slot<orbp_view> view;
-    Layout::Slot<int32_t> counts, list, result, t2pos, t2slot;
-    Layout::Slot<uint8_t> skip, claimed;
-    Layout::Slot<orbp_fused> rec;
-    FrameSlots frame;
     LoopSlots dev;
     LoopBlock(int cap, int lcap, int qcap, const Flags& f) {
-        view = L.add<orbp_view>(1); counts = L.add<int32_t>(2); list = L.add<int32_t>(lcap); skip = L.add<uint8_t>(lcap, f.skip);
-        claimed = L.add<uint8_t>(cap, f.claimed);
-        frame.reserve(L, cap, f.frame, false);
-        L.end_upload();
-        result = L.add<int32_t>(3); t2pos = L.add<int32_t>(cap); t2slot = L.add<int32_t>(cap, f.t2slot); rec = L.add<orbp_fused>(lcap, f.rec);
-        L.end_download();
+        up(cap, lcap, {true, f.skip, f.frame, f.claimed, true, f.t2slot, f.rec});
+        down();
         dev.reserve(L, 1, lcap, cap, qcap, true, !f.rec, false);
     }
 };

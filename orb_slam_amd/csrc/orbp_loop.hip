@@ -5,9 +5,9 @@
 // The call this serves is one view with several thousand list entries, whose queries must come out in list order: the window search behind it
 // lets a match claim its feature.  k_project walks such a list as a serial chain of 256-entry tiles in one workgroup; here the list is flat over
 // (view, tile), and the order is restored by counting, in two launches that only the stream orders:
-//   k_loop_test   one lane per entry, 256 per workgroup: the five tests of ORBP_MODE_FUSE (the helpers of orbp_device.h, shared with k_project
-//                 and k_fuse), the entry's record, and the tile's number of passing entries (ballot, the four wave totals meet in LDS) in the
-//                 tile's own word.
+//   k_loop_test   one lane per entry, 256 per workgroup: the five tests of ORBP_MODE_FUSE (orbp::entry_test of orbp_device.h, the statement
+//                 k_fuse calls too), the entry's record, and the tile's number of passing entries (ballot, the four wave totals meet in LDS)
+//                 in the tile's own word.
 //   k_loop_pack   the same grid: a workgroup adds the words of the tiles in front of it in its view, ranks its passing entries in list order
 //                 again (orbx::tile_rank) and writes window, levels, list position and descriptor at base + rank while that is below qcap.  The
 //                 view's last tile writes the view's counts.
@@ -25,11 +25,6 @@ namespace orbp {
 constexpr int LP_TPB = LOOP_TILE;
 constexpr int LP_WAVES = LP_TPB / 64;
 
-__device__ __forceinline__ int clamped_count(const Lists& L, int p) {
-    const int n = L.nlist[p];
-    return n < 0 ? 0 : (n > L.lcap ? L.lcap : n);
-}
-
 // a view of another mode, or one whose key frame is not there, sees nothing
 __device__ __forceinline__ bool loop_view_known(const Loop& a, int p, int mode) {
     if (mode != ORBP_MODE_LOOP) return false;
@@ -46,7 +41,7 @@ __global__ __launch_bounds__(LP_TPB) void k_loop_test(Loop a, Factors F) {
     const int n = clamped_count(L, p);
     const int i0 = (int)blockIdx.x * LP_TPB;
     if (i0 >= n) return;                                               // uniform: before the barrier
-    if (tid < (int)(sizeof(orbp_view) / 4)) reinterpret_cast<uint32_t*>(&V)[tid] = reinterpret_cast<const uint32_t*>(a.views + p)[tid];
+    stage_view(V, a.views, p);
     __syncthreads();
     const int i = i0 + tid;
     const size_t e = (size_t)p * L.lcap + i;
@@ -57,26 +52,9 @@ __global__ __launch_bounds__(LP_TPB) void k_loop_test(Loop a, Factors F) {
     do {
         if (i >= n || !known || (L.skip && L.skip[e])) break;
         const int slot = L.list[e];
-        if (slot < 0 || slot >= a.capacity || !a.live[slot]) break;
-        const float4* g = reinterpret_cast<const float4*>(a.geom) + (size_t)slot * 2;
-        const float4 g0 = g[0], g1 = g[1];
-        const float P[3] = {g0.x, g0.y, g0.z}, Pn[3] = {g0.w, g1.x, g1.y};
-        const float dmin = g1.z, dmax = g1.w;
-        float Pc[3];
-        to_camera(V, P, Pc);
-        if (Pc[2] < 0.0f) { status = ORBP_FUSE_DEPTH; break; }
-        const float invz = 1.0f / Pc[2];
-        const float x = Pc[0] * invz, y = Pc[1] * invz;
-        u = V.fx * x + V.cx;
-        v = V.fy * y + V.cy;
-        if (!(u >= (float)V.min_x && u < (float)V.max_x && v >= (float)V.min_y && v < (float)V.max_y)) { status = ORBP_FUSE_IMAGE; break; }
-        double PO[3], dot = 0.0;
-        const float dist = centre_distance(V, P, PO);
-        if (dist < dmin || dist > dmax) { status = ORBP_FUSE_DISTANCE; break; }
-        for (int k = 0; k < 3; k++) dot = dot + PO[k] * (double)Pn[k];
-        if (dot < 0.5 * (double)dist) { status = ORBP_FUSE_ANGLE; break; }
-        level = level_of(F, dist / dmin);
-        status = ORBP_LOOP_QUERY;
+        if (slot < 0 || slot >= a.T.capacity || !a.T.live[slot]) break;
+        const float4* g = reinterpret_cast<const float4*>(a.T.geom) + (size_t)slot * 2;
+        status = entry_test(V, F, g[0], g[1], ORBP_LOOP_QUERY, u, v, level);
     } while (false);
 
     if (i < n) {
@@ -119,7 +97,7 @@ __global__ __launch_bounds__(LP_TPB) void k_loop_pack(Loop a, Factors F) {
     if (i < n) {
         r = a.rec[e];
         slot = L.list[e];
-        keep = r.status == ORBP_LOOP_QUERY && slot >= 0 && slot < a.capacity && r.level >= 0 && r.level < F.n;
+        keep = r.status == ORBP_LOOP_QUERY && slot >= 0 && slot < a.T.capacity && r.level >= 0 && r.level < F.n;
     }
     const int q = orbx::tile_rank<LP_WAVES>(keep, wave_total, base);    // base: now through this tile
     if (keep && q < a.qcap) {
@@ -129,7 +107,7 @@ __global__ __launch_bounds__(LP_TPB) void k_loop_pack(Loop a, Factors F) {
         a.Q.qlev[o * 2] = r.level - 1;
         a.Q.qlev[o * 2 + 1] = r.level;
         a.Q.qpos[o] = i;
-        const uint4* d = reinterpret_cast<const uint4*>(a.tdesc) + (size_t)slot * 2;
+        const uint4* d = reinterpret_cast<const uint4*>(a.T.tdesc) + (size_t)slot * 2;
         uint4* od = reinterpret_cast<uint4*>(a.Q.qdesc) + o * 2;
         od[0] = d[0]; od[1] = d[1];
     }
@@ -158,34 +136,27 @@ __global__ __launch_bounds__(LP_TPB) void k_loop_gather(LoopGather g) {
     if (j == 0) g.nt[p] = ok ? K.nt[fr] : 0;
 }
 
-// gridDim.y holds at most 65535 views: ORBP_MAX_VIEWS takes a second launch
 hipError_t launch_loop_project(const Loop& a, int nviews, const Factors& F, hipStream_t st) {
     const int tiles = loop_tiles(a.L.lcap);
-    for (int p0 = 0; p0 < nviews; p0 += 65535) {
+    return for_view_chunks(nviews, [&](int p0, int np) {
         Loop b = a;
         b.p0 = p0;
-        const int np = nviews - p0 < 65535 ? nviews - p0 : 65535;
         k_loop_test<<<dim3(tiles, np), LP_TPB, 0, st>>>(b, F);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         k_loop_pack<<<dim3(tiles, np), LP_TPB, 0, st>>>(b, F);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_loop_gather(const LoopGather& g, int nviews, hipStream_t st) {
     const int most = g.K.cap > ORBF_GRID_CELLS + 1 ? g.K.cap : ORBF_GRID_CELLS + 1;
-    for (int p0 = 0; p0 < nviews; p0 += 65535) {
+    return for_view_chunks(nviews, [&](int p0, int np) {
         LoopGather b = g;
         b.p0 = p0;
-        const int np = nviews - p0 < 65535 ? nviews - p0 : 65535;
         k_loop_gather<<<dim3((most + LP_TPB - 1) / LP_TPB, np), LP_TPB, 0, st>>>(b);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 }  // namespace orbp

@@ -19,14 +19,16 @@
 //              th * factors[level] over the levels [level-1, level+1], its angle and the source frame's (last frame) or the table's
 //              (key frame) descriptor.  The key point's octave and angle do not depend on the slot, so their loads leave with the
 //              list's and overlap the dependent list -> live -> geometry chain that bounds the stage.
-//   (k_refresh, the refresh of slots from their observations, is orbp_refresh.hip; its host side is refresh_locked below.)
-//   (k_fuse, the search of LocalMapping's Fuse over (view, entry), is orbp_fuse.hip; its host side is orbp_fuse* below.)
-//   (k_loop_test / k_loop_pack, the flat projection of loop closing's search, are orbp_loop.hip; their host side is orbp_loop_* below.)
-//   k_t2source orbp_track*, orbp_loop_search*: turns the search's feature -> query table into feature -> list position (the source feature index of
+//   k_t2source every search's last step: turns the search's feature -> query table into feature -> list position (the source feature index of
 //              orbp_track_source*) and feature -> map slot through the list positions the projection left (d_qpos); features
 //              without a match, or beyond the frame's count, get -1.  Either output may be absent, and so may the list (identity).
 // With one workgroup per view the one-view call walks its list as a serial chain of 256-entry tiles (two barriers and a dependent
 // list -> live -> geometry load each): its latency grows linearly with the list length.
+//
+// The host side of every orbp_* entry point is here too; the kernels of the other modes are k_refresh (orbp_refresh.hip), k_fuse
+// (orbp_fuse.hip) and k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip).  Every search ends in search_tail (window search, then
+// k_t2source).  The one-view synchronous forms (orbp_track, orbp_track_source, orbp_loop_search) share one_view over the block orbp::OneView
+// of orbp_host.h, where the argument groups, the checks' clauses and the other forms' blocks are.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,10 +48,7 @@ constexpr int WAVES = TPB / 64;
 // what one walk reads and writes
 struct Walk {
     const orbp_view* views;
-    int capacity;                                      // the table
-    const float* geom;
-    const uint8_t* tdesc;
-    const uint8_t* live;
+    Table T;
     Lists L;
     Source S;                                          // k_project<true> only
     orbp_record* rec;                                  // k_project<false> only, may be NULL
@@ -90,7 +89,9 @@ __device__ __forceinline__ bool to_image(const orbp_view& V, const float Pc[3], 
     return !(u != u || v != v);
 }
 
-// src/Frame.cc:137-198 for one point; true = visible
+// src/Frame.cc:137-198 for one point; true = visible.  Not orbp::entry_test (orbp_device.h) with other constants: the reference's two
+// passages differ in every detail, and so do these.  Here 1 / z is a double division, the image bounds are closed, a NaN is rejected by a
+// rule of its own (to_image), and the angle test is against the view's limit on view_cos, which the caller needs.
 __device__ __forceinline__ bool in_frustum(const orbp_view& V, const Factors& F, const float4 g0, const float4 g1, float& u, float& v,
                                            float& view_cos, int& level) {
     const float P[3] = {g0.x, g0.y, g0.z}, Pn[3] = {g0.w, g1.x, g1.y};
@@ -119,11 +120,10 @@ __global__ __launch_bounds__(TPB) void k_project(Walk a, Factors F) {
     __shared__ orbp_view V;
     __shared__ int wave_total[WAVES];
     const int p = blockIdx.x, tid = threadIdx.x;
-    if (tid < (int)(sizeof(orbp_view) / 4)) reinterpret_cast<uint32_t*>(&V)[tid] = reinterpret_cast<const uint32_t*>(a.views + p)[tid];
+    stage_view(V, a.views, p);
     __syncthreads();
     const Lists& L = a.L;
-    int n = SOURCE || L.list ? L.nlist[p] : a.capacity;
-    n = n < 0 ? 0 : (n > L.lcap ? L.lcap : n);
+    int n = clamp_count(SOURCE || L.list ? L.nlist[p] : a.T.capacity, L.lcap);                          // no list: every slot of the table
     const bool from_last = SOURCE && V.mode == ORBP_MODE_LAST_FRAME;
     const bool known_mode = SOURCE ? (from_last && a.S.desc) || V.mode == ORBP_MODE_KEYFRAME : V.mode == ORBP_MODE_FRAME;
     if (!known_mode) n = 0;                                            // reported below: such a view sees nothing
@@ -140,8 +140,8 @@ __global__ __launch_bounds__(TPB) void k_project(Walk a, Factors F) {
                 slot = L.list[lb + i];
                 const int octave = a.S.kps[lb + i].octave;             // independent of the slot: in flight with the list
                 angle = a.S.kps[lb + i].angle;
-                if (!(L.skip && L.skip[lb + i]) && slot >= 0 && slot < a.capacity && a.live[slot]) {
-                    const float4* g = reinterpret_cast<const float4*>(a.geom) + (size_t)slot * 2;
+                if (!(L.skip && L.skip[lb + i]) && slot >= 0 && slot < a.T.capacity && a.T.live[slot]) {
+                    const float4* g = reinterpret_cast<const float4*>(a.T.geom) + (size_t)slot * 2;
                     const float4 g0 = g[0];
                     const float P[3] = {g0.x, g0.y, g0.z};
                     float Pc[3];
@@ -153,8 +153,8 @@ __global__ __launch_bounds__(TPB) void k_project(Walk a, Factors F) {
         } else {
             if (i < n && !(L.skip && L.skip[lb + i])) {
                 slot = L.list ? L.list[lb + i] : i;
-                if (slot >= 0 && slot < a.capacity && a.live[slot]) {
-                    const float4* g = reinterpret_cast<const float4*>(a.geom) + (size_t)slot * 2;
+                if (slot >= 0 && slot < a.T.capacity && a.T.live[slot]) {
+                    const float4* g = reinterpret_cast<const float4*>(a.T.geom) + (size_t)slot * 2;
                     vis = in_frustum(V, F, g[0], g[1], u, v, vc, level);
                 }
             }
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(TPB) void k_project(Walk a, Factors F) {
             a.Q.qlev[(qb + q) * 2 + 1] = SOURCE ? level + 1 : level;
             if constexpr (SOURCE) a.Q.qangle[qb + q] = angle;
             a.Q.qpos[qb + q] = i;
-            const uint4* d = from_last ? reinterpret_cast<const uint4*>(a.S.desc) + (lb + i) * 2 : reinterpret_cast<const uint4*>(a.tdesc) + (size_t)slot * 2;
+            const uint4* d = from_last ? reinterpret_cast<const uint4*>(a.S.desc) + (lb + i) * 2 : reinterpret_cast<const uint4*>(a.T.tdesc) + (size_t)slot * 2;
             uint4* od = reinterpret_cast<uint4*>(a.Q.qdesc) + (qb + q) * 2;
             od[0] = d[0]; od[1] = d[1];
         }
@@ -296,8 +296,10 @@ int check_refresh_slots(orbp_map* m, const int32_t* slots, int n, bool with_pos,
     return check_slots(m, slots, n, true, !may_create);
 }
 
+orbp::Table table_of(const orbp_map* m) { return {m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>()}; }
+
 int fill_factors(const float* factors, int nlevels, orbp::Factors& F) {
-    if (!factors || nlevels < 1 || nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
+    if (!orbp::factors_ok(factors, nlevels)) return ORBX_ERR_ARG;
     std::memset(&F, 0, sizeof(F));
     for (int i = 0; i < nlevels; i++) F.f[i] = factors[i];
     F.n = nlevels;
@@ -305,7 +307,7 @@ int fill_factors(const float* factors, int nlevels, orbp::Factors& F) {
 }
 
 int check_walk(const orbp_map* m, const void* d_views, int nviews, const int32_t* d_list, const int32_t* d_nlist, int lcap, int qcap) {
-    if (!m || nviews < 0 || nviews > ORBP_MAX_VIEWS || lcap < 1 || qcap < 1) return ORBX_ERR_ARG;
+    if (!m || !orbp::views_ok(nviews, lcap) || qcap < 1) return ORBX_ERR_ARG;
     if (nviews > 0 && !d_views) return ORBX_ERR_ARG;
     if (d_list ? !d_nlist : lcap < m->capacity) return ORBX_ERR_ARG;
     return ORBX_OK;
@@ -314,8 +316,7 @@ int check_walk(const orbp_map* m, const void* d_views, int nviews, const int32_t
 // src == NULL: the frustum test of ORBP_MODE_FRAME (rec may be set); else the source-frame modes
 void launch_project(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const orbp::Lists& lists, const orbp::Source* src,
                     orbp_record* d_rec, const orbp::Queries& q, int32_t* d_nq, int32_t* d_overflow, int qcap, hipStream_t st) {
-    const orbp::Walk w{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), lists, src ? *src : orbp::Source{},
-                       d_rec, q, d_nq, d_overflow, qcap};
+    const orbp::Walk w{d_views, table_of(m), lists, src ? *src : orbp::Source{}, d_rec, q, d_nq, d_overflow, qcap};
     if (src) orbp::k_project<true><<<nviews, orbp::TPB, 0, st>>>(w, F);
     else orbp::k_project<false><<<nviews, orbp::TPB, 0, st>>>(w, F);
 }
@@ -323,9 +324,21 @@ void launch_project(orbp_map* m, const orbp_view* d_views, int nviews, const orb
 // what the source-frame walks need beyond check_walk: a list (entry i is feature i of the source frame) and its key points
 int check_source(const orbp_map* m, const void* d_views, int nviews, const int32_t* d_list, const int32_t* d_nlist, int lcap, int qcap,
                  const void* d_src_kps, const void* d_src_desc) {
-    if (!m || nviews < 0 || nviews > ORBP_MAX_VIEWS || lcap < 1 || qcap < 1) return ORBX_ERR_ARG;
+    if (!m || !orbp::views_ok(nviews, lcap) || qcap < 1) return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
     if (!d_views || !d_list || !d_nlist || !d_src_kps || ((uintptr_t)d_src_desc & 15)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// The two steps every search ends in, inside the caller's call: the in-order window search of the queries `q` in the frames `fr` (problem p =
+// view p), and the result by feature (k_t2source).  q.qangle is null where the rule does not look at angles.
+int search_tail(orbp_map* m, const orbf_bounds* b, const orbs_params& prm, const orbp::Frame& fr, const orbp::Queries& q, int qcap, int nviews,
+                const orbp::Lists& lists, int32_t* d_t2pos, int32_t* d_t2slot, int32_t* d_nmatches, hipStream_t st) {
+    TRY(orbs_window_search_batch_device(b, &prm, fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, fr.cap, fr.claimed, q.qxyr, q.qlev, q.qdesc, q.qangle, nullptr,
+                                        q.nq_clamped, qcap, nviews, q.q2t, q.t2q, nullptr, nullptr, d_nmatches, st));
+    orbp::k_t2source<<<dim3((fr.cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(q.t2q, q.qpos, lists.list, fr.nt, fr.cap, qcap, lists.lcap,
+                                                                                              d_t2pos, d_t2slot);
+    HIPCHK(m, hipGetLastError());
     return ORBX_OK;
 }
 
@@ -336,70 +349,7 @@ int track_locked(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::
                  int32_t* d_t2pos, int32_t* d_t2slot, int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, hipStream_t st) {
     launch_project(m, d_views, nviews, F, lists, src, d_rec, q, d_nq, d_overflow, qcap, st);
     HIPCHK(m, hipGetLastError());
-    TRY(orbs_window_search_batch_device(b, &prm, fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, fr.cap, fr.claimed, q.qxyr, q.qlev, q.qdesc, q.qangle, nullptr,
-                                        q.nq_clamped, qcap, nviews, q.q2t, q.t2q, nullptr, nullptr, d_nmatches, st));
-    orbp::k_t2source<<<dim3((fr.cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(q.t2q, q.qpos, lists.list, fr.nt, fr.cap, qcap, lists.lcap,
-                                                                                              d_t2pos, d_t2slot);
-    HIPCHK(m, hipGetLastError());
-    return ORBX_OK;
-}
-
-// orbp_track_batch_device / orbp_track_source_batch_device after their argument checks: the queries live in the handle's scratch
-int track_batch(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const orbp::Lists& lists, const orbp::Source* src,
-                const orbf_bounds* b, const orbs_params& prm, const orbp::Frame& fr, int qcap, orbp_record* d_rec, int32_t* d_t2pos, int32_t* d_t2slot,
-                int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, void* stream) {
-    if (orbs_lds_bytes(fr.cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
-    Call c(m, stream);
-    if (!c.ok()) return ORBX_ERR_DEVICE;
-    Layout L;
-    orbp::QuerySlots q;
-    q.reserve(L, nviews, fr.cap, qcap, src != nullptr);
-    if (L.total() > m->scratch.size()) {
-        HIPCHK(m, m->chain.wait());                                    // device work that may still use the scratch
-        HIPCHK(m, m->scratch.ensure(L.total()));
-    }
-    TRY(c.begin());
-    TRY(track_locked(m, d_views, nviews, F, lists, src, b, prm, fr, qcap, q.at(m->scratch.as()), d_rec, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow, c.st));
-    return c.end();
-}
-
-// orbp_track / orbp_track_source after their argument checks: one view through the handle's block (orbp::TrackBlock), synchronous.
-// src == NULL: the frame mode.  `frame` holds the caller's host or device arrays and cap = max(nt, 1).
-int track_one(orbp_map* m, const orbp_view* view, const orbp::Factors& F, const int32_t* list, int nlist, const uint8_t* skip, const orbp::Source* src,
-              bool src_on_device, const orbf_bounds* b, const orbs_params& prm, const orbp::Frame& frame, int nt, bool frame_on_device, int qcap,
-              orbp_record* rec, int32_t* t2pos, int32_t* t2slot, int* nmatches, int* nvisible, void* stream) {
-    const int cap = frame.cap, lcap = std::max(nlist, 1);
-    if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
-    Call c(m, stream);
-    const bool up_src = src && !src_on_device && nlist > 0;
-    const orbp::TrackBlock B(cap, lcap, qcap, {src != nullptr, src || list, skip != nullptr, up_src, up_src && view->mode == ORBP_MODE_LAST_FRAME,
-                                              !frame_on_device, frame.claimed != nullptr, t2slot != nullptr, rec != nullptr});
-    Staged s(c, m->block, B.L);
-    TRY(s.fit());
-    uint8_t* const h = s.h;
-    uint8_t* const d = s.d;
-    std::memcpy(Layout::at(h, B.view), view, sizeof(orbp_view));
-    Layout::at(h, B.counts)[0] = nt;
-    Layout::at(h, B.counts)[1] = nlist;
-    const int32_t* d_counts = Layout::at(d, B.counts);
-    const orbp::Lists dl{s.put(B.list, list, nlist), d_counts + 1, lcap, s.put(B.skip, skip, nlist)};
-    const orbp::Frame fr = B.frame.stage(h, d, frame, nt, d_counts);
-    // with nlist == 0 nothing is read through the source pointers; the kernel still wants them non-NULL for a last-frame view
-    orbp::Source d_src{reinterpret_cast<const orbx_keypoint*>(d), d};
-    if (src && nlist > 0) d_src = {s.put(B.src_kps, src->kps, nlist), s.put(B.src_desc, src->desc, (size_t)nlist * 32)};
-    TRY(s.run([&] {
-        int32_t* d_res = Layout::at(d, B.result);                      // nq, overflow, nmatches
-        return track_locked(m, Layout::at(d, B.view), 1, F, dl, src ? &d_src : nullptr, b, prm, fr, qcap, B.q.at(d), Layout::at(d, B.rec), Layout::at(d, B.t2pos),
-                            Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1, c.st);
-    }));
-    const int32_t* res = Layout::at(h, B.result);
-    if (nvisible) *nvisible = res[0];
-    if (res[1]) return ORBX_ERR_CAPACITY;
-    *nmatches = res[2];
-    if (nt > 0 && t2pos) std::memcpy(t2pos, Layout::at(h, B.t2pos), (size_t)nt * 4);
-    if (nt > 0 && t2slot) std::memcpy(t2slot, Layout::at(h, B.t2slot), (size_t)nt * 4);
-    if (rec && nlist > 0) std::memcpy(rec, Layout::at(h, B.rec), (size_t)nlist * sizeof(orbp_record));
-    return ORBX_OK;
+    return search_tail(m, b, prm, fr, q, qcap, nviews, lists, d_t2pos, d_t2slot, d_nmatches, st);
 }
 
 // The device side of orbp_loop_search*, inside the caller's call: the gather of the views' rows (gather slots present), the flat projection,
@@ -414,16 +364,10 @@ int loop_locked(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::F
         HIPCHK(m, orbp::launch_loop_gather(g, nviews, st));
         fr = {g.kps, g.desc, g.cell_off, g.cell_feat, g.nt, K.cap, d_claimed};
     }
-    const orbp::Loop a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), lists, K.frame, K.nframes,
-                       out.rec ? out.rec : Layout::at(scratch, S.rec), Layout::at(scratch, S.tile_count), q, out.nq, out.overflow, qcap, 0};
+    const orbp::Loop a{d_views, table_of(m), lists, K.frame, K.nframes, out.rec ? out.rec : Layout::at(scratch, S.rec), Layout::at(scratch, S.tile_count), q,
+                       out.nq, out.overflow, qcap, 0};
     HIPCHK(m, orbp::launch_loop_project(a, nviews, F, st));
-    const orbs_params prm{ORBS_RULE_BEST, orb_dist, 0.0f, 0};
-    TRY(orbs_window_search_batch_device(b, &prm, fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, fr.cap, fr.claimed, q.qxyr, q.qlev, q.qdesc, nullptr, nullptr,
-                                        q.nq_clamped, qcap, nviews, q.q2t, q.t2q, nullptr, nullptr, out.nmatches, st));
-    orbp::k_t2source<<<dim3((fr.cap + orbp::TPB - 1) / orbp::TPB, nviews), orbp::TPB, 0, st>>>(q.t2q, q.qpos, lists.list, fr.nt, fr.cap, qcap, lists.lcap, out.t2pos,
-                                                                                              out.t2slot);
-    HIPCHK(m, hipGetLastError());
-    return ORBX_OK;
+    return search_tail(m, b, {ORBS_RULE_BEST, orb_dist, 0.0f, 0}, fr, q, qcap, nviews, lists, out.t2pos, out.t2slot, out.nmatches, st);
 }
 
 // the handle's scratch holds `L`: grown synchronously on the first call of a size, after the device work that may still use it
@@ -433,6 +377,61 @@ int fit_scratch(orbp_map* m, const Layout& L) {
         HIPCHK(m, m->scratch.ensure(L.total()));
     }
     return ORBX_OK;
+}
+
+// orbp_track_batch_device / orbp_track_source_batch_device after their argument checks: the queries live in the handle's scratch
+int track_batch(orbp_map* m, const orbp_view* d_views, int nviews, const orbp::Factors& F, const orbp::Lists& lists, const orbp::Source* src,
+                const orbf_bounds* b, const orbs_params& prm, const orbp::Frame& fr, int qcap, orbp_record* d_rec, int32_t* d_t2pos, int32_t* d_t2slot,
+                int32_t* d_nmatches, int32_t* d_nq, int32_t* d_overflow, void* stream) {
+    if (orbs_lds_bytes(fr.cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    Layout L;
+    orbp::QuerySlots q;
+    q.reserve(L, nviews, fr.cap, qcap, src != nullptr);
+    TRY(fit_scratch(m, L));
+    TRY(c.begin());
+    TRY(track_locked(m, d_views, nviews, F, lists, src, b, prm, fr, qcap, q.at(m->scratch.as()), d_rec, d_t2pos, d_t2slot, d_nmatches, d_nq, d_overflow, c.st));
+    return c.end();
+}
+
+// The one-view synchronous forms after their argument checks: one view through the handle's block `B` (an orbp::OneView), which the caller
+// has laid out.  The shared slots are staged, own(s) stages what only this form has, the block goes up, launch(st, d, lists, frame)
+// enqueues the kernels on the device block d, and the download span comes back into the caller's arrays.
+template <class Block, class Rec, class Own, class Launch>
+int one_view(orbp_map* m, void* stream, const Block& B, const orbp::OneViewCall& io, Rec* rec, Own own, Launch launch) {
+    Call c(m, stream);
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    orbp::Lists dl;
+    orbp::Frame fr;
+    B.stage(s.h, s.d, io, dl, fr);
+    own(s);
+    TRY(s.run([&] { return launch(c.st, s.d, dl, fr); }));
+    return B.unpack(s.h, io, rec);
+}
+
+// orbp_track / orbp_track_source after their argument checks (orbp::TrackBlock).  src == NULL: the frame mode.  io.frame holds the caller's
+// host or device arrays.  Its own: the source frame's key points and descriptors.
+int track_one(orbp_map* m, const orbp::OneViewCall& io, const orbp::Factors& F, const orbp::Source* src, bool src_on_device, const orbf_bounds* b,
+              const orbs_params& prm, bool frame_on_device, int qcap, orbp_record* rec, void* stream) {
+    const int cap = io.frame.cap, lcap = std::max(io.nlist, 1), nlist = io.nlist;
+    if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
+    const bool up_src = src && !src_on_device && nlist > 0;
+    const orbp::TrackBlock B(cap, lcap, qcap, {src != nullptr, src || io.list, io.skip != nullptr, up_src, up_src && io.view->mode == ORBP_MODE_LAST_FRAME,
+                                              !frame_on_device, io.frame.claimed != nullptr, io.t2slot != nullptr, rec != nullptr});
+    orbp::Source d_src{};                                              // staged by the first functor, read by the second: one_view calls them in that order
+    return one_view(m, stream, B, io, rec,
+        [&](const Staged& s) {
+            // with nlist == 0 nothing is read through the source pointers; the kernel still wants them non-NULL for a last-frame view
+            d_src = {reinterpret_cast<const orbx_keypoint*>(s.d), s.d};
+            if (src && nlist > 0) d_src = {s.put(B.src_kps, src->kps, nlist), s.put(B.src_desc, src->desc, (size_t)nlist * 32)};
+        },
+        [&](hipStream_t st, uint8_t* d, const orbp::Lists& dl, const orbp::Frame& fr) {
+            int32_t* d_res = Layout::at(d, B.result);                      // nq, overflow, nmatches
+            return track_locked(m, Layout::at(d, B.view), 1, F, dl, src ? &d_src : nullptr, b, prm, fr, qcap, B.q.at(d), Layout::at(d, B.rec), Layout::at(d, B.t2pos),
+                                Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1, st);
+        });
 }
 
 }  // namespace
@@ -614,7 +613,7 @@ int orbp_fuse_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, co
     if (nviews == 0) return ORBX_OK;
     Call c(m, stream);
     TRY(c.begin());
-    const orbp::Fuse a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), L, K, *b, orb_dist, out, 0};
+    const orbp::Fuse a{d_views, table_of(m), L, K, *b, orb_dist, out, 0};
     HIPCHK(m, orbp::launch_fuse(a, nviews, F, c.st));
     return c.end();
 }
@@ -641,7 +640,7 @@ int orbp_fuse(orbp_map* m, const orbp_view* views, int nviews, const float* fact
     orbp::FuseOut dout;
     B.stage(s.h, s.d, views, L, K, dv, dl, dk, dout);
     TRY(s.run([&]() -> int {
-        const orbp::Fuse a{dv, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), dl, dk, *b, orb_dist, dout, 0};
+        const orbp::Fuse a{dv, table_of(m), dl, dk, *b, orb_dist, dout, 0};
         HIPCHK(m, orbp::launch_fuse(a, nviews, F, c.st));
         return ORBX_OK;
     }));
@@ -694,9 +693,8 @@ int orbp_track(orbp_map* m, const orbp_view* view, const float* factors, int nle
     if (fill_factors(factors, nlevels, F) != ORBX_OK || view->mode != ORBP_MODE_FRAME) return ORBX_ERR_ARG;
     if (!list && nlist != m->capacity) return ORBX_ERR_ARG;
     if (!nmatches || (nt > 0 && (!kps_un || !desc || !cell_feat || !t2slot)) || !cell_off) return ORBX_ERR_ARG;
-    return track_one(m, view, F, list, nlist, skip, nullptr, false, b, {ORBS_RULE_MAPPOINTS, ORBS_TH_HIGH, ratio, 0},
-                     {kps_un, desc, cell_off, cell_feat, nullptr, std::max(nt, 1), claimed}, nt, frame_on_device != 0, qcap, rec, nullptr, t2slot, nmatches,
-                     nvisible, stream);
+    return track_one(m, {view, list, nlist, skip, {kps_un, desc, cell_off, cell_feat, nullptr, std::max(nt, 1), claimed}, nt, nullptr, t2slot, nmatches, nvisible}, F,
+                     nullptr, false, b, {ORBS_RULE_MAPPOINTS, ORBS_TH_HIGH, ratio, 0}, frame_on_device != 0, qcap, rec, stream);
 }
 
 int orbp_project_source_batch_device(orbp_map* m, const orbp_view* d_views, int nviews, const float* factors, int nlevels, const int32_t* d_list,
@@ -749,8 +747,8 @@ int orbp_track_source(orbp_map* m, const orbp_view* view, const float* factors, 
     if (src_on_device && ((uintptr_t)src_desc & 15)) return ORBX_ERR_ARG;
     if (!nmatches || (nt > 0 && (!kps_un || !desc || !cell_feat || !t2pos)) || !cell_off) return ORBX_ERR_ARG;
     const orbp::Source src{src_kps, src_desc};
-    return track_one(m, view, F, list, nlist, skip, &src, src_on_device != 0, b, *prm, {kps_un, desc, cell_off, cell_feat, nullptr, std::max(nt, 1), claimed},
-                     nt, frame_on_device != 0, qcap, nullptr, t2pos, t2slot, nmatches, nvisible, stream);
+    return track_one(m, {view, list, nlist, skip, {kps_un, desc, cell_off, cell_feat, nullptr, std::max(nt, 1), claimed}, nt, t2pos, t2slot, nmatches, nvisible}, F,
+                     &src, src_on_device != 0, b, *prm, frame_on_device != 0, qcap, nullptr, stream);
 }
 
 int orbp_view_from_sim3(const float* Scw, orbp_view* view) { return orbp::view_from_sim3(Scw, view); }
@@ -772,7 +770,7 @@ int orbp_loop_project_batch_device(orbp_map* m, const orbp_view* d_views, int nv
     TRY(fit_scratch(m, lay));
     TRY(c.begin());
     void* scratch = m->scratch.as();
-    const orbp::Loop a{d_views, m->capacity, m->geom.as<float>(), m->desc.as<uint8_t>(), m->d_live.as<uint8_t>(), L, nullptr, 0,
+    const orbp::Loop a{d_views, table_of(m), L, nullptr, 0,
                        d_rec ? d_rec : Layout::at(scratch, S.rec), Layout::at(scratch, S.tile_count), {d_qxyr, d_qlev, d_qdesc, d_qpos}, d_nq, d_overflow, qcap, 0};
     HIPCHK(m, orbp::launch_loop_project(a, nviews, F, c.st));
     return c.end();
@@ -807,38 +805,21 @@ int orbp_loop_search(orbp_map* m, const orbp_view* view, const float* factors, i
                      const uint8_t* claimed, int nt, int frame_on_device, int qcap, orbp_fused* rec, int32_t* t2pos, int32_t* t2slot, int* nmatches,
                      int* nvisible, void* stream) {
     const int cap = std::max(nt, 1), lcap = std::max(nlist, 1);
-    const orbp::Frame frame{kps_un, desc, cell_off, cell_feat, nullptr, cap, nullptr};
+    const orbp::Frame frame{kps_un, desc, cell_off, cell_feat, nullptr, cap, claimed};
     orbp::Factors F;
     if (!m || orbp::check_loop_one(view, factors, nlevels, list, nlist, b, orb_dist, frame, nt, frame_on_device != 0, qcap, t2pos, nmatches) != ORBX_OK ||
         fill_factors(factors, nlevels, F) != ORBX_OK)
         return ORBX_ERR_ARG;
     if (orbs_lds_bytes(cap, qcap) > 160 * 1024) return ORBX_ERR_CAPACITY;
-    Call c(m, stream);
+    // its own: nothing goes up beyond the shared slots; the queries, the per-tile counts and unwanted records lie behind the download span
     const orbp::LoopBlock B(cap, lcap, qcap, {skip != nullptr, claimed != nullptr, frame_on_device == 0, t2slot != nullptr, rec != nullptr});
-    Staged s(c, m->block, B.L);
-    TRY(s.fit());
-    uint8_t* const d = s.d;
-    std::memcpy(Layout::at(s.h, B.view), view, sizeof(orbp_view));
-    Layout::at(s.h, B.counts)[0] = nt;
-    Layout::at(s.h, B.counts)[1] = nlist;
-    const int32_t* d_counts = Layout::at(d, B.counts);
-    const orbp::Lists dl{s.put(B.list, list, nlist), d_counts + 1, lcap, s.put(B.skip, skip, nlist)};
-    const orbp::Frame fr = B.frame.stage(s.h, d, frame, nt, d_counts);
-    const orbp::FuseFrames K{fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, d_counts, 1, cap, nullptr};
-    const uint8_t* d_claimed = s.put(B.claimed, claimed, nt);
-    TRY(s.run([&] {
-        int32_t* d_res = Layout::at(d, B.result);                      // nq, overflow, nmatches
-        return loop_locked(m, Layout::at(d, B.view), 1, F, dl, b, orb_dist, K, d_claimed, qcap, B.dev, d,
-                           {Layout::at(d, B.rec), Layout::at(d, B.t2pos), Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1}, c.st);
-    }));
-    const int32_t* res = Layout::at(s.h, B.result);
-    if (nvisible) *nvisible = res[0];
-    if (res[1]) return ORBX_ERR_CAPACITY;
-    *nmatches = res[2];
-    if (nt > 0) std::memcpy(t2pos, Layout::at(s.h, B.t2pos), (size_t)nt * 4);
-    if (nt > 0 && t2slot) std::memcpy(t2slot, Layout::at(s.h, B.t2slot), (size_t)nt * 4);
-    if (rec && nlist > 0) std::memcpy(rec, Layout::at(s.h, B.rec), (size_t)nlist * sizeof(orbp_fused));
-    return ORBX_OK;
+    return one_view(m, stream, B, {view, list, nlist, skip, frame, nt, t2pos, t2slot, nmatches, nvisible}, rec, [](const Staged&) {},
+        [&](hipStream_t st, uint8_t* d, const orbp::Lists& dl, const orbp::Frame& fr) {
+            int32_t* d_res = Layout::at(d, B.result);                      // nq, overflow, nmatches
+            const orbp::FuseFrames K{fr.kps_un, fr.desc, fr.cell_off, fr.cell_feat, fr.nt, 1, cap, nullptr};
+            return loop_locked(m, Layout::at(d, B.view), 1, F, dl, b, orb_dist, K, fr.claimed, qcap, B.dev, d,
+                               {Layout::at(d, B.rec), Layout::at(d, B.t2pos), Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1}, st);
+        });
 }
 
 }  // extern "C"

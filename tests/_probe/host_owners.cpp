@@ -11,8 +11,11 @@
 
 using namespace orbx;
 
-// upload span, download span and total of orbp_track's / orbp_track_source's block against the sizes of the hand-laid block it replaces
+// upload span, download span and total of orbp_track's / orbp_track_source's block (orbp::OneView plus the source slots and the queries)
+// against the sizes of the block before the one-view forms shared a layout, which are those of the hand-laid block before that; one line
+// of the table per flag combination: before -> now
 static bool spans(const orbp::TrackBlock& B, size_t up, size_t down, size_t total) {
+    std::printf("track block: upload %zu -> %zu, download %zu -> %zu, total %zu -> %zu\n", up, B.L.upload(), down, B.L.download(), total, B.L.total());
     const Layout::Slot<int32_t> i32[] = {B.counts, B.list, B.result, B.t2pos, B.t2slot, B.frame.cell_off, B.frame.cell_feat, B.q.qlev, B.q.t2q};
     for (const auto& s : i32)
         if (s.off % 256) return false;

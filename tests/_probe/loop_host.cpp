@@ -1,7 +1,7 @@
 // The host side of orbp_loop_* on the CPU against tests/_probe/hip_stub: orbp_view_from_sim3's arithmetic on a few fixed inputs, the argument
 // checks that need no handle (orbp::check_loop_project, check_loop_search, check_loop_one), the layout of the one-view call's block
-// (orbp::LoopBlock) and its path through orbx::Staged: the upload and download spans are exact, with sentinels around them, and a block that
-// must grow waits for the chain first (tests/test_loop_host.py builds this under AddressSanitizer + UndefinedBehaviorSanitizer).
+// (orbp::LoopBlock over orbp::OneView, whose stage() and unpack() run here) and its path through orbx::Staged: the upload and download spans
+// are exact, with sentinels around them, and a block that must grow waits for the chain first (tests/test_loop_host.py builds this under AddressSanitizer + UndefinedBehaviorSanitizer).
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -62,14 +62,17 @@ int one_view_call(Handle& m, int nt, int nlist, int qcap, bool with_skip, bool w
     std::memset(s.h, 0x11, up);                                       // padding between the slots goes up as it is
     std::memset(s.h + up, 0xA5, hsize - up);
     std::memset(s.d, 0x33, dsize);
-    std::memcpy(Layout::at(s.h, B.view), &view, sizeof(view));
-    Layout::at(s.h, B.counts)[0] = nt;
-    Layout::at(s.h, B.counts)[1] = nlist;
+    std::vector<int32_t> t2pos(cap, -5), t2slot(cap, -5);
+    std::vector<orbp_fused> rec(lcap);
+    std::memset(rec.data(), 0x77, rec.size() * sizeof(orbp_fused));
+    int nmatches = -5, nvisible = -5;
+    const Frame frame{kps.data(), desc.data(), cell_off.data(), cell_feat.data(), nullptr, cap, with_claimed ? claimed.data() : nullptr};
+    const OneViewCall io{&view, list.data(), nlist, with_skip ? skip.data() : nullptr, frame, nt, t2pos.data(), with_t2slot ? t2slot.data() : nullptr, &nmatches, &nvisible};
+    Lists dl;
+    Frame fr;
+    B.stage(s.h, s.d, io, dl, fr);
     const int32_t* d_counts = Layout::at(s.d, B.counts);
-    const Lists dl{s.put(B.list, list.data(), nlist), d_counts + 1, lcap, s.put(B.skip, with_skip ? skip.data() : nullptr, nlist)};
-    const Frame frame{kps.data(), desc.data(), cell_off.data(), cell_feat.data(), nullptr, cap, nullptr};
-    const Frame fr = B.frame.stage(s.h, s.d, frame, nt, d_counts);
-    const uint8_t* d_claimed = s.put(B.claimed, with_claimed ? claimed.data() : nullptr, nt);
+    const uint8_t* d_claimed = fr.claimed;
     bool body_ok = false;
     const int rc = s.run([&] {
         const uint8_t* d = s.d;
@@ -96,6 +99,22 @@ int one_view_call(Handle& m, int nt, int nlist, int qcap, bool with_skip, bool w
     CHECK(hip_stub_up.dst == s.d && hip_stub_up.src == s.h && hip_stub_up.bytes == up);
     CHECK(hip_stub_down.dst == s.h + up && hip_stub_down.src == s.d + up && hip_stub_down.bytes == down);
     CHECK(all(s.h + up, down, 0x22) && all(s.h + up + down, hsize - up - down, 0xA5) && all(s.d + up + down, dsize - up - down, 0x33));
+    // unpack: the result words 0x22222222 mean an overflow, which still reports the visible count and copies nothing else
+    CHECK(B.unpack(s.h, io, with_rec ? rec.data() : nullptr) == ORBX_ERR_CAPACITY && nvisible == 0x22222222 && nmatches == -5 && t2pos[0] == -5);
+    Layout::at(s.h, B.result)[1] = 0;
+    CHECK(B.unpack(s.h, io, with_rec ? rec.data() : nullptr) == ORBX_OK && nmatches == 0x22222222);
+    const bool rec_copied = rec[0].status == 0x22222222 && rec[nlist > 0 ? nlist - 1 : 0].level == 0x22222222;
+    CHECK(nt > 0 ? t2pos[nt - 1] == 0x22222222 : t2pos[0] == -5);
+    CHECK(nt > 0 && with_t2slot ? t2slot[nt - 1] == 0x22222222 : t2slot[0] == -5);
+    CHECK(with_rec && nlist > 0 ? rec_copied : rec[0].status == 0x77777777);
+    return 0;
+}
+
+// the sizes of the block before the one-view forms shared a layout, per flag combination this probe goes through: before -> now
+int same_sizes(int cap, int lcap, int qcap, const LoopBlock::Flags& f, size_t up, size_t down, size_t total) {
+    const LoopBlock B(cap, lcap, qcap, f);
+    std::printf("loop block: upload %zu -> %zu, download %zu -> %zu, total %zu -> %zu\n", up, B.L.upload(), down, B.L.download(), total, B.L.total());
+    CHECK(B.L.upload() <= up && B.L.download() <= down && B.L.total() <= total);
     return 0;
 }
 }  // namespace
@@ -140,11 +159,11 @@ int main() {
     auto off1 = [](auto* p) { return reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + 1); };       // a misaligned address (never read)
     {
         // orbp_loop_project_batch_device
-        const LoopQueries Q{qxyr.data(), ints.data(), qdesc, ints.data()};
+        const Queries Q{qxyr.data(), ints.data(), qdesc, ints.data()};
         int32_t *nq = ints.data(), *ov = ints.data();
         CHECK(check_loop_project(views.data(), nviews, f, 3, L, rec.data(), Q, nq, ov, qcap) == ORBX_OK);
         CHECK(check_loop_project(views.data(), nviews, f, 3, L, nullptr, Q, nq, ov, qcap) == ORBX_OK);          // no records
-        CHECK(check_loop_project(nullptr, 0, f, 3, Lists{nullptr, nullptr, 1, nullptr}, nullptr, LoopQueries{}, nullptr, nullptr, 1) == ORBX_OK);   // no views
+        CHECK(check_loop_project(nullptr, 0, f, 3, Lists{nullptr, nullptr, 1, nullptr}, nullptr, Queries{}, nullptr, nullptr, 1) == ORBX_OK);   // no views
         CHECK(check_loop_project(views.data(), -1, f, 3, L, nullptr, Q, nq, ov, qcap) == ORBX_ERR_ARG);
         CHECK(check_loop_project(views.data(), ORBP_MAX_VIEWS + 1, f, 3, L, nullptr, Q, nq, ov, qcap) == ORBX_ERR_ARG);
         CHECK(check_loop_project(nullptr, nviews, f, 3, L, nullptr, Q, nq, ov, qcap) == ORBX_ERR_ARG);
@@ -169,7 +188,7 @@ int main() {
         CHECK(check_loop_project(views.data(), nviews, f, 3, L, off1(rec.data()), Q, nq, ov, qcap) == ORBX_ERR_ARG);
         CHECK(check_loop_project(views.data(), nviews, f, 3, L, nullptr, Q, nullptr, ov, qcap) == ORBX_ERR_ARG);
         CHECK(check_loop_project(views.data(), nviews, f, 3, L, nullptr, Q, nq, nullptr, qcap) == ORBX_ERR_ARG);
-        LoopQueries q2 = Q;
+        Queries q2 = Q;
         q2.qxyr = nullptr;
         CHECK(check_loop_project(views.data(), nviews, f, 3, L, nullptr, q2, nq, ov, qcap) == ORBX_ERR_ARG);
         q2 = Q; q2.qlev = nullptr;
@@ -305,10 +324,10 @@ int main() {
         // the block with everything in it: slots at multiples of 256, one span up, the results down, the rest behind them
         const LoopBlock B(7, 600, 16, {true, true, true, true, true});
         CHECK(sizeof(orbp_view) == 108 && sizeof(orbp_fused) == 16 && sizeof(orbx_keypoint) == 28 && loop_tiles(600) == 3 && loop_tiles(256) == 1 && loop_tiles(257) == 2);
-        CHECK(B.view.off == 0 && B.counts.off == 256 && B.list.off == 512 && B.skip.off == 512 + 2560 && B.claimed.off == 3072 + 768);
-        CHECK(B.frame.kps.off == 4096 && B.frame.desc.off == 4352 && B.frame.cell_off.off == 4608 && !B.frame.claimed.present);
+        CHECK(B.view.off == 0 && B.counts.off == 256 && B.list.off == 512 && B.skip.off == 512 + 2560);
+        CHECK(B.frame.kps.off == 3072 + 768 && B.frame.desc.off == 4096 && B.frame.cell_off.off == 4352);
         const size_t off_bytes = ((size_t)(ORBF_GRID_CELLS + 1) * 4 + 255) & ~(size_t)255;
-        CHECK(B.frame.cell_feat.off == 4608 + off_bytes && B.L.upload() == 4608 + off_bytes + 256);
+        CHECK(B.frame.cell_feat.off == 4352 + off_bytes && B.frame.claimed.off == 4608 + off_bytes && B.L.upload() == 4608 + off_bytes + 256);
         const size_t up = B.L.upload();
         CHECK(B.result.off == up && B.t2pos.off == up + 256 && B.t2slot.off == up + 512 && B.rec.off == up + 768 && B.L.download() == 768 + 9728);
         const size_t tail = up + B.L.download();
@@ -316,9 +335,16 @@ int main() {
         CHECK(B.L.total() == B.dev.tile_count.off + 256);
         // what the caller does not pass takes no room; records nobody asked for move behind the download span
         const LoopBlock C(7, 600, 16, {false, false, false, false, false});
-        CHECK(!C.skip.present && !C.claimed.present && !C.frame.kps.present && !C.frame.desc.present && !C.frame.cell_off.present && !C.frame.cell_feat.present);
+        CHECK(!C.skip.present && !C.frame.claimed.present && !C.frame.kps.present && !C.frame.desc.present && !C.frame.cell_off.present && !C.frame.cell_feat.present);
         CHECK(C.L.upload() == 512 + 2560 && !C.t2slot.present && !C.rec.present && C.L.download() == 512 && C.dev.rec.present && C.dev.rec.off >= C.L.upload() + 512);
         CHECK(C.L.total() == C.dev.rec.off + 9728);
+        // the flags of a resident key frame are a host array all the same: they go up without the frame
+        const LoopBlock D(7, 600, 16, {false, true, false, false, false});
+        CHECK(D.frame.claimed.present && !D.frame.kps.present && D.frame.claimed.off == 512 + 2560 && D.L.upload() == 3072 + 256);
+        CHECK(same_sizes(7, 600, 16, {true, true, true, true, true}, 17408, 10496, 30208) == 0 && same_sizes(7, 600, 16, {false, false, false, false, false}, 3072, 512, 15616) == 0);
+        CHECK(same_sizes(300, 600, 640, {true, true, true, true, true}, 36352, 12544, 89088) == 0 && same_sizes(1, 1, 1, {false, false, false, false, false}, 768, 512, 3584) == 0);
+        CHECK(same_sizes(1, 1, 1, {false, true, true, true, true}, 14336, 1024, 17408) == 0 && same_sizes(2000, 8000, 8000, {true, true, true, true, true}, 183552, 144640, 816896) == 0);
+        CHECK(same_sizes(2000, 8000, 8192, {true, true, false, false, false}, 42752, 8448, 679424) == 0);
         // the batch forms' scratch: the projection alone has no query arrays of its own; gathered rows only when asked for
         Layout P;
         LoopSlots S;

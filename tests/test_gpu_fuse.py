@@ -211,14 +211,10 @@ def planted_keyframe(rng, b):
     return (k, d, off, feat), named
 
 
-@pytest.mark.parametrize("th", [2.5, 4.0])
-def test_planted_entries(th):
-    rng = np.random.default_rng(7)
-    b = fs.bounds()
-    factors = fr.scale_factors(8)
-    frame, named = planted_keyframe(rng, b)
+def planted_points(rng, b, factors, frame, named, V):
+    """map points on either side of each test of ORBP_MODE_FUSE, seen through the exact view V and aimed at the features planted_keyframe
+    named -> (rows: name, expected status, ..., table: pos, normal, dmin, dmax, desc in the rows' order); tests/test_gpu_entry_test.py plants them too"""
     k, d = frame[0], frame[1]
-    V = exact_view(b, th)
     rows = []                                                          # (name, X, Y, Z, level or None, normal or None, dmin, dmax, desc, expected status)
 
     def aim(name, X, Y, level, desc, status, Z=2.0, normal=None, dmin=None, dmax=None):
@@ -265,7 +261,19 @@ def test_planted_entries(th):
                    "far": F32(dist[i] / F32(100))}[r["dmin"]]
         dmax[i] = {None: F32(dist[i] * F32(2)), "dist": dist[i], "below": np.nextafter(dist[i], F32(0))}[r["dmax"]]
     desc = np.stack([r["desc"] for r in rows])
-    table = dict(pos=pos, normal=nrm, dmin=dmin, dmax=dmax, desc=desc)
+    return rows, dict(pos=pos, normal=nrm, dmin=dmin, dmax=dmax, desc=desc)
+
+
+@pytest.mark.parametrize("th", [2.5, 4.0])
+def test_planted_entries(th):
+    rng = np.random.default_rng(7)
+    b = fs.bounds()
+    factors = fr.scale_factors(8)
+    frame, named = planted_keyframe(rng, b)
+    V = exact_view(b, th)
+    rows, table = planted_points(rng, b, factors, frame, named, V)
+    n = len(rows)
+    pos, nrm, dmin, dmax, desc = (table[key] for key in ("pos", "normal", "dmin", "dmax", "desc"))
     live = np.ones(n + 4, np.uint8)
     live[n:] = 0                                                       # free slots behind the planted points
     tab = capi.MapPointTable(n + 4)
