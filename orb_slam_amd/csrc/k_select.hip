@@ -19,34 +19,52 @@ namespace orbx {
 // QUOTA_MAX_CELLS = what 160 KiB hold)
 struct QuotaLds { int *nkeys, *nret; uint8_t *thr, *done; };
 
-__global__ __launch_bounds__(64) void k_quota(Batch b) {
+__global__ __launch_bounds__(64) void k_quota(Batch b, unsigned magic) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DevGeom& g = b.g;
+    asm volatile("" ::"s"(b.xcd_affinity), "s"(b.nframes), "s"(g.nlevels), "s"(g.quota_cells), "s"(b.cellrec), "s"(b.cstate), "s"(b.csel), "s"(b.cbands),
+                 "s"(g.ncells_total), "s"(g.nbands_total), "s"(g.fast_th));   // (fetched together, see k_cell_select_body)
+    int frame, level;
+    if (!frame_item_magic(b, blockIdx.x, (unsigned)g.nlevels, magic, frame, level)) return;     // (a frame of the padding: nothing touched)
     QuotaLds q;
     q.nkeys = reinterpret_cast<int*>(smem);
     q.nret = q.nkeys + g.quota_cells;
     q.thr = reinterpret_cast<uint8_t*>(q.nret + g.quota_cells);
     q.done = q.thr + g.quota_cells;
-    const int frame = blockIdx.x / g.nlevels, level = blockIdx.x - frame * g.nlevels;
     const int lane = (int)threadIdx.x;
     const LevelGeom& L = g.lv[level];
-    const CellGeom* cg = b.cells + L.cell_base;
+    const CellRec* rec = b.cellrec + L.cell_base;
     const CellState* cs = b.cstate + (long long)frame * g.nbands_total;   // per band; a cell sums its bands
     CellSel* sel = b.csel + (long long)frame * g.ncells_total + L.cell_base;
+    CellBands* sbn = b.cbands + (long long)frame * g.ncells_total + L.cell_base;
     const int nCells = L.ncells, nfc = L.nfeat_cell;
-    // first pass of the reference (:622-641), fused with the gather of the cells' counts
+    // first pass of the reference (:622-641), fused with the gather of the cells' counts.  The bands' states are fetched side by side (one
+    // round trip behind the cell's record, not one per band) and their list lengths go on to k_cell_select: the sum in the cell's CellSel,
+    // those of a cell of several bands in its CellBands.
     int dist = 0, nomore = 0;
     for (int c = lane; c < nCells; c += 64) {
-        const CellGeom cgc = cg[c];
-        int n_hi = 0, n_lo = 0;
-        for (int k = 0; k < cgc.nbands; k++) { const CellState t = cs[cgc.band0 + k]; n_hi += t.n_hi; n_lo += t.n_lo; }
+        const int nb = rec[c].nbands, skipped = rec[c].skipped, band0 = rec[c].band0;
+        CellState t[CELL_REC_BANDS];
+#pragma unroll
+        for (int k = 0; k < CELL_REC_BANDS; k++) { t[k].n_all = 0; t[k].n_hi = 0; t[k].n_lo = 0; t[k].thr = 0; if (k < nb) t[k] = cs[band0 + k]; }
+        int n_hi = 0, n_lo = 0, n_all = 0;
+#pragma unroll
+        for (int k = 0; k < CELL_REC_BANDS; k++) { n_hi += t[k].n_hi; n_lo += t[k].n_lo; n_all += t[k].n_all; }
+        if (nb > 1) {
+            CellBands bn;
+#pragma unroll
+            for (int k = 0; k < CELL_REC_BANDS; k++) bn.n[k] = t[k].n_all;
+            sbn[c] = bn;
+        }
+        for (int k = CELL_REC_BANDS; k < nb; k++) { const CellState u = cs[band0 + k]; n_hi += u.n_hi; n_lo += u.n_lo; n_all += u.n_all; }
+        sel[c].n_all = n_all;
         const bool fallback = n_hi <= 3;                      // :609  size()<=3 -> FAST(...,7,...)
-        const int nk = cgc.skipped ? 0 : (fallback ? n_lo : n_hi);
-        q.thr[c] = (uint8_t)(cgc.skipped || !fallback ? g.fast_th : 7);
+        const int nk = skipped ? 0 : (fallback ? n_lo : n_hi);
+        q.thr[c] = (uint8_t)(skipped || !fallback ? g.fast_th : 7);
         q.nkeys[c] = nk;
         // a skipped cell takes the reference's `continue`: it never reaches the bookkeeping of this pass (and is then treated as an
         // open cell with no keypoints by the passes below, exactly like there)
-        if (cgc.skipped) { q.nret[c] = 0; q.done[c] = 0; }
+        if (skipped) { q.nret[c] = 0; q.done[c] = 0; }
         else if (nk > nfc) { q.nret[c] = nfc; q.done[c] = 0; }
         else { q.nret[c] = nk; dist += nfc - nk; q.done[c] = 1; nomore++; }
     }
@@ -74,11 +92,9 @@ __global__ __launch_bounds__(64) void k_quota(Batch b) {
         const int v = c < nCells ? q.nret[c] : 0;
         const int incl = wave_scan_inclusive(v);
         if (c < nCells) {
-            CellSel r;
-            r.thr = q.thr[c]; r.nkeys = q.nkeys[c];
-            r.nretain = bad ? 0 : v;
-            r.out_off = bad ? 0 : base + incl - v;
-            sel[c] = r;
+            sel[c].thr = q.thr[c];                                     // (n_all was stored above)
+            sel[c].nretain = bad ? 0 : v;
+            sel[c].out_off = bad ? 0 : base + incl - v;
         }
         base += __builtin_amdgcn_readlane(incl, 63);
     }
@@ -306,34 +322,49 @@ __device__ float harris_response(const uint8_t* img, long long step, int x, int 
 // (one-wave workgroups with the full staging area, each looking after 8 consecutive cells).
 constexpr int SEL_SMALL = 384;
 __host__ __device__ constexpr int sel_wave_bytes(int entries) { return (entries * ((int)sizeof(Cand) + 4) + 16 + 15) & ~15; }
-// one wave; returns false when the cell's list belongs to the other length class (it did nothing)
+// The plane Harris reads for the cell of record `rc` (plain_plane with the level's plane offset and stride taken from the record)
 template <bool GATHER>
-__device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int cell, int level, uint8_t* smem, int lds_entries, int min_entries, int lane) {
+__device__ __forceinline__ const uint8_t* cell_plane(const Batch& b, const CellRec& rc, int frame, long long& stride) {
+    if (rc.level == 0) {
+        if constexpr (GATHER) return level0_src(b, frame, stride);
+        stride = b.img_row_stride;
+        return b.img + (long long)frame * b.img_frame_stride;
+    }
+    stride = rc.stride;
+    return b.pyr + (long long)frame * b.g.frame_plane_bytes + rc.plane_off;
+}
+// one wave; returns false when the cell's list belongs to the other length class (it did nothing).
+// A wave's metadata is three records, fetched side by side behind the kernel arguments and waited for once: the cell's CellRec and the
+// (frame, cell)'s CellSel and CellBands.  Every test that ends the wave early comes after that wait; then the list gather.
+template <bool GATHER>
+__device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int cell, uint8_t* smem, int lds_entries, int lane) {
     const DevGeom& g = b.g;
-    const LevelGeom& L = g.lv[level];
-    const CellGeom cgeo = b.cells[cell];
-    const CellSel s = b.csel[(long long)frame * g.ncells_total + cell];
+    CellRec rc;
+    CellSel s;
+    CellBands bn;
+    load_cell_records(b, cell, (long long)frame * g.ncells_total + cell, rc, s, bn);
     if (s.nretain <= 0) return true;
+    const int n_all = s.n_all;
+    if (n_all > lds_entries && lds_entries < g.sel_lds_entries) return false;   // the other class
     // the cell's list = its bands' sub-lists in band (= raster) order
-    const CellState* bst = b.cstate + (long long)frame * g.nbands_total + cgeo.band0;
-    const BandGeom* bgs = b.bands + cgeo.band0;
-    Cand* lbase = b.cand + (long long)frame * g.frame_cands + L.cand_base;
-    Cand* c = lbase + cgeo.cand_off;
-    int n_all = 0;
-    for (int k = 0; k < cgeo.nbands; k++) n_all += bst[k].n_all;
-    if (n_all < min_entries || (n_all > lds_entries && lds_entries < g.sel_lds_entries)) return false;   // the other class
-    Cand* out = b.sel + (long long)frame * g.frame_sel + L.sel_base + s.out_off;
+    Cand* fcand = b.cand + (long long)frame * g.frame_cands;
+    Cand* out = b.sel + (long long)frame * g.frame_sel + rc.sel_base + s.out_off;
     const float thr = (float)s.thr;
-    long long stride;
-    const uint8_t* img = plain_plane<GATHER>(b, L, level, frame, stride);
+    const bool listed = rc.nbands <= CELL_REC_BANDS;          // the records name every band; else the generic walk over BandGeom / CellState
+    // (generic walk only: its pointers are formed where it runs, so that the common path does not wait for their kernel arguments)
+    auto band_list = [&](int k) { return fcand + g.lv[rc.level].cand_base + b.bands[rc.band0 + k].cand_off; };
+    auto band_len = [&](int k) { return b.cstate[(long long)frame * g.nbands_total + rc.band0 + k].n_all; };
     if (n_all > lds_entries) {
         // rare: list longer than the LDS staging area -> the plain sequential algorithm in global memory
         // (filtered entries are compacted to the front of the cell's area; the write index never passes the read index)
         if (lane == 0) {
+            long long stride;
+            const uint8_t* img = cell_plane<GATHER>(b, rc, frame, stride);
+            Cand* c = fcand + rc.cand_off;
             int m = 0;
-            for (int k = 0; k < cgeo.nbands; k++) {
-                const Cand* bc = lbase + bgs[k].cand_off;
-                const int nb = bst[k].n_all;
+            for (int k = 0; k < rc.nbands; k++) {
+                const Cand* bc = band_list(k);
+                const int nb = band_len(k);
                 for (int i = 0; i < nb; i++) { const Cand e = bc[i]; if (e.resp >= thr) c[m++] = e; }
             }
             if (g.score_type == ORBX_HARRIS_SCORE)
@@ -349,9 +380,7 @@ __device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int 
     uint16_t* rpos = lpos + lds_entries;
     const unsigned long long lt = (1ull << lane) - 1ull;
     int m = 0;
-    for (int k = 0; k < cgeo.nbands; k++) {
-        const Cand* bc = lbase + bgs[k].cand_off;
-        const int nb = bst[k].n_all;
+    auto take_band = [&](const Cand* bc, int nb) {
         for (int base = 0; base < nb; base += 256) {           // four loads in flight per lane, then the ordered filter chunk by chunk
             Cand e4[4];
 #pragma unroll
@@ -370,9 +399,20 @@ __device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int 
                 m += __popcll(mk);
             }
         }
+    };
+    if (listed) {
+#pragma unroll
+        for (int k = 0; k < CELL_REC_BANDS; k++) {            // (unrolled: the records sit in SGPRs, which take no run-time index)
+            if (k >= rc.nbands) break;
+            take_band(fcand + rc.band_cand[k], rc.nbands == 1 ? s.n_all : bn.n[k]);
+        }
+    } else {
+        for (int k = 0; k < rc.nbands; k++) take_band(band_list(k), band_len(k));
     }
     wave_lds_fence();
     if (g.score_type == ORBX_HARRIS_SCORE) {
+        long long stride;
+        const uint8_t* img = cell_plane<GATHER>(b, rc, frame, stride);
         for (int i = lane; i < m; i += 64) lst[i].resp = harris_response(img, stride, lst[i].pos & 0xFFFF, lst[i].pos >> 16, g.fp_contract);
         wave_lds_fence();
     }
@@ -382,22 +422,30 @@ __device__ __forceinline__ bool cell_select_body(const Batch& b, int frame, int 
     return true;
 }
 
+// Blocks map to (frame, four cells) through frame_item_magic: with the frame -> XCD affinity a frame's selection waves run on the XCD whose L2
+// k_fast_cells left its lists in and k_describe_od reads the selected ones from.  The waves of a workgroup belong to one frame; those past
+// its last cell exit.
 template <bool GATHER>
-__device__ __forceinline__ void k_cell_select_body(const Batch& b, int lds_entries) {
+__device__ __forceinline__ void k_cell_select_body(const Batch& b, int lds_entries, unsigned magic) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DevGeom& g = b.g;
     const int wave = wave_id(), lane = (int)threadIdx.x & 63;
-    const int id = (int)blockIdx.x * 4 + wave;
-    if (id >= b.nframes * g.ncells_total) return;
-    const int frame = id / g.ncells_total, cell = id - frame * g.ncells_total;
-    const bool done = cell_select_body<GATHER>(b, frame, cell, find_level(g.cell_bases, cell), smem + wave * sel_wave_bytes(lds_entries), lds_entries, 0, lane);
-    if (lane == 0) b.long_cells[id] = done ? 0 : 1;          // a flag per cell: no list, no atomics (one counter for ~150 k long cells of a
-                                                            // noise-like batch serialised for 1.3 ms, 64 sharded ones still for 0.5)
+    // every kernel argument a wave of the common path reads, named once in front: they are fetched together, not each behind the test
+    // that guards its use
+    asm volatile("" ::"s"(b.xcd_affinity), "s"(b.nframes), "s"(g.ncells_total), "s"(b.cellrec), "s"(b.csel), "s"(b.cbands), "s"(g.sel_lds_entries), "s"(b.cand),
+                 "s"(b.sel), "s"(g.frame_cands), "s"(g.frame_sel), "s"(b.long_cells));
+    int frame, item;
+    if (!frame_item_magic(b, blockIdx.x, (unsigned)(g.ncells_total + 3) >> 2, magic, frame, item)) return;
+    const int cell = item * 4 + wave;
+    if (cell >= g.ncells_total) return;
+    const bool done = cell_select_body<GATHER>(b, frame, cell, smem + wave * sel_wave_bytes(lds_entries), lds_entries, lane);
+    if (lane == 0) b.long_cells[frame * g.ncells_total + cell] = done ? 0 : 1;   // a flag per cell: no list, no atomics (one counter for ~150 k long cells of a
+                                                                                // noise-like batch serialised for 1.3 ms, 64 sharded ones still for 0.5)
 }
-__global__ __launch_bounds__(256) void k_cell_select(Batch b, int lds_entries) { k_cell_select_body<false>(b, lds_entries); }
-__global__ __launch_bounds__(256) void k_cell_select_gather(Batch b, int lds_entries) { k_cell_select_body<true>(b, lds_entries); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cell_select(Batch b, int lds_entries, unsigned magic) { k_cell_select_body<false>(b, lds_entries, magic); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cell_select_gather(Batch b, int lds_entries, unsigned magic) { k_cell_select_body<true>(b, lds_entries, magic); }
 // The cells k_cell_select left over (lists beyond its staging area).  A workgroup of four waves looks at the flags of SEL_LONG_CHUNK
-// consecutive cells and shares ONE full staging area (sel_lds_entries entries) by list length: lists that fit a quarter of it are taken
+// consecutive cells of one frame and shares ONE full staging area (sel_lds_entries entries) by list length: lists that fit a quarter of it are taken
 // four at a time (one wave each), lists that fit a third three at a time, half two at a time, the rest one at a time with all of it.  A wave's selection
 // is latency-bound (~20 us per cell whatever its length: ten partition passes of a few dependent LDS round trips each), so what counts
 // is the number of cells in flight per CU, and that is set by the LDS a cell holds.  (Rounds 2-4: one-wave workgroups with the full area
@@ -414,29 +462,17 @@ __host__ __device__ constexpr int sel_long_bytes(int entries) {      // the shar
     for (int share = 1; share <= 4; share++) { const int v = share * sel_wave_bytes((entries + share - 1) / share); m = v > m ? v : m; }
     return m;
 }
-template <bool GATHER>
-__device__ __forceinline__ void k_cell_select_long_body(const Batch& b) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const DevGeom& g = b.g;
-    const int lane = (int)threadIdx.x & 63, wave = wave_id(), total = b.nframes * g.ncells_total;
-    const int id0 = (int)blockIdx.x * SEL_LONG_CHUNK;
-    static_assert(SEL_LONG_CHUNK <= 64, "one flag per lane");
-    const int quarter = (g.sel_lds_entries + 3) / 4, third = (g.sel_lds_entries + 2) / 3, half = (g.sel_lds_entries + 1) / 2;
-    // every wave reads the same flags and list lengths (lane i: cell id0 + i)
-    int n_all = 0;
-    const bool mine = lane < SEL_LONG_CHUNK && id0 + lane < total && b.long_cells[id0 + lane] != 0;
-    if (mine) {
-        const int id = id0 + lane, frame = id / g.ncells_total, cell = id - frame * g.ncells_total;
-        const CellGeom cgeo = b.cells[cell];
-        const CellState* bst = b.cstate + (long long)frame * g.nbands_total + cgeo.band0;
-        for (int k = 0; k < cgeo.nbands; k++) n_all += bst[k].n_all;
-    }
-    const unsigned long long mQ = __ballot(mine && n_all <= quarter), mT = __ballot(mine && n_all > quarter && n_all <= third),
-                             mH = __ballot(mine && n_all > third && n_all <= half), mF = __ballot(mine && n_all > half);
+// The sharing itself, for k_cell_select_long and k_level_select alike: lane i of every wave holds the length n of the workgroup's item i
+// (`mine`: it has a list to select from).  Class by class (quarter, third, half, whole area) `share` waves work side by side, wave w on the
+// class's items of rank w, w + share, ... in its own part of the area: take(item, area, entries).
+template <class Take>
+__device__ __forceinline__ void shared_area_select(bool mine, int n, int sel_lds_entries, uint8_t* smem, int wave, Take take) {
+    const int quarter = (sel_lds_entries + 3) / 4, third = (sel_lds_entries + 2) / 3, half = (sel_lds_entries + 1) / 2;
+    const unsigned long long mQ = __ballot(mine && n <= quarter), mT = __ballot(mine && n > quarter && n <= third),
+                             mH = __ballot(mine && n > third && n <= half), mF = __ballot(mine && n > half);
     if (!(mQ | mT | mH | mF)) return;
-    // class c: `share` waves work side by side, wave w on the class's cells of rank w, w + share, ... in its own part of the area
     const unsigned long long cls_m[4] = {mQ, mT, mH, mF};
-    const int cls_share[4] = {4, 3, 2, 1}, cls_entries[4] = {quarter, third, half, g.sel_lds_entries};
+    const int cls_share[4] = {4, 3, 2, 1}, cls_entries[4] = {quarter, third, half, sel_lds_entries};
 #pragma unroll 1
     for (int c = 0; c < 4; c++) {
         unsigned long long m = cls_m[c];
@@ -445,58 +481,92 @@ __device__ __forceinline__ void k_cell_select_long_body(const Batch& b) {
         if (wave < share) {
             uint8_t* area = smem + wave * sel_wave_bytes(entries);
             for (int r = 0; m; r++) {
-                const int id = id0 + __ffsll((long long)m) - 1;
+                const int item = __ffsll((long long)m) - 1;
                 m &= m - 1;
                 if (r % share != wave) continue;
-                const int frame = id / g.ncells_total, cell = id - frame * g.ncells_total;
-                (void)cell_select_body<GATHER>(b, frame, cell, find_level(g.cell_bases, cell), area, entries, 0, lane);
+                take(item, area, entries);
                 wave_lds_fence();
             }
         }
         __syncthreads();                                       // the parts change owners
     }
 }
-__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long(Batch b) { k_cell_select_long_body<false>(b); }
-__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long_gather(Batch b) { k_cell_select_long_body<true>(b); }
-
-// reference :697-701 (per-level cap), same scheme; one wave
-__device__ __forceinline__ void level_select_body(const Batch& b, int frame, int level, uint8_t* smem, int lane) {
-    const DevGeom& g = b.g;
-    const LevelGeom& L = g.lv[level];
-    const int total = b.level_total[frame * MAX_LEVELS + level];
-    int n = total;
-    if (total > L.ndesired) {
-        n = L.ndesired;
-        if (n > 0) {
-            Cand* v = b.sel + (long long)frame * g.frame_sel + L.sel_base;
-            if (total > g.sel_lds_entries) {
-                if (lane == 0) std::nth_element(v, v + n, v + total, RespGreater());
-            } else {
-                Cand* lst = reinterpret_cast<Cand*>(smem);
-                uint16_t* lpos = reinterpret_cast<uint16_t*>(smem + (size_t)g.sel_lds_entries * sizeof(Cand));
-                uint16_t* rpos = lpos + g.sel_lds_entries;
-                // four loads in flight per lane (one per iteration made the gather a chain of round trips: 7 for a VGA level 0)
-                for (int i0 = 0; i0 < total; i0 += 256) {
-                    Cand e[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { const int i = i0 + 64 * k + lane; if (i < total) e[k] = v[i]; }
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { const int i = i0 + 64 * k + lane; if (i < total) lst[i] = e[k]; }
-                }
-                wave_lds_fence();
-                wave_nth_element(lst, 0, n, total, lpos, rpos, lane);
-                for (int i = lane; i < n; i += 64) v[i] = lst[i];
-            }
-        }
-    }
-    if (lane == 0) b.level_count[frame * MAX_LEVELS + level] = n;
-}
-
-__global__ __launch_bounds__(64) void k_level_select(Batch b) {
+template <bool GATHER>
+__device__ __forceinline__ void k_cell_select_long_body(const Batch& b, unsigned magic) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DevGeom& g = b.g;
-    const int frame = blockIdx.x / g.nlevels, level = blockIdx.x - frame * g.nlevels;
-    level_select_body(b, frame, level, smem, (int)threadIdx.x);
+    const int lane = (int)threadIdx.x & 63, wave = wave_id();
+    static_assert(SEL_LONG_CHUNK <= 64, "one flag per lane");
+    asm volatile("" ::"s"(b.xcd_affinity), "s"(b.nframes), "s"(g.ncells_total), "s"(b.long_cells), "s"(g.sel_lds_entries));   // (fetched together, see k_cell_select_body)
+    int frame, item;
+    if (!frame_item_magic(b, blockIdx.x, (unsigned)(g.ncells_total + SEL_LONG_CHUNK - 1) / SEL_LONG_CHUNK, magic, frame, item)) return;
+    const int cell0 = item * SEL_LONG_CHUNK;
+    // every wave reads the same flags and, of the flagged cells (normally none), the list lengths (lane i: cell cell0 + i)
+    const long long id = (long long)frame * g.ncells_total + cell0 + lane;
+    const bool mine = lane < SEL_LONG_CHUNK && cell0 + lane < g.ncells_total && b.long_cells[id] != 0;
+    const int n_all = mine ? b.csel[id].n_all : 0;
+    shared_area_select(mine, n_all, g.sel_lds_entries, smem, wave, [&](int i, uint8_t* area, int entries) {
+        (void)cell_select_body<GATHER>(b, frame, cell0 + i, area, entries, lane);
+    });
+}
+__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long(Batch b, unsigned magic) { k_cell_select_long_body<false>(b, magic); }
+__global__ __launch_bounds__(SEL_LONG_WAVES * 64) void k_cell_select_long_gather(Batch b, unsigned magic) { k_cell_select_long_body<true>(b, magic); }
+
+// reference :697-701 (per-level cap), same scheme; one wave on a level whose `total` exceeds its ndesired = n > 0, in a staging area of `entries`
+__device__ __forceinline__ void level_select_body(const Batch& b, int frame, int level, int total, int n, uint8_t* smem, int entries, int lane) {
+    const DevGeom& g = b.g;
+    Cand* v = b.sel + (long long)frame * g.frame_sel + g.lv[level].sel_base;
+    if (total > entries) {                                     // (beyond the whole area: entries == sel_lds_entries here)
+        if (lane == 0) std::nth_element(v, v + n, v + total, RespGreater());
+        return;
+    }
+    Cand* lst = reinterpret_cast<Cand*>(smem);
+    uint16_t* lpos = reinterpret_cast<uint16_t*>(smem + (size_t)entries * sizeof(Cand));
+    uint16_t* rpos = lpos + entries;
+    // four loads in flight per lane (one per iteration made the gather a chain of round trips: 7 for a VGA level 0)
+    for (int i0 = 0; i0 < total; i0 += 256) {
+        Cand e[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const int i = i0 + 64 * k + lane; if (i < total) e[k] = v[i]; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const int i = i0 + 64 * k + lane; if (i < total) lst[i] = e[k]; }
+    }
+    wave_lds_fence();
+    wave_nth_element(lst, 0, n, total, lpos, rpos, lane);
+    for (int i = lane; i < n; i += 64) v[i] = lst[i];
+}
+
+// Full launch groups: a workgroup of four waves looks at LSEL_CHUNK consecutive levels of one frame and shares one staging area among their
+// lists by length, exactly like k_cell_select_long (a one-wave workgroup with the whole area for every level, whatever its total, held the
+// launch at six waves per CU).  A level whose total is within its ndesired only stores its count.
+constexpr int LSEL_CHUNK = 4, LSEL_WAVES = 4;
+__global__ __launch_bounds__(LSEL_WAVES * 64) void k_level_select(Batch b, unsigned magic) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const DevGeom& g = b.g;
+    const int lane = (int)threadIdx.x & 63, wave = wave_id();
+    asm volatile("" ::"s"(b.xcd_affinity), "s"(b.nframes), "s"(g.nlevels), "s"(b.level_total), "s"(b.level_count), "s"(g.sel_lds_entries), "s"(b.sel),
+                 "s"(g.frame_sel));                             // (fetched together, see k_cell_select_body)
+    int frame, item;
+    if (!frame_item_magic(b, blockIdx.x, (unsigned)(g.nlevels + LSEL_CHUNK - 1) / LSEL_CHUNK, magic, frame, item)) return;
+    const int level0 = item * LSEL_CHUNK;
+    // every wave reads the same totals (lane i: level level0 + i)
+    const bool valid = lane < LSEL_CHUNK && level0 + lane < g.nlevels;
+    int total = 0, nd = 0;
+    if (valid) { total = b.level_total[frame * MAX_LEVELS + level0 + lane]; nd = g.lv[level0 + lane].ndesired; }
+    if (valid && wave == 0) b.level_count[frame * MAX_LEVELS + level0 + lane] = total > nd ? nd : total;
+    shared_area_select(valid && total > nd && nd > 0, total, g.sel_lds_entries, smem, wave, [&](int i, uint8_t* area, int entries) {
+        level_select_body(b, frame, level0 + i, __builtin_amdgcn_readlane(total, i), __builtin_amdgcn_readlane(nd, i), area, entries, lane);
+    });
+}
+// Launch groups too small to fill the chip (the one-frame call): one wave per level with the whole area.  Their few lists all run at once,
+// so the LDS a list holds limits nothing, and a shared workgroup would take its classes one after the other.
+__global__ __launch_bounds__(64) void k_level_select_one(Batch b) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const DevGeom& g = b.g;
+    const int frame = blockIdx.x / g.nlevels, level = blockIdx.x - frame * g.nlevels, lane = (int)threadIdx.x;
+    const int total = b.level_total[frame * MAX_LEVELS + level], nd = g.lv[level].ndesired;
+    if (lane == 0) b.level_count[frame * MAX_LEVELS + level] = total > nd ? nd : total;
+    if (total > nd && nd > 0) level_select_body(b, frame, level, total, nd, smem, g.sel_lds_entries, lane);
 }
 
 // diagnostics: wave_nth_element on a caller-supplied response list (pos carries the original index)
@@ -524,7 +594,7 @@ int launch_quota(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const DevGeom& g = hg.g;
     const size_t lds = (size_t)g.quota_cells * QUOTA_LDS_PER_CELL;
     if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quota), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
-    hipLaunchKernelGGL(k_quota, dim3(b.nframes * g.nlevels), dim3(64), lds, stream, b);
+    hipLaunchKernelGGL(k_quota, dim3(frame_item_blocks(b, g.nlevels)), dim3(64), lds, stream, b, frame_item_magic_of(g.nlevels));
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }
@@ -538,13 +608,15 @@ int launch_cell_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const size_t lds = (size_t)4 * sel_wave_bytes(small);
     auto* const ksel = b.img_tab ? k_cell_select_gather : k_cell_select;      // (gather form: Harris reads the caller's frames)
     if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ksel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
-    hipLaunchKernelGGL(ksel, dim3((F * g.ncells_total + 3) / 4), dim3(256), lds, stream, b, small);
+    const int per4 = (g.ncells_total + 3) / 4;
+    hipLaunchKernelGGL(ksel, dim3(frame_item_blocks(b, per4)), dim3(256), lds, stream, b, small, frame_item_magic_of(per4));
     ORBX_LAUNCH_CHECK();
     if (small < g.sel_lds_entries) {
         const size_t ldsl = (size_t)sel_long_bytes(g.sel_lds_entries);
         auto* const klong = b.img_tab ? k_cell_select_long_gather : k_cell_select_long;
         if (ldsl > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(klong), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl) != hipSuccess) return ORBX_ERR_DEVICE;
-        hipLaunchKernelGGL(klong, dim3((F * g.ncells_total + SEL_LONG_CHUNK - 1) / SEL_LONG_CHUNK), dim3(SEL_LONG_WAVES * 64), ldsl, stream, b);
+        const int perl = (g.ncells_total + SEL_LONG_CHUNK - 1) / SEL_LONG_CHUNK;
+        hipLaunchKernelGGL(klong, dim3(frame_item_blocks(b, perl)), dim3(SEL_LONG_WAVES * 64), ldsl, stream, b, frame_item_magic_of(perl));
         ORBX_LAUNCH_CHECK();
     }
     return ORBX_OK;
@@ -552,9 +624,16 @@ int launch_cell_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
 
 int launch_level_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const DevGeom& g = hg.g;
-    const size_t lds = (size_t)g.sel_lds_level;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
-    hipLaunchKernelGGL(k_level_select, dim3(b.nframes * g.nlevels), dim3(64), lds, stream, b);
+    if (b.nframes < PYR_FUSED_MAX_FRAMES) {
+        const size_t lds = (size_t)g.sel_lds_level;
+        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level_select_one), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
+        hipLaunchKernelGGL(k_level_select_one, dim3(b.nframes * g.nlevels), dim3(64), lds, stream, b);
+    } else {
+        const size_t lds = (size_t)sel_long_bytes(g.sel_lds_entries);
+        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
+        const int per = (g.nlevels + LSEL_CHUNK - 1) / LSEL_CHUNK;
+        hipLaunchKernelGGL(k_level_select, dim3(frame_item_blocks(b, per)), dim3(LSEL_WAVES * 64), lds, stream, b, frame_item_magic_of(per));
+    }
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }

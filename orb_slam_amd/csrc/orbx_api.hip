@@ -25,8 +25,8 @@ struct orbx_extractor {
     int gw = 0, gh = 0;
     HostGeom hg;
     struct __attribute__((visibility("hidden"))) Geom {
-        DevBuf cells, bands, tabx, taby, pyr_tab;
-        DevBuf pyr, blur, cand, sel, cstate, csel, level_total, level_count, status, long_cells;
+        DevBuf cells, cellrecs, bands, tabx, taby, pyr_tab;
+        DevBuf pyr, blur, cand, sel, cstate, csel, cbands, level_total, level_count, status, long_cells;
     } geo;
     bool fallback_hint = true;        // ORBX_FALLBACK_HINT=0 at orbx_create
     // single-frame staging for orbx_extract
@@ -106,6 +106,7 @@ static int ensure_geometry(orbx_extractor* h, int w, int hgt) {
     const size_t B = (size_t)h->p.max_batch;
     orbx_extractor::Geom& d = h->geo;
     if ((rc = upload(h, d.cells, h->hg.cells)) != ORBX_OK) return rc;
+    if ((rc = upload(h, d.cellrecs, h->hg.cellrecs)) != ORBX_OK) return rc;
     if ((rc = upload(h, d.bands, h->hg.bands)) != ORBX_OK) return rc;
     if ((rc = upload(h, d.tabx, h->hg.tabx)) != ORBX_OK) return rc;
     if ((rc = upload(h, d.taby, h->hg.taby)) != ORBX_OK) return rc;
@@ -117,6 +118,8 @@ static int ensure_geometry(orbx_extractor* h, int w, int hgt) {
     HIPCHK(h, d.cstate.ensure(B * g.nbands_total * sizeof(CellState)));
     HIPCHK(h, hipMemset(d.cstate, 0, B * g.nbands_total * sizeof(CellState)));      // (the fallback runs start at 0: k_fast_cells reads its slot's state before it writes it)
     HIPCHK(h, d.csel.ensure(B * g.ncells_total * sizeof(CellSel)));
+    HIPCHK(h, d.cbands.ensure(B * g.ncells_total * sizeof(CellBands)));
+    HIPCHK(h, hipMemset(d.cbands, 0, B * g.ncells_total * sizeof(CellBands)));
     HIPCHK(h, d.level_total.ensure(B * MAX_LEVELS * sizeof(int32_t)));
     HIPCHK(h, d.level_count.ensure(B * MAX_LEVELS * sizeof(int32_t)));
     HIPCHK(h, hipMemset(d.level_total, 0, B * MAX_LEVELS * sizeof(int32_t)));
@@ -131,9 +134,9 @@ static int ensure_geometry(orbx_extractor* h, int w, int hgt) {
 
 static void fill_batch(orbx_extractor* h, Batch& b) {
     const orbx_extractor::Geom& d = h->geo;
-    b.g = h->hg.g; b.cells = d.cells.as<CellGeom>(); b.bands = d.bands.as<BandGeom>(); b.tabx = d.tabx.as<ResizeX>(); b.taby = d.taby.as<ResizeY>();
+    b.g = h->hg.g; b.cells = d.cells.as<CellGeom>(); b.cellrec = d.cellrecs.as<CellRec>(); b.bands = d.bands.as<BandGeom>(); b.tabx = d.tabx.as<ResizeX>(); b.taby = d.taby.as<ResizeY>();
     b.pyr_tab = d.pyr_tab.as<int>(); b.pyr = d.pyr.as(); b.blur = d.blur.as();
-    b.cand = d.cand.as<Cand>(); b.sel = d.sel.as<Cand>(); b.cstate = d.cstate.as<CellState>(); b.csel = d.csel.as<CellSel>();
+    b.cand = d.cand.as<Cand>(); b.sel = d.sel.as<Cand>(); b.cstate = d.cstate.as<CellState>(); b.csel = d.csel.as<CellSel>(); b.cbands = d.cbands.as<CellBands>();
     b.level_total = d.level_total.as<int32_t>(); b.level_count = d.level_count.as<int32_t>(); b.status = d.status.as<int32_t>();
     b.long_cells = d.long_cells.as<int32_t>();
 }

@@ -81,6 +81,30 @@ __device__ __forceinline__ bool frame_item_magic(const Batch& b, unsigned block,
 static inline int frame_item_blocks(const Batch& b, int per_frame) {
     return (b.xcd_affinity ? (b.nframes + 7) / 8 * 8 : b.nframes) * per_frame;
 }
+static inline unsigned frame_item_magic_of(int per_frame) {     // (host) the `magic` of frame_item_magic for launches whose per_frame is not in DevGeom
+    return per_frame > 1 ? (unsigned)((1ull << 32) / (unsigned)per_frame) + 1u : 0u;
+}
+
+// The selection kernels' records of a cell (orbx_internal.h: CellRec, CellSel, CellBands) for a wave-uniform index: read through the constant
+// address space like level0_src, so each arrives with one scalar load (dwordx16, x4, x8) and all three are in flight together, waited for
+// once.  (CellSel and CellBands are written by k_quota, a launch earlier: constant for the kernels that read them.)
+// The empty asm statement names the records whole as scalar operands: left to itself the compiler cuts each load into the fields a test
+// needs and sinks the pieces behind the early returns, one round trip after the other.
+typedef int rec16_t __attribute__((ext_vector_type(16)));
+typedef int rec8_t __attribute__((ext_vector_type(8)));
+typedef int rec4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void load_cell_records(const Batch& b, int cell, long long frame_cell, CellRec& rc, CellSel& s, CellBands& bn) {
+    typedef const rec16_t __attribute__((address_space(4)))* c16_t;
+    typedef const rec8_t __attribute__((address_space(4)))* c8_t;
+    typedef const rec4_t __attribute__((address_space(4)))* c4_t;
+    rec16_t vr = *((c16_t)(uintptr_t)b.cellrec + cell);
+    rec4_t vs = *((c4_t)(uintptr_t)b.csel + frame_cell);
+    rec8_t vb = *((c8_t)(uintptr_t)b.cbands + frame_cell);
+    asm volatile("" : "+s"(vr), "+s"(vs), "+s"(vb));
+    rc = __builtin_bit_cast(CellRec, vr);
+    s = __builtin_bit_cast(CellSel, vs);
+    bn = __builtin_bit_cast(CellBands, vb);
+}
 
 constexpr unsigned long long UMAX_NIBBLES = 0x3689ABCDDEEEFFFFull;   // umax[v] for v = 0..15 (15,15,15,15,14,14,14,13,13,12,11,10,9,8,6,3)
 

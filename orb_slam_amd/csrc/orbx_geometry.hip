@@ -191,6 +191,17 @@ static int build_geometry_band(const orbx_params& p, int w, int h, HostGeom& out
                 }
                 out.cells.push_back(c);
             }
+        // the selection kernels' constant records (orbx_internal.h: CellRec)
+        for (int ci = L.cell_base; ci < L.cell_base + L.ncells; ci++) {
+            const CellGeom& c = out.cells[ci];
+            CellRec r;
+            memset(&r, 0, sizeof(r));
+            r.level = l; r.nbands = c.nbands; r.skipped = c.skipped; r.band0 = c.band0;
+            r.sel_base = sel_base; r.plane_off = L.plane_off; r.stride = L.stride;
+            r.cand_off = L.cand_base + c.cand_off;
+            for (int k = 0; k < c.nbands && k < CELL_REC_BANDS; k++) r.band_cand[k] = L.cand_base + out.bands[c.band0 + k].cand_off;
+            out.cellrecs.push_back(r);
+        }
         cell_base += L.ncells;
         cand_base += cand_off;
         L.sel_base = sel_base;

@@ -180,7 +180,23 @@ constexpr int QUOTA_MAX_CELLS = 160 * 1024 / QUOTA_LDS_PER_CELL / 64 * 64;   // 
 // band of it was listed at 7): k_quota reads n_lo exactly when sum(n_hi) <= 3.  A list made at 7 is filtered by score >= the cell's
 // threshold in k_cell_select (survivors@fastTh = survivors@7 with score >= fastTh).
 struct CellState { int32_t n_all, n_hi, n_lo, thr; };     // survivors listed, of them with score >= fastTh, with score >= 7; list threshold (low byte) | run of fallbacks of this frame slot << 8
-struct CellSel { int32_t thr, nkeys, nretain, out_off; };
+// What the selection kernels need of a cell, in records that a wave fetches with one scalar load each, side by side: everything that does
+// not depend on the frame (CellRec, 64 bytes, built on the host and uploaded with the geometry) and everything that does (CellSel, 16 bytes,
+// and CellBands, 32 bytes, both written by k_quota; CellBands only for cells of two bands and more — a one-band cell's list length is n_all).
+// CellRec and CellBands list a cell's bands up to CELL_REC_BANDS = 8 of them (a VGA level-0 cell has 2, a 1080p one 5); a cell with more
+// bands keeps the generic walk over BandGeom / CellState from band0 on.
+constexpr int CELL_REC_BANDS = 8;
+struct alignas(64) CellRec {
+    int32_t level, nbands, skipped, band0;
+    int32_t sel_base;                      // the level's list in a frame's sel block
+    int32_t plane_off, stride;             // the level's plane in a frame's pyramid block (level >= 1)
+    int32_t cand_off;                      // the cell's first Cand slot in a frame's candidate block (level base included)
+    int32_t band_cand[CELL_REC_BANDS];     // ... and its bands' (level base included)
+};
+struct alignas(16) CellSel { int32_t n_all, thr, nretain, out_off; };   // entries listed for the cell (sum over its bands; stored by k_quota's first pass), then what its
+                                                                        // last pass stores: threshold, nToRetain, offset in the level's list
+struct alignas(32) CellBands { int32_t n[CELL_REC_BANDS]; };            // entries listed band by band
+static_assert(sizeof(CellRec) == 64 && sizeof(CellSel) == 16 && sizeof(CellBands) == 32, "one scalar load per record");
 
 struct DevGeom {
     int nlevels;
@@ -224,6 +240,7 @@ static_assert(sizeof(ImgSrc) == 16, "one scalar dwordx4 per table entry");
 struct Batch {
     DevGeom g;
     const CellGeom* cells;
+    const CellRec* cellrec;   // [ncells_total]  the selection kernels' constant record per cell
     const BandGeom* bands;
     const ResizeX* tabx;
     const ResizeY* taby;
@@ -237,7 +254,8 @@ struct Batch {
     CellState* cstate;        // [frame][nbands_total]  (per band: survivors, and how many reach fastTh / 7)
     int fallback_hint;        // 1: a band starts at threshold 7 once its slot fell back FAST_HINT_RUN launch groups in a row (the run rides in CellState::thr);
                               // 0 (ORBX_FALLBACK_HINT=0): every band is scored at fastTh first
-    CellSel* csel;            // [frame][ncells_total]
+    CellSel* csel;            // [frame][ncells_total]  k_quota's verdict
+    CellBands* cbands;        // [frame][ncells_total]  the bands' list lengths (cells of 2 .. CELL_REC_BANDS bands)
     int32_t* level_total;     // [frame][MAX_LEVELS]  keypoints gathered from the cells
     int32_t* level_count;     // [frame][MAX_LEVELS]  after the per-level cap
     int32_t* status;          // [frame]
@@ -296,6 +314,7 @@ int launch_to_gray(const ColorArgs& a, int nframes, int fmt, hipStream_t stream)
 struct HostGeom {
     DevGeom g;
     std::vector<CellGeom> cells;
+    std::vector<CellRec> cellrecs;
     std::vector<BandGeom> bands;
     std::vector<ResizeX> tabx;
     std::vector<ResizeY> taby;
