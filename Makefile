@@ -9,7 +9,7 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -ffp-contract=off -mll
 ORBX_SRCS  := $(wildcard orb_slam_amd/csrc/*.hip)
 ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*.h)
 
-all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
+all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
 
 # the hash of the kernel sources travels inside the library (orbx_build_id): counters replayed by bench.py must come from THIS build
 SRC_HASH   := $(shell cat $(sort $(ORBX_SRCS) $(ORBX_HDRS)) | sha256sum | cut -c1-16)
@@ -107,6 +107,15 @@ tests/loop_dropin/harness: tests/loop_dropin/harness.cpp $(LP_DROPIN) include/or
 	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsLoop.cc -o $@ -Lorb_slam_amd -lorbx \
 	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
 
+# LocalMapPoints::SearchBySim3 (orb_slam_amd/cpp/LocalMapPointsSim3.cc, over residentForFuse of LocalMapPointsFuse.cc and the key-frame store of
+# LocalMapPointsRefresh.cc), driven by scripts (tests/test_gpu_sim3_dropin.py); MapPoint.h is this directory's (it adds GetIndexInKeyFrame), KeyFrame.h
+# that of tests/loop_dropin, Frame.h and cvmini.h those of tests/mappoints_dropin
+S3_DROPIN := orb_slam_amd/cpp/LocalMapPointsSim3.cc $(FU_DROPIN) $(wildcard tests/sim3_dropin/*.h) tests/loop_dropin/KeyFrame.h
+tests/sim3_dropin/harness: tests/sim3_dropin/harness.cpp $(S3_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
+	$(CXX) -O2 -std=c++14 -Wall -Itests/sim3_dropin -Itests/loop_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
+	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsSim3.cc -o $@ -Lorb_slam_amd -lorbx \
+	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+
 # the NewMapPoints drop-in (orb_slam_amd/cpp/NewMapPoints.cc) over a stand-in KeyFrame.h, driven by scripts
 # (tests/test_gpu_triangulate_dropin.py); cvmini.h is that of tests/mappoints_dropin
 TRI_DROPIN := orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h tests/triangulate_dropin/KeyFrame.h tests/mappoints_dropin/cvmini.h
@@ -129,6 +138,10 @@ tools/libfuse_host.so: tools/fuse_host_route.cpp include/orbp.h
 
 # the host route tools/bench_loop.py measures orbp_loop_search and orbp_fuse over a similarity against: the decomposition of Scw and the projection on one host core
 tools/libloop_host.so: tools/loop_host_route.cpp tools/fuse_host_route.cpp include/orbp.h
+	$(CXX) -O2 -std=c++14 -ffp-contract=off -fPIC -shared -Iinclude $< -o $@
+
+# the host route tools/bench_sim3.py measures orbp_sim3_search against: the pair arithmetic and the projection of both directions on one host core, packed as queries
+tools/libsim3_host.so: tools/sim3_host_route.cpp include/orbp.h
 	$(CXX) -O2 -std=c++14 -ffp-contract=off -fPIC -shared -Iinclude $< -o $@
 
 # the host-query route tools/bench_source_track.py measures the device-resident last-frame / key-frame searches against (one host core)
@@ -159,7 +172,7 @@ tools/microbench/ta_shapes: tools/microbench/ta_shapes.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++20 -Wno-unused-value $< -o $@
 
 clean:
-	rm -f tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
+	rm -f tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
 	rm -rf oracle/_ref oracle/_ref_native build/orbx
 
 .PHONY: all clean oracle_ref

@@ -32,6 +32,11 @@
  *                                <- int ORBmatcher::SearchByProjection(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, vector<MapPoint*>& vpMatched, int th)
  *                                   src/ORBmatcher.cc:286-407 (LoopClosing::ComputeSim3, src/LoopClosing.cc:370; ORBP_MODE_LOOP)
  *                                   (projection + orbs_window_search_batch_device with ORBS_RULE_BEST, TH_LOW, no rotation check)
+ *   orbp_sim3_from_pair, orbp_sim3_search[_batch_device]
+ *                                <- int ORBmatcher::SearchBySim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, const float& s12, const cv::Mat& R12, const cv::Mat& t12, float th)
+ *                                   src/ORBmatcher.cc:1267-1505, for every candidate whose RANSAC converged in LoopClosing::ComputeSim3
+ *                                   (src/LoopClosing.cc: `matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)`; ORBP_MODE_SIM3):
+ *                                   both directions of every pair in one launch, the agreement (:1486-1502) in a second
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -91,6 +96,32 @@
  * (TH_LOW in the reference, accepted when <=), no rotation check and d_claimed = `vpMatched[idx] != NULL` on entry: a match takes its feature,
  * and later entries pass that feature over (:378, :398-402).
  *
+ * Arithmetic of orbp_sim3_from_pair (src/ORBmatcher.cc:1284-1286), the cv::Mat primitives as DESIGN.md §2 lists them:
+ *   sR12[i] = (float)((double)R12[i] * (double)s12) (`float * Mat`: the scalar is a double inside the expression);
+ *   inv = 1.0 / (double)s12, a DOUBLE; sR21[r][c] = (float)((double)R12[c][r] * inv) (`double * Mat::t()`);
+ *   t21[r] = ((0.0f + (-sR21[r][0])*t12[0]) + (-sR21[r][1])*t12[1]) + (-sR21[r][2])*t12[2] in float (`-sR21*t12`: the product of the negated matrix).
+ *
+ * Arithmetic of ORBP_MODE_SIM3 (src/ORBmatcher.cc:1319-1399 for direction 1 -> 2, :1402-1484 for 2 -> 1: the same text with the key frames swapped),
+ * one direction a -> b: the points of key frame a are searched in key frame b.  List entry i is feature i of key frame a; the first rejection that
+ * applies names its status:
+ *   the entry is skipped, or its slot out of range or free -> ORBP_FUSE_SKIPPED;
+ *   Pa = Raw*P + taw, exactly Pc above (the `0.0f +` included);
+ *   Pb[r] = (((0.0f + S[r][0]*Pa[0]) + S[r][1]*Pa[1]) + S[r][2]*Pa[2]) + t[r] in float; S, t = sR21, t21 for 1 -> 2 and sR12, t12 for 2 -> 1;
+ *   Pb[2] < 0.0f -> ORBP_FUSE_DEPTH;
+ *   invz = 1.0f / Pb[2] (rounds as the reference's `float invz = 1.0/z` does); x = Pb[0]*invz; y = Pb[1]*invz; u = fx*x + cx; v = fy*y + cy;
+ *   KeyFrame::IsInImage as in ORBP_MODE_FUSE: half-open, a NaN or infinite u or v fails it -> ORBP_FUSE_IMAGE.  No deviation;
+ *   dist3D = (float)sqrt(sum of (double)Pb[k]*(double)Pb[k]), a double sum from 0.0 in index order (`cv::norm(p3Dc2)`: the norm in camera b's
+ *   frame, NOT the distance to a camera centre); dist3D < minDistance || dist3D > maxDistance -> ORBP_FUSE_DISTANCE;
+ *   there is NO viewing-angle test: the slot's normal is not read and ORBP_FUSE_ANGLE never occurs;
+ *   level = min(lower_bound(factors, dist3D / minDistance), nlevels - 1); radius = th * factors[level];
+ *   the window, the octave rule [level - 1, level], the candidate order and "a strictly smaller distance wins" are ORBP_MODE_FUSE's, the same
+ *   statement on the device; no cell window or no feature kept -> ORBP_FUSE_EMPTY;
+ *   best distance <= orb_dist (TH_HIGH in the reference) -> ORBP_FUSE_FUSED with that feature, which is vnMatch of the entry; else ORBP_FUSE_FAR and -1.
+ * Nothing is claimed: every entry is on its own.  The factors are those of the one extractor, as everywhere in this header.
+ * The agreement (:1486-1502): match12[i1] = idx2 iff vnMatch1[i1] = idx2 >= 0, idx2 lies inside direction 2 -> 1's list and vnMatch2[idx2] == i1;
+ * otherwise -1.  nfound counts the entries that are not -1.  An entry that was matched on entry (vbAlreadyMatched1 / 2) is marked skipped by the
+ * host, so it never agrees.
+ *
  * ONE DELIBERATE DEVIATION.  Where the reference leaves u or v NaN (PcZ == 0 together with PcX == 0 or PcY == 0: a point at
  * the camera centre) all its comparisons fail, the point passes with a NaN window and GetFeaturesInArea converts NaN to
  * int, which is undefined.  Here a point whose u or v is NaN is not visible, and is not a query in the source-frame modes.
@@ -124,7 +155,9 @@ extern "C" {
 #define ORBP_MODE_FUSE 3              /* orbp_fuse*: map points into key frames (LocalMapping's Fuse, and the Scw overload of LoopClosing's through
                                          orbp_view_from_sim3).  To orbp_project* / orbp_track* it is an unknown mode */
 #define ORBP_MODE_LOOP 4              /* orbp_loop_*: the loop map points into one key frame through a similarity (LoopClosing's SearchByProjection).  To
-                                         every other entry point it is an unknown mode; SearchBySim3 has no mode */
+                                         every other entry point it is an unknown mode */
+#define ORBP_MODE_SIM3 5              /* orbp_sim3_*: the map points of one key frame into another through a similarity and back (LoopClosing's SearchBySim3);
+                                         the mode of an orbp_sim3_dir.  To every other entry point it is an unknown mode */
 
 typedef struct orbp_map orbp_map;
 
@@ -151,7 +184,7 @@ typedef struct orbp_record {
 } orbp_record;
 
 /* ORBX_ERR_ARG for capacity outside [1, ORBP_MAX_CAPACITY] or a NULL `out`; ORBX_ERR_DEVICE without a usable GPU.
- * Device memory: 65 bytes per slot; the scratch of orbp_track* and orbp_loop_* and the blocks of orbp_refresh and orbp_fuse are allocated on first use and kept. */
+ * Device memory: 65 bytes per slot; the scratch of orbp_track* and orbp_loop_* and the block of orbp_refresh, orbp_fuse and orbp_sim3_search are allocated on first use and kept. */
 int orbp_create(int capacity, int device, orbp_map** out);
 void orbp_destroy(orbp_map* map);
 int orbp_capacity(const orbp_map* map);
@@ -455,6 +488,61 @@ int orbp_loop_search(orbp_map* map, const orbp_view* view, const float* factors,
                      const orbf_bounds* b, int orb_dist, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
                      const int32_t* cell_feat, const uint8_t* claimed, int nt, int frame_on_device, int qcap, orbp_fused* rec, int32_t* t2pos,
                      int32_t* t2slot, int* nmatches, int* nvisible, void* stream);
+
+/* ---- SearchBySim3 (src/ORBmatcher.cc:1267-1505): the arithmetic is stated at the top of this file (ORBP_MODE_SIM3).
+ *
+ * One direction a -> b of one pair: key frame a's pose, the similarity that takes camera a's frame into camera b's, key frame b's camera and image
+ * bounds, SearchBySim3's th.  A multiple of 16 bytes; an orbp_view has no room for the second 3 x 4. */
+typedef struct orbp_sim3_dir {
+    float Raw[9];                            /* the SOURCE key frame's GetRotation(), row major */
+    float taw[3];                            /* its GetTranslation() */
+    float S[9];                              /* sR21 (direction 1 -> 2) or sR12 (2 -> 1), row major */
+    float t[3];                              /* t21 or t12 */
+    float fx, fy, cx, cy;
+    int32_t min_x, max_x, min_y, max_y;      /* KeyFrame::mnMinX .. mnMaxY of the key frame searched in */
+    float th;                                /* SearchBySim3's th: 7.5 in LoopClosing */
+    int32_t mode;                            /* ORBP_MODE_SIM3 */
+    int32_t reserved[2];                     /* 0 */
+} orbp_sim3_dir;
+
+/* Fills dirs[0] (direction 1 -> 2: R1w, t1w, sR21, t21) and dirs[1] (direction 2 -> 1: R2w, t2w, sR12, t12) from SearchBySim3's arguments by the
+ * arithmetic at the top of this file; camera, bounds (those of b: min_x, max_x, min_y, max_y) and th go into both, mode = ORBP_MODE_SIM3.
+ * ORBX_ERR_ARG for a NULL pointer or an s12 that is zero or not finite (dirs is then untouched).  Host only: needs no GPU. */
+int orbp_sim3_from_pair(float s12, const float R12[9], const float t12[3], const float R1w[9], const float t1w[3], const float R2w[9],
+                        const float t2w[3], float fx, float fy, float cx, float cy, const orbf_bounds* b, float th, orbp_sim3_dir dirs[2]);
+
+/* npairs pairs of key frames, both directions of all of them in ONE launch of 2 * npairs rows, then the agreement on the same stream.  All arrays
+ * are device buffers except `factors`.  Pair p owns rows 2p (direction 1 -> 2) and 2p + 1 (2 -> 1) of the per-row arrays d_dirs, d_nlist and
+ * d_frame, and of the per-entry arrays (row r's entries at r*lcap + i).  Row r walks d_list[r*lcap + i], i < d_nlist[r] (clamped to [0, lcap]): list
+ * entry i is FEATURE i of the row's source key frame, its map slot or -1 for "no map point"; d_skip (may be NULL) passes an entry over (isBad(), or
+ * matched on entry), as does a slot that is out of range or free.  Row r searches key frame d_frame[r] (d_frame == NULL: key frame r) of the
+ * nframes key frames in the batch layout of orbp_fuse_batch_device: row 2p searches key frame 2 of the pair, row 2p + 1 key frame 1.
+ * b: the key frames' image bounds and grid; orb_dist: ORBmatcher::TH_HIGH in the reference.
+ *
+ * Outputs for every i < d_nlist[r], at r*lcap + i: d_best_idx (vnMatch1 in row 2p, vnMatch2 in row 2p + 1; -1 unless the status is ORBP_FUSE_FUSED),
+ * d_best_dist, d_rec (may be NULL) as orbp_fuse_batch_device.  A row whose mode is not ORBP_MODE_SIM3 or whose key frame is outside [0, nframes)
+ * writes -1 / INT32_MAX / ORBP_FUSE_SKIPPED for its entries, and its pair finds nothing.  d_match12[p*lcap + i1] for i1 < d_nlist[2p]: the feature
+ * of key frame 2 whose map point vpMatches12[i1] becomes (-1 none); d_nfound[p]: the reference's return value, counted on the device.
+ *
+ * ORBX_ERR_ARG before anything touches the GPU for npairs outside [0, ORBP_MAX_VIEWS / 2], and otherwise as orbp_fuse_batch_device (with
+ * nviews = 2 * npairs), d_match12 and d_nfound being required.  Asynchronous on `stream` (NULL: the map's own), inside the handle's event chain;
+ * allocates nothing. */
+int orbp_sim3_search_batch_device(orbp_map* map, const orbp_sim3_dir* d_dirs, int npairs, const float* factors, int nlevels, const int32_t* d_list,
+                                  const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const int32_t* d_frame, const orbx_keypoint* d_kps_un,
+                                  const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat, const int32_t* d_nt, int nframes, int cap,
+                                  const orbf_bounds* b, int orb_dist, int32_t* d_best_idx, int32_t* d_best_dist, orbp_fused* d_rec, int32_t* d_match12,
+                                  int32_t* d_nfound, void* stream);
+
+/* The same with HOST arrays in and out, synchronous: the latency / test form, one pinned block up and one down.  dirs, list, nlist, skip, frame
+ * (2 * npairs rows; frame may be NULL), nt and the outputs are host memory and need no alignment: best_idx, best_dist, rec (2 * npairs * lcap entries
+ * each; each may be NULL), match12 (npairs * lcap) and nfound (npairs).  The key frames' arrays are host memory (the whole batch layout is copied),
+ * or device memory when frames_on_device != 0 (a caller who keeps its key frames resident uploads the directions and the lists only).  Checked
+ * here in addition: ORBX_ERR_ARG for a row whose mode is not ORBP_MODE_SIM3 or whose key frame is outside [0, nframes).  Entries behind a list
+ * are not written.  The block is the handle's own, grown on first use and kept. */
+int orbp_sim3_search(orbp_map* map, const orbp_sim3_dir* dirs, int npairs, const float* factors, int nlevels, const int32_t* list, const int32_t* nlist,
+                     int lcap, const uint8_t* skip, const int32_t* frame, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
+                     const int32_t* cell_feat, const int32_t* nt, int nframes, int cap, int frames_on_device, const orbf_bounds* b, int orb_dist,
+                     int32_t* best_idx, int32_t* best_dist, orbp_fused* rec, int32_t* match12, int32_t* nfound, void* stream);
 
 #ifdef __cplusplus
 }

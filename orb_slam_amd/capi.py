@@ -57,12 +57,13 @@ EXPORTS_D = ["orbd_create", "orbd_destroy", "orbd_size", "orbd_add", "orbd_add_b
 EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_clear", "orbp_put", "orbp_put_device", "orbp_erase", "orbp_get",
              "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
              "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh", "orbp_fuse_batch_device",
-             "orbp_fuse", "orbp_view_from_sim3", "orbp_loop_project_batch_device", "orbp_loop_search_batch_device", "orbp_loop_search"]
+             "orbp_fuse", "orbp_view_from_sim3", "orbp_loop_project_batch_device", "orbp_loop_search_batch_device", "orbp_loop_search",
+             "orbp_sim3_from_pair", "orbp_sim3_search_batch_device", "orbp_sim3_search"]
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
-# orbp_view.mode
-MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP = 0, 1, 2, 3, 4
+# orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
+MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
 # orbp_fused.status
 (FUSE_FUSED, FUSE_SKIPPED, FUSE_DEPTH, FUSE_IMAGE, FUSE_DISTANCE, FUSE_ANGLE, FUSE_EMPTY, FUSE_FAR) = range(8)
 LOOP_QUERY = 8              # orbp_loop_*: the entry passed every test and is a query
@@ -148,6 +149,19 @@ def view_from_sim3(Scw, view):
     return view
 
 
+def sim3_from_pair(s12, R12, t12, R1w, t1w, R2w, t2w, fx, fy, cx, cy, bounds, th):
+    """orbp_sim3_from_pair: SearchBySim3's arguments and the two key frames' poses -> SIM3_DIR_DTYPE[2], direction 1 -> 2 (R1w, t1w, sR21, t21) and
+    direction 2 -> 1 (R2w, t2w, sR12, t12).  Host arithmetic: needs no GPU.  Raises OrbxError(ORBX_ERR_ARG) for a zero or non-finite scale."""
+    a = lambda x, n: np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(n))
+    R12, t12, R1w, t1w, R2w, t2w = a(R12, 9), a(t12, 3), a(R1w, 9), a(t1w, 3), a(R2w, 9), a(t2w, 3)
+    dirs = np.zeros(2, SIM3_DIR_DTYPE)
+    rc = lib().orbp_sim3_from_pair(float(s12), R12.ctypes.data, t12.ctypes.data, R1w.ctypes.data, t1w.ctypes.data, R2w.ctypes.data, t2w.ctypes.data,
+                                   float(fx), float(fy), float(cx), float(cy), ctypes.addressof(bounds), float(th), dirs.ctypes.data)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbp_sim3_from_pair")
+    return dirs
+
+
 class TriCamera(ctypes.Structure):
     """orbt_camera: one key frame's pose and camera"""
     _fields_ = [("Rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("Ow", ctypes.c_float * 3),
@@ -179,6 +193,11 @@ assert REFRESHED_DTYPE.itemsize == 32
 # orbp_fused
 FUSED_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("level", np.int32), ("status", np.int32)])
 assert FUSED_DTYPE.itemsize == 16
+# orbp_sim3_dir: one direction of one pair of orbp_sim3_search* (arrays of directions are uploaded as they are)
+SIM3_DIR_DTYPE = np.dtype([("Raw", np.float32, 9), ("taw", np.float32, 3), ("S", np.float32, 9), ("t", np.float32, 3), ("fx", np.float32),
+                           ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("min_x", np.int32), ("max_x", np.int32), ("min_y", np.int32),
+                           ("max_y", np.int32), ("th", np.float32), ("mode", np.int32), ("reserved", np.int32, 2)])
+assert SIM3_DIR_DTYPE.itemsize == 144
 
 GRID_COLS, GRID_ROWS = 64, 48
 GRID_CELLS = GRID_COLS * GRID_ROWS
@@ -313,6 +332,10 @@ def lib():
         L.orbp_fuse_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.orbp_fuse.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]
         L.orbp_view_from_sim3.argtypes = [vp, vp]
+        cf = ctypes.c_float
+        L.orbp_sim3_from_pair.argtypes = [cf, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, vp, cf, vp]
+        L.orbp_sim3_search_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+        L.orbp_sim3_search.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp]
         L.orbp_loop_project_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_loop_search_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
         L.orbp_loop_search.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
@@ -1289,6 +1312,56 @@ class MapPointTable:
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_fuse")
         return best_idx, best_dist, rec
+
+    def sim3_search_batch_device(self, d_dirs, npairs, factors, d_list, d_nlist, lcap, d_skip, d_frame, d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt,
+                                 nframes, cap, bounds, orb_dist, d_best_idx, d_best_dist, d_rec, d_match12, d_nfound, stream=0):
+        """ORBmatcher::SearchBySim3 for npairs pairs of key frames, asynchronous: both directions of every pair in one launch (rows 2p and 2p + 1 of the
+        per-row arrays), the agreement in a second.  factors: host array; everything else device pointers as ints (0 = NULL: d_skip, d_frame, d_rec)"""
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        rc = lib().orbp_sim3_search_batch_device(self.h, d_dirs or None, npairs, f.ctypes.data, len(f), d_list or None, d_nlist or None, lcap, d_skip or None,
+                                                 d_frame or None, d_kps_un or None, d_desc or None, d_cell_off or None, d_cell_feat or None, d_nt or None,
+                                                 nframes, cap, ctypes.addressof(bounds), orb_dist, d_best_idx or None, d_best_dist or None, d_rec or None,
+                                                 d_match12 or None, d_nfound or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_sim3_search_batch_device")
+
+    def sim3_search(self, dirs, factors, lists, nlist, frame, bounds, orb_dist, kps_un, desc, cell_off, cell_feat, nt, skip=None, nframes=None, cap=None):
+        """The same with host arrays, synchronous: -> dict(match12 i32[npairs, lcap] (vpMatches12[i1] = key frame 2's feature, -1 none), nfound
+        i32[npairs], best_idx / best_dist i32[2 npairs, lcap], rec FUSED_DTYPE[2 npairs, lcap]); entries at i >= nlist[row] are -1 / INT32_MAX / zero.
+        dirs: SIM3_DIR_DTYPE[2 npairs] (sim3_from_pair per pair); lists (2 npairs, lcap) int32 slots by source feature (-1: no map point); frame
+        (2 npairs) the key frame each row searches (None: row r searches key frame r).  The key frames in the batch layout as for fuse(): host
+        arrays, or device pointers as ints (nframes and cap must then be given); nt (nframes) is a host array."""
+        dirs = np.ascontiguousarray(dirs, dtype=SIM3_DIR_DTYPE).reshape(-1)
+        assert len(dirs) % 2 == 0
+        nrows, npairs = len(dirs), len(dirs) // 2
+        f = np.ascontiguousarray(factors, dtype=np.float32)
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        lists = lists.reshape(nrows, -1) if nrows else lists.reshape(0, lists.shape[-1] if lists.ndim == 2 and lists.shape[-1] else 1)
+        lcap = lists.shape[1]
+        nlist = np.ascontiguousarray(nlist, dtype=np.int32).reshape(nrows)
+        opt = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)
+        skip = opt(skip, np.uint8, (nrows, lcap)); frame = opt(frame, np.int32, nrows)
+        on_dev = isinstance(kps_un, int)
+        if not on_dev:
+            kps_un = np.ascontiguousarray(kps_un)
+            assert kps_un.dtype.itemsize == 28 and kps_un.ndim == 2
+            nframes, cap = kps_un.shape
+            desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(nframes, cap, 32)
+            cell_off = np.ascontiguousarray(cell_off, dtype=np.int32).reshape(nframes, GRID_CELLS + 1)
+            cell_feat = np.ascontiguousarray(cell_feat, dtype=np.int32).reshape(nframes, cap)
+        nt = np.ascontiguousarray(nt, dtype=np.int32).reshape(nframes)
+        best_idx = np.full((nrows, lcap), -1, np.int32)
+        best_dist = np.full((nrows, lcap), np.iinfo(np.int32).max, np.int32)
+        rec = np.zeros((nrows, lcap), FUSED_DTYPE)
+        match12 = np.full((npairs, lcap), -1, np.int32)
+        nfound = np.zeros(max(npairs, 1), np.int32)
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        rc = lib().orbp_sim3_search(self.h, ptr(dirs), npairs, f.ctypes.data, len(f), ptr(lists), ptr(nlist), lcap, ptr(skip), ptr(frame), ptr(kps_un),
+                                    ptr(desc), ptr(cell_off), ptr(cell_feat), ptr(nt), nframes, cap, 1 if on_dev else 0, ctypes.addressof(bounds), orb_dist,
+                                    ptr(best_idx), ptr(best_dist), ptr(rec), ptr(match12), ptr(nfound), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_sim3_search")
+        return dict(match12=match12, nfound=nfound[:npairs], best_idx=best_idx, best_dist=best_dist, rec=rec)
 
     def project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
                              d_overflow, qcap, stream=0):

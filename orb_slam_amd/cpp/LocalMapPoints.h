@@ -17,6 +17,9 @@
 // LoopClosing::SearchAndFuse as one orbp_fuse over every corrected key frame, followed by the reference's in-order loop on the host.  Both read
 // the points' positions from the mirror: a caller who moved points (CorrectLoop does, before it fuses) must Put them first, or construct
 // with refresh_every_call.
+// SearchBySim3 (LocalMapPointsSim3.cc) replaces ORBmatcher::SearchBySim3 as LoopClosing::ComputeSim3 calls it for every candidate whose RANSAC
+// converged: both key frames' points are searched in each other's resident row by ONE orbp_sim3_search, all candidates of a call together, and
+// only two poses, the similarity and two slot lists per candidate go up.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
@@ -101,6 +104,23 @@ public:
     // pMPinKF->Replace(pMP), or AddObservation + AddMapPoint, as the reference does.  nFused (may be NULL) receives each call's return value.
     void SearchAndFuse(const std::vector<std::pair<KeyFrame*, cv::Mat> >& vCorrectedScw, const std::vector<MapPoint*>& vpLoopMapPoints, float th = 4,
                        std::vector<int>* nFused = 0);
+
+    // int ORBmatcher::SearchBySim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, const float&, const cv::Mat&, const cv::Mat&, float)
+    // (src/ORBmatcher.cc:1267-1505, called in LoopClosing::ComputeSim3 as SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)) with the
+    // reference's signature, return value and effect on vpMatches12 (LocalMapPointsSim3.cc; links only when that file, LocalMapPointsFuse.cc and
+    // LocalMapPointsRefresh.cc are built in).  Reads of the key frames GetRotation(), GetTranslation(), GetMapPointMatches(), GetScaleFactors(),
+    // GetScaleLevels(), pKF1's fx, fy, cx, cy and, once per key frame, the features and the grid (the resident key-frame store); of the points
+    // isBad() and, for those in vpMatches12 on entry, GetIndexInKeyFrame(pKF2).  Points not yet mirrored are Put on the way.
+    int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, const float& s12, const cv::Mat& R12, const cv::Mat& t12, float th);
+    // The same for every converged candidate of one ComputeSim3 against the one pKF1, in ONE call: 2 * vCandidates.size() directions in one launch.
+    // Each candidate's vpMatches12 is written as its own call would write it; nFound (may be NULL) receives the return values.
+    struct Sim3Candidate {
+        KeyFrame* pKF2;
+        float s12;
+        cv::Mat R12, t12;
+        std::vector<MapPoint*>* vpMatches12;
+    };
+    void SearchBySim3(KeyFrame* pKF1, const std::vector<Sim3Candidate>& vCandidates, float th, std::vector<int>* nFound = 0);
 
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }

@@ -7,9 +7,8 @@
 //   second distance, no ratio, no rotation histogram, no order.  So there is no compaction, no per-problem staging and no commit, and a long
 //   list of one view spreads over as many workgroups as it has tiles (the one-workgroup walk of k_project is a serial chain of tiles there).
 //   A lane runs the five tests on its point (orbp::entry_test of orbp_device.h, the statement k_loop_test shares), opens the cell window
-//   (orbf::window_cells) and scans it column by column: the cells of one grid column are neighbours in the CSR, so a column is one run
-//   cell_off[ix*48 + y0] .. cell_off[ix*48 + y1 + 1] in the reference's order.  The point's descriptor sits in eight registers, a candidate's
-//   arrives as two 16-byte loads; a strictly smaller distance replaces the best.
+//   (orbf::window_cells) and scans it column by column (orbp::scan_window of orbp_device.h, the statement k_sim3 shares).  The point's descriptor
+//   sits in eight registers, a candidate's arrives as two 16-byte loads; a strictly smaller distance replaces the best.
 //   The stage is a chain of dependent loads (list -> live -> geometry -> cell offsets -> cell features -> key point -> descriptor) with a
 //   handful of candidates at its end; what hides it is the number of entries in flight.  LDS holds the view only, and the one barrier is
 //   the one behind staging it.  Plain vector stores, no atomics: every entry owns its outputs.
@@ -17,7 +16,6 @@
 
 #include <climits>
 
-#include "orbf_math.h"
 #include "orbp.h"
 #include "orbp_device.h"
 #include "orbp_host.h"
@@ -51,33 +49,7 @@ __global__ __launch_bounds__(FU_TPB) void k_fuse(Fuse a, Factors F) {
         status = entry_test(V, F, g[0], g[1], ORBP_FUSE_EMPTY, u, v, level);
         if (status != ORBP_FUSE_EMPTY) break;
         const float radius = V.th * F.f[level];
-        int x0, x1, y0, y1;
-        if (!orbf::window_cells(a.b, u, v, radius, &x0, &x1, &y0, &y1)) break;
-        int nt = a.K.nt[fr];
-        nt = nt < 0 ? 0 : (nt > a.K.cap ? a.K.cap : nt);
-        const size_t fb = (size_t)fr * a.K.cap;
-        const int32_t* off = a.K.cell_off + (size_t)fr * (ORBF_GRID_CELLS + 1);
-        const int32_t* feat = a.K.cell_feat + fb;
-        const orbx_keypoint* kps = a.K.kps_un + fb;
-        const uint4* kd = reinterpret_cast<const uint4*>(a.K.desc) + fb * 2;
-        const uint4* td = reinterpret_cast<const uint4*>(a.T.tdesc) + (size_t)slot * 2;
-        const uint4 qa = td[0], qb = td[1];
-        const uint32_t q0 = qa.x, q1 = qa.y, q2 = qa.z, q3 = qa.w, q4 = qb.x, q5 = qb.y, q6 = qb.z, q7 = qb.w;
-        for (int ix = x0; ix <= x1; ix++) {
-            int j = off[ix * ORBF_GRID_ROWS + y0], jend = off[ix * ORBF_GRID_ROWS + y1 + 1];
-            j = j < 0 ? 0 : j;                                         // a grid that breaks its contract reads nothing outside the row
-            jend = jend > nt ? nt : jend;
-            for (; j < jend; j++) {
-                const int f = feat[j];
-                if ((unsigned)f >= (unsigned)nt) continue;
-                const orbx_keypoint kp = kps[f];
-                if (fabsf(kp.x - u) > radius || fabsf(kp.y - v) > radius || kp.octave < level - 1 || kp.octave > level) continue;
-                const uint4 ca = kd[(size_t)f * 2], cb = kd[(size_t)f * 2 + 1];
-                const int d = __popc(q0 ^ ca.x) + __popc(q1 ^ ca.y) + __popc(q2 ^ ca.z) + __popc(q3 ^ ca.w) + __popc(q4 ^ cb.x) + __popc(q5 ^ cb.y) +
-                              __popc(q6 ^ cb.z) + __popc(q7 ^ cb.w);
-                if (d < best) { best = d; best_f = f; }
-            }
-        }
+        scan_window(a.b, a.K, fr, reinterpret_cast<const uint4*>(a.T.tdesc) + (size_t)slot * 2, u, v, radius, level, best, best_f);
         if (best_f < 0) break;
         status = best <= a.orb_dist ? ORBP_FUSE_FUSED : ORBP_FUSE_FAR;
     } while (false);

@@ -1,8 +1,9 @@
 // The argument groups of the map-point table's entry points (orbp_project.hip), the clauses their argument checks are composed of, and the
 // layouts the synchronous host forms give the one block an orbp_map keeps (orbx::Staged): OneView, the shared form of the one-view calls
-// (orbp_track, orbp_track_source: TrackBlock; orbp_loop_search: LoopBlock), RefreshBlock and FuseBlock.  Each layout's stage() goes through
+// (orbp_track, orbp_track_source: TrackBlock; orbp_loop_search: LoopBlock), RefreshBlock and FlatBlock (orbp_fuse: FuseBlock; orbp_sim3_search:
+// Sim3Block).  Each layout's stage() goes through
 // Layout::put: a host array is copied into its slot and named on the device, an absent one is passed through.  Host C++ only:
-// tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp, tests/_probe/fuse_host.cpp and tests/_probe/loop_host.cpp hold the checks
+// tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp, tests/_probe/fuse_host.cpp, tests/_probe/loop_host.cpp and tests/_probe/sim3_host.cpp hold the checks
 // and the layouts against their sizes without a GPU.
 #pragma once
 #include <cmath>
@@ -259,49 +260,59 @@ inline bool frame_aligned(const orbx_keypoint* kps_un, const uint8_t* desc, cons
 template <class... P>
 bool words_aligned(const P*... p) { return (((uintptr_t)p | ...) & 3) == 0; }
 
-// The arguments of orbp_fuse* that do not need the handle.  on_device: views, lists and outputs are device memory (orbp_fuse_batch_device),
-// so only their presence and alignment can be checked; else the views' modes and rows are walked.  frames_device: the key frames are device
-// addresses, read in place (host arrays are copied into aligned slots).
-inline int check_fuse(const orbp_view* views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
-                      const FuseFrames& K, const FuseOut& out, bool on_device, bool frames_device) {
+// The arguments of the flat searches (orbp_fuse*: View = orbp_view, mode = ORBP_MODE_FUSE; orbp_sim3_search*: View = orbp_sim3_dir, mode =
+// ORBP_MODE_SIM3, a view being one direction) that do not need the handle.  on_device: views, lists and outputs are device memory (the
+// batch-device forms), so only their presence and alignment can be checked; else the views' modes and rows are walked.  frames_device: the key
+// frames are device addresses, read in place (host arrays are copied into aligned slots).  out_optional: the caller need not want best_idx / best_dist
+// (orbp_sim3_search, whose block holds them for the agreement either way).
+template <class View>
+int check_flat(const View* views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist, const FuseFrames& K,
+               const FuseOut& out, bool on_device, bool frames_device, int mode, bool out_optional = false) {
     if (!flat_views_ok(nviews, L.lcap, factors, nlevels) || !keyframes_ok(b, orb_dist, K)) return ORBX_ERR_ARG;
     if (nviews == 0) return ORBX_OK;
-    if (!views || !L.list || !L.nlist || !keyframes_present(K) || !out.best_idx || !out.best_dist) return ORBX_ERR_ARG;
+    if (!views || !L.list || !L.nlist || !keyframes_present(K) || (!out_optional && (!out.best_idx || !out.best_dist))) return ORBX_ERR_ARG;
     if (frames_device && !frame_aligned(K.kps_un, K.desc, K.cell_off, K.cell_feat)) return ORBX_ERR_ARG;
     if (on_device) return words_aligned(views, L.list, L.nlist, K.nt, K.frame, out.best_idx, out.best_dist, out.rec) ? ORBX_OK : ORBX_ERR_ARG;
     for (int p = 0; p < nviews; p++) {
         const int f = K.frame ? K.frame[p] : p;
-        if (views[p].mode != ORBP_MODE_FUSE || f < 0 || f >= K.nframes) return ORBX_ERR_ARG;
+        if (views[p].mode != mode || f < 0 || f >= K.nframes) return ORBX_ERR_ARG;
     }
     return ORBX_OK;
 }
+inline int check_fuse(const orbp_view* views, int nviews, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
+                      const FuseFrames& K, const FuseOut& out, bool on_device, bool frames_device) {
+    return check_flat(views, nviews, factors, nlevels, L, b, orb_dist, K, out, on_device, frames_device, ORBP_MODE_FUSE);
+}
 
-// The block of orbp_fuse, one pinned copy up and one down:
+// The block of a flat search over `nviews` views of type View, one pinned copy up and one down:
 //   up    [views | nlist | frame | nt | list | skip | kps_un | desc | cell_off | cell_feat]     (absent: frame and skip when the caller passes none,
 //                                                                                                the key frames' arrays when they are on the device)
-//   down  [best_idx | best_dist | rec]                                                          (rec absent when the caller wants none)
-struct FuseBlock {
+//   down  [best_idx | best_dist | rec | match12 | nfound]                                       (rec absent when the caller wants none; match12 and
+//                                                                                                nfound, npairs > 0 only: the agreement of orbp_sim3_search)
+template <class View>
+struct FlatBlock {
     Layout L;
-    Layout::Slot<orbp_view> views;
-    Layout::Slot<int32_t> nlist, frame, nt, list, cell_off, cell_feat, best_idx, best_dist;
+    Layout::Slot<View> views;
+    Layout::Slot<int32_t> nlist, frame, nt, list, cell_off, cell_feat, best_idx, best_dist, match12, nfound;
     Layout::Slot<uint8_t> skip, desc;
     Layout::Slot<orbx_keypoint> kps;
     Layout::Slot<orbp_fused> rec;
     int nviews, nframes;
     size_t nent, nfeat;                                // nviews * lcap, nframes * cap
-    FuseBlock(int nviews_, const Lists& l, const FuseFrames& k, bool frames_upload, bool with_rec)
+    FlatBlock(int nviews_, const Lists& l, const FuseFrames& k, bool frames_upload, bool with_rec, int npairs = 0)
         : nviews(nviews_), nframes(k.nframes), nent((size_t)nviews_ * l.lcap), nfeat((size_t)k.nframes * k.cap) {
-        views = L.add<orbp_view>(nviews); nlist = L.add<int32_t>(nviews); frame = L.add<int32_t>(nviews, k.frame != nullptr); nt = L.add<int32_t>(nframes);
+        views = L.add<View>(nviews); nlist = L.add<int32_t>(nviews); frame = L.add<int32_t>(nviews, k.frame != nullptr); nt = L.add<int32_t>(nframes);
         list = L.add<int32_t>(nent); skip = L.add<uint8_t>(nent, l.skip != nullptr);
         kps = L.add<orbx_keypoint>(nfeat, frames_upload); desc = L.add<uint8_t>(nfeat * 32, frames_upload);
         cell_off = L.add<int32_t>((size_t)nframes * (ORBF_GRID_CELLS + 1), frames_upload); cell_feat = L.add<int32_t>(nfeat, frames_upload);
         L.end_upload();
         best_idx = L.add<int32_t>(nent); best_dist = L.add<int32_t>(nent); rec = L.add<orbp_fused>(nent, with_rec);
+        match12 = L.add<int32_t>((size_t)npairs * l.lcap, npairs > 0); nfound = L.add<int32_t>(npairs, npairs > 0);
         L.end_download();
     }
     // copies the caller's host arrays into the pinned block h and names everything inside the device block d; key frames that are not part
     // of the block are passed through
-    void stage(uint8_t* h, uint8_t* d, const orbp_view* v, const Lists& l, const FuseFrames& k, const orbp_view*& dv, Lists& dl, FuseFrames& dk, FuseOut& dout) const {
+    void stage(uint8_t* h, uint8_t* d, const View* v, const Lists& l, const FuseFrames& k, const View*& dv, Lists& dl, FuseFrames& dk, FuseOut& dout) const {
         dv = Layout::put(h, d, views, v, nviews);
         dl = {Layout::put(h, d, list, l.list, nent), Layout::put(h, d, nlist, l.nlist, nviews), l.lcap, Layout::put(h, d, skip, l.skip, nent)};
         dk = {Layout::put(h, d, kps, k.kps_un, nfeat), Layout::put(h, d, desc, k.desc, nfeat * 32),
@@ -309,6 +320,84 @@ struct FuseBlock {
               Layout::put(h, d, nt, k.nt, nframes), k.nframes, k.cap, Layout::put(h, d, frame, k.frame, nviews)};
         dout = {Layout::at(d, best_idx), Layout::at(d, best_dist), Layout::at(d, rec)};
     }
+    // what the kernel wrote, out of the pinned block h into the caller's arrays (a null one is passed over): entries at i >= nlist[p] stay as they were
+    void unpack(uint8_t* h, const Lists& l, const FuseOut& out) const {
+        for (int p = 0; p < nviews; p++) {
+            const int n = l.nlist[p] < 0 ? 0 : (l.nlist[p] > l.lcap ? l.lcap : l.nlist[p]);
+            const size_t e = (size_t)p * l.lcap;
+            if (n == 0) continue;
+            if (out.best_idx) std::memcpy(out.best_idx + e, Layout::at(h, best_idx) + e, (size_t)n * 4);
+            if (out.best_dist) std::memcpy(out.best_dist + e, Layout::at(h, best_dist) + e, (size_t)n * 4);
+            if (out.rec) std::memcpy(out.rec + e, Layout::at(h, rec) + e, (size_t)n * sizeof(orbp_fused));
+        }
+    }
+};
+using FuseBlock = FlatBlock<orbp_view>;
+
+// ---- SearchBySim3: ORBP_MODE_SIM3 (orbp_sim3.hip)
+
+// orbp_sim3_from_pair: the arithmetic include/orbp.h states, every step a single IEEE operation (the build has -ffp-contract=off)
+inline int sim3_from_pair(float s12, const float* R12, const float* t12, const float* R1w, const float* t1w, const float* R2w, const float* t2w, float fx,
+                          float fy, float cx, float cy, const orbf_bounds* b, float th, orbp_sim3_dir* dirs) {
+    if (!R12 || !t12 || !R1w || !t1w || !R2w || !t2w || !b || !dirs) return ORBX_ERR_ARG;
+    if (s12 == 0.0f || !std::isfinite(s12)) return ORBX_ERR_ARG;
+    orbp_sim3_dir d12{}, d21{};                        // named by the similarity they carry: d21 is direction 1 -> 2
+    const double inv = 1.0 / (double)s12;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            d12.S[r * 3 + c] = (float)((double)R12[r * 3 + c] * (double)s12);
+            d21.S[r * 3 + c] = (float)((double)R12[c * 3 + r] * inv);
+        }
+    for (int r = 0; r < 3; r++) {
+        float s = 0.0f;
+        for (int k = 0; k < 3; k++) s = s + (-d21.S[r * 3 + k]) * t12[k];
+        d21.t[r] = s;
+        d12.t[r] = t12[r];
+    }
+    std::memcpy(d21.Raw, R1w, 36); std::memcpy(d21.taw, t1w, 12);
+    std::memcpy(d12.Raw, R2w, 36); std::memcpy(d12.taw, t2w, 12);
+    for (orbp_sim3_dir* d : {&d21, &d12}) {
+        d->fx = fx; d->fy = fy; d->cx = cx; d->cy = cy;
+        d->min_x = b->min_x; d->max_x = b->max_x; d->min_y = b->min_y; d->max_y = b->max_y;
+        d->th = th; d->mode = ORBP_MODE_SIM3;
+    }
+    dirs[0] = d21;
+    dirs[1] = d12;
+    return ORBX_OK;
+}
+
+// what the two kernels of orbp_sim3.hip read and write; the rows are the 2 * npairs directions, K.frame the key frame each searches, p0 the first
+// row (k_sim3) or pair (k_sim3_agree) of a launch
+struct Sim3 {
+    const orbp_sim3_dir* dirs;
+    Table T;
+    Lists L;
+    FuseFrames K;
+    orbf_bounds b;
+    int orb_dist;
+    FuseOut out;
+    int32_t* match12;
+    int32_t* nfound;
+    int p0;
+};
+hipError_t launch_sim3(const Sim3& a, int npairs, const Factors& F, hipStream_t st);
+
+// The arguments of orbp_sim3_search* that do not need the handle: those of the flat search over the 2 * npairs directions (the directions' own outputs
+// are required on the device only), and the agreement's outputs
+inline int check_sim3(const orbp_sim3_dir* dirs, int npairs, const float* factors, int nlevels, const Lists& L, const orbf_bounds* b, int orb_dist,
+                      const FuseFrames& K, const FuseOut& out, const int32_t* match12, const int32_t* nfound, bool on_device, bool frames_device) {
+    if (npairs < 0 || npairs > ORBP_MAX_VIEWS / 2) return ORBX_ERR_ARG;
+    const int rc = check_flat(dirs, 2 * npairs, factors, nlevels, L, b, orb_dist, K, out, on_device, frames_device, ORBP_MODE_SIM3, !on_device);
+    if (rc != ORBX_OK || npairs == 0) return rc;
+    if (!match12 || !nfound || (on_device && !words_aligned(match12, nfound))) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// orbp_sim3_search: the flat block over the directions, with the agreement's outputs in the download span
+struct Sim3Block : FlatBlock<orbp_sim3_dir> {
+    int npairs;
+    Sim3Block(int npairs_, const Lists& l, const FuseFrames& k, bool frames_upload, bool with_rec)
+        : FlatBlock<orbp_sim3_dir>(2 * npairs_, l, k, frames_upload, with_rec, npairs_), npairs(npairs_) {}
 };
 
 // ---- loop closing: ORBP_MODE_LOOP (orbp_loop.hip) and the view of a similarity

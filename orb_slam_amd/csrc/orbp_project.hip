@@ -26,7 +26,7 @@
 // list -> live -> geometry load each): its latency grows linearly with the list length.
 //
 // The host side of every orbp_* entry point is here too; the kernels of the other modes are k_refresh (orbp_refresh.hip), k_fuse
-// (orbp_fuse.hip) and k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip).  Every search ends in search_tail (window search, then
+// (orbp_fuse.hip), k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip) and k_sim3 / k_sim3_agree (orbp_sim3.hip).  Every search ends in search_tail (window search, then
 // k_t2source).  The one-view synchronous forms (orbp_track, orbp_track_source, orbp_loop_search) share one_view over the block orbp::OneView
 // of orbp_host.h, where the argument groups, the checks' clauses and the other forms' blocks are.
 #include <hip/hip_runtime.h>
@@ -644,15 +644,67 @@ int orbp_fuse(orbp_map* m, const orbp_view* views, int nviews, const float* fact
         HIPCHK(m, orbp::launch_fuse(a, nviews, F, c.st));
         return ORBX_OK;
     }));
-    // only what the kernel wrote reaches the caller: entries at i >= nlist[p] stay as they were
-    for (int p = 0; p < nviews; p++) {
-        const int n = std::min(std::max(nlist[p], 0), lcap);
-        const size_t e = (size_t)p * lcap;
-        if (n == 0) continue;
-        std::memcpy(best_idx + e, Layout::at(s.h, B.best_idx) + e, (size_t)n * 4);
-        std::memcpy(best_dist + e, Layout::at(s.h, B.best_dist) + e, (size_t)n * 4);
-        if (rec) std::memcpy(rec + e, Layout::at(s.h, B.rec) + e, (size_t)n * sizeof(orbp_fused));
+    B.unpack(s.h, L, out);                                                // only what the kernel wrote reaches the caller
+    return ORBX_OK;
+}
+
+int orbp_sim3_from_pair(float s12, const float* R12, const float* t12, const float* R1w, const float* t1w, const float* R2w, const float* t2w, float fx,
+                        float fy, float cx, float cy, const orbf_bounds* b, float th, orbp_sim3_dir* dirs) {
+    return orbp::sim3_from_pair(s12, R12, t12, R1w, t1w, R2w, t2w, fx, fy, cx, cy, b, th, dirs);
+}
+
+int orbp_sim3_search_batch_device(orbp_map* m, const orbp_sim3_dir* d_dirs, int npairs, const float* factors, int nlevels, const int32_t* d_list,
+                                  const int32_t* d_nlist, int lcap, const uint8_t* d_skip, const int32_t* d_frame, const orbx_keypoint* d_kps_un,
+                                  const uint8_t* d_desc, const int32_t* d_cell_off, const int32_t* d_cell_feat, const int32_t* d_nt, int nframes, int cap,
+                                  const orbf_bounds* b, int orb_dist, int32_t* d_best_idx, int32_t* d_best_dist, orbp_fused* d_rec, int32_t* d_match12,
+                                  int32_t* d_nfound, void* stream) {
+    const orbp::Lists L{d_list, d_nlist, lcap, d_skip};
+    const orbp::FuseFrames K{d_kps_un, d_desc, d_cell_off, d_cell_feat, d_nt, nframes, cap, d_frame};
+    const orbp::FuseOut out{d_best_idx, d_best_dist, d_rec};
+    orbp::Factors F;
+    if (!m || orbp::check_sim3(d_dirs, npairs, factors, nlevels, L, b, orb_dist, K, out, d_match12, d_nfound, true, true) != ORBX_OK ||
+        fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (npairs == 0) return ORBX_OK;
+    Call c(m, stream);
+    TRY(c.begin());
+    const orbp::Sim3 a{d_dirs, table_of(m), L, K, *b, orb_dist, out, d_match12, d_nfound, 0};
+    HIPCHK(m, orbp::launch_sim3(a, npairs, F, c.st));
+    return c.end();
+}
+
+int orbp_sim3_search(orbp_map* m, const orbp_sim3_dir* dirs, int npairs, const float* factors, int nlevels, const int32_t* list, const int32_t* nlist, int lcap,
+                     const uint8_t* skip, const int32_t* frame, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
+                     const int32_t* cell_feat, const int32_t* nt, int nframes, int cap, int frames_on_device, const orbf_bounds* b, int orb_dist,
+                     int32_t* best_idx, int32_t* best_dist, orbp_fused* rec, int32_t* match12, int32_t* nfound, void* stream) {
+    const orbp::Lists L{list, nlist, lcap, skip};
+    const orbp::FuseFrames K{kps_un, desc, cell_off, cell_feat, nt, nframes, cap, frame};
+    const orbp::FuseOut out{best_idx, best_dist, rec};
+    orbp::Factors F;
+    if (!m || orbp::check_sim3(dirs, npairs, factors, nlevels, L, b, orb_dist, K, out, match12, nfound, false, frames_on_device != 0) != ORBX_OK ||
+        fill_factors(factors, nlevels, F) != ORBX_OK)
+        return ORBX_ERR_ARG;
+    if (npairs == 0) return ORBX_OK;
+    Call c(m, stream);
+    const orbp::Sim3Block B(npairs, L, K, frames_on_device == 0, rec != nullptr);
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    const orbp_sim3_dir* dv;
+    orbp::Lists dl;
+    orbp::FuseFrames dk;
+    orbp::FuseOut dout;
+    B.stage(s.h, s.d, dirs, L, K, dv, dl, dk, dout);
+    TRY(s.run([&]() -> int {
+        const orbp::Sim3 a{dv, table_of(m), dl, dk, *b, orb_dist, dout, Layout::at(s.d, B.match12), Layout::at(s.d, B.nfound), 0};
+        HIPCHK(m, orbp::launch_sim3(a, npairs, F, c.st));
+        return ORBX_OK;
+    }));
+    B.unpack(s.h, L, out);
+    for (int p = 0; p < npairs; p++) {
+        const int n1 = std::min(std::max(nlist[2 * p], 0), lcap);
+        if (n1 > 0) std::memcpy(match12 + (size_t)p * lcap, Layout::at(s.h, B.match12) + (size_t)p * lcap, (size_t)n1 * 4);
     }
+    std::memcpy(nfound, Layout::at(s.h, B.nfound), (size_t)npairs * 4);
     return ORBX_OK;
 }
 

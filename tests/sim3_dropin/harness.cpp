@@ -1,0 +1,178 @@
+// Drives ORB_SLAM::LocalMapPoints::SearchBySim3 (orb_slam_amd/cpp/LocalMapPointsSim3.cc, over the stand-in MapPoint.h of this directory, the
+// KeyFrame.h of tests/loop_dropin and the Frame.h of tests/mappoints_dropin) through a script, and on request runs the reference's last step
+// (src/ORBmatcher.cc:1489-1502: vpMatches12[i1] = vpMapPoints2[idx2], nFound++) over an agreement table the script supplies instead of the two
+// searches; tests/test_gpu_sim3_dropin.py builds two identical object graphs that way and compares what is left of vpMatches12.
+// Floats travel as the hex of their bit pattern.
+//
+//   harness SCRIPT
+//
+// Script lines (cam, factors, new, mp, bad, kfs and kf as tests/loop_dropin/harness.cpp):
+//   sim3 K1 K2 S12 R12(9) T12(3) TH M mid ...            LocalMapPoints::SearchBySim3(&kf[K1], &kf[K2], vpMatches12, s12, R12, t12, TH) with
+//                                                        vpMatches12 given per feature of K1 (-1 none); prints "S ret" and "M id ..." (afterwards)
+//   sim3batch K1 TH NC {K2 S12 R12(9) T12(3) M mid ...}  the batch form over NC candidates; prints "S ret" and "M id ..." per candidate, in order
+//   refsim3 K2 N i1 idx2 ... M mid ...                   the reference's last step with the N agreed pairs in place of the searches
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <sstream>
+#include <string>
+
+#include "Frame.h"
+#include "KeyFrame.h"
+#include "LocalMapPoints.h"
+#include "MapPoint.h"
+
+namespace ORB_SLAM {
+float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
+int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
+float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
+int MapPoint::nReplaced = 0;
+}
+using namespace ORB_SLAM;
+
+namespace {
+
+float rdf(std::istringstream& in) {
+    std::string h;
+    in >> h;
+    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+void rddesc(std::istringstream& in, unsigned char* d) {
+    std::string h;
+    in >> h;
+    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
+}
+
+typedef std::map<long, std::unique_ptr<MapPoint> > Points;
+
+// "M n id ..." -> vpMatches12 on entry
+std::vector<MapPoint*> rdmatches(std::istringstream& in, Points& mps) {
+    std::string tag;
+    int m;
+    in >> tag >> m;
+    std::vector<MapPoint*> v(m);
+    for (int i = 0; i < m; i++) { long id; in >> id; v[i] = id < 0 ? nullptr : mps.at(id).get(); }
+    return v;
+}
+struct Similarity { float s; cv::Mat R, t; };
+Similarity rdsim(std::istringstream& in) {
+    Similarity S{rdf(in), cv::Mat(3, 3, CV_32F), cv::Mat(3, 1, CV_32F)};
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) S.R.at<float>(r, c) = rdf(in);
+    for (int r = 0; r < 3; r++) S.t.at<float>(r) = rdf(in);
+    return S;
+}
+void report(int ret, const std::vector<MapPoint*>& matches) {
+    printf("S %d\nM", ret);
+    for (MapPoint* p : matches) printf(" %ld", p ? (long)p->mnId : -1L);
+    printf("\n");
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream f(argv[1]);
+    std::string line;
+    Points mps;
+    std::vector<KeyFrame> kfs;
+    std::unique_ptr<LocalMapPoints> L;
+    std::vector<float> factors;
+    while (std::getline(f, line)) {
+        std::istringstream in(line);
+        std::string op;
+        if (!(in >> op)) continue;
+        if (op == "cam") {
+            Frame::fx = rdf(in); Frame::fy = rdf(in); Frame::cx = rdf(in); Frame::cy = rdf(in);
+            in >> Frame::mnMinX >> Frame::mnMaxX >> Frame::mnMinY >> Frame::mnMaxY;
+            Frame::mfGridElementWidthInv = rdf(in); Frame::mfGridElementHeightInv = rdf(in);
+        } else if (op == "factors") {
+            int n; in >> n;
+            factors.resize(n);
+            for (int i = 0; i < n; i++) factors[i] = rdf(in);
+        } else if (op == "new") {
+            int refresh, cap; in >> refresh >> cap;
+            L.reset(new LocalMapPoints(0.8f, refresh != 0, cap));
+        } else if (op == "mp") {
+            long id; in >> id;
+            if (!mps.count(id)) { mps[id].reset(new MapPoint); mps[id]->mnId = id; }
+            MapPoint& m = *mps[id];
+            for (int k = 0; k < 3; k++) m.mWorldPos.at<float>(k) = rdf(in);
+            for (int k = 0; k < 3; k++) m.mNormalVector.at<float>(k) = rdf(in);
+            m.mfMinDistance = rdf(in); m.mfMaxDistance = rdf(in);
+            rddesc(in, m.mDescriptor.ptr<unsigned char>(0));
+        } else if (op == "bad") { long id; int v; in >> id >> v; mps.at(id)->mbBad = v != 0;
+        } else if (op == "kfs") {
+            int n; in >> n;
+            kfs.assign(n, KeyFrame());
+        } else if (op == "kf") {
+            int k, n; in >> k;
+            KeyFrame& K = kfs.at(k);
+            K.mnId = k;
+            K.fx = Frame::fx; K.fy = Frame::fy; K.cx = Frame::cx; K.cy = Frame::cy;
+            K.mfGridElementWidthInv = Frame::mfGridElementWidthInv; K.mfGridElementHeightInv = Frame::mfGridElementHeightInv;
+            K.Rcw = cv::Mat(3, 3, CV_32F); K.tcw = cv::Mat(3, 1, CV_32F); K.Ow = cv::Mat(3, 1, CV_32F);
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) K.Rcw.at<float>(r, c) = rdf(in);
+            for (int r = 0; r < 3; r++) K.tcw.at<float>(r) = rdf(in);
+            for (int r = 0; r < 3; r++) K.Ow.at<float>(r) = 0.0f;          // the camera centre is not read by this search
+            in >> n;
+            K.mvScaleFactors = factors;
+            K.mvKeysUn.assign(n, cv::KeyPoint());
+            K.mvpMapPoints.assign(n, nullptr);
+            K.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
+            for (int i = 0; i < n; i++) {
+                std::getline(f, line);
+                std::istringstream kin(line);
+                cv::KeyPoint& kp = K.mvKeysUn[i];
+                kp.pt.x = rdf(kin); kp.pt.y = rdf(kin);
+                kin >> kp.octave;
+                rddesc(kin, K.mDescriptors.ptr<unsigned char>(i));
+                long id; kin >> id;
+                if (id >= 0) { K.mvpMapPoints[i] = mps.at(id).get(); mps.at(id)->mObservations[&K] = (size_t)i; }
+            }
+        } else if (op == "sim3") {
+            int k1, k2; in >> k1 >> k2;
+            const Similarity S = rdsim(in);
+            const float th = rdf(in);
+            std::vector<MapPoint*> matches = rdmatches(in, mps);
+            const int ret = L->SearchBySim3(&kfs.at(k1), &kfs.at(k2), matches, S.s, S.R, S.t, th);
+            report(ret, matches);
+        } else if (op == "sim3batch") {
+            int k1, nc; in >> k1;
+            const float th = rdf(in);
+            in >> nc;
+            std::vector<std::vector<MapPoint*> > matches(nc);
+            std::vector<LocalMapPoints::Sim3Candidate> cand(nc);
+            for (int c = 0; c < nc; c++) {
+                int k2; in >> k2;
+                const Similarity S = rdsim(in);
+                matches[c] = rdmatches(in, mps);
+                cand[c] = LocalMapPoints::Sim3Candidate{&kfs.at(k2), S.s, S.R, S.t, &matches[c]};
+            }
+            std::vector<int> found;
+            L->SearchBySim3(&kfs.at(k1), cand, th, &found);
+            for (int c = 0; c < nc; c++) report(found[c], matches[c]);
+        } else if (op == "refsim3") {
+            int k2, n; in >> k2 >> n;
+            std::vector<std::pair<int, int> > agreed(n);
+            for (int i = 0; i < n; i++) in >> agreed[i].first >> agreed[i].second;
+            std::vector<MapPoint*> matches = rdmatches(in, mps);
+            const std::vector<MapPoint*> vpMapPoints2 = kfs.at(k2).GetMapPointMatches();
+            int nFound = 0;
+            for (size_t i = 0; i < agreed.size(); i++) {
+                matches[agreed[i].first] = vpMapPoints2[agreed[i].second];
+                nFound++;
+            }
+            report(nFound, matches);
+        } else {
+            fprintf(stderr, "unknown script line: %s\n", line.c_str());
+            return 2;
+        }
+    }
+    return 0;
+}
