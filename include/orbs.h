@@ -21,7 +21,8 @@
  *                           (a train feature may be re-matched by a later query with a strictly smaller distance)
  *   ORBS_RULE_BOW        <- int ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&)                 :155-281
  *                           (candidates = the features of the same vocabulary node instead of a grid window:
- *                           orbs_bow_ranges_batch_device + orbs_list_search_batch_device; accept best <= th && best < ratio*second)
+ *                           orbs_bow_ranges_batch_device + orbs_list_search_batch_device, or orbs_bow_rows_search_batch_device over the rows of a
+ *                           resident store; accept best <= th && best < ratio*second)
  *                           int ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&)              :715-850
  *                           (the same with d_claimed = "pMP2 is NULL or bad" and th = TH_LOW - 1: that function tests `bestDist1<TH_LOW`)
  *   ORBS_RULE_TRIANGULATION <- int ORBmatcher::SearchForTriangulation(KeyFrame*, KeyFrame*, cv::Mat F12, ...)  :852-1014
@@ -159,6 +160,49 @@ int orbs_agreement_batch_device(const int32_t* d_match12, const int32_t* d_n1, i
 int orbs_bow_ranges_batch_device(const uint32_t* d_fvq_node, const int32_t* d_fvq_off, const int32_t* d_nfv_q,
                                  const uint32_t* d_fvt_node, const int32_t* d_fvt_off, const int32_t* d_nfv_t, int cap,
                                  int nproblems, int32_t* d_qrange, int32_t* d_nq, void* stream);
+
+/* ---- SearchByBoW over the rows of a resident key-frame store (orbs_bow_rows.hip): every pair in one launch ----------------------------
+ *
+ * Replaces, per pair, orbs_bow_ranges_batch_device + orbs_list_search_batch_device without their per-problem slots: pair p searches the
+ * features of row d_pair[2p] (the QUERY side: pKF of SearchByBoW(pKF, F, ..), pKF1 of SearchByBoW(pKF1, pKF2, ..)) in row d_pair[2p+1] (the TRAIN
+ * side: F, pKF2).  Several pairs may share a query row or a train row; nothing per row is written.
+ *
+ * Rows: row r has d_nt[r] features (clamped to [0, cap]) at d_kps + r*cap (only .angle is read, and only with check_orientation) and
+ * d_desc + (r*cap)*32, and its FeatureVector as orbv_transform_batch_device writes it: d_nfv[r] nodes, ascending ids at d_fv_node + r*cap,
+ * offsets at d_fv_off + r*(cap+1), feature indices at d_fv_feat + r*cap (every feature at most once).  A row that has no FeatureVector yet has
+ * d_nfv[r] = 0 and matches nothing.
+ * Per pair: d_qvalid[p*cap + idx1] (NULL = all): the query feature holds a good map point; d_claimed[p*cap + idx2] (NULL = none): the train
+ * feature may not be matched.
+ *
+ * Semantics: exactly the two reference functions as ORBS_RULE_BOW states them above (prm->rule must be ORBS_RULE_BOW).  th = ORBS_TH_LOW and
+ * d_claimed = NULL is the key-frame / frame form; th = ORBS_TH_LOW - 1 with d_claimed = "pMP2 is NULL or bad" the key-frame / key-frame form.
+ * Accept best <= th && (float)best < ratio * (float)second; ties go to the first listed candidate; a match claims its train feature for the
+ * later queries of its node; with check_orientation the matches outside the three largest rotation bins (orbs_three_maxima) are cleared from
+ * both outputs but keep their claim during the scan, as in the reference.
+ *
+ * Outputs per pair, FEATURE indexed: d_q2t[p*cap + idx1] the train feature (-1 none), d_t2q[p*cap + idx2] the query feature (-1 none), d_best /
+ * d_second[p*cap + idx1] the two distances the scan of that query left (INT_MAX as in the reference; -1 when the query was never visited: not
+ * valid, or its node is not in the train row), d_nmatches[p] the function's return value.  All cap entries of a pair are written: those at or
+ * behind a row's count are -1.  d_q2t, d_t2q, d_best and d_second may each be NULL.  A pair whose row is outside [0, nrows) finds nothing
+ * (d_nmatches[p] = 0, all -1).
+ *
+ * ORBX_ERR_ARG before anything touches the GPU for a rule that is not ORBS_RULE_BOW, th outside [0, 256], a NaN ratio, npairs < 0, nrows < 1, cap
+ * outside [1, ORBF_MAX_FEATURES], npairs * cap or nrows * (cap + 1) >= 2^31, a NULL required array, d_desc not 16-byte aligned, another word array
+ * not 4-byte aligned.  Asynchronous on `stream`, ordered behind the process's earlier calls on the same device (they share the scratch between
+ * the two kernels: 16 bytes per pair and feature, grown on the first call of a size, synchronously, and kept); otherwise nothing is allocated. */
+int orbs_bow_rows_search_batch_device(const orbs_params* prm, const int32_t* d_pair, int npairs, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                      const int32_t* d_nt, const uint32_t* d_fv_node, const int32_t* d_fv_off, const uint32_t* d_fv_feat,
+                                      const int32_t* d_nfv, int nrows, int cap, const uint8_t* d_qvalid, const uint8_t* d_claimed, int32_t* d_q2t,
+                                      int32_t* d_t2q, int32_t* d_best, int32_t* d_second, int32_t* d_nmatches, void* stream);
+
+/* The same, synchronous, over host arrays: one pinned block up, one down.  pair, qvalid, claimed, the rows' counts nt and nfv and the outputs are host
+ * memory; the rows' arrays (kps, desc, fv_node, fv_off, fv_feat) are host memory, or device memory read in place when rows_on_device != 0 (aligned
+ * as above).  Here in
+ * addition: ORBX_ERR_ARG for a pair whose row is outside [0, nrows).  The block is the process's own per device, grown on first use and kept. */
+int orbs_bow_rows_search(const orbs_params* prm, const int32_t* pair, int npairs, const orbx_keypoint* kps, const uint8_t* desc, const int32_t* nt,
+                         const uint32_t* fv_node, const int32_t* fv_off, const uint32_t* fv_feat, const int32_t* nfv, int nrows, int cap,
+                         int rows_on_device, const uint8_t* qvalid, const uint8_t* claimed, int32_t* q2t, int32_t* t2q, int32_t* best, int32_t* second,
+                         int32_t* nmatches, void* stream);
 
 /* ORBmatcher::ComputeThreeMaxima on a histogram of bin sizes (host, re-entrant): ind[3], -1 = none */
 void orbs_three_maxima(const int32_t* sizes, int L, int32_t* ind);

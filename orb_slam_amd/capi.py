@@ -42,7 +42,8 @@ EXPORTS_F = [
 ]
 # include/orbs.h (greedy grid-window searches)
 EXPORTS_S = ["orbs_lds_bytes", "orbs_debug_set_buckets", "orbs_debug_set_wide_max", "orbs_three_maxima", "orbs_window_search_batch_device", "orbs_list_search_batch_device",
-             "orbs_bow_ranges_batch_device", "orbs_triangulation_search_batch_device", "orbs_epipolar_bound", "orbs_agreement_batch_device"]
+             "orbs_bow_ranges_batch_device", "orbs_triangulation_search_batch_device", "orbs_epipolar_bound", "orbs_agreement_batch_device",
+             "orbs_bow_rows_search_batch_device", "orbs_bow_rows_search"]
 PHASE_PYRAMID, PHASE_DETECT, PHASE_DESCRIBE, PHASE_ALL = 1, 2, 4, 7
 RULE_MAPPOINTS, RULE_WINDOW, RULE_BEST, RULE_INIT, RULE_BOW, RULE_FREE, RULE_TRIANGULATION = 0, 1, 2, 3, 4, 5, 6
 TH_HIGH, TH_LOW = 100, 50
@@ -291,6 +292,8 @@ def lib():
         L.orbs_epipolar_bound.argtypes = [ctypes.c_float]
         L.orbs_epipolar_bound.restype = ctypes.c_float
         L.orbs_agreement_batch_device.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]
+        L.orbs_bow_rows_search_batch_device.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbs_bow_rows_search.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbv_create.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, ctypes.POINTER(vp)]
         L.orbv_load_text.argtypes = [ctypes.c_char_p, ci, ctypes.POINTER(vp)]
         L.orbv_destroy.argtypes = [vp]
@@ -1070,6 +1073,66 @@ def bow_ranges_batch_device(d_fvq_node, d_fvq_off, d_nfv_q, d_fvt_node, d_fvt_of
     rc = lib().orbs_bow_ranges_batch_device(d_fvq_node, d_fvq_off, d_nfv_q, d_fvt_node, d_fvt_off, d_nfv_t, cap, nproblems, d_qrange, d_nq, stream or None)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbs_bow_ranges_batch_device")
+
+
+def bow_rows_search_batch_device(th, ratio, check_orientation, d_pair, npairs, d_kps, d_desc, d_nt, d_fv_node, d_fv_off, d_fv_feat, d_nfv, nrows, cap,
+                                 d_qvalid, d_claimed, d_q2t, d_t2q, d_best, d_second, d_nmatches, stream=0):
+    """SearchByBoW over the rows of a resident key-frame store, every (query row, train row) pair in one launch (include/orbs.h); device
+    pointers as ints (0 = NULL).  Asynchronous on `stream`."""
+    prm = SearchParams(RULE_BOW, th, ratio, 1 if check_orientation else 0)
+    rc = lib().orbs_bow_rows_search_batch_device(ctypes.byref(prm), d_pair or None, npairs, d_kps or None, d_desc or None, d_nt or None, d_fv_node or None,
+                                                 d_fv_off or None, d_fv_feat or None, d_nfv or None, nrows, cap, d_qvalid or None, d_claimed or None,
+                                                 d_q2t or None, d_t2q or None, d_best or None, d_second or None, d_nmatches or None, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbs_bow_rows_search_batch_device")
+
+
+def bow_rows_search(th, ratio, check_orientation, pairs, kps, desc, nt, fv_node, fv_off, fv_feat, nfv, nrows, cap, qvalid=None, claimed=None,
+                    rows_on_device=False, want_dist=True, stream=0):
+    """The same, synchronous: pairs[npairs, 2] and the per-pair flags qvalid / claimed [npairs, cap] are host arrays; the rows are host arrays
+    (kps[nrows, cap] of KP_DTYPE, desc[nrows, cap, 32], nt[nrows], fv_node[nrows, cap], fv_off[nrows, cap + 1], fv_feat[nrows, cap], nfv[nrows]) or,
+    with rows_on_device, device pointers as ints for all but the counts nt and nfv, which stay host arrays.  -> (nmatches[npairs], q2t[npairs, cap], t2q[npairs, cap], best, second (None without want_dist))"""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    npairs = len(pr)
+    keep = []
+
+    def flags(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.shape != (npairs, cap):
+            raise ValueError("per-pair flags must be [npairs, cap]")
+        keep.append(a)
+        return a.ctypes.data
+
+    if rows_on_device:
+        counts = [np.ascontiguousarray(a, dtype=np.int32) for a in (nt, nfv)]
+        if any(a.shape != (nrows,) for a in counts):
+            raise ValueError("nt and nfv must have one entry per row")
+        keep.extend(counts)
+        rows = [int(kps) or None, int(desc) or None, counts[0].ctypes.data, int(fv_node) or None, int(fv_off) or None, int(fv_feat) or None, counts[1].ctypes.data]
+    else:
+        shapes = ((KP_DTYPE, (nrows, cap)), (np.uint8, (nrows, cap, 32)), (np.int32, (nrows,)), (np.uint32, (nrows, cap)), (np.int32, (nrows, cap + 1)),
+                  (np.uint32, (nrows, cap)), (np.int32, (nrows,)))
+        rows = []
+        for a, (dt, shape) in zip((kps, desc, nt, fv_node, fv_off, fv_feat, nfv), shapes):
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != shape:
+                raise ValueError("a row array has the wrong shape: %s, not %s" % (a.shape, shape))
+            keep.append(a)
+            rows.append(a.ctypes.data)
+    n = max(npairs, 1)
+    nm = np.zeros(n, np.int32)
+    q2t = np.zeros((n, cap), np.int32); t2q = np.zeros((n, cap), np.int32)
+    best = np.zeros((n, cap), np.int32) if want_dist else None
+    second = np.zeros((n, cap), np.int32) if want_dist else None
+    prm = SearchParams(RULE_BOW, th, ratio, 1 if check_orientation else 0)
+    rc = lib().orbs_bow_rows_search(ctypes.byref(prm), pr.ctypes.data if npairs else None, npairs, *rows, nrows, cap, 1 if rows_on_device else 0,
+                                    flags(qvalid), flags(claimed), q2t.ctypes.data, t2q.ctypes.data, best.ctypes.data if want_dist else None,
+                                    second.ctypes.data if want_dist else None, nm.ctypes.data, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbs_bow_rows_search")
+    return nm[:npairs], q2t[:npairs], t2q[:npairs], (best[:npairs] if want_dist else None), (second[:npairs] if want_dist else None)
 
 
 class KeyFrameDatabase:

@@ -38,6 +38,9 @@ LocalMapPoints::~LocalMapPoints() {
     if (d_kf_desc_) orbx_device_free(device_, d_kf_desc_);
     if (d_kf_cell_off_) orbx_device_free(device_, d_kf_cell_off_);
     if (d_kf_cell_feat_) orbx_device_free(device_, d_kf_cell_feat_);
+    if (d_kf_fv_node_) orbx_device_free(device_, d_kf_fv_node_);
+    if (d_kf_fv_off_) orbx_device_free(device_, d_kf_fv_off_);
+    if (d_kf_fv_feat_) orbx_device_free(device_, d_kf_fv_feat_);
 }
 
 void LocalMapPoints::grow() {

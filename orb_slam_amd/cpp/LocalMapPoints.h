@@ -20,6 +20,9 @@
 // SearchBySim3 (LocalMapPointsSim3.cc) replaces ORBmatcher::SearchBySim3 as LoopClosing::ComputeSim3 calls it for every candidate whose RANSAC
 // converged: both key frames' points are searched in each other's resident row by ONE orbp_sim3_search, all candidates of a call together, and
 // only two poses, the similarity and two slot lists per candidate go up.
+// SearchByBoW (LocalMapPointsBoW.cc) replaces both ORBmatcher::SearchByBoW overloads as Tracking::Relocalisation and LoopClosing::ComputeSim3 call
+// them per candidate: the rows of the key-frame store gain their FeatureVector, and every candidate of a call is one pair of ONE
+// orbs_bow_rows_search.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
@@ -122,6 +125,24 @@ public:
     };
     void SearchBySim3(KeyFrame* pKF1, const std::vector<Sim3Candidate>& vCandidates, float th, std::vector<int>* nFound = 0);
 
+    // int ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:155-281) as Tracking::Relocalisation calls it for every
+    // candidate (src/Tracking.cc:880-901, ORBmatcher(0.75, true)), with the reference's effect on vpMapPointMatches and its return value
+    // (LocalMapPointsBoW.cc; links only when that file, LocalMapPointsFuse.cc and LocalMapPointsRefresh.cc are built in).  pKF's features come from
+    // the resident key-frame store, whose rows also carry the key frame's FeatureVector from the first such call on (GetFeatureVector(), once per
+    // key frame, until ForgetKeyFrame); F goes up per call as one extra row (mvKeys, mDescriptors, mFeatVec).  Reads GetMapPointMatches() and isBad().
+    int SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches, float nnratio = 0.75f, bool checkOrientation = true);
+    // The same for every candidate of one Relocalisation in ONE launch: F goes up once.  vvpMatches[i] is what candidate i's own call leaves; a
+    // NULL or bad candidate is passed over with an empty vector and 0 matches, so the caller's loop keeps its shape.
+    void SearchByBoW(const std::vector<KeyFrame*>& vpCandidates, Frame& F, std::vector<std::vector<MapPoint*> >& vvpMatches, std::vector<int>* nmatches = 0,
+                     float nnratio = 0.75f, bool checkOrientation = true);
+    // int ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&) (src/ORBmatcher.cc:715-850) as LoopClosing::ComputeSim3 calls it for every
+    // consistent candidate (src/LoopClosing.cc:246-274, ORBmatcher(0.75, true)).  Both key frames are resident rows: per call only the pair list
+    // and the two flag arrays built from GetMapPointMatches() and isBad() go up.
+    int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, float nnratio = 0.75f, bool checkOrientation = true);
+    // One pKF1 against every candidate in ONE launch; NULL and bad candidates as above.
+    void SearchByBoW(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpCandidates, std::vector<std::vector<MapPoint*> >& vvpMatches12,
+                     std::vector<int>* nmatches = 0, float nnratio = 0.75f, bool checkOrientation = true);
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
@@ -171,6 +192,18 @@ private:
     void* d_kf_cell_off_ = nullptr;
     void* d_kf_cell_feat_ = nullptr;
     int kf_rows_ = 0, feat_cap_ = 0;
+    // the rows' FeatureVectors (LocalMapPointsBoW.cc), as CSR, for kf_rows_ + 1 rows of feat_cap_: the last row is the frame of the call.  The
+    // features' arrays above have that extra row too.
+    void residentForBoW(const std::vector<KeyFrame*>& kfs, int frameFeatures);
+    void searchBoW(const std::vector<int32_t>& pairs, int frameFeatures, int frameNodes, int th, float nnratio, bool checkOrientation,
+                   const std::vector<uint8_t>& qvalid, const std::vector<uint8_t>* claimed, std::vector<int32_t>* q2t, std::vector<int32_t>* t2q,
+                   std::vector<int32_t>& found);
+    std::vector<uint8_t> kf_fv_resident_;        // per row: its FeatureVector is on the device
+    std::vector<int32_t> kf_nfv_;                // per row: its number of nodes
+    void* d_kf_fv_node_ = nullptr;
+    void* d_kf_fv_off_ = nullptr;
+    void* d_kf_fv_feat_ = nullptr;
+    int fv_rows_ = 0, fv_cap_ = 0;               // the dimensions the three arrays were allocated for
     // per call
     std::vector<int32_t> list_, t2slot_, t2pos_, cell_off_, cell_feat_;
     std::vector<uint8_t> skip_, claimed_;

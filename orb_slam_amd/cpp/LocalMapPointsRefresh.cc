@@ -19,8 +19,9 @@ void LocalMapPoints::growKeyFrames(int rows, int feats) {
     if (d_kf_cell_off_) orbx_device_free(device_, d_kf_cell_off_);
     if (d_kf_cell_feat_) orbx_device_free(device_, d_kf_cell_feat_);
     d_kf_kps_ = d_kf_desc_ = d_kf_cell_off_ = d_kf_cell_feat_ = nullptr;
-    int rc = orbx_device_alloc(device_, (size_t)rows * feats * sizeof(orbx_keypoint), &d_kf_kps_);
-    if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)rows * feats * 32, &d_kf_desc_);
+    // one row more than the key frames have: the frame of a SearchByBoW call (LocalMapPointsBoW.cc)
+    int rc = orbx_device_alloc(device_, (size_t)(rows + 1) * feats * sizeof(orbx_keypoint), &d_kf_kps_);
+    if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)(rows + 1) * feats * 32, &d_kf_desc_);
     // the rows' grids, for Fuse (LocalMapPointsFuse.cc fills them): 12 KiB per row
     if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)rows * (ORBF_GRID_CELLS + 1) * 4, &d_kf_cell_off_);
     if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)rows * feats * 4, &d_kf_cell_feat_);
@@ -29,6 +30,8 @@ void LocalMapPoints::growKeyFrames(int rows, int feats) {
     kf_owner_.resize(rows, nullptr);
     kf_resident_.assign(rows, 0);
     kf_grid_resident_.assign(rows, 0);
+    kf_fv_resident_.assign(rows, 0);
+    kf_nfv_.assign(rows, 0);
     kf_nt_.assign(rows, 0);
     kf_rows_ = rows;
     feat_cap_ = feats;
@@ -44,6 +47,7 @@ int LocalMapPoints::keyFrameRow(KeyFrame* pKF) {
     kf_owner_[row] = pKF;
     kf_resident_[row] = 0;
     kf_grid_resident_[row] = 0;
+    kf_fv_resident_[row] = 0;
     return row;
 }
 
@@ -53,6 +57,8 @@ void LocalMapPoints::ForgetKeyFrame(KeyFrame* pKF) {
     kf_owner_[it->second] = nullptr;
     kf_resident_[it->second] = 0;
     kf_grid_resident_[it->second] = 0;
+    kf_fv_resident_[it->second] = 0;                                  // its FeatureVector goes with it
+    kf_nfv_[it->second] = 0;
     kf_free_.push_back(it->second);
     kf_row_.erase(it);
 }
