@@ -9,7 +9,7 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -ffp-contract=off -mll
 ORBX_SRCS  := $(wildcard orb_slam_amd/csrc/*.hip)
 ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*.h)
 
-all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
+all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tests/newpoints_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
 
 # the hash of the kernel sources travels inside the library (orbx_build_id): counters replayed by bench.py must come from THIS build
 SRC_HASH   := $(shell cat $(sort $(ORBX_SRCS) $(ORBX_HDRS)) | sha256sum | cut -c1-16)
@@ -125,6 +125,16 @@ tests/bow_dropin/harness: tests/bow_dropin/harness.cpp $(BW_DROPIN) include/orbp
 	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsBoW.cc -o $@ -Lorb_slam_amd -lorbx \
 	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
 
+# LocalMapPoints::CreateNewMapPoints (orb_slam_amd/cpp/LocalMapPointsNewPoints.cc, over residentForBoW of LocalMapPointsBoW.cc) next to the loop over
+# TriangulateNewMapPoints (orb_slam_amd/cpp/NewMapPoints.cc), driven by scripts (tests/test_gpu_newpoints_dropin.py); KeyFrame.h is this directory's (it
+# adds the level tables), Frame.h that of tests/bow_dropin, MapPoint.h that of tests/fuse_dropin, cvmini.h that of tests/mappoints_dropin
+NP_DROPIN := orb_slam_amd/cpp/LocalMapPointsNewPoints.cc orb_slam_amd/cpp/NewPointsPacking.h orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h \
+    orb_slam_amd/cpp/LocalMapPointsBoW.cc orb_slam_amd/cpp/FeatureVectorCSR.h $(FU_DROPIN) tests/bow_dropin/Frame.h $(wildcard tests/newpoints_dropin/*.h)
+tests/newpoints_dropin/harness: tests/newpoints_dropin/harness.cpp $(NP_DROPIN) include/orbt.h include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
+	$(CXX) -O2 -std=c++14 -Wall -Itests/newpoints_dropin -Itests/bow_dropin -Itests/fuse_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< \
+	    orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsBoW.cc \
+	    orb_slam_amd/cpp/LocalMapPointsNewPoints.cc orb_slam_amd/cpp/NewMapPoints.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+
 # the NewMapPoints drop-in (orb_slam_amd/cpp/NewMapPoints.cc) over a stand-in KeyFrame.h, driven by scripts
 # (tests/test_gpu_triangulate_dropin.py); cvmini.h is that of tests/mappoints_dropin
 TRI_DROPIN := orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h tests/triangulate_dropin/KeyFrame.h tests/mappoints_dropin/cvmini.h
@@ -181,7 +191,7 @@ tools/microbench/ta_shapes: tools/microbench/ta_shapes.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++20 -Wno-unused-value $< -o $@
 
 clean:
-	rm -f tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
+	rm -f tests/newpoints_dropin/harness tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
 	rm -rf oracle/_ref oracle/_ref_native build/orbx
 
 .PHONY: all clean oracle_ref

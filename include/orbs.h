@@ -26,7 +26,8 @@
  *                           int ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&)              :715-850
  *                           (the same with d_claimed = "pMP2 is NULL or bad" and th = TH_LOW - 1: that function tests `bestDist1<TH_LOW`)
  *   ORBS_RULE_TRIANGULATION <- int ORBmatcher::SearchForTriangulation(KeyFrame*, KeyFrame*, cv::Mat F12, ...)  :852-1014
- *                           with ORBmatcher::CheckDistEpipolarLine :136-153 (orbs_triangulation_search_batch_device: candidates of the
+ *                           with ORBmatcher::CheckDistEpipolarLine :136-153 (orbs_triangulation_search_batch_device, or
+ *                           orbs_tri_rows_search_batch_device over the rows of a resident store: candidates of the
  *                           same vocabulary node with distance <= th, sorted by (distance, index); the first one within
  *                           2 x the best distance that lies on the query's epipolar line is taken)
  *   ORBS_RULE_FREE       <- the searches WITHOUT the "already matched" masking, every query independent: the scan of
@@ -203,6 +204,44 @@ int orbs_bow_rows_search(const orbs_params* prm, const int32_t* pair, int npairs
                          const uint32_t* fv_node, const int32_t* fv_off, const uint32_t* fv_feat, const int32_t* nfv, int nrows, int cap,
                          int rows_on_device, const uint8_t* qvalid, const uint8_t* claimed, int32_t* q2t, int32_t* t2q, int32_t* best, int32_t* second,
                          int32_t* nmatches, void* stream);
+
+/* ---- SearchForTriangulation over the rows of a resident key-frame store (orbs_tri_rows.hip) -----------------------------------------------
+ *
+ * Replaces, per pair, orbs_bow_ranges_batch_device + orbs_triangulation_search_batch_device without their per-problem slots and without the train
+ * frame staged in list order: pair p searches the features of row d_pair[2p] (pKF1, the QUERY side) in row d_pair[2p+1] (pKF2, the TRAIN side) under
+ * d_F12 + 9p (row major, `F12.at<float>(r,c)`).  Rows as above, with .x, .y, .octave of the undistorted key points read too (.angle with
+ * check_orientation).  level_sigma2: HOST pointer to pKF2's mvLevelSigma2 (1 <= nlevels <= ORBS_MAX_LEVELS), one table for the call.
+ * Per pair: d_qvalid[p*qstride + idx1] (NULL = all): pKF1's feature holds NO map point yet; qstride == 0: all pairs share one array, otherwise
+ * qstride >= cap.  d_claimed[p*cap + idx2] (NULL = none): pKF2's feature already holds a map point.
+ *
+ * Semantics: exactly the reference function as ORBS_RULE_TRIANGULATION states it (prm->rule must be that; th = ORBS_TH_LOW there; ratio unused).
+ * Per common vocabulary node, the queries in list order: among the train features of the node that are unclaimed and have distance <= th, BestDist
+ * is the smallest distance; the candidate with the smallest (distance, idx2) that lies on the query's epipolar line (CheckDistEpipolarLine with
+ * orbs_epipolar_bound per octave of the train key point) is taken when its distance is <= 2 * BestDist, and claims its train feature for the later
+ * queries of the node.  Ties are broken by idx2 as the reference's sort of (dist, idx2) does: the lists need not ascend within a node.  With
+ * check_orientation the matches outside the three largest rotation bins are cleared from both outputs but keep their claim during the scan.
+ *
+ * Outputs per pair, FEATURE indexed as in orbs_bow_rows_search_batch_device: d_q2t[p*cap + idx1] is vMatches12, d_t2q[p*cap + idx2] its inverse,
+ * d_best[p*cap + idx1] = BestDist of the query's candidate list (INT_MAX when empty), d_second[p*cap + idx1] = the distance of the match taken
+ * (INT_MAX none), both -1 when the query was never visited (not valid, or its node is not in the train row), d_nmatches[p] the function's return
+ * value.  Pairs of one call see the flags as they were on entry.  A pair whose row is outside [0, nrows) finds nothing.
+ *
+ * ORBX_ERR_ARG before anything touches the GPU for everything orbs_bow_rows_search_batch_device refuses (with ORBS_RULE_TRIANGULATION as the rule and
+ * no test of the ratio), a NULL level_sigma2, nlevels outside [1, ORBS_MAX_LEVELS], a NULL or misaligned d_F12, qstride != 0 && qstride < cap,
+ * npairs * qstride + cap >= 2^31.  Asynchronous on `stream`; scratch and ordering as there (16 bytes per pair and feature, grown on first use). */
+int orbs_tri_rows_search_batch_device(const orbs_params* prm, const int32_t* d_pair, int npairs, const float* d_F12, const float* level_sigma2,
+                                      int nlevels, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_nt, const uint32_t* d_fv_node,
+                                      const int32_t* d_fv_off, const uint32_t* d_fv_feat, const int32_t* d_nfv, int nrows, int cap,
+                                      const uint8_t* d_qvalid, int qstride, const uint8_t* d_claimed, int32_t* d_q2t, int32_t* d_t2q, int32_t* d_best,
+                                      int32_t* d_second, int32_t* d_nmatches, void* stream);
+
+/* The same, synchronous, over host arrays: one pinned block up, one down.  pair, F12, qvalid, claimed, the rows' counts nt and nfv and the outputs are
+ * host memory; the rows' arrays are host memory, or device memory read in place when rows_on_device != 0.  Here in addition: ORBX_ERR_ARG for a pair
+ * whose row is outside [0, nrows). */
+int orbs_tri_rows_search(const orbs_params* prm, const int32_t* pair, int npairs, const float* F12, const float* level_sigma2, int nlevels,
+                         const orbx_keypoint* kps, const uint8_t* desc, const int32_t* nt, const uint32_t* fv_node, const int32_t* fv_off,
+                         const uint32_t* fv_feat, const int32_t* nfv, int nrows, int cap, int rows_on_device, const uint8_t* qvalid, int qstride,
+                         const uint8_t* claimed, int32_t* q2t, int32_t* t2q, int32_t* best, int32_t* second, int32_t* nmatches, void* stream);
 
 /* ORBmatcher::ComputeThreeMaxima on a histogram of bin sizes (host, re-entrant): ind[3], -1 = none */
 void orbs_three_maxima(const int32_t* sizes, int L, int32_t* ind);

@@ -132,6 +132,40 @@ int orbt_triangulate(const orbt_pair* pair, const float* factors1, const float* 
                      int nlevels, const orbx_keypoint* kps1, int n1, const orbx_keypoint* kps2, int n2, const int32_t* match12,
                      uint8_t* status, float* x3d, float* v, int32_t* acc_idx, float* acc_x3d, int ocap, int* count, int device);
 
+/* ---- LocalMapping::CreateNewMapPoints over the rows of a resident key-frame store (orbs_tri_rows.hip): the whole neighbour loop in one call ----
+ *
+ * For p = 0 .. npairs-1, on `stream`, with no allocation, upload or synchronisation in between: the search of
+ * orbs_tri_rows_search_batch_device for pair p, then orbt_triangulate_batch_device for pair p with d_qindex = NULL (d_q2t IS vMatches12).  The
+ * triangulation of pair p clears d_qvalid and sets d_claimed at what it accepted, so the search of pair p + 1 is not offered those features: the
+ * order the reference's `mpCurrentKeyFrame->AddMapPoint` (src/LocalMapping.cc:360) gives its neighbour loop.
+ *   pair: a HOST list of (query row, train row), all with ONE query row (mpCurrentKeyFrame) and with train rows distinct from each other and from
+ *       the query row; d_pairs[npairs], d_F12[9*npairs] on the device; the four level tables are HOST pointers (sigma2_2 is what the search's
+ *       epipolar test reads); rows as in orbs_tri_rows_search_batch_device.
+ *   d_qvalid[cap]: "mpCurrentKeyFrame's feature holds no map point yet", shared by the pairs, updated in place; d_claimed[npairs*cap]: "the
+ *       neighbour's feature holds a map point", pair p at + p*cap, updated in place.
+ *   d_q2t, d_t2q (may be NULL), d_nmatches: the search's outputs, pair p at + p*cap; the other arrays are those of orbt_triangulate_batch_device with
+ *       cap1 = qcap = cap (pair p at + p*cap resp. + p*ocap).
+ * ORBX_ERR_ARG before anything touches the GPU for what the two functions refuse, for a pair list that breaks the rule above, npairs outside
+ * [0, ORBT_MAX_PAIRS], a NULL d_qvalid, d_claimed or d_q2t. */
+int orbt_new_points_rows_device(const orbs_params* prm, const int32_t* pair, int npairs, const orbt_pair* d_pairs, const float* d_F12,
+                                const float* factors1, const float* sigma2_1, const float* factors2, const float* sigma2_2, int nlevels,
+                                const orbx_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_nt, const uint32_t* d_fv_node,
+                                const int32_t* d_fv_off, const uint32_t* d_fv_feat, const int32_t* d_nfv, int nrows, int cap, uint8_t* d_qvalid,
+                                uint8_t* d_claimed, int32_t* d_q2t, int32_t* d_t2q, int32_t* d_nmatches, uint8_t* d_status, float* d_x3d, float* d_v,
+                                int32_t* d_match12, int32_t* d_acc_idx, float* d_acc_x3d, int32_t* d_count, int32_t* d_overflow, int ocap,
+                                void* stream);
+
+/* The same, synchronous, over host arrays: one pinned copy up, the chain, one copy down.  The rows' arrays are host memory, or device memory read in
+ * place when rows_on_device != 0 (nt and nfv are host arrays either way).  qvalid[cap] and claimed[npairs*cap] are updated in place; entries of
+ * the outputs that the kernels leave alone come back as zeros.  overflow[p] = 1 where pair p accepted more than ocap matches (count[p] holds the
+ * number). */
+int orbt_new_points_rows(const orbs_params* prm, const int32_t* pair, int npairs, const orbt_pair* pairs, const float* F12, const float* factors1,
+                         const float* sigma2_1, const float* factors2, const float* sigma2_2, int nlevels, const orbx_keypoint* kps,
+                         const uint8_t* desc, const int32_t* nt, const uint32_t* fv_node, const int32_t* fv_off, const uint32_t* fv_feat,
+                         const int32_t* nfv, int nrows, int cap, int rows_on_device, uint8_t* qvalid, uint8_t* claimed, int32_t* q2t, int32_t* t2q,
+                         int32_t* nmatches, uint8_t* status, float* x3d, float* v, int32_t* match12, int32_t* acc_idx, float* acc_x3d, int32_t* count,
+                         int32_t* overflow, int ocap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

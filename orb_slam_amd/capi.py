@@ -43,7 +43,7 @@ EXPORTS_F = [
 # include/orbs.h (greedy grid-window searches)
 EXPORTS_S = ["orbs_lds_bytes", "orbs_debug_set_buckets", "orbs_debug_set_wide_max", "orbs_three_maxima", "orbs_window_search_batch_device", "orbs_list_search_batch_device",
              "orbs_bow_ranges_batch_device", "orbs_triangulation_search_batch_device", "orbs_epipolar_bound", "orbs_agreement_batch_device",
-             "orbs_bow_rows_search_batch_device", "orbs_bow_rows_search"]
+             "orbs_bow_rows_search_batch_device", "orbs_bow_rows_search", "orbs_tri_rows_search_batch_device", "orbs_tri_rows_search"]
 PHASE_PYRAMID, PHASE_DETECT, PHASE_DESCRIBE, PHASE_ALL = 1, 2, 4, 7
 RULE_MAPPOINTS, RULE_WINDOW, RULE_BEST, RULE_INIT, RULE_BOW, RULE_FREE, RULE_TRIANGULATION = 0, 1, 2, 3, 4, 5, 6
 TH_HIGH, TH_LOW = 100, 50
@@ -61,7 +61,7 @@ EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_
              "orbp_fuse", "orbp_view_from_sim3", "orbp_loop_project_batch_device", "orbp_loop_search_batch_device", "orbp_loop_search",
              "orbp_sim3_from_pair", "orbp_sim3_search_batch_device", "orbp_sim3_search"]
 # include/orbt.h (triangulation of new map points)
-EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate"]
+EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate", "orbt_new_points_rows_device", "orbt_new_points_rows"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
@@ -294,6 +294,9 @@ def lib():
         L.orbs_agreement_batch_device.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]
         L.orbs_bow_rows_search_batch_device.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbs_bow_rows_search.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbs_tri_rows_search_batch_device.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp,
+                                                        vp, vp]
+        L.orbs_tri_rows_search.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
         L.orbv_create.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, ctypes.POINTER(vp)]
         L.orbv_load_text.argtypes = [ctypes.c_char_p, ci, ctypes.POINTER(vp)]
         L.orbv_destroy.argtypes = [vp]
@@ -350,6 +353,10 @@ def lib():
         L.orbt_triangulate_batch_device.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp,
                                                     ci, vp, vp, vp]
         L.orbt_triangulate.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ci), ci]
+        L.orbt_new_points_rows_device.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp,
+                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.orbt_new_points_rows.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         _LIB = L
     return _LIB
 
@@ -1133,6 +1140,134 @@ def bow_rows_search(th, ratio, check_orientation, pairs, kps, desc, nt, fv_node,
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbs_bow_rows_search")
     return nm[:npairs], q2t[:npairs], t2q[:npairs], (best[:npairs] if want_dist else None), (second[:npairs] if want_dist else None)
+
+
+def _host_rows(kps, desc, nt, fv_node, fv_off, fv_feat, nfv, nrows, cap, rows_on_device, keep):
+    """the seven row arguments of the searches over resident rows as ctypes values: host arrays of the stated shapes, or with rows_on_device device
+    pointers as ints for all but the counts nt and nfv"""
+    if rows_on_device:
+        counts = [np.ascontiguousarray(a, dtype=np.int32) for a in (nt, nfv)]
+        if any(a.shape != (nrows,) for a in counts):
+            raise ValueError("nt and nfv must have one entry per row")
+        keep.extend(counts)
+        return [int(kps) or None, int(desc) or None, counts[0].ctypes.data, int(fv_node) or None, int(fv_off) or None, int(fv_feat) or None, counts[1].ctypes.data]
+    shapes = ((KP_DTYPE, (nrows, cap)), (np.uint8, (nrows, cap, 32)), (np.int32, (nrows,)), (np.uint32, (nrows, cap)), (np.int32, (nrows, cap + 1)),
+              (np.uint32, (nrows, cap)), (np.int32, (nrows,)))
+    rows = []
+    for a, (dt, shape) in zip((kps, desc, nt, fv_node, fv_off, fv_feat, nfv), shapes):
+        a = np.ascontiguousarray(a, dtype=dt)
+        if a.shape != shape:
+            raise ValueError("a row array has the wrong shape: %s, not %s" % (a.shape, shape))
+        keep.append(a)
+        rows.append(a.ctypes.data)
+    return rows
+
+
+def tri_rows_search_batch_device(th, check_orientation, d_pair, npairs, d_F12, level_sigma2, d_kps, d_desc, d_nt, d_fv_node, d_fv_off, d_fv_feat, d_nfv,
+                                 nrows, cap, d_qvalid, qstride, d_claimed, d_q2t, d_t2q, d_best, d_second, d_nmatches, stream=0):
+    """SearchForTriangulation over the rows of a resident key-frame store, every (query row, train row) pair in one launch (include/orbs.h);
+    device pointers as ints (0 = NULL), level_sigma2 a host float array (mvLevelSigma2 of pKF2).  Asynchronous on `stream`."""
+    prm = SearchParams(RULE_TRIANGULATION, th, 0.0, 1 if check_orientation else 0)
+    s2 = np.ascontiguousarray(level_sigma2, dtype=np.float32)
+    rc = lib().orbs_tri_rows_search_batch_device(ctypes.byref(prm), d_pair or None, npairs, d_F12 or None, s2.ctypes.data, len(s2), d_kps or None,
+                                                 d_desc or None, d_nt or None, d_fv_node or None, d_fv_off or None, d_fv_feat or None, d_nfv or None, nrows,
+                                                 cap, d_qvalid or None, qstride, d_claimed or None, d_q2t or None, d_t2q or None, d_best or None,
+                                                 d_second or None, d_nmatches or None, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbs_tri_rows_search_batch_device")
+
+
+def tri_rows_search(th, check_orientation, pairs, F12, level_sigma2, kps, desc, nt, fv_node, fv_off, fv_feat, nfv, nrows, cap, qvalid=None, claimed=None,
+                    rows_on_device=False, want_dist=True, stream=0):
+    """The same, synchronous: pairs[npairs, 2], F12[npairs, 9] and the flags are host arrays (qvalid [cap]: shared by the pairs, or [npairs, cap];
+    claimed [npairs, cap]); the rows as in bow_rows_search.  -> (nmatches[npairs], q2t[npairs, cap], t2q[npairs, cap], best, second (None without want_dist))"""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    npairs = len(pr)
+    keep = []
+    F = np.ascontiguousarray(F12, dtype=np.float32).reshape(-1, 9)
+    if len(F) != npairs:
+        raise ValueError("F12 must have nine floats per pair")
+    s2 = np.ascontiguousarray(level_sigma2, dtype=np.float32)
+    qstride, qv, cl = 0, None, None
+    if qvalid is not None:
+        qv = np.ascontiguousarray(qvalid, dtype=np.uint8)
+        if qv.shape not in ((cap,), (npairs, cap)):
+            raise ValueError("qvalid must be [cap] or [npairs, cap]")
+        qstride = cap if qv.ndim == 2 else 0
+    if claimed is not None:
+        cl = np.ascontiguousarray(claimed, dtype=np.uint8)
+        if cl.shape != (npairs, cap):
+            raise ValueError("claimed must be [npairs, cap]")
+    rows = _host_rows(kps, desc, nt, fv_node, fv_off, fv_feat, nfv, nrows, cap, rows_on_device, keep)
+    n = max(npairs, 1)
+    nm = np.zeros(n, np.int32)
+    q2t = np.zeros((n, cap), np.int32); t2q = np.zeros((n, cap), np.int32)
+    best = np.zeros((n, cap), np.int32) if want_dist else None
+    second = np.zeros((n, cap), np.int32) if want_dist else None
+    prm = SearchParams(RULE_TRIANGULATION, th, 0.0, 1 if check_orientation else 0)
+    rc = lib().orbs_tri_rows_search(ctypes.byref(prm), pr.ctypes.data if npairs else None, npairs, F.ctypes.data if npairs else None, s2.ctypes.data, len(s2),
+                                    *rows, nrows, cap, 1 if rows_on_device else 0, qv.ctypes.data if qv is not None else None, qstride,
+                                    cl.ctypes.data if cl is not None else None, q2t.ctypes.data, t2q.ctypes.data, best.ctypes.data if want_dist else None,
+                                    second.ctypes.data if want_dist else None, nm.ctypes.data, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbs_tri_rows_search")
+    return nm[:npairs], q2t[:npairs], t2q[:npairs], (best[:npairs] if want_dist else None), (second[:npairs] if want_dist else None)
+
+
+def new_points_rows_device(th, check_orientation, pairs, d_pairs, d_F12, factors1, sigma2_1, factors2, sigma2_2, d_kps, d_desc, d_nt, d_fv_node, d_fv_off,
+                           d_fv_feat, d_nfv, nrows, cap, d_qvalid, d_claimed, d_q2t, d_t2q, d_nmatches, d_status, d_x3d, d_v, d_match12, d_acc_idx,
+                           d_acc_x3d, d_count, d_overflow, ocap, stream=0):
+    """The neighbour loop of LocalMapping::CreateNewMapPoints as one stream-ordered chain over resident rows (include/orbt.h): per pair the
+    search, its finish and the triangulation, whose flag updates the next pair's search reads.  pairs[npairs, 2] is a HOST list; device pointers
+    as ints (0 = NULL); the level tables host float arrays.  Asynchronous on `stream`."""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    f1, s1, f2, s2 = _level_tables(factors1, sigma2_1, factors2, sigma2_2)
+    prm = SearchParams(RULE_TRIANGULATION, th, 0.0, 1 if check_orientation else 0)
+    rc = lib().orbt_new_points_rows_device(ctypes.byref(prm), pr.ctypes.data if len(pr) else None, len(pr), d_pairs or None, d_F12 or None, f1.ctypes.data,
+                                           s1.ctypes.data, f2.ctypes.data, s2.ctypes.data, len(f1), d_kps or None, d_desc or None, d_nt or None,
+                                           d_fv_node or None, d_fv_off or None, d_fv_feat or None, d_nfv or None, nrows, cap, d_qvalid or None,
+                                           d_claimed or None, d_q2t or None, d_t2q or None, d_nmatches or None, d_status or None, d_x3d or None,
+                                           d_v or None, d_match12 or None, d_acc_idx or None, d_acc_x3d or None, d_count or None, d_overflow or None, ocap,
+                                           stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbt_new_points_rows_device")
+
+
+def new_points_rows(th, check_orientation, pairs, tri_pairs, F12, factors1, sigma2_1, factors2, sigma2_2, kps, desc, nt, fv_node, fv_off, fv_feat, nfv,
+                    nrows, cap, qvalid, claimed, ocap=None, rows_on_device=False, want_v=True, stream=0):
+    """The same, synchronous, over host arrays: tri_pairs[npairs] of TRI_PAIR_DTYPE, F12[npairs, 9], qvalid[cap], claimed[npairs, cap] (both are
+    copied; the updated flags are returned).  -> dict(nmatches, q2t, t2q, status, x3d, v (None without want_v), match12, acc_idx, acc_x3d, count,
+    overflow, qvalid, claimed), per pair; acc_idx[p, :count[p]] are the accepted (idx1, idx2) in ascending idx1"""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    npairs = len(pr)
+    tp = np.ascontiguousarray(tri_pairs, dtype=TRI_PAIR_DTYPE).reshape(-1)
+    F = np.ascontiguousarray(F12, dtype=np.float32).reshape(-1, 9)
+    if len(tp) != npairs or len(F) != npairs:
+        raise ValueError("one orbt_pair record and nine floats of F12 per pair")
+    f1, s1, f2, s2 = _level_tables(factors1, sigma2_1, factors2, sigma2_2)
+    qv = np.array(qvalid, dtype=np.uint8); cl = np.array(claimed, dtype=np.uint8).reshape(-1, cap)
+    if qv.shape != (cap,) or cl.shape != (npairs, cap):
+        raise ValueError("qvalid must be [cap], claimed [npairs, cap]")
+    keep = []
+    rows = _host_rows(kps, desc, nt, fv_node, fv_off, fv_feat, nfv, nrows, cap, rows_on_device, keep)
+    ocap = cap if ocap is None else ocap
+    n = max(npairs, 1)
+    o = dict(nmatches=np.zeros(n, np.int32), q2t=np.zeros((n, cap), np.int32), t2q=np.zeros((n, cap), np.int32), status=np.zeros((n, cap), np.uint8),
+             x3d=np.zeros((n, cap, 3), np.float32), v=np.zeros((n, cap, 4), np.float32) if want_v else None, match12=np.zeros((n, cap), np.int32),
+             acc_idx=np.zeros((n, max(ocap, 1), 2), np.int32), acc_x3d=np.zeros((n, max(ocap, 1), 3), np.float32), count=np.zeros(n, np.int32),
+             overflow=np.zeros(n, np.int32))
+    prm = SearchParams(RULE_TRIANGULATION, th, 0.0, 1 if check_orientation else 0)
+    rc = lib().orbt_new_points_rows(ctypes.byref(prm), pr.ctypes.data if npairs else None, npairs, tp.ctypes.data if npairs else None,
+                                    F.ctypes.data if npairs else None, f1.ctypes.data, s1.ctypes.data, f2.ctypes.data, s2.ctypes.data, len(f1), *rows, nrows,
+                                    cap, 1 if rows_on_device else 0, qv.ctypes.data, cl.ctypes.data, o["q2t"].ctypes.data, o["t2q"].ctypes.data,
+                                    o["nmatches"].ctypes.data, o["status"].ctypes.data, o["x3d"].ctypes.data, o["v"].ctypes.data if want_v else None,
+                                    o["match12"].ctypes.data, o["acc_idx"].ctypes.data, o["acc_x3d"].ctypes.data, o["count"].ctypes.data,
+                                    o["overflow"].ctypes.data, ocap, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbt_new_points_rows")
+    o = {k: (a[:npairs] if a is not None else None) for k, a in o.items()}
+    o["qvalid"], o["claimed"] = qv, cl
+    return o
 
 
 class KeyFrameDatabase:

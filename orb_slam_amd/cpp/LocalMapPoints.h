@@ -23,6 +23,8 @@
 // SearchByBoW (LocalMapPointsBoW.cc) replaces both ORBmatcher::SearchByBoW overloads as Tracking::Relocalisation and LoopClosing::ComputeSim3 call
 // them per candidate: the rows of the key-frame store gain their FeatureVector, and every candidate of a call is one pair of ONE
 // orbs_bow_rows_search.
+// CreateNewMapPoints (LocalMapPointsNewPoints.cc) replaces ORBmatcher::SearchForTriangulation and the match loop behind it for every neighbour of
+// LocalMapping::CreateNewMapPoints: one stream-ordered chain search -> triangulate per neighbour over the same rows, one call, one synchronisation.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
@@ -41,6 +43,7 @@ namespace ORB_SLAM {
 class MapPoint;
 class Frame;
 class KeyFrame;
+struct NewMapPoint;             // NewMapPoints.h
 
 class LocalMapPoints {
 public:
@@ -142,6 +145,17 @@ public:
     // One pKF1 against every candidate in ONE launch; NULL and bad candidates as above.
     void SearchByBoW(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpCandidates, std::vector<std::vector<MapPoint*> >& vvpMatches12,
                      std::vector<int>* nmatches = 0, float nnratio = 0.75f, bool checkOrientation = true);
+
+    // The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:205-370) between ComputeF12 and `new MapPoint`, for every neighbour in
+    // ONE call (LocalMapPointsNewPoints.cc; links only when that file, LocalMapPointsBoW.cc and what it needs are built in): per neighbour
+    // ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, ...) of an ORBmatcher(0.6, checkOrientation) and the match loop (:269-353), chained on the
+    // device so that a neighbour is not offered the features of pKF1 for which an earlier neighbour's loop reached `new MapPoint` (what AddMapPoint,
+    // :360, means to the next search).  vvNew[i]: the accepted (idx1, idx2, x3D) of vpNeighKFs[i] in the order of vMatchedIndices; empty for a
+    // neighbour that is NULL, bad, pKF1 itself, listed before, or whose vF12[i] is empty: the caller's loop with its baseline test keeps its shape.
+    // Both key frames are resident rows with their FeatureVector; per call the two flag arrays (GetMapPointMatches(): NULL or not), the poses
+    // (GetRotation(), GetTranslation(), GetCameraCenter(), fx, fy, cx, cy), the level tables and F12 go up.  NewMapPoint: NewMapPoints.h.
+    void CreateNewMapPoints(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpNeighKFs, const std::vector<cv::Mat>& vF12,
+                            std::vector<std::vector<NewMapPoint> >& vvNew, bool checkOrientation = false);
 
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }

@@ -17,9 +17,8 @@
 //   listed candidate on ties.  Queries are loaded 64 at a time, one per lane, and broadcast by readlane; a lane collects its query's result and
 //   stores ONE 16-byte record per list position of the query row (a node without a partner stores "never visited"), so the records of a pair
 //   are complete without having been initialised.
-// k_bow_rows_finish: one workgroup per pair behind it on the same stream.  It sets the pair's outputs to -1, walks the records, builds the
-//   rotation histogram in LDS (integer adds: the result does not depend on their order), takes the three maxima, writes the surviving matches
-//   to q2t / t2q, best / second of every visited query, and the count.  A filtered match kept its claim during the scan, as in the reference.
+// k_bow_rows_finish: one workgroup per pair behind it on the same stream: rows_finish of orbs_rows_device.h, which the triangulation search over
+//   rows (orbs_tri_rows.hip) ends with too.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -29,11 +28,9 @@
 
 #include "orbs.h"
 #include "orbs_bow_rows.h"
-#include "orbs_device.h"
+#include "orbs_rows_device.h"
 
 namespace orbs {
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 __global__ __launch_bounds__(BOW_ROWS_WAVES * 64) void k_bow_rows(orbs_params prm, BowRows a, int blocks_per_pair) {
     const int lane = threadIdx.x & 63;
@@ -140,61 +137,11 @@ __global__ __launch_bounds__(BOW_ROWS_WAVES * 64) void k_bow_rows(orbs_params pr
     }
 }
 
-constexpr int BOW_FINISH_TPB = 256;
+constexpr int BOW_FINISH_TPB = ROWS_FINISH_TPB;
 
 __global__ __launch_bounds__(BOW_FINISH_TPB) void k_bow_rows_finish(orbs_params prm, BowRows a) {
-    __shared__ int hist[32];
-    __shared__ int total;
-    const int p = blockIdx.x, tid = threadIdx.x, cap = a.S.cap;
-    const size_t ob = (size_t)p * cap;
-    for (int i = tid; i < cap; i += BOW_FINISH_TPB) {
-        if (a.O.q2t) a.O.q2t[ob + i] = -1;
-        if (a.O.t2q) a.O.t2q[ob + i] = -1;
-        if (a.O.best) a.O.best[ob + i] = -1;
-        if (a.O.second) a.O.second[ob + i] = -1;
-    }
-    if (tid < 32) hist[tid] = 0;
-    if (tid == 0) total = 0;
-    const int qr = a.P.pair[2 * p], tr = a.P.pair[2 * p + 1];
-    const bool known = (unsigned)qr < (unsigned)a.S.nrows && (unsigned)tr < (unsigned)a.S.nrows;
-    __syncthreads();                                                     // the -1s are in place before any entry is written again
-    if (!known) {
-        if (tid == 0) a.O.nmatches[p] = 0;
-        return;
-    }
-    const int32_t* qo = a.S.fv_off + (size_t)qr * (cap + 1);
-    const uint32_t* qf = a.S.fv_feat + (size_t)qr * cap;
-    const int nfq = clampi(a.S.nfv[qr], 0, cap);
-    const int ntq = clampi(a.S.nt[qr], 0, cap), ntt = clampi(a.S.nt[tr], 0, cap);
-    const int k0 = nfq > 0 ? clampi(qo[0], 0, cap) : 0, k1 = nfq > 0 ? clampi(qo[nfq], k0, cap) : 0;
-    const bool rot = prm.check_orientation != 0;
-
-    for (int k = k0 + tid; k < k1; k += BOW_FINISH_TPB) {
-        const uint32_t idx1 = qf[k];
-        if (idx1 >= (uint32_t)ntq) continue;
-        const BowRec r = a.rec[ob + k];
-        if (a.O.best) a.O.best[ob + idx1] = r.best;
-        if (a.O.second) a.O.second[ob + idx1] = r.second;
-        if (rot && (unsigned)r.idx2 < (unsigned)ntt && (unsigned)r.bin < (unsigned)HISTO_LENGTH) atomicAdd(&hist[r.bin], 1);
-    }
-    __syncthreads();
-    int i1 = -1, i2 = -1, i3 = -1;
-    if (rot) three_maxima(hist, HISTO_LENGTH, i1, i2, i3);
-    int cnt = 0;
-    for (int k = k0 + tid; k < k1; k += BOW_FINISH_TPB) {
-        const uint32_t idx1 = qf[k];
-        if (idx1 >= (uint32_t)ntq) continue;
-        const BowRec r = a.rec[ob + k];
-        if ((unsigned)r.idx2 >= (unsigned)ntt) continue;
-        if (rot && (unsigned)r.bin < (unsigned)HISTO_LENGTH && r.bin != i1 && r.bin != i2 && r.bin != i3) continue;      // cleared; its claim held during the scan
-        if (a.O.q2t) a.O.q2t[ob + idx1] = r.idx2;
-        if (a.O.t2q) a.O.t2q[ob + r.idx2] = (int)idx1;
-        cnt++;
-    }
-    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s, 64);
-    if ((tid & 63) == 0 && cnt) atomicAdd(&total, cnt);
-    __syncthreads();
-    if (tid == 0) a.O.nmatches[p] = total;
+    const int p = blockIdx.x;
+    rows_finish<BOW_FINISH_TPB>(prm.check_orientation != 0, a.S, a.P.pair[2 * p], a.P.pair[2 * p + 1], a.O, a.rec, p);
 }
 
 static hipError_t launch_bow_rows(const orbs_params& prm, const BowRows& a, hipStream_t st) {

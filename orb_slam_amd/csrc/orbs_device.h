@@ -1,5 +1,5 @@
-// Device helpers the search kernels share (orbs_search.hip, orbs_bow_rows.hip): the wave minimum, lane broadcasts, the Hamming distance of two
-// staged descriptors, the rotation bin and ORBmatcher::ComputeThreeMaxima.
+// Device helpers the search kernels share (orbs_search.hip, orbs_bow_rows.hip, orbs_tri_rows.hip): the wave minimum, lane broadcasts, the Hamming
+// distance of two staged descriptors, the rotation bin, ORBmatcher::ComputeThreeMaxima and ORBmatcher::CheckDistEpipolarLine.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +57,30 @@ __host__ __device__ inline void three_maxima(const int* sizes, int L, int& ind1,
     if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
     else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
 }
+
+// ORBmatcher::CheckDistEpipolarLine (src/ORBmatcher.cc:136-153) split in two: the query's line l = x1' F12 once per query ...
+struct EpiLine { float a, b, c, den; int th; };
+
+__device__ __forceinline__ EpiLine epi_line(float x, float y, const float* F, int th) {
+    EpiLine e;          // every product and sum rounded on its own, as the reference's float expressions are (no fma)
+    e.a = __fadd_rn(__fadd_rn(__fmul_rn(x, F[0]), __fmul_rn(y, F[3])), F[6]);
+    e.b = __fadd_rn(__fadd_rn(__fmul_rn(x, F[1]), __fmul_rn(y, F[4])), F[7]);
+    e.c = __fadd_rn(__fadd_rn(__fmul_rn(x, F[2]), __fmul_rn(y, F[5])), F[8]);
+    e.den = __fadd_rn(__fmul_rn(e.a, e.a), __fmul_rn(e.b, e.b));
+    e.th = th;
+    return e;
+}
+// ... and the distance test per candidate.  thr = the smallest float t with (double)t >= 3.84 * sigma2(octave), so that
+// `dsqr < thr` in float IS the reference's `(double)dsqr < 3.84*sigma2` (host: orbs_epipolar_bound()).
+__device__ __forceinline__ bool epi_ok(const EpiLine& e, float x2, float y2, float thr) {
+    const float num = __fadd_rn(__fadd_rn(__fmul_rn(e.a, x2), __fmul_rn(e.b, y2)), e.c);
+    if (e.den == 0.0f) return false;
+    const float dsqr = __fdiv_rn(__fmul_rn(num, num), e.den);
+    return dsqr < thr;
+}
+// the entry of the per-octave bound table a key point's octave selects (the table has ORBS_MAX_LEVELS = 16 entries; the octave as the staged
+// 16-bit field holds it, so a negative one selects the last entry)
+__device__ __forceinline__ int epi_level(int octave) { return (int)min((uint32_t)octave & 0xFFFFu, 15u); }
 
 __device__ __forceinline__ uint32_t hamming_key(const uint4& t0, const uint4& t1, const uint4& q0, const uint4& q1) {
     return __popc(t0.x ^ q0.x) + __popc(t0.y ^ q0.y) + __popc(t0.z ^ q0.z) + __popc(t0.w ^ q0.w) +

@@ -117,27 +117,6 @@ __device__ __forceinline__ void staged_desc(const Staged& S, int j, uint32_t met
     else { const uint4* d = (const uint4*)(S.gdesc + (size_t)(meta & 0xFFFFu) * 32); t0 = d[0]; t1 = d[1]; }
 }
 
-// ORBmatcher::CheckDistEpipolarLine (src/ORBmatcher.cc:136-153) split in two: the query's line l = x1' F12 once per query ...
-struct EpiLine { float a, b, c, den; int th; };
-
-__device__ __forceinline__ EpiLine epi_line(float x, float y, const float* F, int th) {
-    EpiLine e;          // every product and sum rounded on its own, as the reference's float expressions are (no fma)
-    e.a = __fadd_rn(__fadd_rn(__fmul_rn(x, F[0]), __fmul_rn(y, F[3])), F[6]);
-    e.b = __fadd_rn(__fadd_rn(__fmul_rn(x, F[1]), __fmul_rn(y, F[4])), F[7]);
-    e.c = __fadd_rn(__fadd_rn(__fmul_rn(x, F[2]), __fmul_rn(y, F[5])), F[8]);
-    e.den = __fadd_rn(__fmul_rn(e.a, e.a), __fmul_rn(e.b, e.b));
-    e.th = th;
-    return e;
-}
-// ... and the distance test per candidate.  thr = the smallest float t with (double)t >= 3.84 * sigma2(octave), so that
-// `dsqr < thr` in float IS the reference's `(double)dsqr < 3.84*sigma2` (host: epi_bound()).
-__device__ __forceinline__ bool epi_ok(const EpiLine& e, float x2, float y2, float thr) {
-    const float num = __fadd_rn(__fadd_rn(__fmul_rn(e.a, x2), __fmul_rn(e.b, y2)), e.c);
-    if (e.den == 0.0f) return false;
-    const float dsqr = __fdiv_rn(__fmul_rn(num, num), e.den);
-    return dsqr < thr;
-}
-
 // One candidate of a window: its key (distance << 16 | CSR position) when it is admissible under the current claim state,
 // KEY_NONE when it is in the window but claimed; `inwin` says whether it was in the window at all.
 // ORBS_RULE_TRIANGULATION: admissible = unclaimed && distance <= th; bit 15 of the key says whether the candidate also lies on

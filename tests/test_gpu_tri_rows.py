@@ -1,0 +1,375 @@
+"""orbs_tri_rows_search[_batch_device] (include/orbs.h) on the GPU: ORBmatcher::SearchForTriangulation over the rows of a resident store, every
+(query row, train row) pair of a call in one launch.  Every output array is compared with the oracle on the same data (tests/tri_rows_scenes.py:
+expect(), which tests/test_tri_rows_ref_pin.py holds against recordings of the reference's own function), the recordings themselves are
+reproduced, and the result equals the per-slot route orbs_bow_ranges_batch_device + orbs_triangulation_search_batch_device on index-ordered lists."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import bow_rows_scenes as bs
+import tri_rows_scenes as ts
+from orb_slam_amd import capi
+from tri_rows_scenes import Store, dev
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+INT_MAX = np.iinfo(np.int32).max
+FILL = -77
+TH_LOW = ts.TH_LOW
+SIG = ts.SIGMA2
+# x1' F12 = (0, -1, y1): the epipolar line of (x1, y1) is the row y2 = y1, den = 1 and dsqr = (y1 - y2)^2 exactly
+F_ROWS = np.array([0, 0, 0, 0, 0, 1, 0, -1, 0], np.float32)
+
+
+def run_host(S, pairs, F, th, check, qvalid=None, claimed=None, rows_on_device=False, sigma2=SIG):
+    return capi.tri_rows_search(th, check, pairs, F, sigma2, *S.host_or_device(rows_on_device), S.nrows, S.cap, qvalid=qvalid, claimed=claimed,
+                                rows_on_device=rows_on_device)
+
+
+def run_device(S, pairs, F, th, check, qvalid=None, claimed=None, want_dist=True, sigma2=SIG):
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    P = len(pr)
+    out = [torch.full((P, S.cap), FILL, dtype=torch.int32, device="cuda") for _ in range(4)] + [torch.full((P,), FILL, dtype=torch.int32, device="cuda")]
+    dp, dF = dev(pr), dev(np.ascontiguousarray(F, np.float32).reshape(P, 9))
+    dq = dev(qvalid) if qvalid is not None else None
+    dc = dev(claimed) if claimed is not None else None
+    qstride = S.cap if qvalid is not None and np.ndim(qvalid) == 2 else 0
+    capi.tri_rows_search_batch_device(th, check, dp.data_ptr(), P, dF.data_ptr(), sigma2, *S.ptrs(), S.nrows, S.cap, dq.data_ptr() if dq is not None else 0,
+                                      qstride, dc.data_ptr() if dc is not None else 0, out[0].data_ptr(), out[1].data_ptr(),
+                                      out[2].data_ptr() if want_dist else 0, out[3].data_ptr() if want_dist else 0, out[4].data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    q2t, t2q, best, second, nm = (o.cpu().numpy() for o in out)
+    return nm, q2t, t2q, best, second
+
+
+def check_against_oracle(S, pairs, F, th, check, got, qvalid=None, claimed=None, sigma2=SIG):
+    """every pair of a result (nmatches, q2t, t2q, best, second) against the oracle; returns the total number of matches"""
+    nm, q2t, t2q, best, second = got
+    F = np.ascontiguousarray(F, np.float32).reshape(len(pairs), 9)
+    total = 0
+    for p, (a, b) in enumerate(pairs):
+        q, t = S.rows[a], S.rows[b]
+        qv = np.ones(S.cap, np.uint8) if qvalid is None else (qvalid if np.ndim(qvalid) == 1 else qvalid[p])
+        cl = np.zeros(S.cap, np.uint8) if claimed is None else claimed[p]
+        w = ts.expect(th, check, F[p], sigma2, q, t, S.cap, qv, cl)
+        assert nm[p] == w[0], (p, nm[p], w[0])
+        for name, g, e in (("q2t", q2t, w[1]), ("t2q", t2q, w[2]), ("best", best, w[3]), ("second", second, w[4])):
+            assert np.array_equal(g[p], e), (p, name, np.nonzero(g[p] != e)[0][:8])
+        total += int(w[0])
+    return total
+
+
+def same(a, b):
+    assert all(np.array_equal(x, y) for x, y in zip(a, b)), [i for i, (x, y) in enumerate(zip(a, b)) if not np.array_equal(x, y)]
+
+
+def clustered_row(rng, sizes, centres, nodes, y_line=None, spread=24):
+    """a row whose node j (id nodes[j]) holds sizes[j] features around centres[j], its lists in random order; the FeatureVector is built by hand so
+    that a node may be EMPTY.  y_line None: a query row, every key point at (300, 200); else a train row under F_ROWS, about two thirds of its
+    key points within the bound of the row y = y_line at their octave"""
+    desc, off, feat = [], [0], []
+    for j, n in enumerate(sizes):
+        for _ in range(n):
+            desc.append(bs.flip(centres[j], rng.choice(256, int(rng.integers(0, spread)), replace=False)))
+    n_all = len(desc)
+    order = rng.permutation(n_all)                     # features in no particular node order
+    inv = np.argsort(order)
+    i = 0
+    for n in sizes:
+        feat.extend(rng.permutation([int(inv[k]) for k in range(i, i + n)]).tolist())
+        i += n
+        off.append(len(feat))
+    d = np.array(desc, np.uint8).reshape(-1, 32)[order] if desc else np.zeros((0, 32), np.uint8)
+    octave = rng.integers(0, 8, n_all)
+    if y_line is None:
+        x, y = np.full(n_all, 300.0), np.full(n_all, 200.0)
+    else:
+        x = rng.random(n_all) * 640
+        y = y_line + np.where(rng.random(n_all) < 0.67, rng.normal(0, 0.6, n_all), 5 + 20 * rng.random(n_all)) * np.sqrt(SIG[octave])
+    kps = ts.keypoints(x.astype(np.float32), y.astype(np.float32), (rng.random(n_all) * 360).astype(np.float32), octave)
+    return ts.make_row(kps, d, (np.array(nodes, np.uint32), np.array(off, np.int32), np.array(feat, np.uint32)))
+
+
+def test_node_size_edges():
+    """runs of 0, 1, 63, 64, 65 and 130 features on either side in one row pair (640 slots: the stated runs do not fit 256)"""
+    rng = np.random.default_rng(1)
+    sq = [0, 1, 63, 64, 65, 130, 130, 65, 1, 64, 0]
+    st = [130, 65, 64, 63, 1, 0, 130, 64, 1, 65, 0]
+    nodes = [3 + 5 * j for j in range(len(sq))]
+    centres = rng.integers(0, 256, (len(sq), 32)).astype(np.uint8)
+    S = Store([clustered_row(rng, sq, centres, nodes), clustered_row(rng, st, centres, nodes, y_line=200.0)], 640)
+    pairs = [(0, 1)]
+    total = 0
+    for check in (True, False):
+        total += check_against_oracle(S, pairs, F_ROWS, TH_LOW, check, run_host(S, pairs, F_ROWS, TH_LOW, check))
+    assert total > 50
+    # with flags on both sides, and the sides exchanged (row 1's key points lie on many rows: few of row 0's are on their lines)
+    pairs = [(0, 1), (1, 0)]
+    F2 = np.stack([F_ROWS, F_ROWS])
+    qv = (rng.random((2, 640)) < 0.8).astype(np.uint8); cl = (rng.random((2, 640)) < 0.2).astype(np.uint8)
+    assert check_against_oracle(S, pairs, F2, TH_LOW, True, run_host(S, pairs, F2, TH_LOW, True, qv, cl), qv, cl) > 20
+
+
+def test_one_large_node():
+    """a single node holding every feature, 200 x 200: the chunked scan with its claim masks over four chunks"""
+    rng = np.random.default_rng(2)
+    centres = rng.integers(0, 256, (1, 32)).astype(np.uint8)
+    S = Store([clustered_row(rng, [200], centres, [9], spread=40), clustered_row(rng, [200], centres, [9], y_line=200.0, spread=40)], 256)
+    assert check_against_oracle(S, [(0, 1)], F_ROWS, TH_LOW, True, run_host(S, [(0, 1)], F_ROWS, TH_LOW, True)) > 30
+    cl = (rng.random((1, 256)) < 0.3).astype(np.uint8)
+    assert check_against_oracle(S, [(0, 1)], F_ROWS, 40, False, run_host(S, [(0, 1)], F_ROWS, 40, False, None, cl), None, cl) > 10
+
+
+def test_merge_walk():
+    """disjoint node sets, interleaved node ids, an empty FeatureVector on either side, nt = 0"""
+    rng = np.random.default_rng(3)
+    centres = rng.integers(0, 256, (40, 32)).astype(np.uint8)
+    odd, even = list(range(1, 40, 2)), list(range(0, 40, 2))
+    mixed = [0, 1, 4, 5, 7, 8, 9, 13, 20, 21, 22, 30, 31, 38, 39]
+    row = lambda ids, y=None: clustered_row(rng, [int(rng.integers(1, 9)) for _ in ids], centres[ids], [100 + 3 * i for i in ids], y_line=y, spread=12)
+    no_fv = row(mixed, 200.0)
+    no_fv["fv"] = (np.zeros(0, np.uint32), np.zeros(1, np.int32), np.zeros(0, np.uint32))
+    empty = clustered_row(rng, [], centres[:0], [])
+    S = Store([row(odd), row(even, 200.0), row(mixed, 200.0), no_fv, empty, row(mixed)], 256)
+    pairs = [(0, 1), (0, 2), (5, 2), (5, 1), (0, 3), (3, 2), (4, 2), (0, 4), (4, 4)]
+    F = np.stack([F_ROWS] * len(pairs))
+    got = run_host(S, pairs, F, TH_LOW, True)
+    total = check_against_oracle(S, pairs, F, TH_LOW, True, got)
+    assert got[0][0] == 0 and (got[0][4:] == 0).all() and total > 5 and got[0][2] > 0
+
+
+def planted(run_q, run_t, y_t, oct_t=None, node=7, t_order=None):
+    """one node: the query descriptors at (300, 200), the train descriptors at rows y_t as listed (t_order: the train list's order)"""
+    nq, nt = len(run_q), len(run_t)
+    kq = ts.keypoints(np.full(nq, 300, np.float32), np.full(nq, 200, np.float32), np.zeros(nq, np.float32), np.zeros(nq, np.int32))
+    kt = ts.keypoints(np.full(nt, 100, np.float32), np.array(y_t, np.float32), np.zeros(nt, np.float32), np.zeros(nt, np.int32) if oct_t is None else oct_t)
+    fv = lambda order: (np.array([node], np.uint32), np.array([0, len(order)], np.int32), np.array(order, np.uint32))
+    return Store([ts.make_row(kq, np.array(run_q, np.uint8), fv(range(nq))), ts.make_row(kt, np.array(run_t, np.uint8), fv(t_order or range(nt)))], 256)
+
+
+def one(S, th=TH_LOW, check=False, F=F_ROWS, sigma2=SIG):
+    got = run_host(S, [(0, 1)], F, th, check, sigma2=sigma2)
+    check_against_oracle(S, [(0, 1)], F, th, check, got, sigma2=sigma2)
+    return got
+
+
+def test_planted_cases():
+    rng = np.random.default_rng(4)
+    D = rng.integers(0, 256, 32).astype(np.uint8)
+    fl = lambda lo, n: bs.flip(D, range(lo, lo + n))
+    # the best candidate is off the line, the match a later one within 2 * BestDist ...
+    got = one(planted([D], [fl(0, 10), fl(100, 15)], [230, 200]))
+    assert got[0][0] == 1 and got[1][0, 0] == 1 and got[3][0, 0] == 10 and got[4][0, 0] == 15
+    # ... at exactly 2 * BestDist still, one beyond no more
+    got = one(planted([D], [fl(0, 10), fl(100, 20)], [230, 200]))
+    assert got[0][0] == 1 and got[4][0, 0] == 20
+    got = one(planted([D], [fl(0, 10), fl(100, 21)], [230, 200]))
+    assert got[0][0] == 0 and got[1][0, 0] == -1 and got[3][0, 0] == 10 and got[4][0, 0] == INT_MAX
+    # a claim chain: three queries share the nearest feature X, the second moves on to Y, the third to Z (BestDist is taken over what is left)
+    A, B, C = bs.flip(D, [200]), bs.flip(D, [200, 201]), bs.flip(D, [200, 201, 202])
+    got = one(planted([A, B, C], [D, fl(0, 10), fl(100, 25)], [200, 200, 200]))
+    assert got[1][0, :3].tolist() == [0, 1, 2] and got[3][0, :3].tolist() == [1, 12, 28] and got[4][0, :3].tolist() == [1, 12, 28] and got[0][0] == 3
+    got = one(planted([A, B, C], [D, fl(0, 10)], [200, 200]))
+    assert got[1][0, :3].tolist() == [0, 1, -1] and got[3][0, :3].tolist() == [1, 12, INT_MAX] and got[0][0] == 2
+    # an exact tie on the line: the lower idx2 wins although the list names the higher one first
+    got = one(planted([D, D], [bs.flip(D, [5]), bs.flip(D, [9]), bs.flip(D, [77])], [200, 200, 200], t_order=[2, 1, 0]))
+    assert got[1][0, :2].tolist() == [0, 1] and got[4][0, :2].tolist() == [1, 1]
+    # dist == th is a candidate, th + 1 is not
+    assert one(planted([D], [fl(0, 50)], [200]))[0][0] == 1 and one(planted([D], [fl(0, 51)], [200]))[0][0] == 0
+    got = one(planted([D], [fl(0, 50)], [200]), th=49)
+    assert got[0][0] == 0 and got[3][0, 0] == INT_MAX
+    # den == 0 in the epipolar line: F12 with only its last entry set gives the line (0, 0, 1); nothing is on it
+    got = one(planted([D], [fl(0, 3)], [200]), F=np.array([0, 0, 0, 0, 0, 0, 0, 0, 1], np.float32))
+    assert got[0][0] == 0 and got[3][0, 0] == 3 and got[4][0, 0] == INT_MAX
+
+
+def test_epipolar_bound_at_both_ends_of_the_pyramid():
+    """dsqr on either side of orbs_epipolar_bound at octave 0 and at octave nlevels - 1: the query at y = 0, so num = -y2 and dsqr = y2 * y2"""
+    rng = np.random.default_rng(5)
+    D = rng.integers(0, 256, 32).astype(np.uint8)
+    for octave in (0, len(SIG) - 1):
+        bound = np.float32(capi.epipolar_bound(float(SIG[octave])))
+        y = np.float32(np.sqrt(np.float64(bound)))
+        while np.float32(y * y) < bound:
+            y = np.nextafter(y, np.float32(np.inf))
+        while np.float32(y * y) >= bound:
+            y = np.nextafter(y, np.float32(-np.inf))
+        inside, outside = y, np.nextafter(y, np.float32(np.inf))
+        assert np.float32(inside * inside) < bound <= np.float32(outside * outside)
+        for y2, n in ((inside, 1), (outside, 0)):
+            S = planted([D], [bs.flip(D, [1])], [y2], oct_t=np.array([octave], np.int32))
+            S.rows[0]["kps"]["y"][:] = 0
+            S = Store(S.rows, 256)
+            assert one(S)[0][0] == n, (octave, y2, n)
+
+
+def test_rotation():
+    """isolated one-to-one nodes with chosen rotations: 900 degrees rounds to bin 30 and lands in bin 0; two, then three, equal maxima"""
+    rng = np.random.default_rng(6)
+    for rots, kept in (([0, 0, 0, 900, 60, 60, 60, 60, 150, 150, 210], 10), ([0, 0, 900, 60, 60, 60, 150, 150, 150, 210, 210, 270], 9)):
+        n = len(rots)
+        d = rng.integers(0, 256, (n, 32)).astype(np.uint8)
+        fv = bs.fv_from_nodes([10 + 2 * i for i in range(n)])
+        kq = ts.keypoints(np.full(n, 300, np.float32), np.full(n, 200, np.float32), np.array(rots, np.float32), np.zeros(n, np.int32))
+        kt = ts.keypoints(np.full(n, 100, np.float32), np.full(n, 200, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32))
+        S = Store([ts.make_row(kq, d, fv), ts.make_row(kt, d, fv)], 256)
+        got = one(S, check=True)
+        assert got[0][0] == kept and got[1][0, rots.index(900)] == rots.index(900)
+        assert (got[1][0, :n] >= 0).sum() == kept and (got[2][0, :n] >= 0).sum() == kept
+        off = one(S, check=False)
+        assert off[0][0] == n and off[1][0, :n].tolist() == list(range(n))
+
+
+def recorded(name):
+    return ts.load_scene(os.path.join(GOLDEN, "tri_ref_%s.npz" % name))
+
+
+def test_row_indirection():
+    """four pairs over three rows in one launch, sharing a query row and a train row, with per-pair flags: equal to the four single-pair launches and
+    to the oracle; an out-of-range row among them finds nothing and disturbs no neighbour; one qvalid array shared by all pairs"""
+    r1, r2, Fa, _, _ = recorded("a")
+    r3, _, Fb, _, _ = recorded("b")
+    S = Store([r1, r2, r3], 320)
+    pairs = [(0, 1), (2, 1), (0, 2), (1, 0)]
+    F = np.stack([Fa, Fb, Fa, Fb])
+    rng = np.random.default_rng(7)
+    qv = (rng.random((4, 320)) < 0.85).astype(np.uint8); cl = (rng.random((4, 320)) < 0.15).astype(np.uint8)
+    got = run_device(S, pairs, F, TH_LOW, True, qv, cl)
+    assert check_against_oracle(S, pairs, F, TH_LOW, True, got, qv, cl) > 40
+    for p, pr in enumerate(pairs):
+        same([a[p:p + 1] for a in got], run_device(S, [pr], F[p:p + 1], TH_LOW, True, qv[p:p + 1], cl[p:p + 1]))
+    # the same four with a row out of range in their middle (the device form reports it per pair; the host form refuses it)
+    five = pairs[:2] + [(0, 3)] + pairs[2:]
+    sel = [0, 1, 3, 4]
+    F5 = np.insert(F, 2, Fa, axis=0); qv5 = np.insert(qv, 2, 1, axis=0); cl5 = np.insert(cl, 2, 0, axis=0)
+    g5 = run_device(S, five, F5, TH_LOW, True, qv5, cl5)
+    same([a[sel] for a in g5], got)
+    assert g5[0][2] == 0 and all((a[2] == -1).all() for a in g5[1:])
+    with pytest.raises(capi.OrbxError) as e:
+        run_host(S, five, F5, TH_LOW, True, qv5, cl5)
+    assert e.value.code == capi.ORBX_ERR_ARG
+    # qstride == 0: the pairs share one array
+    shared = run_device(S, pairs[:3], F[:3], TH_LOW, False, qv[0], cl[:3])
+    check_against_oracle(S, pairs[:3], F[:3], TH_LOW, False, shared, qv[0], cl[:3])
+    same(shared, run_host(S, pairs[:3], F[:3], TH_LOW, False, qv[0], cl[:3]))
+
+
+def index_ordered(r):
+    """the row with every node's list in ascending feature order: what orbv_transform_batch_device writes, what the list search presumes"""
+    node, off, feat = r["fv"]
+    feat = feat.copy()
+    for j in range(len(node)):
+        feat[off[j]:off[j + 1]] = np.sort(feat[off[j]:off[j + 1]])
+    return dict(r, fv=(node, off, feat))
+
+
+def list_search_route(S, pairs, F, th, check, qvalid, claimed):
+    """gather the pairs' rows into per-problem slots, then orbs_bow_ranges_batch_device + orbs_triangulation_search_batch_device; results by feature"""
+    P, cap = len(pairs), S.cap
+    kps, desc, nt, fn, fo, ff, nfv = S.host
+    qi, ti = [p[0] for p in pairs], [p[1] for p in pairs]
+    g = lambda a, idx: dev(np.ascontiguousarray(a[idx]))
+    dqn, dqo, dqf, dqnfv, dqd, dqk = g(fn, qi), g(fo, qi), g(ff, qi), g(nfv, qi), g(desc, qi), g(kps, qi)
+    dtn, dto, dtf, dtnfv, dtd, dtk, dtnt = g(fn, ti), g(fo, ti), g(ff, ti), g(nfv, ti), g(desc, ti), g(kps, ti), g(nt, ti)
+    nlist = dev(np.array([fo[t, nfv[t]] for t in ti], np.int32))
+    qrange = torch.zeros((P, cap, 2), dtype=torch.int32, device="cuda"); nq = torch.zeros(P, dtype=torch.int32, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    capi.bow_ranges_batch_device(dqn.data_ptr(), dqo.data_ptr(), dqnfv.data_ptr(), dtn.data_ptr(), dto.data_ptr(), dtnfv.data_ptr(), cap, P,
+                                 qrange.data_ptr(), nq.data_ptr(), st)
+    out = [torch.full((P, cap), -9, dtype=torch.int32, device="cuda") for _ in range(4)] + [torch.zeros(P, dtype=torch.int32, device="cuda")]
+    dv, dc, dF = dev(qvalid), dev(claimed), dev(np.ascontiguousarray(F, np.float32).reshape(P, 9))
+    capi.triangulation_search_batch_device(th, check, dF.data_ptr(), SIG, dtk.data_ptr(), dtd.data_ptr(), dtf.data_ptr(), nlist.data_ptr(), dtnt.data_ptr(), cap,
+                                           dc.data_ptr(), qrange.data_ptr(), dqf.data_ptr(), dqk.data_ptr(), dqd.data_ptr(), dv.data_ptr(), nq.data_ptr(), cap, P,
+                                           *(o.data_ptr() for o in out), st)
+    torch.cuda.synchronize()
+    q2t_p, t2q_p, best_p, second_p, nm = (o.cpu().numpy() for o in out)
+    q2t = np.full((P, cap), -1, np.int32); t2q = np.full((P, cap), -1, np.int32)
+    best = np.full((P, cap), -1, np.int32); second = np.full((P, cap), -1, np.int32)
+    for p in range(P):
+        pos = ff[qi[p], :fo[qi[p], nfv[qi[p]]]].astype(np.int64)          # query position -> feature
+        q2t[p, pos] = q2t_p[p, :len(pos)]; best[p, pos] = best_p[p, :len(pos)]; second[p, pos] = second_p[p, :len(pos)]
+        n2 = nt[ti[p]]
+        m = t2q_p[p, :n2] >= 0
+        t2q[p, :n2][m] = pos[t2q_p[p, :n2][m]]
+    return nm, q2t, t2q, best, second
+
+
+def pad(a, cap):
+    out = np.zeros((1, cap), np.uint8)
+    out[0, :len(a)] = a
+    return out
+
+
+def test_forms_and_recordings():
+    """the host form, the device form and rows_on_device are equal; every recording of the reference is reproduced; the per-slot route
+    (gather + orbs_bow_ranges_batch_device + orbs_triangulation_search_batch_device) gives the same on the same data in index order"""
+    scenes = [(s, recorded(s[0])) for s in ts.SCENES]
+    for (name, check), (r1, r2, F, res, n) in scenes:
+        S = Store([r1, r2], 336)
+        qv, cl = (x[None] for x in ts.flags(r1, r2, 336))
+        host = run_host(S, [(0, 1)], F, TH_LOW, check, qv, cl)
+        same(host, run_device(S, [(0, 1)], F, TH_LOW, check, qv, cl))
+        same(host, run_host(S, [(0, 1)], F, TH_LOW, check, qv, cl, rows_on_device=True))
+        same(host[:3], run_device(S, [(0, 1)], F, TH_LOW, check, qv, cl, want_dist=False)[:3])          # the distances are optional
+        # the recording: vMatches12 as the reference left it, with no oracle in the loop
+        assert host[0][0] == n > 60 and np.array_equal(host[1][0, :len(res)], res)
+        check_against_oracle(S, [(0, 1)], F, TH_LOW, check, host, qv, cl)
+        So = Store([index_ordered(r1), index_ordered(r2)], 336)
+        ordered = run_device(So, [(0, 1)], F, TH_LOW, check, qv, cl)
+        check_against_oracle(So, [(0, 1)], F, TH_LOW, check, ordered, qv, cl)
+        same(ordered, list_search_route(So, [(0, 1)], F, TH_LOW, check, qv, cl))
+    # all recorded scenes as rows of one store, every pair in one launch
+    rows = [index_ordered(r) for _, (r1, r2, _, _, _) in scenes for r in (r1, r2)]
+    S = Store(rows, 336)
+    pairs = [(2 * i, 2 * i + 1) for i in range(len(scenes))] + [(1, 0), (3, 8)]
+    F = np.stack([sc[1][2] for sc in scenes] + [scenes[0][1][2], scenes[1][1][2]])
+    qv = np.stack([ts.flags(S.rows[a], S.rows[b], 336)[0] for a, b in pairs]); cl = np.stack([ts.flags(S.rows[a], S.rows[b], 336)[1] for a, b in pairs])
+    got = run_device(S, pairs, F, TH_LOW, True, qv, cl)
+    assert check_against_oracle(S, pairs, F, TH_LOW, True, got, qv, cl) > 300
+    same(got, list_search_route(S, pairs, F, TH_LOW, True, qv, cl))
+
+
+def test_argument_errors():
+    """ORBX_ERR_ARG before anything touches the GPU: the output buffers keep their fill"""
+    r1, r2, F, _, _ = recorded("b")
+    S = Store([r1, r2], 336)
+    L = capi.lib()
+    out = [torch.full((1, 336), FILL, dtype=torch.int32, device="cuda") for _ in range(4)] + [torch.full((1,), FILL, dtype=torch.int32, device="cuda")]
+    dp, dF = dev(np.array([[0, 1]], np.int32)), dev(F.reshape(1, 9))
+    rows = S.ptrs()
+    sig = np.ascontiguousarray(SIG)
+
+    def call(rule=capi.RULE_TRIANGULATION, th=TH_LOW, pair=dp.data_ptr(), npairs=1, F12=dF.data_ptr(), s2=sig.ctypes.data, nlevels=8, rows=rows, nrows=2,
+             cap=336, qstride=0, outs=None):
+        prm = capi.SearchParams(rule, th, 0.0, 1)
+        o = [t.data_ptr() for t in out] if outs is None else outs
+        return L.orbs_tri_rows_search_batch_device(ctypes.byref(prm), pair, npairs, F12, s2, nlevels, *rows, nrows, cap, None, qstride, None, *o, None)
+
+    assert call(rule=capi.RULE_BOW) == capi.ORBX_ERR_ARG
+    assert call(th=-1) == capi.ORBX_ERR_ARG and call(th=257) == capi.ORBX_ERR_ARG
+    assert call(npairs=-1) == capi.ORBX_ERR_ARG and call(nrows=0) == capi.ORBX_ERR_ARG
+    assert call(cap=0) == capi.ORBX_ERR_ARG and call(cap=8193) == capi.ORBX_ERR_ARG
+    assert call(npairs=2 ** 31 // 336 + 1) == capi.ORBX_ERR_ARG and call(nrows=2 ** 31 // 337 + 1) == capi.ORBX_ERR_ARG
+    assert call(pair=None) == capi.ORBX_ERR_ARG and call(F12=None) == capi.ORBX_ERR_ARG and call(F12=dF.data_ptr() + 2) == capi.ORBX_ERR_ARG
+    assert call(s2=None) == capi.ORBX_ERR_ARG and call(nlevels=0) == capi.ORBX_ERR_ARG and call(nlevels=17) == capi.ORBX_ERR_ARG
+    assert call(qstride=335) == capi.ORBX_ERR_ARG and call(qstride=-1) == capi.ORBX_ERR_ARG
+    for i in range(7):
+        assert call(rows=rows[:i] + [None] + rows[i + 1:]) == capi.ORBX_ERR_ARG, i
+    assert call(rows=[rows[0], rows[1] + 8] + rows[2:]) == capi.ORBX_ERR_ARG                 # descriptors are read in 16-byte pieces
+    o = [t.data_ptr() for t in out]
+    assert call(outs=o[:4] + [None]) == capi.ORBX_ERR_ARG and call(outs=[o[0] + 1] + o[1:]) == capi.ORBX_ERR_ARG
+    torch.cuda.synchronize()
+    assert all((t.cpu().numpy() == FILL).all() for t in out)
+    assert call(npairs=0, pair=None) == capi.ORBX_OK                                         # no pairs: nothing is looked at
+    for bad in ([(0, 2)], [(-1, 1)]):
+        with pytest.raises(capi.OrbxError) as e:
+            run_host(S, bad, F, TH_LOW, True)
+        assert e.value.code == capi.ORBX_ERR_ARG
+    assert call() == capi.ORBX_OK
+    torch.cuda.synchronize()
+    assert out[4].cpu().numpy()[0] > 5
