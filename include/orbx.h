@@ -330,6 +330,9 @@ int orbx_debug_set_blur_on_demand(orbx_extractor* h, int mode);
 int orbx_debug_stage_timing(orbx_extractor* h, int enable);
 int orbx_debug_stage_time(orbx_extractor* h, int stage, double* total_ms, long* launches);
 int orbx_debug_level_size(const orbx_extractor* h, int level, int* w, int* hgt);
+/* how the last launch group built pyramid level `level` (>= 1): form 0 = k_resize (256-px tile columns), 1 = k_resize_strip (full-width row
+ * strips of rows_out output rows), 2 = the fused k_pyramid cones of a small launch group; rows_out is 0 unless form is 1 */
+int orbx_debug_resize_form(const orbx_extractor* h, int level, int* form, int* rows_out);
 /* copies stage data of `frame` (index inside the last batch) / `level` into host memory; returns bytes or <0 */
 long orbx_debug_fetch(orbx_extractor* h, int what, int frame, int level, void* host_out, long cap_bytes);
 /* evaluate the device arithmetic on arrays (kind 0: fast_atan2(in0,in1)->out0; kind 1: sincos(in0)->out0,out1) */

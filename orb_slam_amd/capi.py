@@ -30,7 +30,7 @@ EXPORTS = [
     "orbm_count_accepted", "orbm_match_top2_segments", "orbm_match_top2_segments_device", "orbm_distinctive", "orbm_distinctive_device",
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_download",
     "orbx_stream_create", "orbx_stream_create_priority", "orbx_stream_destroy", "orbx_stream_synchronize", "orbx_event_create", "orbx_event_destroy", "orbx_event_record",
-    "orbx_stream_wait_event", "orbx_device_copy_async", "orbx_host_alloc", "orbx_host_free", "orbx_device_upload_async", "orbx_device_download_async", "orbx_debug_set_stop_after", "orbx_debug_set_blur_on_demand", "orbx_debug_level_size", "orbx_debug_fetch",
+    "orbx_stream_wait_event", "orbx_device_copy_async", "orbx_host_alloc", "orbx_host_free", "orbx_device_upload_async", "orbx_device_download_async", "orbx_debug_set_stop_after", "orbx_debug_set_blur_on_demand", "orbx_debug_level_size", "orbx_debug_resize_form", "orbx_debug_fetch",
     "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_eval_blur_window", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
     "orbm_debug_set_match_path",
     "orbm_debug_get_match_path",
@@ -264,6 +264,8 @@ def lib():
         L.orbx_debug_set_stop_after.argtypes = [vp, ci]
         L.orbx_debug_set_blur_on_demand.argtypes = [vp, ci]
         L.orbx_debug_level_size.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        if hasattr(L, "orbx_debug_resize_form"):       # (an older library through ORBX_LIB, for an A/B, lacks it)
+            L.orbx_debug_resize_form.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.orbx_debug_fetch.argtypes = [vp, ci, ci, ci, vp, cl]
         L.orbx_debug_fetch.restype = cl
         L.orbx_debug_eval_math.argtypes = [ci, vp, vp, vp, vp, ci, ci]
@@ -629,6 +631,14 @@ class ORBextractor:
         if rc != ORBX_OK:
             raise self._err(rc)
         return w.value, hh.value
+
+    def resize_form(self, level):
+        """(form, rows_out) of pyramid level `level` in the last launch group: RZ_FORM_TILED / RZ_FORM_STRIP / RZ_FORM_FUSED"""
+        form, rows = ctypes.c_int(), ctypes.c_int()
+        rc = self.L.orbx_debug_resize_form(self.h, level, ctypes.byref(form), ctypes.byref(rows))
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbx_debug_resize_form")
+        return form.value, rows.value
 
     def fetch_plane(self, what, level, frame=0):
         w, hh = self.level_size(level)

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "k_resize_strip.h"
 #include "orbx_device.h"
 #include "orbx_launch.h"
 
@@ -173,6 +174,159 @@ __global__ __launch_bounds__(256) void k_resize(Batch b, int level) { k_resize_b
 template <bool ALIGNED, bool WINDOW>
 __global__ __launch_bounds__(256) void k_resize_gather(Batch b, int level) { k_resize_body<ALIGNED, WINDOW, true>(b, level); }
 
+// Strip form of the per-level resize, k_resize_strip (k_resize_strip.h): a workgroup produces rows_out consecutive output rows across the WHOLE width of
+// the level.  The source rows of such a strip are one contiguous byte range of the plane below, so the staging is a flat list of 16-byte
+// LDS-DMA chunks with no row / column split at all (k_resize's 256-px tile columns need one 4-byte DMA instruction per row and 64-dword
+// piece, each with its own address arithmetic: ~300 per level-1 tile), and there are no narrow tail tiles whose four waves walk their rows
+// with a few live lanes.  The arithmetic is k_resize's windowed form, bit for bit: the same tables, v_dot2, >> 4, v_mul_hi, + 2 >> 2.
+// Wave v owns rows_out / 4 consecutive output rows (scalar row weights, the lower source row's horizontal results reused) and walks the
+// level's groups of 64 dword columns; a last group of at most RZS_ROWPAR_MAX columns is row-parallel instead: lanes hold (column, row) pairs
+// with per-lane row weights and source-row offsets, and always compute both source rows.
+// NG: the level's groups when they are few enough to keep every group's column constants in registers (fetched before the staging wait);
+// 0: any number, fetched group by group.
+struct RzsCols {
+    uint32_t sel[4], apair[4];     // v_perm selectors and weight pairs of the lane's four output pixels (row-invariant)
+    int wa, sh;                    // first tap of the lane: aligned byte column of its three-dword window, byte shift inside it
+};
+__device__ __forceinline__ void rzs_load_cols(const ResizeX* tx, int w, int dcol, RzsCols& c) {
+    ResizeX rx[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) rx[k] = tx[min(4 * dcol + k, w - 1)];
+    const int w0 = rx[0].sx;
+    c.wa = w0 & ~3;
+    c.sh = w0 & 3;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        c.sel[k] = (uint32_t)(rx[k].sx - w0) | 0x0C000C00u | ((uint32_t)(rx[k].sx1 - w0) << 16);     // bytes: s[sx], 0, s[sx1], 0
+        c.apair[k] = (uint32_t)(uint16_t)rx[k].a0 | ((uint32_t)(uint16_t)rx[k].a1 << 16);
+    }
+}
+// horizontal pass of one source row (LDS byte offset `off` of the lane's aligned window): D >> 4 of the lane's four pixels
+__device__ __forceinline__ void rzs_hrow(const uint8_t* s_src, int off, const RzsCols& c, uint32_t (&d)[4]) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(s_src + off);
+    const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
+    const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)c.sh), hi = __builtin_amdgcn_alignbyte(d2, d1, (uint32_t)c.sh);
+#pragma unroll
+    for (int k = 0; k < 4; k++) d[k] = __builtin_amdgcn_udot2(as_us2v(__builtin_amdgcn_perm(hi, lo, c.sel[k])), as_us2v(c.apair[k]), 0u, false) >> 4;
+}
+__device__ __forceinline__ uint32_t rzs_vpack(const uint32_t (&da)[4], const uint32_t (&db)[4], uint32_t b0s, uint32_t b1s) {
+    uint32_t packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) packed |= ((__umulhi(da[k], b0s) + __umulhi(db[k], b1s) + 2u) >> 2) << (8 * k);
+    return packed;
+}
+
+template <bool GATHER, int NG>
+__device__ __forceinline__ void k_resize_strip_body(Batch b, int level, int rows_out, int nstrips, unsigned magic) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_src[];
+    const DevGeom& g = b.g;
+    const LevelGeom& L = g.lv[level];
+    const LevelGeom& P = g.lv[level - 1];
+    int frame, strip;
+    if (!frame_item_magic(b, blockIdx.x, (unsigned)nstrips, magic, frame, strip)) return;      // (nstrips = rzs_strips(L.h, rows_out) and its magic: host)
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+    long long sstride64;
+    const uint8_t* src = plain_plane<GATHER>(b, P, level - 1, frame, sstride64);
+    const int sstride = (int)sstride64;                          // (a strip fits the LDS budget: host-checked)
+    const ResizeX* tx = b.tabx + L.tabx_off;
+    const ResizeY* ty = b.taby + L.taby_off;
+    const int RPW = rows_out >> 2;                               // consecutive output rows per wave
+    const int row0 = strip * rows_out + wave * RPW;
+    // the row-table entries of this wave's output rows, one per lane (see k_resize)
+    const uint2 ryl = *reinterpret_cast<const uint2*>(ty + min(row0 + min(lane, RPW - 1), L.h - 1));
+    const int ngroups = NG ? NG : rzs_groups(L.w);
+    const int rem = rzs_rem_cols(L.w);
+    const bool rowpar = rem <= RZS_ROWPAR_MAX;
+    const int shift = rzs_rowpar_shift(rem);
+    auto group_col = [&](int gi) { return gi == ngroups - 1 && rowpar ? 64 * gi + rzs_rowpar_slot(lane, shift) : rzs_loop_col(gi, lane); };
+    // the column constants of every group, independent of the staging below: issued first
+    RzsCols cols[NG ? NG : 1];
+    if (NG) {
+#pragma unroll
+        for (int gi = 0; gi < NG; gi++) rzs_load_cols(tx, L.w, group_col(gi), cols[gi]);
+    }
+    // the strip's source rows: fetched behind the table loads above, so that one wait covers them all (not a round trip of its own in front of them)
+    __builtin_amdgcn_sched_barrier(0);
+    const StripSpan sp = rzs_span(ty, L.h, rows_out, strip, sstride64, rzs_readable(level == 1, sstride64, P.w));
+    const int r0 = sp.r0, nchunks = (int)sp.chunks;
+    {
+        typedef const void __attribute__((address_space(1))) * gptr_t;
+        typedef void __attribute__((address_space(3))) * lptr_t;
+        const uint8_t* base = src + (long long)r0 * sstride64;
+        // dwords behind the last whole chunk (a level-0 pitch that is no multiple of 16): plain loads, in front of the DMA (the compiler
+        // orders every LDS write behind outstanding LDS-DMA loads)
+        if (tid < sp.tail_dwords)
+            *reinterpret_cast<uint32_t*>(s_src + 16 * nchunks + 4 * tid) = *reinterpret_cast<const uint32_t*>(base + 16 * (long long)nchunks + 4 * tid);
+        // chunk q of the range -> LDS offset 16 q; a wave instruction moves 64 consecutive chunks (lane i's 16 bytes land at M0 + 16 i)
+        for (int q0 = 64 * wave; q0 < nchunks; q0 += 256)
+            if (q0 + lane < nchunks) __builtin_amdgcn_global_load_lds((gptr_t)(base + 16 * (q0 + lane)), (lptr_t)(s_src + 16 * q0), 16, 0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA writes have landed; the barrier below covers the other waves
+    }
+    __syncthreads();
+    uint8_t* dplane = b.pyr + (long long)frame * g.frame_plane_bytes + L.plane_off;      // (wave-uniform; a frame's planes are below 2^31 bytes: 32-bit offsets)
+    const unsigned dstride = (unsigned)L.stride;
+    const int nrows = min(RPW, L.h - row0);                      // this wave's rows inside the level (<= 0: none)
+    auto process = [&](int gi, const RzsCols& c) {
+        const int dcol = group_col(gi);
+        if (gi == ngroups - 1 && rowpar) {
+            // row-parallel remainder: 2^shift column slots x (64 >> shift) rows per pass; a lane's row entry comes from the lane that holds it
+            const int slot = rzs_rowpar_slot(lane, shift);
+            for (int pass = 0; pass * (64 >> shift) < RPW; pass++) {
+                const int j = rzs_rowpar_row(lane, shift, pass);
+                const uint32_t ry_rows = (uint32_t)__shfl((int)ryl.x, min(j, RPW - 1)), ry_w = (uint32_t)__shfl((int)ryl.y, min(j, RPW - 1));
+                const int dy = row0 + j;
+                if (slot < rem && j < RPW && dy < L.h) {
+                    const int sy0 = (int16_t)(ry_rows & 0xffffu), sy1 = (int16_t)(ry_rows >> 16);
+                    uint32_t da[4], db[4];
+                    rzs_hrow(s_src, (sy0 - r0) * sstride + c.wa, c, da);
+                    rzs_hrow(s_src, (sy1 - r0) * sstride + c.wa, c, db);
+                    // columns past L.w (clamped in rzs_load_cols) land in the row padding: stride is a multiple of 64
+                    *reinterpret_cast<uint32_t*>(dplane + ((unsigned)dy * dstride + 4u * (unsigned)dcol)) = rzs_vpack(da, db, ry_w << 16, ry_w & 0xffff0000u);
+                }
+            }
+        } else if (4 * dcol < L.w) {
+            // The lower source row's horizontal results stay in `cur` for the next output row; the upper row's share of the vertical pass is
+            // taken before `cur` is overwritten, so nothing is copied from row to row.
+            int have = -1;
+            uint32_t cur[4] = {0, 0, 0, 0};
+            for (int j = 0; j < nrows; j++) {
+                const int dy = row0 + j;
+                const uint32_t ry_rows = (uint32_t)__builtin_amdgcn_readlane((int)ryl.x, j), ry_w = (uint32_t)__builtin_amdgcn_readlane((int)ryl.y, j);
+                const int sy0 = (int16_t)(ry_rows & 0xffffu), sy1 = (int16_t)(ry_rows >> 16);
+                const uint32_t b0s = ry_w << 16, b1s = ry_w & 0xffff0000u;      // the weights (0 .. 2048) in the high halves
+                if (sy0 != have) rzs_hrow(s_src, (sy0 - r0) * sstride + c.wa, c, cur);
+                uint32_t t[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) t[k] = __umulhi(cur[k], b0s);
+                asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));      // (taken HERE: sunk below the second hrow, `cur` has to be copied first)
+                if (sy1 != sy0) rzs_hrow(s_src, (sy1 - r0) * sstride + c.wa, c, cur);
+                have = sy1;
+                uint32_t packed = 0;
+#pragma unroll
+                for (int k = 0; k < 4; k++) packed |= ((t[k] + __umulhi(cur[k], b1s) + 2u) >> 2) << (8 * k);
+                // columns past L.w (clamped in rzs_load_cols) land in the row padding: stride is a multiple of 64
+                *reinterpret_cast<uint32_t*>(dplane + ((unsigned)dy * dstride + 4u * (unsigned)dcol)) = packed;
+            }
+        }
+    };
+    if constexpr (NG != 0) {
+#pragma unroll
+        for (int gi = 0; gi < NG; gi++) process(gi, cols[gi]);
+    } else {
+        for (int gi = 0; gi < ngroups; gi++) {
+            rzs_load_cols(tx, L.w, group_col(gi), cols[0]);
+            process(gi, cols[0]);
+        }
+    }
+}
+// The entry points are overloads of k_resize / k_resize_gather, k_resize<NG>: the benchmark's per-stage counters and the profile tools find the pyramid
+// stage by that kernel name, whichever form a level takes.
+typedef void (*resize_strip_fn)(Batch, int, int, int, unsigned);
+template <int NG>
+__global__ __launch_bounds__(256) void k_resize(Batch b, int level, int rows_out, int nstrips, unsigned magic) { k_resize_strip_body<false, NG>(b, level, rows_out, nstrips, magic); }
+template <int NG>
+__global__ __launch_bounds__(256) void k_resize_gather(Batch b, int level, int rows_out, int nstrips, unsigned magic) { k_resize_strip_body<true, NG>(b, level, rows_out, nstrips, magic); }
+
 // Fused pyramid: one launch produces the levels l0+1 .. l0+depth of a PyrGroup (round 2: 2 launches for 8 levels instead of 7
 // dependent ones — on one frame each k_resize launch cost ~9 us of latency, 65 of the ~150 us of a frame's kernel chain).
 // A workgroup owns a tile of the deepest level and the cone above it.  The region of the source level it needs is staged in
@@ -273,6 +427,29 @@ __global__ __launch_bounds__(256) void k_pyramid(Batch b, int group) {
 }
 
 
+// Form of level `level`'s resize in this launch group (orbx_internal.h).  Levels >= 2 read pyramid planes: decided with the geometry.
+// Level 1 reads the caller's frames: decided here from their alignment and (largest) pitch, which is the pitch of the LDS tile.
+int resize_form(const Batch& b, const HostGeom& hg, int level, StripChoice& sc) {
+    const DevGeom& g = hg.g;
+    sc = StripChoice{0, 0};
+    if (level < 1 || level >= g.nlevels) return RZ_FORM_TILED;
+    if (g.npyr_groups > 0 && b.nframes < PYR_FUSED_MAX_FRAMES) return RZ_FORM_FUSED;
+    const LevelGeom& L = g.lv[level];
+    if (level >= 2 || (level0_max_stride(b) == g.lv[0].w && (level0_bits(b) & 3) == 0)) sc = StripChoice{L.rs_rows, L.rs_lds};
+    else sc = resize_strip_choice(hg, level, level0_max_stride(b), level0_bits(b));
+    return sc.rows_out ? RZ_FORM_STRIP : RZ_FORM_TILED;
+}
+
+template <int NG>
+static void launch_resize_strip(const Batch& b, int l, const StripChoice& sc, hipStream_t stream) {
+    const LevelGeom& L = b.g.lv[l];
+    const int nstrips = rzs_strips(L.h, sc.rows_out);
+    const unsigned magic = frame_item_magic_of(nstrips);
+    dim3 grid(frame_item_blocks(b, nstrips));
+    const resize_strip_fn fn = b.img_tab && l == 1 ? static_cast<resize_strip_fn>(&k_resize_gather<NG>) : static_cast<resize_strip_fn>(&k_resize<NG>);
+    hipLaunchKernelGGL(fn, grid, dim3(256), (size_t)sc.lds_bytes, stream, b, l, sc.rows_out, nstrips, magic);
+}
+
 // (launch_extract's pyramid stage; the per-frame status fill that rides on it stays with the caller)
 int launch_pyramid(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     const DevGeom& g = hg.g;
@@ -297,6 +474,18 @@ int launch_pyramid(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     } else {
         for (int l = 1; l < g.nlevels; l++) {
             const LevelGeom& L = g.lv[l];
+            StripChoice sc;
+            if (resize_form(b, hg, l, sc) == RZ_FORM_STRIP) {
+                switch (rzs_groups(L.w)) {      // groups of 64 dword columns: up to four keep their column constants in registers
+                    case 1: launch_resize_strip<1>(b, l, sc, stream); break;
+                    case 2: launch_resize_strip<2>(b, l, sc, stream); break;
+                    case 3: launch_resize_strip<3>(b, l, sc, stream); break;
+                    case 4: launch_resize_strip<4>(b, l, sc, stream); break;
+                    default: launch_resize_strip<0>(b, l, sc, stream); break;
+                }
+                ORBX_LAUNCH_CHECK();
+                continue;
+            }
             dim3 grid(frame_item_blocks(b, ((L.w + 255) / 256) * ((L.h + RZ_ROWS - 1) / RZ_ROWS)));
             const bool al = l > 1 || al0;
             const size_t lds = (size_t)L.rz_pitch * L.rz_rows;

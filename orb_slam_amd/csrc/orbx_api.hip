@@ -203,13 +203,14 @@ static int extract_gather(orbx_extractor* h, int fmt, const uint8_t* const* imgs
         ImgSrc* ht = h->h_tab.as<ImgSrc>() + (size_t)slot * mb;
         ImgSrc* dt = h->d_tab.as<ImgSrc>() + (size_t)slot * mb;
         unsigned long long bits = 0;
-        long long min_stride = LLONG_MAX;
+        long long min_stride = LLONG_MAX, max_stride = 0;
         for (int i = 0; i < n; i++) {
             const long long s = row_strides ? (long long)row_strides[f0 + i] : (long long)w * pix_channels(fmt);
             ht[i].data = imgs[f0 + i];
             ht[i].row_stride = s;
             bits |= (uintptr_t)imgs[f0 + i] | (unsigned long long)s;
             min_stride = std::min(min_stride, s);
+            max_stride = std::max(max_stride, s);
         }
         HIPCHK(h, hipMemcpyAsync(dt, ht, (size_t)n * sizeof(ImgSrc), hipMemcpyHostToDevice, stream));
         Batch b;
@@ -219,6 +220,7 @@ static int extract_gather(orbx_extractor* h, int fmt, const uint8_t* const* imgs
             b.img_tab = dt;
             b.img_tab_bits = bits;
             b.img_tab_min_stride = min_stride;
+            b.img_tab_max_stride = max_stride;
         } else {
             const int rc = convert(h, nullptr, 0, 0, dt, bits, n, w, hgt, fmt, h->d_cring.as(), (ptrdiff_t)gp, (ptrdiff_t)(gp * hgt), nullptr, stream);
             if (rc != ORBX_OK) return rc;
@@ -715,6 +717,14 @@ int orbx_debug_level_size(const orbx_extractor* h, int level, int* w, int* hgt) 
     if (!h || h->gw == 0 || level < 0 || level >= h->hg.g.nlevels) return ORBX_ERR_ARG;
     *w = h->hg.g.lv[level].w;
     *hgt = h->hg.g.lv[level].h;
+    return ORBX_OK;
+}
+
+int orbx_debug_resize_form(const orbx_extractor* h, int level, int* form, int* rows_out) {
+    if (!h || !h->have_last || !form || !rows_out || level < 1 || level >= h->hg.g.nlevels) return ORBX_ERR_ARG;
+    StripChoice sc;
+    *form = resize_form(h->last, h->hg, level, sc);
+    *rows_out = sc.rows_out;
     return ORBX_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "k_resize_strip.h"
 #include "orbx_internal.h"
 
 namespace orbx {
@@ -24,6 +25,27 @@ static inline int16_t sat16(float v) {   // saturate_cast<short>(float)
     return (int16_t)(iv < SHRT_MIN ? SHRT_MIN : iv > SHRT_MAX ? SHRT_MAX : iv);
 }
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+StripChoice resize_strip_choice(const HostGeom& hg, int level, long long src_stride, unsigned long long src_bits) {
+    StripChoice sc = {0, 0};
+    const DevGeom& g = hg.g;
+    if (level < 1 || level >= g.nlevels) return sc;
+    const LevelGeom& L = g.lv[level];
+    const LevelGeom& P = g.lv[level - 1];
+    if (!L.rz_window) return sc;
+    long long stride = P.stride;
+    if (level == 1) {
+        // the caller's rows: 4-byte aligned bases and pitch (LDS-DMA), rows that do not overlap
+        stride = src_stride;
+        if (((src_bits | (unsigned long long)stride) & 3) != 0 || stride < P.w) return sc;
+    }
+    const long long readable = rzs_readable(level == 1, stride, P.w);
+    if (stride > RZS_LDS_BUDGET) return sc;                     // (not even two rows: keeps the sums below small)
+    const ResizeY* ty = hg.taby.data() + L.taby_off;
+    sc.rows_out = rzs_pick_rows(ty, L.h, stride, readable);
+    if (sc.rows_out) sc.lds_bytes = (int)rzs_lds_bytes(ty, L.h, sc.rows_out, stride, readable);
+    return sc;
+}
 
 static int build_geometry_band(const orbx_params& p, int w, int h, HostGeom& out, std::string& err, const int band_px, const FastShape& shape) {
     const int threads = shape.threads;
@@ -283,6 +305,10 @@ static int build_geometry_band(const orbx_params& p, int w, int h, HostGeom& out
                 for (int x0 = 0; x0 < dw; x0 += 4) span = std::max(span, tx[std::min(x0 + 3, dw - 1)].sx1 - tx[x0].sx + 1);
                 L.rz_window = span <= 8 ? 1 : 0;
                 if (L.rz_pitch * L.rz_rows > 64 * 1024) { err = "resize tile does not fit the LDS"; return ORBX_ERR_CAPACITY; }
+                // strip form (k_resize_strip.h) for packed source rows: a pyramid plane, or for level 1 a frame of pitch w
+                const StripChoice sc = resize_strip_choice(out, l, l == 1 ? (long long)sw : 0, 0);
+                L.rs_rows = sc.rows_out;
+                L.rs_lds = sc.lds_bytes;
             }
         }
     }

@@ -42,6 +42,8 @@ struct LevelGeom {
     int tabx_off, taby_off;// offsets into the ResizeX / ResizeY tables (level >= 1)
     int rz_window;         // k_resize: 1 = the four output pixels of a lane read at most 8 adjacent source bytes per row (windowed form)
     int rz_pitch, rz_rows; // k_resize: LDS source tile of one 256x16 output tile (bytes per row, rows), maxima over the level's tiles
+    int rs_rows, rs_lds;   // k_resize_strip (k_resize_strip.h): output rows per strip and LDS bytes when the source rows are packed (a pyramid plane for level >= 2; a frame
+                           // of pitch w for level 1, whose launch decides again from the caller's pitch); rs_rows 0: the level keeps the tiled k_resize
     int btile_base, btiles_x, btiles_y;// blur wave tasks: 248-px strips x 32-row bands of the whole plane
     int btile_base_s, btiles_y_s;      // the same with BLUR_ROWS_SMALL-row bands (launch groups too small to fill the chip: shorter waves)
     int mb_base, mb_n;     // k_blur_mfma work items of the level: mb_strips 64-px strips x mb_bands row bands of mb_band_steps 32-row steps, band-major
@@ -274,6 +276,7 @@ struct Batch {
     const ImgSrc* img_tab;
     unsigned long long img_tab_bits;   // host: OR of every data pointer and row stride in the table (alignment choice)
     long long img_tab_min_stride;      // host: smallest row stride in the table (describe_od_supported)
+    long long img_tab_max_stride;      // host: largest row stride in the table (resize_form: the LDS tile of k_resize_strip has the source's pitch)
 };
 
 // Level-0 alignment bits of a launch group: the OR of every frame base and row stride (the frame-stride term is 0 in the gather form).
@@ -282,6 +285,7 @@ static inline unsigned long long level0_bits(const Batch& b) {
 }
 // Smallest level-0 row stride of a launch group.
 static inline long long level0_min_stride(const Batch& b) { return b.img_tab ? b.img_tab_min_stride : b.img_row_stride; }
+static inline long long level0_max_stride(const Batch& b) { return b.img_tab ? b.img_tab_max_stride : b.img_row_stride; }
 
 // One launch of the colour -> gray conversion (k_color.hip): nframes frames from `src` (frame f at src + f*src_frame_stride) or, when `tab`
 // is set, from the DEVICE table tab[f] (gather forms; tab_bits = OR of its bases and row strides), to dst + f*dst_frame_stride, and the
@@ -325,6 +329,15 @@ struct HostGeom {
 
 // Fills `out` for a w x h input; returns ORBX_OK / ORBX_ERR_GEOMETRY / ORBX_ERR_ARG.
 int build_geometry(const orbx_params& p, int w, int h, HostGeom& out, std::string& err);
+
+// Which form of the per-level resize level `level` (>= 1) takes when its source rows are `src_stride` bytes apart and the OR of every source
+// base and stride is `src_bits` (both ignored for level >= 2: the source is a pyramid plane): rows_out of k_resize_strip and its LDS bytes, or
+// rows_out = 0 for the tiled k_resize.  Strip form: the windowed arithmetic applies, the source is 4-byte aligned, and some rows_out >= RZS_ROWS_MIN fits
+// RZS_LDS_BUDGET.  Host arithmetic only (orbx_geometry.hip).
+struct StripChoice { int rows_out, lds_bytes; };
+StripChoice resize_strip_choice(const HostGeom& hg, int level, long long src_stride, unsigned long long src_bits);
+// ... of a launch group: RZ_FORM_* (k_pyramid.hip; RZ_FORM_FUSED: the group is small enough for the k_pyramid cones)
+int resize_form(const Batch& b, const HostGeom& hg, int level, StripChoice& sc);
 
 enum Stage { ST_PYRAMID = 0, ST_FAST_CELLS, ST_QUOTA, ST_CELL_SELECT, ST_LEVEL_SELECT, ST_BLUR, ST_DESCRIBE, ST_COUNT };
 

@@ -3,7 +3,8 @@
 // launch cost is amortised over the batch and the 256 CUs always see >> 256 workgroups.
 //
 // Stage            reference (under /root/reference/src/ORBextractor.cc)        kernel
-//   pyramid        ComputePyramid :781-822 (cv::resize INTER_LINEAR)             k_resize (per level, 7 launches) | k_pyramid (cones of levels, 2 launches; < 32 frames)
+//   pyramid        ComputePyramid :781-822 (cv::resize INTER_LINEAR)             k_resize_strip | k_resize (per level, 7 launches: full-width row strips where a strip's source rows fit the LDS
+//                                                                                budget, 256-px tile columns otherwise) | k_pyramid (cones of levels, 2 launches; < 32 frames)
 //   FAST + NMS     cv::FAST(cell, th, true) :607/:613 + raster-ordered cell lists  k_fast_cells (one workgroup per grid-cell row band)
 //   quotas         :622-670                                                      k_quota      (one wave per level; a pass of the rule = one sweep of the lanes + two reductions)
 //   retainBest     :683-685 (per cell), :697-701 (per level)                     k_cell_select (+ _long) / k_level_select (wave-parallel, permutation-exact introselect)
