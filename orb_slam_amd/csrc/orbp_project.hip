@@ -232,8 +232,6 @@ using orbx::DeviceScope;
 using orbx::Layout;
 using Call = orbx::Call<orbp_map>;
 using Staged = orbx::Staged<orbp_map>;
-// leaves the entry point with a status that is not ORBX_OK
-#define TRY(call) do { const int rc_ = (call); if (rc_ != ORBX_OK) return rc_; } while (0)
 
 // the slots of a put / erase: range, and for a put no slot twice
 int check_slots(orbp_map* m, const int32_t* slots, int n, bool unique, bool need_live) {

@@ -25,6 +25,8 @@
     } while (0)
 // the same for the entry points without a handle
 #define HIPTRY(call) do { if ((call) != hipSuccess) return ORBX_ERR_DEVICE; } while (0)
+// a step that returns an ORBX status: anything but ORBX_OK is the function's own result
+#define TRY(call) do { const int rc_ = (call); if (rc_ != ORBX_OK) return rc_; } while (0)
 
 // internal to the library: none of these types is exported
 #pragma GCC visibility push(hidden)

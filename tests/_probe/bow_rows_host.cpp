@@ -1,7 +1,7 @@
 // The host side of orbs_bow_rows_search* on the CPU against tests/_probe/hip_stub: the argument checks (orbs::check_bow_rows), the layout, staging
-// and unpacking of the host form's block (orbs::BowRowsBlock), whose copies run over heap blocks of exactly the computed sizes, and the CSR packing
-// of a FeatureVector (orb_slam_amd/cpp/FeatureVectorCSR.h, what LocalMapPointsBoW.cc uploads per row).  tests/test_bow_rows_host.py builds this
-// under AddressSanitizer + UndefinedBehaviorSanitizer and runs it as a program.
+// and unpacking of the host form's block (orbs::RowsBlock of orbs_rows.h, here without an F12 slot), whose copies run over heap blocks of exactly
+// the computed sizes, and the CSR packing of a FeatureVector (orb_slam_amd/cpp/FeatureVectorCSR.h, what LocalMapPointsBoW.cc uploads per row).
+// tests/test_bow_rows_host.py builds this under AddressSanitizer + UndefinedBehaviorSanitizer and runs it as a program.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "FeatureVectorCSR.h"
-#include "orbs_bow_rows.h"
+#include "orbs_rows.h"
 
 using namespace orbs;
 
@@ -28,7 +28,7 @@ int main() {
     fv_off.back() = 9;
     std::vector<uint8_t> qvalid((size_t)npairs * cap, 1), claimed((size_t)npairs * cap, 2);
     std::vector<int32_t> q2t((size_t)npairs * cap, -7), t2q(q2t), best(q2t), second(q2t), nm(npairs, -7);
-    const BowPairs P{pair.data(), npairs, qvalid.data(), claimed.data()};
+    const RowPairs P{pair.data(), npairs, qvalid.data(), cap, claimed.data(), nullptr, 0, 0};
     const BowStore S{kps.data(), desc, nt.data(), fv_node.data(), fv_off.data(), fv_feat.data(), nfv.data(), nrows, cap};
     const BowOut O{q2t.data(), t2q.data(), best.data(), second.data(), nm.data()};
     {
@@ -48,10 +48,10 @@ int main() {
             CHECK(check_bow_rows(&q, P, S, O, d, d) == ORBX_OK);
             q = prm; q.ratio = std::nanf("");
             CHECK(check_bow_rows(&q, P, S, O, d, d) == ORBX_ERR_ARG);
-            BowPairs p2 = P;
+            RowPairs p2 = P;
             p2.npairs = -1;
             CHECK(check_bow_rows(&prm, p2, S, O, d, d) == ORBX_ERR_ARG);
-            p2 = BowPairs{nullptr, 0, nullptr, nullptr};                          // no pairs: nothing is looked at
+            p2 = RowPairs{nullptr, 0, nullptr, 1, nullptr, nullptr, 0, 0};                          // no pairs: nothing is looked at
             CHECK(check_bow_rows(&prm, p2, BowStore{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1}, BowOut{}, d, d) == ORBX_OK);
             p2 = P; p2.pair = nullptr;
             CHECK(check_bow_rows(&prm, p2, S, O, d, d) == ORBX_ERR_ARG);
@@ -93,7 +93,7 @@ int main() {
         // the host form walks the pairs; the device form reports a row out of range per pair
         std::vector<int32_t> bad = pair;
         bad[3] = nrows;
-        BowPairs p2 = P;
+        RowPairs p2 = P;
         p2.pair = bad.data();
         CHECK(check_bow_rows(&prm, p2, S, O, false, false) == ORBX_ERR_ARG);
         CHECK(check_bow_rows(&prm, p2, S, O, true, true) == ORBX_OK);
@@ -102,7 +102,7 @@ int main() {
     }
     {
         // the block with everything in it: slots at multiples of 256, one span up, one down, the records behind
-        const BowRowsBlock B(P, S, O, true);
+        const RowsBlock B(P, S, O, true);
         CHECK(B.pair.off == 0 && B.qvalid.off == 256 && B.claimed.off == 512 && B.nt.off == 768 && B.nfv.off == 1024 && B.kps.off == 1280);
         CHECK(B.desc.off == 1280 + 1024 && B.fv_node.off == 2304 + 1024 && B.fv_off.off == 3328 + 256 && B.fv_feat.off == 3584 + 256);
         const size_t up = B.L.upload();
@@ -114,7 +114,7 @@ int main() {
         CHECK((const uint8_t*)a.S.nt == d.data() + 768 && (const uint8_t*)a.S.nfv == d.data() + 1024 && (const uint8_t*)a.S.kps == d.data() + 1280);
         CHECK(a.S.desc == d.data() + 2304 && ((uintptr_t)(a.S.desc - d.data()) & 15) == 0 && (const uint8_t*)a.S.fv_feat == d.data() + 3840);
         CHECK(a.S.nrows == nrows && a.S.cap == cap && (uint8_t*)a.O.nmatches == d.data() + up && (uint8_t*)a.O.second == d.data() + up + 1024);
-        CHECK((uint8_t*)a.rec == d.data() + up + 1280);
+        CHECK((uint8_t*)a.rec == d.data() + up + 1280 && !B.F12.present && !a.P.F12 && a.P.qstride == cap && B.nqv == (size_t)npairs * cap);
         CHECK(reinterpret_cast<const int32_t*>(h.data())[5] == 1 && h[256 + npairs * cap - 1] == 1 && h[512 + npairs * cap - 1] == 2);
         CHECK(reinterpret_cast<const int32_t*>(h.data() + 768)[3] == 5 && reinterpret_cast<const int32_t*>(h.data() + 1024)[3] == 2);
         CHECK(reinterpret_cast<const orbx_keypoint*>(h.data() + 1280)[nrows * cap - 1].octave == nrows * cap - 1 && h[2304 + nrows * cap * 32 - 1] == 0xAB);
@@ -127,9 +127,9 @@ int main() {
     }
     {
         // what the caller does not pass takes no room and resolves to null; resident rows are passed through, their counts still go up
-        const BowPairs p2{pair.data(), 1, nullptr, nullptr};
+        const RowPairs p2{pair.data(), 1, nullptr, cap, nullptr, nullptr, 0, 0};
         const BowOut o2{nullptr, t2q.data(), nullptr, nullptr, nm.data()};
-        const BowRowsBlock B(p2, S, o2, false);
+        const RowsBlock B(p2, S, o2, false);
         CHECK(!B.qvalid.present && !B.claimed.present && !B.kps.present && !B.desc.present && !B.fv_node.present && !B.fv_off.present && !B.fv_feat.present);
         CHECK(B.nt.present && B.nfv.present && !B.q2t.present && B.t2q.present && !B.best.present && !B.second.present);
         CHECK(B.pair.off == 0 && B.nt.off == 256 && B.nfv.off == 512 && B.L.upload() == 768 && B.nmatches.off == 768 && B.t2q.off == 1024 && B.rec.off == 1280);

@@ -1,15 +1,15 @@
 // The host side of orbs_tri_rows_search* and orbt_new_points_rows* on the CPU against tests/_probe/hip_stub: the argument checks
 // (orbs::check_tri_rows, check_chain_pairs, check_new_points: every ORBX_ERR_ARG condition include/orbs.h and include/orbt.h list), the layout,
-// staging and unpacking of the two host forms' blocks (orbs::TriRowsBlock, NewPointsBlock), whose copies run over heap blocks of exactly the
-// computed sizes, and what LocalMapPointsNewPoints.cc packs per call (orb_slam_amd/cpp/NewPointsPacking.h).  tests/test_tri_rows_host.py builds this
-// under AddressSanitizer + UndefinedBehaviorSanitizer and runs it as a program.
+// staging and unpacking of the two host forms' blocks (orbs::RowsBlock of orbs_rows.h with its F12 slot, NewPointsBlock), whose copies run over
+// heap blocks of exactly the computed sizes, and what LocalMapPointsNewPoints.cc packs per call (orb_slam_amd/cpp/NewPointsPacking.h).
+// tests/test_tri_rows_host.py builds this under AddressSanitizer + UndefinedBehaviorSanitizer and runs it as a program.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "NewPointsPacking.h"
-#include "orbs_tri_rows.h"
+#include "orbs_rows.h"
 
 using namespace orbs;
 
@@ -39,14 +39,14 @@ int main() {
     std::vector<float> F12(9 * npairs, 0.5f), sigma2 = {1.0f, 1.44f, 2.0736f};
     F12.back() = 7.0f;
     std::vector<int32_t> q2t((size_t)npairs * cap, -7), t2q(q2t), best(q2t), second(q2t), nm(npairs, -7);
-    const TriPairs P{pair.data(), npairs, qvalid.data(), cap, claimed.data(), F12.data(), 0, 0};
+    const RowPairs P{pair.data(), npairs, qvalid.data(), cap, claimed.data(), F12.data(), 0, 0};
     const BowStore S{kps.data(), desc, nt.data(), fv_node.data(), fv_off.data(), fv_feat.data(), nfv.data(), nrows, cap};
     const BowOut O{q2t.data(), t2q.data(), best.data(), second.data(), nm.data()};
     {
         // orbs_tri_rows_search*: the checks, host form and device form
         for (int dev = 0; dev < 2; dev++) {
             const bool d = dev != 0;
-            auto chk = [&](const orbs_params* q, const TriPairs& p, const BowStore& s, const BowOut& o, const float* s2 = nullptr, int nl = 3) {
+            auto chk = [&](const orbs_params* q, const RowPairs& p, const BowStore& s, const BowOut& o, const float* s2 = nullptr, int nl = 3) {
                 return check_tri_rows(q, p, s, o, s2 ? s2 : sigma2.data(), nl, d, d);
             };
             CHECK(chk(&prm, P, S, O) == ORBX_OK);
@@ -62,10 +62,10 @@ int main() {
             CHECK(chk(&q, P, S, O) == ORBX_OK);
             CHECK(check_tri_rows(&prm, P, S, O, nullptr, 3, d, d) == ORBX_ERR_ARG);
             CHECK(chk(&prm, P, S, O, nullptr, 0) == ORBX_ERR_ARG && chk(&prm, P, S, O, nullptr, ORBS_MAX_LEVELS + 1) == ORBX_ERR_ARG);
-            TriPairs p2 = P;
+            RowPairs p2 = P;
             p2.npairs = -1;
             CHECK(chk(&prm, p2, S, O) == ORBX_ERR_ARG);
-            p2 = TriPairs{nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0};           // no pairs: nothing is looked at
+            p2 = RowPairs{nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0};           // no pairs: nothing is looked at
             CHECK(chk(&prm, p2, BowStore{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1}, BowOut{}) == ORBX_OK);
             p2 = P; p2.pair = nullptr;
             CHECK(chk(&prm, p2, S, O) == ORBX_ERR_ARG);
@@ -110,7 +110,7 @@ int main() {
         s2.desc = desc + 4;
         CHECK(check_tri_rows(&prm, P, s2, O, sigma2.data(), 3, false, false) == ORBX_OK);
         CHECK(check_tri_rows(&prm, P, s2, O, sigma2.data(), 3, false, true) == ORBX_ERR_ARG);
-        TriPairs p2 = P;
+        RowPairs p2 = P;
         p2.F12 = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(F12.data()) + 2);
         CHECK(check_tri_rows(&prm, p2, S, O, sigma2.data(), 3, true, true) == ORBX_ERR_ARG);
         CHECK(check_tri_rows(&prm, p2, S, O, sigma2.data(), 3, false, false) == ORBX_OK);
@@ -126,14 +126,14 @@ int main() {
     }
     {
         // the block of orbs_tri_rows_search with everything in it: slots at multiples of 256, one span up, one down, the records behind
-        const TriRowsBlock B(P, S, O, true);
+        const RowsBlock B(P, S, O, true);
         CHECK(B.pair.off == 0 && B.F12.off == 256 && B.qvalid.off == 512 && B.claimed.off == 768 && B.nt.off == 1024 && B.nfv.off == 1280 && B.kps.off == 1536);
         CHECK(B.desc.off == 1536 + 1024 && B.fv_node.off == 2560 + 1024 && B.fv_off.off == 3584 + 256 && B.fv_feat.off == 3840 + 256);
         const size_t up = B.L.upload();
         CHECK(up == 4096 + 256 && B.nmatches.off == up && B.q2t.off == up + 256 && B.second.off == up + 1024 && B.L.download() == 1280);
         CHECK(B.rec.off == up + 1280 && B.L.total() == up + 1280 + 512 && B.nqv == (size_t)(npairs - 1) * cap + cap);
         std::vector<uint8_t> h(B.L.upload() + B.L.download()), d(B.L.total());
-        const TriRows a = B.stage(h.data(), d.data(), P, S);
+        const BowRows a = B.stage(h.data(), d.data(), P, S);
         CHECK((const uint8_t*)a.P.pair == d.data() && (const uint8_t*)a.P.F12 == d.data() + 256 && a.P.qvalid == d.data() + 512 && a.P.claimed == d.data() + 768);
         CHECK(a.P.npairs == npairs && a.P.qstride == cap && (const uint8_t*)a.S.nt == d.data() + 1024 && (const uint8_t*)a.S.kps == d.data() + 1536);
         CHECK(a.S.desc == d.data() + 2560 && (const uint8_t*)a.S.fv_feat == d.data() + 4096 && a.S.nrows == nrows && a.S.cap == cap);
@@ -146,13 +146,13 @@ int main() {
         B.unpack(h.data(), BowOut{q2t.data(), nullptr, best.data(), nullptr, nm.data()});
         CHECK(q2t[0] == 100 && q2t[npairs * cap - 1] == 100 + npairs * cap - 1 && best[3] == 203 && t2q[0] == -7 && second[0] == -7 && nm[2] == 12);
         // one qvalid array for all pairs takes cap bytes; resident rows and absent arrays take no room
-        TriPairs p2 = P;
+        RowPairs p2 = P;
         p2.qstride = 0; p2.claimed = nullptr;
-        const TriRowsBlock C(p2, S, BowOut{nullptr, t2q.data(), nullptr, nullptr, nm.data()}, false);
+        const RowsBlock C(p2, S, BowOut{nullptr, t2q.data(), nullptr, nullptr, nm.data()}, false);
         CHECK(C.nqv == (size_t)cap && !C.claimed.present && !C.kps.present && !C.desc.present && !C.fv_feat.present && C.nt.present && C.nfv.present);
         CHECK(!C.q2t.present && C.t2q.present && C.L.upload() == 1280 && C.L.download() == 512 && C.L.total() == 1280 + 512 + 512);
         std::vector<uint8_t> h2(C.L.upload() + C.L.download()), d2(C.L.total());
-        const TriRows c = C.stage(h2.data(), d2.data(), p2, S);
+        const BowRows c = C.stage(h2.data(), d2.data(), p2, S);
         CHECK(!c.P.claimed && c.S.kps == kps.data() && c.S.desc == desc && c.S.fv_off == fv_off.data() && !c.O.q2t && (uint8_t*)c.O.t2q == d2.data() + 1280 + 256);
     }
     {
@@ -172,13 +172,13 @@ int main() {
         std::vector<float> x3d((size_t)npairs * cap * 3), v_store((size_t)npairs * cap * 4 + 4), ax((size_t)npairs * ocap * 3);
         float* v = v_store.data() + ((16 - ((uintptr_t)v_store.data() & 15)) & 15) / 4;
         std::vector<int32_t> m12((size_t)npairs * cap), ai((size_t)npairs * ocap * 2), count(npairs), overflow(npairs);
-        TriPairs Q = P;
+        RowPairs Q = P;
         Q.qstride = 0;
         const BowOut QO{q2t.data(), t2q.data(), nullptr, nullptr, nm.data()};
         const NewPointsOut N{status.data(), x3d.data(), v, m12.data(), ai.data(), ax.data(), count.data(), overflow.data(), ocap};
         for (int dev = 0; dev < 2; dev++) {
             const bool d = dev != 0;
-            auto chk = [&](const TriPairs& p, const BowOut& o, const NewPointsOut& n, const orbs_params* q = nullptr) {
+            auto chk = [&](const RowPairs& p, const BowOut& o, const NewPointsOut& n, const orbs_params* q = nullptr) {
                 return check_new_points(q ? q : &prm, p.pair, npairs, poses.data(), p, S, o, n, fac.data(), sigma2.data(), fac.data(), sigma2.data(), 3, d, d);
             };
             CHECK(chk(Q, QO, N) == ORBX_OK);
@@ -191,7 +191,7 @@ int main() {
             CHECK(check_new_points(&prm, Q.pair, npairs, poses.data(), Q, S, QO, N, fac.data(), sigma2.data(), fac.data(), nullptr, 3, d, d) == ORBX_ERR_ARG);
             CHECK(check_new_points(&prm, Q.pair, npairs, poses.data(), Q, S, QO, N, fac.data(), sigma2.data(), fac.data(), sigma2.data(), 17, d, d) == ORBX_ERR_ARG);
             CHECK(check_new_points(&prm, Q.pair, npairs, nullptr, Q, S, QO, N, fac.data(), sigma2.data(), fac.data(), sigma2.data(), 3, d, d) == ORBX_ERR_ARG);
-            TriPairs p2 = Q;
+            RowPairs p2 = Q;
             p2.qstride = cap;                                                       // the pairs share one flag array
             CHECK(chk(p2, QO, N) == ORBX_ERR_ARG);
             p2 = Q; p2.qvalid = nullptr;

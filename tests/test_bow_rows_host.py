@@ -1,6 +1,6 @@
 """The host side of orbs_bow_rows_search* without a GPU: the new names of include/orbs.h in orb_slam_amd.capi, the entry points' refusals before
 anything touches a GPU, and tests/_probe/bow_rows_host.cpp: the argument checks, the block's layout, staging and unpacking
-(orb_slam_amd/csrc/orbs_bow_rows.h) and the FeatureVector packing of the drop-in (orb_slam_amd/cpp/FeatureVectorCSR.h) against the stand-in HIP
+(orb_slam_amd/csrc/orbs_rows.h) and the FeatureVector packing of the drop-in (orb_slam_amd/cpp/FeatureVectorCSR.h) against the stand-in HIP
 runtime of tests/_probe/hip_stub under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program."""
 import ctypes
 import os

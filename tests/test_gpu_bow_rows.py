@@ -129,6 +129,53 @@ def test_one_large_node():
     assert check_against_oracle(S, pairs, TH_LOW - 1, 1.1, False, run_host(S, pairs, TH_LOW - 1, 1.1, False, None, cl), None, cl) > 100
 
 
+def past_4096_scene():
+    """one node on both sides (cap 4224): a train run of 4096 + 65 entries (claim chunks 0..65, the second mask word, the last chunk partial)
+    against 70 queries (a second pass of 64).  The train descriptors are random (near distance 128); planted partners are copies of a query with
+    5 to 20 bits flipped: queries 0..19 have theirs below 4096, queries 20..59 at the list positions 4096..4160.  Query 60 is query 20 but for two
+    bits, so it wants 20's partner, finds it claimed and takes its own, farther one beyond 4096; query 61 wants 21's in the same way and has no
+    other.  The partners of queries 30..33 are claimed on entry.  List position == feature here (bs.make_row lists a node ascending).
+    -> (rows, cap, claimed[1, cap])"""
+    rng = np.random.default_rng(11)
+    T, Q, cap = 4096 + 65, 70, 4224
+    q = rng.integers(0, 256, (Q, 32)).astype(np.uint8)
+    t = rng.integers(0, 256, (T, 32)).astype(np.uint8)
+    near = lambda d, n=None: bs.flip(d, rng.choice(256, int(rng.integers(5, 21)) if n is None else n, replace=False))
+    low, high = rng.choice(4096, 20, replace=False), 4096 + rng.permutation(65)
+    for i in range(20):
+        t[low[i]] = near(q[i])
+    for i in range(20, 60):
+        t[high[i - 20]] = near(q[i], 6 if i in (20, 21) else None)
+    q[60] = bs.flip(q[20], [3, 200]); t[high[40]] = near(q[60], 18)
+    q[61] = bs.flip(q[21], [5, 100])
+    claimed = np.zeros((1, cap), np.uint8)
+    claimed[0, high[10:14]] = 1
+    rows = [bs.make_row(d, np.zeros(len(d), np.float32), [9] * len(d)) for d in (q, t)]
+    return rows, cap, claimed
+
+
+def test_run_past_4096():
+    """a train run longer than 4096 entries: the claim masks of chunks 64 and 65 live in the second mask word of lanes 0 and 1"""
+    rows, cap, cl = past_4096_scene()
+    q, t = rows
+    # what makes the scene meaningful, on the oracle's own result
+    n, q2t, t2q, _, _ = bs.expect(TH_LOW, 0.75, True, q, t, cap)
+    assert (q2t >= 4096).sum() >= 20 and ((q2t >= 0) & (q2t < 4096)).sum() >= 15
+    first = np.argmin(bs.hamming(q["desc"], t["desc"]), axis=1)          # every query's nearest train entry (the first listed on ties)
+    stolen = [i for i in range(len(first)) if first[i] >= 4096 and 0 <= t2q[first[i]] < i]      # ... taken by a query listed before it
+    assert len(stolen) >= 2 and any(q2t[i] >= 4096 for i in stolen) and any(q2t[i] < 0 for i in stolen)
+    nc, q2c, _, _, _ = bs.expect(TH_LOW - 1, 0.75, False, q, t, cap, None, cl[0])
+    pre = np.nonzero(cl[0])[0]
+    assert len(pre) >= 4 and (pre >= 4096).all() and (q2t[:60] == first[:60]).all() and np.isin(pre, q2t).all() and not np.isin(pre, q2c).any() and nc == n - len(pre)
+    S = Store(rows, cap)
+    host = run_host(S, [(0, 1)], TH_LOW, 0.75, True)
+    assert check_against_oracle(S, [(0, 1)], TH_LOW, 0.75, True, host) == n
+    same(host, run_device(S, [(0, 1)], TH_LOW, 0.75, True))
+    host = run_host(S, [(0, 1)], TH_LOW - 1, 0.75, False, None, cl)
+    assert check_against_oracle(S, [(0, 1)], TH_LOW - 1, 0.75, False, host, None, cl) == nc
+    same(host, run_device(S, [(0, 1)], TH_LOW - 1, 0.75, False, None, cl))
+
+
 def test_merge_walk():
     """disjoint node sets, interleaved node ids, an empty FeatureVector on either side, nt = 0"""
     rng = np.random.default_rng(3)

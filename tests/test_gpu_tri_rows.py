@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import bow_rows_scenes as bs
+import kf_pairs
 import tri_rows_scenes as ts
 from orb_slam_amd import capi
 from tri_rows_scenes import Store, dev
@@ -123,6 +124,72 @@ def test_one_large_node():
     assert check_against_oracle(S, [(0, 1)], F_ROWS, TH_LOW, True, run_host(S, [(0, 1)], F_ROWS, TH_LOW, True)) > 30
     cl = (rng.random((1, 256)) < 0.3).astype(np.uint8)
     assert check_against_oracle(S, [(0, 1)], F_ROWS, 40, False, run_host(S, [(0, 1)], F_ROWS, 40, False, None, cl), None, cl) > 10
+
+
+def past_4096_scene():
+    """one node on both sides (cap 4224), both lists in random feature order: a train run of 4096 + 65 entries (claim chunks 0..65, the second
+    mask word, the last chunk partial) against 70 queries (a second pass of 64).  The train descriptors are random (near distance 128) at random
+    places; planted partners are copies of a query with 5 to 20 bits flipped ON the query's epipolar line: the queries at list positions 0..19
+    have theirs at train list positions below 4096, those at 20..59 at 4096..4160.  Query 60 is query 20 but for two bits at the same place, so
+    it wants 20's partner, finds it claimed and takes its own, farther one beyond 4096; query 61 wants 21's in the same way and has no other;
+    query 62's partner lies OFF its line.  The partners of queries 30..33 are claimed on entry.
+    -> (rows, cap, F12[9], claimed[1, cap], query feature per list position, train list position per feature)"""
+    rng = np.random.default_rng(12)
+    T, Q, cap = 4096 + 65, 70, 4224
+    F = kf_pairs.fundamental(29)
+    qd = rng.integers(0, 256, (Q, 32)).astype(np.uint8)
+    td = rng.integers(0, 256, (T, 32)).astype(np.uint8)
+    kq = ts.keypoints((rng.random(Q) * 640).astype(np.float32), (rng.random(Q) * 480).astype(np.float32), np.zeros(Q, np.float32), rng.integers(0, 8, Q))
+    kt = ts.keypoints((rng.random(T) * 640).astype(np.float32), (rng.random(T) * 480).astype(np.float32), np.zeros(T, np.float32), rng.integers(0, 8, T))
+    fvq, fvt = ts.fv_shuffled(np.full(Q, 9), rng), ts.fv_shuffled(np.full(T, 9), rng)
+    ql, tl = fvq[2].astype(np.int64), fvt[2].astype(np.int64)
+    low, high = rng.choice(4096, 20, replace=False), 4096 + rng.permutation(65)
+
+    def plant(k, pos, nbits=None, across=None):
+        """the train entry at list position `pos` becomes a partner of the query at list position k"""
+        i, f = ql[k], tl[pos]
+        td[f] = bs.flip(qd[i], rng.choice(256, int(rng.integers(5, 21)) if nbits is None else nbits, replace=False))
+        x, y = ts.on_line_point(F, float(kq["x"][i]), float(kq["y"][i]), rng, int(kt["octave"][f]), float(rng.uniform(-1, 1)) if across is None else across)
+        kt["x"][f], kt["y"][f] = x, y
+
+    for k in range(20):
+        plant(k, low[k])
+    for k in range(20, 60):
+        plant(k, high[k - 20], 6 if k in (20, 21) else None)
+    for k, src in ((60, 20), (61, 21)):
+        qd[ql[k]] = bs.flip(qd[ql[src]], [3, 200])
+        kq["x"][ql[k]], kq["y"][ql[k]] = kq["x"][ql[src]], kq["y"][ql[src]]
+    plant(60, high[40], 18)
+    plant(62, high[41], 10, across=12.0)
+    claimed = np.zeros((1, cap), np.uint8)
+    claimed[0, tl[high[10:14]]] = 1
+    return [ts.make_row(kq, qd, fvq), ts.make_row(kt, td, fvt)], cap, F.reshape(9).copy(), claimed, ql, np.argsort(tl)
+
+
+def test_run_past_4096():
+    """a train run longer than 4096 entries: the claim masks of chunks 64 and 65 live in the second mask word of lanes 0 and 1"""
+    rows, cap, F, cl, ql, tpos = past_4096_scene()
+    q, t = rows
+    ones, none = np.ones(cap, np.uint8), np.zeros(cap, np.uint8)
+    # what makes the scene meaningful, on the oracle's own result
+    n, q2t, t2q, best, second = ts.expect(TH_LOW, True, F, SIG, q, t, cap, ones, none)
+    assert (tpos[q2t[q2t >= 0]] >= 4096).sum() >= 20 and (tpos[q2t[q2t >= 0]] < 4096).sum() >= 15
+    first = np.argmin(bs.hamming(q["desc"], t["desc"]), axis=1)          # every query's nearest train feature (the lowest index on ties)
+    qpos = np.argsort(ql)
+    stolen = [i for i in ql if tpos[first[i]] >= 4096 and t2q[first[i]] >= 0 and qpos[t2q[first[i]]] < qpos[i]]      # ... taken by a query listed before it
+    assert len(stolen) >= 2 and any(q2t[i] >= 0 and tpos[q2t[i]] >= 4096 for i in stolen) and any(q2t[i] < 0 for i in stolen)
+    off = ql[62]                                                         # the partner off the line: BestDist is its distance, nothing is taken
+    assert best[off] == 10 and q2t[off] == -1 and second[off] == INT_MAX and tpos[first[off]] >= 4096
+    nc, q2c, _, _, _ = ts.expect(TH_LOW, False, F, SIG, q, t, cap, ones, cl[0])
+    pre = np.nonzero(cl[0])[0]
+    assert len(pre) >= 4 and (tpos[pre] >= 4096).all() and np.isin(pre, q2t).all() and not np.isin(pre, q2c).any() and nc == n - len(pre)
+    S = Store(rows, cap)
+    host = run_host(S, [(0, 1)], F, TH_LOW, True)
+    assert check_against_oracle(S, [(0, 1)], F, TH_LOW, True, host) == n
+    same(host, run_device(S, [(0, 1)], F, TH_LOW, True))
+    host = run_host(S, [(0, 1)], F, TH_LOW, False, None, cl)
+    assert check_against_oracle(S, [(0, 1)], F, TH_LOW, False, host, None, cl) == nc
+    same(host, run_device(S, [(0, 1)], F, TH_LOW, False, None, cl))
 
 
 def test_merge_walk():

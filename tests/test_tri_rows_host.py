@@ -1,6 +1,6 @@
 """The host side of orbs_tri_rows_search* and orbt_new_points_rows* without a GPU: the new names of include/orbs.h and include/orbt.h in
 orb_slam_amd.capi, the entry points' refusals before anything touches a GPU, and tests/_probe/tri_rows_host.cpp: the argument checks, the two
-blocks' layouts, staging and unpacking (orb_slam_amd/csrc/orbs_tri_rows.h) and the flag and F12 packing of the drop-in
+blocks' layouts, staging and unpacking (orb_slam_amd/csrc/orbs_rows.h) and the flag and F12 packing of the drop-in
 (orb_slam_amd/cpp/NewPointsPacking.h) against the stand-in HIP runtime of tests/_probe/hip_stub under AddressSanitizer +
 UndefinedBehaviorSanitizer, as a stand-alone program."""
 import ctypes
