@@ -37,6 +37,13 @@
  *                                   src/ORBmatcher.cc:1267-1505, for every candidate whose RANSAC converged in LoopClosing::ComputeSim3
  *                                   (src/LoopClosing.cc: `matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)`; ORBP_MODE_SIM3):
  *                                   both directions of every pair in one launch, the agreement (:1486-1502) in a second
+ *   orbp_local_votes[_batch_device]
+ *                                <- the counting of void Tracking::UpdateReferenceKeyFrames()      src/Tracking.cc:768-783
+ *                                   and of void KeyFrame::UpdateConnections()                     src/KeyFrame.cc:334-363
+ *   orbp_local_points[_batch_device]
+ *                                <- void Tracking::UpdateReferencePoints()                         src/Tracking.cc:738-761
+ *                                   and the stamps of Tracking::SearchReferencePointsInFrustum's first loop   src/Tracking.cc:678-694
+ *   orbp_rows_purge_device       <- what MapPoint::SetBadFlag / KeyFrame::EraseMapPointMatch do to mvpMapPoints, for the resident columns
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -543,6 +550,67 @@ int orbp_sim3_search(orbp_map* map, const orbp_sim3_dir* dirs, int npairs, const
                      int lcap, const uint8_t* skip, const int32_t* frame, const orbx_keypoint* kps_un, const uint8_t* desc, const int32_t* cell_off,
                      const int32_t* cell_feat, const int32_t* nt, int nframes, int cap, int frames_on_device, const orbf_bounds* b, int orb_dist,
                      int32_t* best_idx, int32_t* best_dist, orbp_fused* rec, int32_t* match12, int32_t* nfound, void* stream);
+
+/* ---- The local map: key-frame votes and the local point list, over a map-point COLUMN of the resident key-frame rows.
+ *
+ * Row k of the nkf resident key frames (the rows orbs_* and orbt_* read, `cap` features each) has the column d_kf_slot[k*cap + i]: the table
+ * slot of pKF->mvpMapPoints[i], or -1; d_kf_nt[k] (clamped to [0, cap]) is the row's feature count.  Under the reference's map invariant
+ * (pKF->mvpMapPoints[idx] == pMP exactly when pMP->mObservations[pKF] == idx, kept under its map mutex) the column is the transpose of the
+ * observation maps, so "which key frames observe this point" is a scan over integer columns and no observation list goes up.
+ * PRECONDITION, stated and not checked on the device: a slot occurs at most once per row.  An entry that is -1, out of range or not live in the
+ * table is passed over, never dereferenced.
+ *
+ * orbp_local_votes*: the counting of Tracking::UpdateReferenceKeyFrames (src/Tracking.cc:768-783) and of KeyFrame::UpdateConnections
+ * (src/KeyFrame.cc:334-363).  Query p is the list of slots d_query[p*qcap + j], j < d_nquery[p] (clamped to [0, qcap]); an entry may be -1, out
+ * of range or repeated.  d_votes[p*nkf + k] = the sum, over the features i < d_kf_nt[k] of row k whose slot is live, of the MULTIPLICITY of that
+ * slot in query p: the reference increments once per frame feature, so a frame that holds one point at two features votes twice.  Every word
+ * of d_votes has one writer and is a plain store; the multiplicities are integer atomic adds, so nothing depends on arrival order.
+ *
+ * orbp_local_points*: the list of Tracking::UpdateReferencePoints (src/Tracking.cc:742-760) with the stamps of the first loop of
+ * Tracking::SearchReferencePointsInFrustum (:678-694), in the layout orbp_track_batch_device reads.  Problem p walks the rows
+ * d_rows[p*rcap + j], j < d_nrows[p] (clamped to [0, rcap]), in list order and each row's features in index order; a row outside [0, nkf) is passed
+ * over, never dereferenced.  d_list[p*lcap ..] holds the slots met that are >= 0, in range and live, each at its FIRST occurrence only, in exactly
+ * that order (so a row listed twice contributes nothing the second time).  d_nlist[p] is always the true count; beyond lcap only the first lcap
+ * entries are written and d_overflow[p] = 1 (else 0): clamp d_nlist before it is used as a count (orbp_track_batch_device does).
+ * d_skip[p*lcap + i] = 1 when the slot's multiplicity in query p is > 0 (the point the frame holds already: mnLastFrameSeen == mnId), else 0;
+ * d_query == NULL: no query, every flag 0.  The call is self-contained: it takes the query list itself and leaves nothing behind.
+ * The first occurrence is decided by an integer atomicMin of the walk position j*cap + i per slot, and the order is restored by counting (tile
+ * counts, their sum in front of a tile, scatter), as orbp_loop_project_batch_device does: launch boundaries are the only ordering.
+ *
+ * orbp_rows_purge_device: sets every column entry (all nkf*cap of them) that names one of the n slots (HOST array, as orbp_erase takes them) to
+ * -1, in one scan.  Run it before orbp_erase whenever slots die while a column is resident: a freed and re-assigned slot would otherwise alias
+ * stale column entries.
+ *
+ * The handle owns the scratch: two words per (problem, slot) and one per (problem, listed row, 256-feature tile), grown on the first call of a
+ * size (synchronously, after a wait for the chain) and kept.  The kernels put back every word they changed, so resetting the scratch needs
+ * no host synchronisation and costs what the call itself touched, not the capacity.  nproblems <= ORBP_LOCAL_MAX_PROBLEMS, rcap <= ORBP_LOCAL_MAX_ROWS.
+ *
+ * ORBX_ERR_ARG before anything touches the GPU, with nothing changed, for a NULL handle, nproblems outside [0, ORBP_LOCAL_MAX_PROBLEMS], a negative
+ * nkf or n, cap < 1, nkf * cap >= 2^31, qcap < 1 (lcap < 1, rcap outside [1, ORBP_LOCAL_MAX_ROWS], rcap * cap >= 2^31, nproblems * lcap >= 2^31), a
+ * NULL required array, an array that is not 4-byte aligned (d_skip needs none), a purged slot out of range.  The batch-device forms are
+ * asynchronous on `stream` (NULL: the map's own), inside the handle's event chain, and allocate nothing in the steady state. */
+#define ORBP_LOCAL_MAX_PROBLEMS 64
+#define ORBP_LOCAL_MAX_ROWS     65535
+
+int orbp_local_votes_batch_device(orbp_map* map, const int32_t* d_query, const int32_t* d_nquery, int qcap, int nproblems, const int32_t* d_kf_slot,
+                                  const int32_t* d_kf_nt, int nkf, int cap, int32_t* d_votes, void* stream);
+
+/* The same with HOST arrays in and out, synchronous: one pinned block up and one down.  query, nquery and votes (nproblems * nkf) are host
+ * memory; the columns (kf_slot, kf_nt) are host memory, or device memory when kf_on_device != 0 (the resident form: only the query goes up). */
+int orbp_local_votes(orbp_map* map, const int32_t* query, const int32_t* nquery, int qcap, int nproblems, const int32_t* kf_slot, const int32_t* kf_nt,
+                     int kf_on_device, int nkf, int cap, int32_t* votes, void* stream);
+
+int orbp_local_points_batch_device(orbp_map* map, const int32_t* d_query, const int32_t* d_nquery, int qcap, int nproblems, const int32_t* d_rows,
+                                   const int32_t* d_nrows, int rcap, const int32_t* d_kf_slot, const int32_t* d_kf_nt, int nkf, int cap, int32_t* d_list,
+                                   int32_t* d_nlist, uint8_t* d_skip, int32_t* d_overflow, int lcap, void* stream);
+
+/* The same with HOST arrays in and out, synchronous.  query (may be NULL), nquery, rows, nrows, list and skip (nproblems * lcap each; of problem p
+ * the first min(nlist[p], lcap) entries are written), nlist and overflow (nproblems; overflow may be NULL) are host memory; the columns as above. */
+int orbp_local_points(orbp_map* map, const int32_t* query, const int32_t* nquery, int qcap, int nproblems, const int32_t* rows, const int32_t* nrows,
+                      int rcap, const int32_t* kf_slot, const int32_t* kf_nt, int kf_on_device, int nkf, int cap, int32_t* list, int32_t* nlist,
+                      uint8_t* skip, int32_t* overflow, int lcap, void* stream);
+
+int orbp_rows_purge_device(orbp_map* map, const int32_t* slots, int n, int32_t* d_kf_slot, int nkf, int cap, void* stream);
 
 #ifdef __cplusplus
 }

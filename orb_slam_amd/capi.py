@@ -59,7 +59,9 @@ EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_
              "orbp_project_batch_device", "orbp_track_batch_device", "orbp_track", "orbp_project_source_batch_device",
              "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh", "orbp_fuse_batch_device",
              "orbp_fuse", "orbp_view_from_sim3", "orbp_loop_project_batch_device", "orbp_loop_search_batch_device", "orbp_loop_search",
-             "orbp_sim3_from_pair", "orbp_sim3_search_batch_device", "orbp_sim3_search"]
+             "orbp_sim3_from_pair", "orbp_sim3_search_batch_device", "orbp_sim3_search", "orbp_local_votes_batch_device", "orbp_local_votes",
+             "orbp_local_points_batch_device", "orbp_local_points", "orbp_rows_purge_device"]
+LOCAL_MAX_PROBLEMS, LOCAL_MAX_ROWS = 64, 65535      # ORBP_LOCAL_MAX_PROBLEMS, ORBP_LOCAL_MAX_ROWS
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate", "orbt_new_points_rows_device", "orbt_new_points_rows"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
@@ -347,6 +349,11 @@ def lib():
         L.orbp_loop_project_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_loop_search_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
         L.orbp_loop_search.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), vp]
+        L.orbp_local_votes_batch_device.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp]
+        L.orbp_local_votes.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, vp, vp]
+        L.orbp_local_points_batch_device.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]
+        L.orbp_local_points.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp]
+        L.orbp_rows_purge_device.argtypes = [vp, vp, ci, vp, ci, ci, vp]
         L.orbp_project_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_track_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
                                                      vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
@@ -1570,6 +1577,83 @@ class MapPointTable:
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_sim3_search")
         return dict(match12=match12, nfound=nfound[:npairs], best_idx=best_idx, best_dist=best_dist, rec=rec)
+
+    def local_votes_batch_device(self, d_query, d_nquery, qcap, nproblems, d_kf_slot, d_kf_nt, nkf, cap, d_votes, stream=0):
+        """The votes of Tracking::UpdateReferenceKeyFrames / KeyFrame::UpdateConnections for nproblems queries over the map-point column of nkf
+        resident rows, asynchronous: d_votes[p*nkf + k].  Device pointers as ints."""
+        rc = lib().orbp_local_votes_batch_device(self.h, d_query or None, d_nquery or None, qcap, nproblems, d_kf_slot or None, d_kf_nt or None, nkf, cap,
+                                                 d_votes or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_local_votes_batch_device")
+
+    @staticmethod
+    def _columns(kf_slot, kf_nt, nkf, cap):
+        """the columns as host arrays (nkf, cap) / (nkf), or device pointers as ints (nkf and cap must then be given)"""
+        on_dev = isinstance(kf_slot, int)
+        if not on_dev:
+            kf_slot = np.ascontiguousarray(kf_slot, dtype=np.int32)
+            assert kf_slot.ndim == 2
+            nkf, cap = kf_slot.shape
+            kf_nt = np.ascontiguousarray(kf_nt, dtype=np.int32).reshape(nkf)
+        return kf_slot, kf_nt, nkf, cap, on_dev
+
+    @staticmethod
+    def _padded(lists, width=None):
+        """a sequence of int sequences (or a 2-D array with its counts) as (array (n, width), counts (n))"""
+        n = np.array([len(q) for q in lists], np.int32)
+        width = width or max(1, int(n.max()) if len(n) else 1)
+        out = np.full((len(lists), width), -1, np.int32)
+        for p, q in enumerate(lists):
+            out[p, :len(q)] = q
+        return out, n
+
+    def local_votes(self, queries, kf_slot, kf_nt, nkf=None, cap=None):
+        """The same with host arrays, synchronous: queries is a sequence of slot sequences -> votes i32[nproblems, nkf]."""
+        query, nquery = self._padded(queries)
+        kf_slot, kf_nt, nkf, cap, on_dev = self._columns(kf_slot, kf_nt, nkf, cap)
+        votes = np.zeros((len(nquery), nkf), np.int32)
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        rc = lib().orbp_local_votes(self.h, ptr(query), ptr(nquery), query.shape[1], len(nquery), ptr(kf_slot), ptr(kf_nt), 1 if on_dev else 0, nkf, cap,
+                                    ptr(votes), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_local_votes")
+        return votes
+
+    def local_points_batch_device(self, d_query, d_nquery, qcap, nproblems, d_rows, d_nrows, rcap, d_kf_slot, d_kf_nt, nkf, cap, d_list, d_nlist, d_skip,
+                                  d_overflow, lcap, stream=0):
+        """The list of Tracking::UpdateReferencePoints with the skip flags of SearchReferencePointsInFrustum's first loop, asynchronous, in the
+        layout track_batch_device reads.  Device pointers as ints (d_query 0: no query, every flag 0)."""
+        rc = lib().orbp_local_points_batch_device(self.h, d_query or None, d_nquery or None, qcap, nproblems, d_rows or None, d_nrows or None, rcap,
+                                                  d_kf_slot or None, d_kf_nt or None, nkf, cap, d_list or None, d_nlist or None, d_skip or None,
+                                                  d_overflow or None, lcap, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_local_points_batch_device")
+
+    def local_points(self, queries, rows, kf_slot, kf_nt, lcap, nkf=None, cap=None):
+        """The same with host arrays, synchronous: queries (or None) and rows are sequences of sequences, one per problem
+        -> (list i32[nproblems, lcap], nlist i32[nproblems], skip u8[nproblems, lcap], overflow i32[nproblems]); entries behind a list are -1 / 0."""
+        rws, nrows = self._padded(rows)
+        npr = len(nrows)
+        query, nquery = self._padded(queries) if queries is not None else (None, None)
+        assert query is None or len(nquery) == npr
+        kf_slot, kf_nt, nkf, cap, on_dev = self._columns(kf_slot, kf_nt, nkf, cap)
+        lst = np.full((npr, lcap), -1, np.int32)
+        skip = np.zeros((npr, lcap), np.uint8)
+        nlist = np.zeros(npr, np.int32)
+        overflow = np.zeros(npr, np.int32)
+        ptr = lambda a: (a or None) if isinstance(a, int) else (a.ctypes.data if a is not None else None)
+        rc = lib().orbp_local_points(self.h, ptr(query), ptr(nquery), query.shape[1] if query is not None else 1, npr, ptr(rws), ptr(nrows), rws.shape[1],
+                                     ptr(kf_slot), ptr(kf_nt), 1 if on_dev else 0, nkf, cap, ptr(lst), ptr(nlist), ptr(skip), ptr(overflow), lcap, None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_local_points")
+        return lst, nlist, skip, overflow
+
+    def rows_purge_device(self, slots, d_kf_slot, nkf, cap, stream=0):
+        """every entry of the device column d_kf_slot[nkf*cap] that names one of `slots` (host array) becomes -1; asynchronous"""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        rc = lib().orbp_rows_purge_device(self.h, slots.ctypes.data, len(slots), d_kf_slot or None, nkf, cap, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_rows_purge_device")
 
     def project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
                              d_overflow, qcap, stream=0):

@@ -41,6 +41,9 @@ LocalMapPoints::~LocalMapPoints() {
     if (d_kf_fv_node_) orbx_device_free(device_, d_kf_fv_node_);
     if (d_kf_fv_off_) orbx_device_free(device_, d_kf_fv_off_);
     if (d_kf_fv_feat_) orbx_device_free(device_, d_kf_fv_feat_);
+    if (d_kf_slot_) orbx_device_free(device_, d_kf_slot_);
+    if (d_kf_col_nt_) orbx_device_free(device_, d_kf_col_nt_);
+    if (d_local_) orbx_device_free(device_, d_local_);
 }
 
 void LocalMapPoints::grow() {
@@ -56,7 +59,9 @@ void LocalMapPoints::grow() {
     pos_.resize((size_t)capacity_ * 3, 0.f); nrm_.resize((size_t)capacity_ * 3, 0.f);
     dmin_.resize(capacity_, 0.f); dmax_.resize(capacity_, 0.f); desc_.resize((size_t)capacity_ * 32, 0);
     for (int s = capacity_ - 1; s >= old; s--) free_.push_back(s);
-    // the new table is empty: every owned slot goes up again from the host copy, nothing is left to erase
+    // the new table is empty: every owned slot goes up again from the host copy, nothing is left to erase (the resident columns still forget
+    // the slots that died)
+    purgeColumns();
     dead_list_.clear();
     for (int s = 0; s < old; s++)
         if (owner_[s] && !dirty_[s]) { dirty_[s] = 1; dirty_list_.push_back(s); }
@@ -104,8 +109,18 @@ void LocalMapPoints::Forget(MapPoint* pMP) {
     if (!dead_[slot]) { dead_[slot] = 1; dead_list_.push_back(slot); }
 }
 
+// The key frames' columns (LocalMapPointsLocalMap.cc) must not name a slot that died: freed and assigned again, it would alias the stale entries.
+// Every slot of dead_list_ goes, also one that has an owner again: the columns that name the new owner are uploaded after this.
+void LocalMapPoints::purgeColumns() {
+    if (!d_kf_slot_ || dead_list_.empty()) return;
+    int rc = orbp_rows_purge_device(map_, dead_list_.data(), (int)dead_list_.size(), static_cast<int32_t*>(d_kf_slot_), col_rows_, col_cap_, nullptr);
+    if (rc == ORBX_OK) rc = orbx_stream_synchronize(device_, nullptr);
+    if (rc != ORBX_OK) fail("orbp_rows_purge_device", rc);
+}
+
 // one orbp_erase and one orbp_put for everything that changed since the last search
 void LocalMapPoints::flush() {
+    purgeColumns();
     std::vector<int32_t> gone;
     for (size_t i = 0; i < dead_list_.size(); i++) {
         const int s = dead_list_[i];

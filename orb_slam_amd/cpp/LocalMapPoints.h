@@ -25,10 +25,15 @@
 // orbs_bow_rows_search.
 // CreateNewMapPoints (LocalMapPointsNewPoints.cc) replaces ORBmatcher::SearchForTriangulation and the match loop behind it for every neighbour of
 // LocalMapping::CreateNewMapPoints: one stream-ordered chain search -> triangulate per neighbour over the same rows, one call, one synchronisation.
+// PutKeyFrame / UpdateReferenceKeyFrames / SearchLocalMap / ConnectionWeights (LocalMapPointsLocalMap.cc) replace the three host walks in front of
+// Tracking's local-map search (UpdateReferenceKeyFrames, UpdateReferencePoints, the list building of SearchReferencePointsInFrustum) and the counting
+// half of KeyFrame::UpdateConnections: every row of the key-frame store gains a map-point column, the votes are a scan over those columns, and the
+// local point list is built on the device and handed to the search without visiting the host.
 // Not thread safe: call it from the tracking thread, or guard it with the lock that guards the map.
 // There is no CPU fallback: without a usable GPU the constructor throws std::runtime_error, as does a failing search.
 #pragma once
 #include <cstdint>
+#include <map>
 #include <set>
 #include <unordered_map>
 #include <utility>
@@ -157,13 +162,74 @@ public:
     void CreateNewMapPoints(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpNeighKFs, const std::vector<cv::Mat>& vF12,
                             std::vector<std::vector<NewMapPoint> >& vvNew, bool checkOrientation = false);
 
+    // ---- The local map of Tracking (LocalMapPointsLocalMap.cc; links only when that file and LocalMapPointsRefresh.cc are built in): the three host
+    // object-graph walks in front of the local-map search, over a map-point COLUMN per resident key-frame row (include/orbp.h: orbp_local_*).
+    // CONTRACT.  Results equal the reference's when the map invariant holds (pKF->mvpMapPoints[idx] == pMP exactly when
+    // pMP->mObservations[pKF] == idx, which the reference keeps under its map mutex), bad points have been Forgotten, and every key frame of the
+    // map has been Put (PutKeyFrame).  A key frame never Put receives no votes and lists no points.
+    //
+    // Mirrors pKF->GetMapPointMatches() as the column of pKF's row: points not yet mirrored are Put on the way, NULL or bad points become -1.  Only
+    // host state changes here; the column is built and uploaded at the start of the next local-map call.  Column residency is independent of
+    // feature, grid and FeatureVector residency; ForgetKeyFrame drops the column too.  Fuse, FuseInNeighbors, SearchAndFuse and
+    // CreateNewMapPoints mark the key frames they change themselves; re-Put a key frame whose mvpMapPoints changed elsewhere (INTEGRATION.md lists
+    // the places).
+    void PutKeyFrame(KeyFrame* pKF);
+    // void Tracking::UpdateReferenceKeyFrames() (src/Tracking.cc:764-839) in full, for the frame F: bad points of F.mvpMapPoints are nulled and the
+    // slot list is built on the host (a loop over the frame's features only), the votes come from the GPU (one int per row down), and the walk in
+    // std::map<KeyFrame*,int> order (pointer order), the bad-key-frame test, the first-maximum rule and the neighbour extension with its `> 80` test at
+    // the top of each iteration stay on the host.  KeyFrame::mnTrackReferenceForFrame is written as the reference writes it; vpLocalKeyFrames and
+    // pReferenceKF are Tracking's mvpLocalKeyFrames and mpReferenceKF.
+    void UpdateReferenceKeyFrames(Frame& F, std::vector<KeyFrame*>& vpLocalKeyFrames, KeyFrame*& pReferenceKF);
+    // void Tracking::UpdateReferencePoints() (:738-761) followed by void Tracking::SearchReferencePointsInFrustum() (:675-726).  The first loop over the
+    // frame's own points (:678-694) runs on the host; then orbp_local_points_batch_device feeds orbp_track_batch_device on one stream, the list
+    // never visits the host on the way, and the list and the records come down once.  The mTrack* write-back, IncreaseVisible() and F.mvpMapPoints
+    // are handled as in SearchReferencePointsInFrustum above; returns SearchByProjection's return value (0 when nothing is to match), *nToMatch as
+    // there, *vpLocalMapPoints (may be NULL) Tracking's mvpLocalMapPoints.
+    // DELIBERATE DEVIATION: MapPoint::mnTrackReferenceForFrame is NOT written.  Nothing but :752 / :757 reads it in the reference, and writing it
+    // would reintroduce the per-point walk this call removes.  With F.mnId == 0 the reference lists nothing (the field's initial value is 0, so
+    // :752 passes every point over); so does this.
+    int SearchLocalMap(Frame& F, const std::vector<KeyFrame*>& vpLocalKeyFrames, float th, std::vector<MapPoint*>* vpLocalMapPoints = 0, int* nToMatch = 0);
+    // The counting half of void KeyFrame::UpdateConnections() (src/KeyFrame.cc:334-363): KFcounter as the reference leaves it at :363, the query being
+    // the key frame's own column.  The key frame with mnId == pKF->mnId is left out, a key frame with count 0 is absent.  The caller's
+    // UpdateConnections continues from :365.
+    void ConnectionWeights(KeyFrame* pKF, std::map<KeyFrame*, int>& KFcounter);
+    // The same for several key frames (LocalMapping after SearchInNeighbors, LoopClosing::CorrectLoop for a covisibility group): one votes launch
+    // per ORBP_LOCAL_MAX_PROBLEMS key frames.
+    void ConnectionWeights(const std::vector<KeyFrame*>& vpKFs, std::vector<std::map<KeyFrame*, int> >& vKFcounter);
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
 private:
+    // the columns (LocalMapPointsLocalMap.cc): builds and uploads what PutKeyFrame / ForgetKeyFrame left pending, around flush()
+    void syncColumns();
+    // the slots of pKF->GetMapPointMatches(): -1 for NULL or bad, Put on the way
+    void columnOf(KeyFrame* pKF, std::vector<int32_t>& col);
+    void votesFor(const std::vector<int32_t>& query, const std::vector<int32_t>& nquery, int qcap, std::vector<int32_t>& votes);
+    // mvpMapPoints of these key frames changed (or is about to, in the caller's hands): the column of each that was Put is read from the key frame
+    // again at the next local-map call.  Inline, so that the files that call it need not link LocalMapPointsLocalMap.cc.
+    void columnsChanged(const std::vector<KeyFrame*>& kfs) {
+        for (std::size_t i = 0; i < kfs.size(); i++) {
+            std::unordered_map<KeyFrame*, int>::const_iterator it = kf_row_.find(kfs[i]);
+            if (it == kf_row_.end() || (std::size_t)it->second >= kf_col_put_.size() || !kf_col_put_[it->second] || kf_col_dirty_[it->second]) continue;
+            kf_col_dirty_[it->second] = 1;
+            col_pending_.push_back(it->second);
+        }
+    }
+    std::vector<uint8_t> kf_col_put_, kf_col_dirty_;   // per row: the key frame was Put; its column (or its absence) is to be uploaded
+    std::vector<int32_t> col_pending_;           // the rows with kf_col_dirty_
+    std::vector<int32_t> kf_col_n_;              // per row: the entries of its column on the device
+    void* d_kf_slot_ = nullptr;                  // [col_rows_][col_cap_]
+    void* d_kf_col_nt_ = nullptr;                // [col_rows_]
+    int col_rows_ = 0, col_cap_ = 0;
+    void* d_local_ = nullptr;                    // the block of one SearchLocalMap call
+    std::size_t local_bytes_ = 0;
+    std::vector<uint8_t> local_h_;               // its host image
+
     // throws std::runtime_error: `what` failed with status rc
     static void fail(const char* what, int rc);
     void flush();
+    void purgeColumns();
     void grow();
     void mirror(int slot, MapPoint* pMP);
     void viewOf(Frame& F, orbp_view& V, orbf_bounds& b);

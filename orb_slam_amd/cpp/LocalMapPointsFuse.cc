@@ -3,6 +3,7 @@
 // translation unit of its own because it names MapPoint::Replace / AddObservation and KeyFrame::AddMapPoint, which a build that only wants the
 // searches need not have; it needs LocalMapPointsRefresh.cc (the key-frame store) built in.
 #include <algorithm>
+#include <map>
 #include <cstring>
 
 #include "LocalMapPoints.h"
@@ -21,7 +22,8 @@ namespace ORB_SLAM {
 namespace {
 // the loop of src/ORBmatcher.cc:1033-1131 over a search that is already done: isBad() and IsInKeyFrame() are read as of NOW, because a
 // Replace or an AddMapPoint of an earlier iteration (or of an earlier key frame's loop) changes them
-int fuseLoop(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const std::vector<int32_t>& best) {
+// touched: the key frames whose mvpMapPoints this changes (Replace rewrites the match in every key frame that observes the replaced point)
+int fuseLoop(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const std::vector<int32_t>& best, std::vector<KeyFrame*>& touched) {
     int nFused = 0;
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPoint* pMP = vpMapPoints[i];
@@ -30,10 +32,15 @@ int fuseLoop(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const std
         if (bestIdx < 0) continue;
         MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
         if (pMPinKF) {
-            if (!pMPinKF->isBad()) pMP->Replace(pMPinKF);
+            if (!pMPinKF->isBad()) {
+                const std::map<KeyFrame*, size_t> obs = pMP->GetObservations();
+                for (std::map<KeyFrame*, size_t>::const_iterator mit = obs.begin(); mit != obs.end(); ++mit) touched.push_back(mit->first);
+                pMP->Replace(pMPinKF);
+            }
         } else {
             pMP->AddObservation(pKF, bestIdx);
             pKF->AddMapPoint(pMP, bestIdx);
+            touched.push_back(pKF);
         }
         nFused++;
     }
@@ -151,7 +158,10 @@ void LocalMapPoints::searchFuse(const std::vector<KeyFrame*>& targets, const std
 int LocalMapPoints::Fuse(KeyFrame* pKF, std::vector<MapPoint*>& vpMapPoints, float th) {
     std::vector<std::vector<int32_t> > best;
     searchFuse(std::vector<KeyFrame*>(1, pKF), std::vector<const std::vector<MapPoint*>*>(1, &vpMapPoints), th, best);
-    return fuseLoop(pKF, vpMapPoints, best[0]);
+    std::vector<KeyFrame*> touched;
+    const int n = fuseLoop(pKF, vpMapPoints, best[0], touched);
+    columnsChanged(touched);
+    return n;
 }
 
 void LocalMapPoints::FuseInNeighbors(KeyFrame* pCurrent, const std::vector<KeyFrame*>& vpTargetKFs, float th, std::vector<int>* nFused) {
@@ -160,10 +170,12 @@ void LocalMapPoints::FuseInNeighbors(KeyFrame* pCurrent, const std::vector<KeyFr
     const std::vector<MapPoint*> vpMapPointMatches = pCurrent->GetMapPointMatches();
     std::vector<std::vector<int32_t> > best;
     searchFuse(vpTargetKFs, std::vector<const std::vector<MapPoint*>*>(vpTargetKFs.size(), &vpMapPointMatches), th, best);
+    std::vector<KeyFrame*> touched;
     for (size_t k = 0; k < vpTargetKFs.size(); k++) {
-        const int n = fuseLoop(vpTargetKFs[k], vpMapPointMatches, best[k]);
+        const int n = fuseLoop(vpTargetKFs[k], vpMapPointMatches, best[k], touched);
         if (nFused) nFused->push_back(n);
     }
+    columnsChanged(touched);
     // :408-428: the targets' points, each once, as they are after the forward pass
     std::vector<MapPoint*> vpFuseCandidates;
     vpFuseCandidates.reserve(vpTargetKFs.size() * vpMapPointMatches.size());

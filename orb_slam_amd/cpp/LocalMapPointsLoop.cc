@@ -3,6 +3,7 @@
 // LocalMapPointsRefresh.cc.  A translation unit of its own because it names KeyFrame::GetMapPoints and MapPoint::Replace, which a build that only
 // wants the tracking searches need not have; it needs LocalMapPointsRefresh.cc (the key-frame store) and LocalMapPointsFuse.cc (searchFuse) built in.
 #include <algorithm>
+#include <map>
 #include <cstring>
 #include <set>
 
@@ -22,7 +23,8 @@ namespace ORB_SLAM {
 namespace {
 // src/ORBmatcher.cc:1152-1261 over a search that is already done: the key frame's points are read as its turn begins, isBad() as of each
 // iteration, because a Replace of an earlier iteration (or of an earlier key frame's turn) changes both
-int loopFuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpPoints, const std::vector<int32_t>& best) {
+// touched: the key frames whose mvpMapPoints this changes
+int loopFuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpPoints, const std::vector<int32_t>& best, std::vector<KeyFrame*>& touched) {
     const std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();
     int nFused = 0;
     for (size_t i = 0; i < vpPoints.size(); i++) {
@@ -32,10 +34,15 @@ int loopFuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpPoints, const std::v
         if (bestIdx < 0) continue;
         MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
         if (pMPinKF) {
-            if (!pMPinKF->isBad()) pMPinKF->Replace(pMP);
+            if (!pMPinKF->isBad()) {
+                const std::map<KeyFrame*, size_t> obs = pMPinKF->GetObservations();
+                for (std::map<KeyFrame*, size_t>::const_iterator mit = obs.begin(); mit != obs.end(); ++mit) touched.push_back(mit->first);
+                pMPinKF->Replace(pMP);
+            }
         } else {
             pMP->AddObservation(pKF, bestIdx);
             pKF->AddMapPoint(pMP, bestIdx);
+            touched.push_back(pKF);
         }
         nFused++;
     }
@@ -90,10 +97,12 @@ void LocalMapPoints::SearchAndFuse(const std::vector<std::pair<KeyFrame*, cv::Ma
     }
     std::vector<std::vector<int32_t> > best;
     searchFuse(targets, std::vector<const std::vector<MapPoint*>*>(targets.size(), &vpLoopMapPoints), th, best, &vScw);
+    std::vector<KeyFrame*> touched;
     for (size_t k = 0; k < targets.size(); k++) {
-        const int n = loopFuse(targets[k], vpLoopMapPoints, best[k]);
+        const int n = loopFuse(targets[k], vpLoopMapPoints, best[k], touched);
         if (nFused) nFused->push_back(n);
     }
+    columnsChanged(touched);
 }
 
 }  // namespace ORB_SLAM

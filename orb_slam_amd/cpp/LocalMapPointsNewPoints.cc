@@ -89,6 +89,9 @@ void LocalMapPoints::CreateNewMapPoints(KeyFrame* pKF1, const std::vector<KeyFra
             for (int i = 0; i < 3; i++) out[k].x3D.at<float>(i) = acc_x3d[3 * e + i];
         }
     }
+    // the caller makes a map point of every accepted pair and adds it to both key frames (src/LocalMapping.cc:355-362): their map-point columns
+    // are read again at the next local-map call, when that has happened
+    columnsChanged(kfs);
 }
 
 }  // namespace ORB_SLAM

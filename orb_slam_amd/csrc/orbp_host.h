@@ -1,7 +1,7 @@
 // The argument groups of the map-point table's entry points (orbp_project.hip), the clauses their argument checks are composed of, and the
 // layouts the synchronous host forms give the one block an orbp_map keeps (orbx::Staged): OneView, the shared form of the one-view calls
 // (orbp_track, orbp_track_source: TrackBlock; orbp_loop_search: LoopBlock), RefreshBlock and FlatBlock (orbp_fuse: FuseBlock; orbp_sim3_search:
-// Sim3Block).  Each layout's stage() goes through
+// Sim3Block), LocalVotesBlock and LocalPointsBlock (orbp_local_votes, orbp_local_points; tests/_probe/local_map_host.cpp).  Each layout's stage() goes through
 // Layout::put: a host array is copied into its slot and named on the device, an absent one is passed through.  Host C++ only:
 // tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp, tests/_probe/fuse_host.cpp, tests/_probe/loop_host.cpp and tests/_probe/sim3_host.cpp hold the checks
 // and the layouts against their sizes without a GPU.
@@ -523,6 +523,138 @@ struct LoopBlock : OneView<orbp_fused> {
         up(cap, lcap, {true, f.skip, f.frame, f.claimed, true, f.t2slot, f.rec});
         down();
         dev.reserve(L, 1, lcap, cap, qcap, true, !f.rec, false);
+    }
+};
+
+// ---- the local map: key-frame votes and the local point list over the rows' map-point column (orbp_local.hip)
+
+constexpr int LOCAL_TILE = 256;                        // features of one workgroup of the point list's kernels
+inline int local_tiles(int cap) { return (cap + LOCAL_TILE - 1) / LOCAL_TILE; }
+
+// the column of the resident key-frame rows: slot[k*cap + i] the table slot of feature i of row k (or -1), nt[k] the row's feature count
+struct Columns { const int32_t* slot; const int32_t* nt; int nkf, cap; };
+// the queries: problem p holds the slots q[p*qcap + j], j < nq[p] (q == NULL: no query)
+struct Query { const int32_t* q; const int32_t* nq; int qcap; };
+// the rows each problem walks, in list order
+struct RowLists { const int32_t* rows; const int32_t* nrows; int rcap; };
+// the point list as orbp_track_batch_device reads it
+struct LocalOut { int32_t* list; int32_t* nlist; uint8_t* skip; int32_t* overflow; int lcap; };
+// The handle's scratch.  mult: the query multiplicity of every (problem, slot), all 0 between calls; first: the least walk position of every
+// (problem, slot), all 0xFFFFFFFF between calls; tile_count: the kept entries of every (problem, listed row, tile).  The kernels put back what
+// they changed.
+struct LocalScratch { uint32_t* mult; uint32_t* first; int32_t* tile_count; };
+// the words of tile_count
+inline size_t local_tile_words(int nproblems, int rcap, int cap) { return (size_t)nproblems * rcap * local_tiles(cap); }
+
+struct LocalVotes { Table T; Query Q; Columns K; LocalScratch S; int32_t* votes; };
+struct LocalPoints { Table T; Query Q; RowLists R; Columns K; LocalScratch S; LocalOut O; };
+// slots: the uploaded slot table; mark: problem 0 of LocalScratch::mult; nent: nkf * cap
+struct RowsPurge { int n; const int32_t* slots; int capacity; uint32_t* mark; int32_t* kf_slot; size_t nent; };
+hipError_t launch_local_votes(const LocalVotes& a, int nproblems, hipStream_t st);
+hipError_t launch_local_points(const LocalPoints& a, int nproblems, hipStream_t st);
+hipError_t launch_rows_purge(const RowsPurge& a, hipStream_t st);
+
+// the sizes of the columns, and of the problems over them
+inline bool columns_ok(int nkf, int cap) { return nkf >= 0 && cap >= 1 && (long long)nkf * cap < (1ll << 31); }
+inline bool local_problems_ok(int nproblems, int qcap) { return nproblems >= 0 && nproblems <= ORBP_LOCAL_MAX_PROBLEMS && qcap >= 1; }
+
+// The arguments of orbp_local_votes* that do not need the handle.  on_device: query and votes are device memory (alignment is checked); kf_device:
+// the columns are.  Nothing to do (no problem or no row) passes before the arrays are looked at.
+inline int check_local_votes(const Query& Q, int nproblems, const Columns& K, const int32_t* votes, bool on_device, bool kf_device) {
+    if (!local_problems_ok(nproblems, Q.qcap) || !columns_ok(K.nkf, K.cap)) return ORBX_ERR_ARG;
+    if (nproblems == 0 || K.nkf == 0) return ORBX_OK;
+    if (!Q.q || !Q.nq || !K.slot || !K.nt || !votes) return ORBX_ERR_ARG;
+    if (on_device && !words_aligned(Q.q, Q.nq, votes)) return ORBX_ERR_ARG;
+    if (kf_device && !words_aligned(K.slot, K.nt)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// The arguments of orbp_local_points* that do not need the handle; on_device / kf_device as above.  The query is optional (with it, its counts are
+// required), overflow is optional in the host form; the columns are required only when there are rows to name.
+inline int check_local_points(const Query& Q, int nproblems, const RowLists& R, const Columns& K, const LocalOut& O, bool on_device, bool kf_device) {
+    if (!local_problems_ok(nproblems, Q.qcap) || !columns_ok(K.nkf, K.cap)) return ORBX_ERR_ARG;
+    if (R.rcap < 1 || R.rcap > ORBP_LOCAL_MAX_ROWS || O.lcap < 1) return ORBX_ERR_ARG;
+    if ((long long)R.rcap * K.cap >= (1ll << 31) || (long long)nproblems * O.lcap >= (1ll << 31)) return ORBX_ERR_ARG;
+    if (nproblems == 0) return ORBX_OK;
+    if ((Q.q && !Q.nq) || !R.rows || !R.nrows || !O.list || !O.nlist || !O.skip || (on_device && !O.overflow)) return ORBX_ERR_ARG;
+    if (K.nkf > 0 && (!K.slot || !K.nt)) return ORBX_ERR_ARG;
+    if (on_device && !words_aligned(Q.q, Q.nq, R.rows, R.nrows, O.list, O.nlist, O.overflow)) return ORBX_ERR_ARG;
+    if (kf_device && !words_aligned(K.slot, K.nt)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// The arguments of orbp_rows_purge_device that do not need the handle (the slots' range does)
+inline int check_rows_purge(const int32_t* slots, int n, const int32_t* d_kf_slot, int nkf, int cap) {
+    if (n < 0 || !columns_ok(nkf, cap)) return ORBX_ERR_ARG;
+    if (n == 0 || nkf == 0) return ORBX_OK;
+    return slots && d_kf_slot && words_aligned(d_kf_slot) ? ORBX_OK : ORBX_ERR_ARG;
+}
+
+// The upload slots the two host forms share: the queries and the columns
+struct LocalIn {
+    Layout::Slot<int32_t> query, nquery, kf_slot, kf_nt;
+    int nproblems = 0, nkf = 0;
+    size_t nq = 0, nfeat = 0;                          // nproblems * qcap, nkf * cap
+    void reserve(Layout& L, int nproblems_, const Query& Q, const Columns& K, bool kf_upload) {
+        nproblems = nproblems_; nkf = K.nkf; nq = (size_t)nproblems * Q.qcap; nfeat = (size_t)K.nkf * K.cap;
+        query = L.add<int32_t>(nq, Q.q != nullptr); nquery = L.add<int32_t>(nproblems, Q.q != nullptr);
+        kf_slot = L.add<int32_t>(nfeat, kf_upload && K.slot); kf_nt = L.add<int32_t>(nkf, kf_upload && K.nt);
+    }
+    void stage(uint8_t* h, uint8_t* d, const Query& Q, const Columns& K, Query& dq, Columns& dk) const {
+        dq = {Layout::put(h, d, query, Q.q, nq), Layout::put(h, d, nquery, Q.nq, nproblems), Q.qcap};
+        dk = {Layout::put(h, d, kf_slot, K.slot, nfeat), Layout::put(h, d, kf_nt, K.nt, nkf), K.nkf, K.cap};
+    }
+};
+
+// The block of orbp_local_votes, one pinned copy up and one down:
+//   up    [query | nquery | kf_slot | kf_nt]     (absent: the columns when they are on the device)
+//   down  [votes]
+struct LocalVotesBlock {
+    Layout L;
+    LocalIn in;
+    Layout::Slot<int32_t> votes;
+    size_t nvotes;                                     // nproblems * nkf
+    LocalVotesBlock(int nproblems, const Query& Q, const Columns& K, bool kf_upload) : nvotes((size_t)nproblems * K.nkf) {
+        in.reserve(L, nproblems, Q, K, kf_upload);
+        L.end_upload();
+        votes = L.add<int32_t>(nvotes);
+        L.end_download();
+    }
+};
+
+// The block of orbp_local_points:
+//   up    [query | nquery | kf_slot | kf_nt | rows | nrows]     (absent: the query when the caller has none, the columns when they are on the device)
+//   down  [nlist | overflow | list | skip]
+struct LocalPointsBlock {
+    Layout L;
+    LocalIn in;
+    Layout::Slot<int32_t> rows, nrows, nlist, overflow, list;
+    Layout::Slot<uint8_t> skip;
+    int nproblems, rcap, lcap;
+    LocalPointsBlock(int nproblems_, const Query& Q, const RowLists& R, const Columns& K, int lcap_, bool kf_upload) : nproblems(nproblems_), rcap(R.rcap), lcap(lcap_) {
+        in.reserve(L, nproblems, Q, K, kf_upload);
+        rows = L.add<int32_t>((size_t)nproblems * rcap); nrows = L.add<int32_t>(nproblems);
+        L.end_upload();
+        nlist = L.add<int32_t>(nproblems); overflow = L.add<int32_t>(nproblems); list = L.add<int32_t>((size_t)nproblems * lcap);
+        skip = L.add<uint8_t>((size_t)nproblems * lcap);
+        L.end_download();
+    }
+    void stage(uint8_t* h, uint8_t* d, const Query& Q, const RowLists& R, const Columns& K, Query& dq, RowLists& dr, Columns& dk, LocalOut& dout) const {
+        in.stage(h, d, Q, K, dq, dk);
+        dr = {Layout::put(h, d, rows, R.rows, (size_t)nproblems * rcap), Layout::put(h, d, nrows, R.nrows, nproblems), rcap};
+        dout = {Layout::at(d, list), Layout::at(d, nlist), Layout::at(d, skip), Layout::at(d, overflow), lcap};
+    }
+    // what the kernels wrote, out of the pinned block h: the counts, and of every problem the entries it has (at most lcap)
+    void unpack(uint8_t* h, const LocalOut& out) const {
+        const int32_t* n = Layout::at(h, nlist);
+        std::memcpy(out.nlist, n, (size_t)nproblems * 4);
+        if (out.overflow) std::memcpy(out.overflow, Layout::at(h, overflow), (size_t)nproblems * 4);
+        for (int p = 0; p < nproblems; p++) {
+            const size_t e = (size_t)p * lcap, k = n[p] < 0 ? 0 : (n[p] > lcap ? lcap : n[p]);
+            if (k == 0) continue;
+            std::memcpy(out.list + e, Layout::at(h, list) + e, k * 4);
+            std::memcpy(out.skip + e, Layout::at(h, skip) + e, k);
+        }
     }
 };
 

@@ -26,7 +26,7 @@
 // list -> live -> geometry load each): its latency grows linearly with the list length.
 //
 // The host side of every orbp_* entry point is here too; the kernels of the other modes are k_refresh (orbp_refresh.hip), k_fuse
-// (orbp_fuse.hip), k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip) and k_sim3 / k_sim3_agree (orbp_sim3.hip).  Every search ends in search_tail (window search, then
+// (orbp_fuse.hip), k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip), k_sim3 / k_sim3_agree (orbp_sim3.hip) and the local map's (orbp_local.hip).  Every search ends in search_tail (window search, then
 // k_t2source).  The one-view synchronous forms (orbp_track, orbp_track_source, orbp_loop_search) share one_view over the block orbp::OneView
 // of orbp_host.h, where the argument groups, the checks' clauses and the other forms' blocks are.
 #include <hip/hip_runtime.h>
@@ -218,6 +218,8 @@ struct orbp_map {
     std::vector<uint32_t> stamp;                      // duplicate check of one put
     uint32_t stamp_now = 0;
     orbx::DevBuf geom, desc, d_live, d_tab, scratch;
+    orbx::DevBuf lmult, lfirst, ltiles;               // orbp::LocalScratch of orbp_local_* / orbp_rows_purge_device
+    bool local_dirty = true;                          // lmult / lfirst are not (known to be) all 0 / all 0xFF: the next call fills them first
     orbx::PinnedBuf h_tab;
     orbx::Block block;                                // of the synchronous host forms (orbx::Staged), one at a time under `mu`
     orbx::Stream own;
@@ -374,6 +376,50 @@ int fit_scratch(orbp_map* m, const Layout& L) {
         HIPCHK(m, m->chain.wait());
         HIPCHK(m, m->scratch.ensure(L.total()));
     }
+    return ORBX_OK;
+}
+
+// The local map's scratch holds `nproblems` problems and `tile_words` tile counts: grown synchronously on the first call of a size, after the device
+// work that may still use it.  New words are unknown, so the next local_begin fills them.
+int fit_local(orbp_map* m, int nproblems, size_t tile_words) {
+    const size_t words = (size_t)nproblems * m->capacity * 4, tiles = tile_words * 4;
+    if (words > m->lmult.size() || words > m->lfirst.size() || tiles > m->ltiles.size()) {
+        HIPCHK(m, m->chain.wait());
+        m->local_dirty = true;
+        HIPCHK(m, m->lmult.ensure(words));
+        HIPCHK(m, m->lfirst.ensure(words));
+        HIPCHK(m, m->ltiles.ensure(tiles));
+    }
+    return ORBX_OK;
+}
+
+// Inside the caller's call, in front of the kernels of orbp_local.hip: the scratch in its between-calls state.  In the steady state the last call
+// left it so; after a grow, or a call whose launches failed half way, the whole of it is filled on the stream.  The scratch counts as dirty until
+// local_end: every way out in between leaves the flag set.
+int local_begin(orbp_map* m, hipStream_t st, orbp::LocalScratch& S) {
+    if (m->local_dirty) {
+        if (m->lmult.size()) HIPCHK(m, hipMemsetAsync(m->lmult.as(), 0, m->lmult.size(), st));
+        if (m->lfirst.size()) HIPCHK(m, hipMemsetAsync(m->lfirst.as(), 0xFF, m->lfirst.size(), st));
+    }
+    m->local_dirty = true;
+    S = {m->lmult.as<uint32_t>(), m->lfirst.as<uint32_t>(), m->ltiles.as<int32_t>()};
+    return ORBX_OK;
+}
+void local_end(orbp_map* m) { m->local_dirty = false; }
+
+int local_votes_locked(orbp_map* m, const orbp::Query& Q, int nproblems, const orbp::Columns& K, int32_t* d_votes, hipStream_t st) {
+    orbp::LocalScratch S;
+    TRY(local_begin(m, st, S));
+    HIPCHK(m, orbp::launch_local_votes({table_of(m), Q, K, S, d_votes}, nproblems, st));
+    local_end(m);
+    return ORBX_OK;
+}
+
+int local_points_locked(orbp_map* m, const orbp::Query& Q, int nproblems, const orbp::RowLists& R, const orbp::Columns& K, const orbp::LocalOut& O, hipStream_t st) {
+    orbp::LocalScratch S;
+    TRY(local_begin(m, st, S));
+    HIPCHK(m, orbp::launch_local_points({table_of(m), Q, R, K, S, O}, nproblems, st));
+    local_end(m);
     return ORBX_OK;
 }
 
@@ -870,6 +916,98 @@ int orbp_loop_search(orbp_map* m, const orbp_view* view, const float* factors, i
             return loop_locked(m, Layout::at(d, B.view), 1, F, dl, b, orb_dist, K, fr.claimed, qcap, B.dev, d,
                                {Layout::at(d, B.rec), Layout::at(d, B.t2pos), Layout::at(d, B.t2slot), d_res + 2, d_res, d_res + 1}, st);
         });
+}
+
+int orbp_local_votes_batch_device(orbp_map* m, const int32_t* d_query, const int32_t* d_nquery, int qcap, int nproblems, const int32_t* d_kf_slot,
+                                  const int32_t* d_kf_nt, int nkf, int cap, int32_t* d_votes, void* stream) {
+    const orbp::Query Q{d_query, d_nquery, qcap};
+    const orbp::Columns K{d_kf_slot, d_kf_nt, nkf, cap};
+    if (!m || orbp::check_local_votes(Q, nproblems, K, d_votes, true, true) != ORBX_OK) return ORBX_ERR_ARG;
+    if (nproblems == 0 || nkf == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    TRY(fit_local(m, nproblems, 0));
+    TRY(c.begin());
+    TRY(local_votes_locked(m, Q, nproblems, K, d_votes, c.st));
+    return c.end();
+}
+
+int orbp_local_votes(orbp_map* m, const int32_t* query, const int32_t* nquery, int qcap, int nproblems, const int32_t* kf_slot, const int32_t* kf_nt,
+                     int kf_on_device, int nkf, int cap, int32_t* votes, void* stream) {
+    const orbp::Query Q{query, nquery, qcap};
+    const orbp::Columns K{kf_slot, kf_nt, nkf, cap};
+    if (!m || orbp::check_local_votes(Q, nproblems, K, votes, false, kf_on_device != 0) != ORBX_OK) return ORBX_ERR_ARG;
+    if (nproblems == 0 || nkf == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    TRY(fit_local(m, nproblems, 0));
+    const orbp::LocalVotesBlock B(nproblems, Q, K, kf_on_device == 0);
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    orbp::Query dq;
+    orbp::Columns dk;
+    B.in.stage(s.h, s.d, Q, K, dq, dk);
+    TRY(s.run([&] { return local_votes_locked(m, dq, nproblems, dk, Layout::at(s.d, B.votes), c.st); }));
+    std::memcpy(votes, Layout::at(s.h, B.votes), B.nvotes * 4);
+    return ORBX_OK;
+}
+
+int orbp_local_points_batch_device(orbp_map* m, const int32_t* d_query, const int32_t* d_nquery, int qcap, int nproblems, const int32_t* d_rows,
+                                   const int32_t* d_nrows, int rcap, const int32_t* d_kf_slot, const int32_t* d_kf_nt, int nkf, int cap, int32_t* d_list,
+                                   int32_t* d_nlist, uint8_t* d_skip, int32_t* d_overflow, int lcap, void* stream) {
+    const orbp::Query Q{d_query, d_nquery, qcap};
+    const orbp::RowLists R{d_rows, d_nrows, rcap};
+    const orbp::Columns K{d_kf_slot, d_kf_nt, nkf, cap};
+    const orbp::LocalOut O{d_list, d_nlist, d_skip, d_overflow, lcap};
+    if (!m || orbp::check_local_points(Q, nproblems, R, K, O, true, true) != ORBX_OK) return ORBX_ERR_ARG;
+    if (nproblems == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    TRY(fit_local(m, nproblems, orbp::local_tile_words(nproblems, rcap, cap)));
+    TRY(c.begin());
+    TRY(local_points_locked(m, Q, nproblems, R, K, O, c.st));
+    return c.end();
+}
+
+int orbp_local_points(orbp_map* m, const int32_t* query, const int32_t* nquery, int qcap, int nproblems, const int32_t* rows, const int32_t* nrows, int rcap,
+                      const int32_t* kf_slot, const int32_t* kf_nt, int kf_on_device, int nkf, int cap, int32_t* list, int32_t* nlist, uint8_t* skip,
+                      int32_t* overflow, int lcap, void* stream) {
+    const orbp::Query Q{query, nquery, qcap};
+    const orbp::RowLists R{rows, nrows, rcap};
+    const orbp::Columns K{kf_slot, kf_nt, nkf, cap};
+    const orbp::LocalOut O{list, nlist, skip, overflow, lcap};
+    if (!m || orbp::check_local_points(Q, nproblems, R, K, O, false, kf_on_device != 0) != ORBX_OK) return ORBX_ERR_ARG;
+    if (nproblems == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    TRY(fit_local(m, nproblems, orbp::local_tile_words(nproblems, rcap, cap)));
+    const orbp::LocalPointsBlock B(nproblems, Q, R, K, lcap, kf_on_device == 0);
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    orbp::Query dq;
+    orbp::RowLists dr;
+    orbp::Columns dk;
+    orbp::LocalOut dout;
+    B.stage(s.h, s.d, Q, R, K, dq, dr, dk, dout);
+    TRY(s.run([&] { return local_points_locked(m, dq, nproblems, dr, dk, dout, c.st); }));
+    B.unpack(s.h, O);
+    return ORBX_OK;
+}
+
+int orbp_rows_purge_device(orbp_map* m, const int32_t* slots, int n, int32_t* d_kf_slot, int nkf, int cap, void* stream) {
+    if (!m || orbp::check_rows_purge(slots, n, d_kf_slot, nkf, cap) != ORBX_OK) return ORBX_ERR_ARG;
+    if (n == 0 || nkf == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    if (check_slots(m, slots, n, false, false) != ORBX_OK) return ORBX_ERR_ARG;
+    TRY(fit_local(m, 1, 0));
+    TRY(c.begin());
+    TRY(upload_slots(m, slots, n, c.st));
+    orbp::LocalScratch S;
+    TRY(local_begin(m, c.st, S));
+    HIPCHK(m, orbp::launch_rows_purge({n, m->d_tab.as<int32_t>(), m->capacity, S.mult, d_kf_slot, (size_t)nkf * cap}, c.st));
+    local_end(m);
+    return c.end();
 }
 
 }  // extern "C"

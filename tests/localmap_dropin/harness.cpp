@@ -1,0 +1,205 @@
+// Drives ORB_SLAM::LocalMapPoints::PutKeyFrame / UpdateReferenceKeyFrames / SearchLocalMap / ConnectionWeights (orb_slam_amd/cpp/LocalMapPointsLocalMap.cc,
+// over the stand-in Frame.h / KeyFrame.h / MapPoint.h of this directory) through scenes; tests/test_gpu_local_map_dropin.py writes the scenes of
+// tests/golden/localmap_ref_*.npz and compares what comes out with what the reference's own text left behind.
+//
+//   harness SCENES
+//
+// SCENES: the number of scenes, then per scene "NKF NPTS FRAMEID NFEAT", per key frame "ID RANK BAD TRACK NT mvp[NT] NN neigh[NN]" (map points and key
+// frames by index, -1 = NULL), per map point "BAD TRACK NOBS {kf idx}[NOBS]", and the frame's "mvp[NFEAT]".  Key frame k lives at slot RANK of one
+// array, so the address order of std::map<KeyFrame*, ...> is the scene's rank order.  The geometry is made here: the camera at the origin, feature i
+// somewhere in the image, map point p in front of feature p % NFEAT with that feature's descriptor but for a few bits, so that the search has
+// matches to make.
+// Per scene, the key frames and points are Put (the bad ones as good ones first, so that their slots die under resident columns), then:
+//   local N k..  ref K  kftrack t..  frame p..      after UpdateReferenceKeyFrames: mvpLocalKeyFrames, mpReferenceKF, every key frame's
+//                                                   mnTrackReferenceForFrame, F.mvpMapPoints
+//   points N p..  skip s..  mptrack t..             after SearchLocalMap: mvpLocalMapPoints, mnLastFrameSeen == F.mnId per listed point, every point's
+//                                                   mnTrackReferenceForFrame (left alone: the documented deviation)
+//   search RET NTOMATCH SAME                        SAME: 1 when the first loop of :678-694 by hand + SearchReferencePointsInFrustum over that list leave
+//                                                   the same return value, nToMatch, F.mvpMapPoints and per-point mTrack* / visible counts
+//   weights N {k c}..  (per key frame)  wbatch B    ConnectionWeights one by one, and whether the batch form says the same
+//   reread N                                        GetMapPointMatches calls during a second round of the first two: the columns are resident
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <cmath>
+#include <fstream>
+#include <map>
+#include <vector>
+
+#include "Frame.h"
+#include "KeyFrame.h"
+#include "LocalMapPoints.h"
+#include "MapPoint.h"
+
+namespace ORB_SLAM {
+float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
+int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
+float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
+}
+using namespace ORB_SLAM;
+
+namespace {
+uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
+
+struct Track { float x, y, c; int level, visible; bool in_view; long unsigned seen; };
+Track trackOf(MapPoint& m) { return {m.mTrackProjX, m.mTrackProjY, m.mTrackViewCos, m.mnTrackScaleLevel, m.mnVisible, m.mbTrackInView, m.mnLastFrameSeen}; }
+void restore(MapPoint& m, const Track& t) {
+    m.mTrackProjX = t.x; m.mTrackProjY = t.y; m.mTrackViewCos = t.c; m.mnTrackScaleLevel = t.level; m.mnVisible = t.visible; m.mbTrackInView = t.in_view; m.mnLastFrameSeen = t.seen;
+}
+bool same(const Track& a, const Track& b) { return std::memcmp(&a.x, &b.x, 4) == 0 && std::memcmp(&a.y, &b.y, 4) == 0 && std::memcmp(&a.c, &b.c, 4) == 0 && a.level == b.level && a.visible == b.visible && a.in_view == b.in_view && a.seen == b.seen; }
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream in(argv[1]);
+    int nscenes = 0;
+    in >> nscenes;
+    Frame::fx = 500.f; Frame::fy = 500.f; Frame::cx = 320.f; Frame::cy = 240.f;
+    Frame::mnMinX = 0; Frame::mnMaxX = 640; Frame::mnMinY = 0; Frame::mnMaxY = 480;
+    Frame::mfGridElementWidthInv = FRAME_GRID_COLS / 640.f; Frame::mfGridElementHeightInv = FRAME_GRID_ROWS / 480.f;
+    std::vector<float> factors(8, 1.f);
+    for (int i = 1; i < 8; i++) factors[i] = factors[i - 1] * 1.2f;
+    for (int s = 0; s < nscenes; s++) {
+        int nkf, npts, nfeat;
+        long unsigned fid;
+        if (!(in >> nkf >> npts >> fid >> nfeat)) return 2;
+        std::vector<KeyFrame> pool(nkf);
+        std::vector<MapPoint> mps(npts);
+        std::vector<KeyFrame*> kf(nkf);
+        std::vector<std::vector<int> > mvp(nkf), nb(nkf);
+        for (int k = 0; k < nkf; k++) {
+            long unsigned id, rank, bad, track;
+            int nt, nn;
+            in >> id >> rank >> bad >> track >> nt;
+            kf[k] = &pool[rank];
+            kf[k]->mnId = id; kf[k]->mbBad = bad != 0; kf[k]->mnTrackReferenceForFrame = track;
+            mvp[k].resize(nt);
+            for (int i = 0; i < nt; i++) in >> mvp[k][i];
+            in >> nn;
+            nb[k].resize(nn);
+            for (int i = 0; i < nn; i++) in >> nb[k][i];
+        }
+        for (int k = 0; k < nkf; k++) {
+            for (int p : mvp[k]) kf[k]->mvpMapPoints.push_back(p >= 0 ? &mps[p] : nullptr);
+            for (int j : nb[k]) kf[k]->mvpOrderedConnectedKeyFrames.push_back(kf[j]);
+        }
+        std::vector<int> bad(npts);
+        for (int p = 0; p < npts; p++) {
+            long unsigned track;
+            int nobs;
+            in >> bad[p] >> track >> nobs;
+            mps[p].mnId = p; mps[p].mnTrackReferenceForFrame = track;
+            for (int j = 0; j < nobs; j++) { int k, i; in >> k >> i; mps[p].mObservations[kf[k]] = i; }
+        }
+        // the frame and the geometry
+        Frame F;
+        F.mnId = fid;
+        F.mvKeysUn.assign(nfeat, cv::KeyPoint());
+        F.mDescriptors = cv::Mat(nfeat > 0 ? nfeat : 1, 32, CV_8U);
+        F.mnScaleLevels = 8;
+        F.mvScaleFactors = factors;
+        F.mTcw = cv::Mat(4, 4, CV_32F);
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) F.mTcw.at<float>(r, c) = r == c ? 1.f : 0.f;
+        uint32_t seed = 12345u + (uint32_t)s;
+        for (int i = 0; i < nfeat; i++) {
+            cv::KeyPoint& kp = F.mvKeysUn[i];
+            kp.pt.x = 20.f + (float)(lcg(seed) % 6000) / 10.f; kp.pt.y = 20.f + (float)(lcg(seed) % 4400) / 10.f;
+            kp.octave = i % 4;
+            for (int b = 0; b < 32; b++) F.mDescriptors.ptr<unsigned char>(i)[b] = (unsigned char)lcg(seed);
+            const int px = (int)std::round((kp.pt.x - Frame::mnMinX) * Frame::mfGridElementWidthInv);      // Frame::PosInGrid
+            const int py = (int)std::round((kp.pt.y - Frame::mnMinY) * Frame::mfGridElementHeightInv);
+            if (px >= 0 && px < FRAME_GRID_COLS && py >= 0 && py < FRAME_GRID_ROWS) F.mGrid[px][py].push_back(i);
+        }
+        for (int i = 0; i < nfeat; i++) {
+            int p;
+            in >> p;
+            F.mvpMapPoints.push_back(p >= 0 ? &mps[p] : nullptr);
+        }
+        for (int p = 0; p < npts; p++) {
+            MapPoint& m = mps[p];
+            const int f = nfeat ? p % nfeat : 0;
+            const float z = 2.f + 0.5f * (float)(p % 7), x = nfeat ? F.mvKeysUn[f].pt.x : 320.f, y = nfeat ? F.mvKeysUn[f].pt.y : 240.f;
+            const float P[3] = {(x - 320.f) / 500.f * z, (y - 240.f) / 500.f * z, z};
+            const float d = std::sqrt(P[0] * P[0] + P[1] * P[1] + P[2] * P[2]);
+            for (int k = 0; k < 3; k++) { m.mWorldPos.at<float>(k) = P[k]; m.mNormalVector.at<float>(k) = P[k] / d; }
+            m.mfMinDistance = d / (factors[nfeat ? F.mvKeysUn[f].octave : 0] * 0.95f);
+            m.mfMaxDistance = m.mfMinDistance * 4.3f;
+            if (nfeat) std::memcpy(m.mDescriptor.ptr<unsigned char>(0), F.mDescriptors.ptr<unsigned char>(f), 32);
+            for (int b = 0; b < p / (nfeat ? nfeat : 1) && b < 32; b++) m.mDescriptor.ptr<unsigned char>(0)[b] ^= 1;
+        }
+        std::map<KeyFrame*, int> kidx;
+        for (int k = 0; k < nkf; k++) kidx[kf[k]] = k;
+        auto pidx = [&](MapPoint* m) { return m ? (int)(m - &mps[0]) : -1; };
+
+        LocalMapPoints L(0.8f, false, 64);                       // a small table: it grows on the way
+        for (int p = 0; p < npts; p++) L.Put(&mps[p]);
+        for (int k = 0; k < nkf; k++) L.PutKeyFrame(kf[k]);
+        {
+            std::map<KeyFrame*, int> c;                           // the columns go up with the stale entries alive ...
+            if (nkf) L.ConnectionWeights(kf[0], c);
+        }
+        for (int p = 0; p < npts; p++)                            // ... and the bad points are Forgotten under them
+            if (bad[p]) { mps[p].mbBad = true; L.Forget(&mps[p]); }
+
+        const Frame F0 = F;
+        std::vector<Track> before(npts);
+        for (int p = 0; p < npts; p++) before[p] = trackOf(mps[p]);
+        std::vector<KeyFrame*> local;
+        KeyFrame* ref = nullptr;
+        L.UpdateReferenceKeyFrames(F, local, ref);
+        printf("local %zu", local.size());
+        for (KeyFrame* k : local) printf(" %d", kidx[k]);
+        printf("\nref %d\nkftrack", ref ? kidx[ref] : -1);
+        for (int k = 0; k < nkf; k++) printf(" %lu", kf[k]->mnTrackReferenceForFrame);
+        printf("\nframe");
+        for (MapPoint* m : F.mvpMapPoints) printf(" %d", pidx(m));
+        std::vector<MapPoint*> points;
+        int nToMatch = -1;
+        const Frame F1 = F;
+        const int ret = L.SearchLocalMap(F, local, 1.0f, &points, &nToMatch);
+        printf("\npoints %zu", points.size());
+        for (MapPoint* m : points) printf(" %d", pidx(m));
+        printf("\nskip");
+        for (MapPoint* m : points) printf(" %d", m->mnLastFrameSeen == F.mnId ? 1 : 0);
+        printf("\nmptrack");
+        for (int p = 0; p < npts; p++) printf(" %lu", mps[p].mnTrackReferenceForFrame);
+        // the same by the route that existed: the first loop by hand, then the list on the host
+        std::vector<Track> after(npts);
+        for (int p = 0; p < npts; p++) { after[p] = trackOf(mps[p]); restore(mps[p], before[p]); }
+        Frame F2 = F1;
+        for (MapPoint*& m : F2.mvpMapPoints) {
+            if (!m) continue;
+            if (m->isBad()) { m = nullptr; continue; }
+            m->IncreaseVisible(); m->mnLastFrameSeen = F2.mnId; m->mbTrackInView = false;
+        }
+        int nToMatch2 = -1;
+        const int ret2 = points.empty() ? 0 : L.SearchReferencePointsInFrustum(F2, points, 1.0f, &nToMatch2);
+        if (points.empty()) nToMatch2 = 0;
+        bool eq = ret == ret2 && nToMatch == nToMatch2 && F.mvpMapPoints == F2.mvpMapPoints;
+        for (int p = 0; p < npts; p++) eq = eq && same(after[p], trackOf(mps[p]));
+        printf("\nsearch %d %d %d\n", ret, nToMatch, eq ? 1 : 0);
+        std::vector<std::map<KeyFrame*, int> > all;
+        L.ConnectionWeights(kf, all);
+        bool batch_same = true;
+        for (int k = 0; k < nkf; k++) {
+            std::map<KeyFrame*, int> c;
+            L.ConnectionWeights(kf[k], c);
+            batch_same = batch_same && c == all[k];
+            printf("weights %zu", c.size());
+            for (auto& it : c) printf(" %d %d", kidx[it.first], it.second);
+            printf("\n");
+        }
+        printf("wbatch %d\n", batch_same ? 1 : 0);
+        int fetched = 0;
+        for (int k = 0; k < nkf; k++) fetched -= kf[k]->getMatches;
+        Frame F3 = F0;
+        for (int k = 0; k < nkf; k++) kf[k]->mnTrackReferenceForFrame = 0;
+        F3.mnId = fid + 1;
+        std::vector<KeyFrame*> local3;
+        L.UpdateReferenceKeyFrames(F3, local3, ref);
+        L.SearchLocalMap(F3, local3, 1.0f);
+        for (int k = 0; k < nkf; k++) fetched += kf[k]->getMatches;
+        printf("reread %d\n", fetched);
+    }
+    return 0;
+}
