@@ -9,7 +9,7 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -ffp-contract=off -mll
 ORBX_SRCS  := $(wildcard orb_slam_amd/csrc/*.hip)
 ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*.h)
 
-all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tests/newpoints_dropin/harness tests/localmap_dropin/harness tools/libmappoints_host.so tools/liblocalmap_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
+all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tests/newpoints_dropin/harness tests/localmap_dropin/harness tests/cull_dropin/harness tools/libmappoints_host.so tools/liblocalmap_host.so tools/libcull_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
 
 # the hash of the kernel sources travels inside the library (orbx_build_id): counters replayed by bench.py must come from THIS build
 SRC_HASH   := $(shell cat $(sort $(ORBX_SRCS) $(ORBX_HDRS)) | sha256sum | cut -c1-16)
@@ -144,6 +144,15 @@ tests/localmap_dropin/harness: tests/localmap_dropin/harness.cpp $(LM_DROPIN) in
 	$(CXX) -O2 -std=c++14 -Wall -Itests/localmap_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
 	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsLocalMap.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
 
+# LocalMapPoints::KeyFrameCulling (orb_slam_amd/cpp/LocalMapPointsCull.cc, over the columns of LocalMapPointsLocalMap.cc and the rows of
+# LocalMapPointsRefresh.cc), driven by scenes (tests/test_gpu_cull_dropin.py); Frame.h, KeyFrame.h and MapPoint.h are this directory's (they add
+# SetBadFlag, EraseObservation, SetNotErase and the covisibility list), cvmini.h that of tests/mappoints_dropin
+CULL_DROPIN := orb_slam_amd/cpp/LocalMapPointsCull.cc orb_slam_amd/cpp/LocalMapPointsLocalMap.cc orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPoints.cc \
+    orb_slam_amd/cpp/LocalMapPoints.h orb_slam_amd/cpp/ORBmatcherAccess.h $(wildcard tests/cull_dropin/*.h) tests/mappoints_dropin/cvmini.h
+tests/cull_dropin/harness: tests/cull_dropin/harness.cpp $(CULL_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
+	$(CXX) -O2 -std=c++14 -Wall -Itests/cull_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
+	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsLocalMap.cc orb_slam_amd/cpp/LocalMapPointsCull.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+
 # the NewMapPoints drop-in (orb_slam_amd/cpp/NewMapPoints.cc) over a stand-in KeyFrame.h, driven by scripts
 # (tests/test_gpu_triangulate_dropin.py); cvmini.h is that of tests/mappoints_dropin
 TRI_DROPIN := orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h tests/triangulate_dropin/KeyFrame.h tests/mappoints_dropin/cvmini.h
@@ -176,6 +185,10 @@ tools/libsim3_host.so: tools/sim3_host_route.cpp include/orbp.h
 tools/liblocalmap_host.so: tools/local_map_host_route.cpp
 	$(CXX) -O2 -std=c++14 -fPIC -shared $< -o $@
 
+# the host route tools/bench_cull.py measures orbp_cull against: LocalMapping::KeyFrameCulling over flat stand-in arrays with a std::map per point, one host core
+tools/libcull_host.so: tools/cull_host_route.cpp
+	$(CXX) -O2 -std=c++14 -fPIC -shared $< -o $@
+
 # the host-query route tools/bench_source_track.py measures the device-resident last-frame / key-frame searches against (one host core)
 tools/libsource_host.so: tools/source_host_route.cpp include/orbp.h
 	$(CXX) -O2 -std=c++14 -ffp-contract=off -fPIC -shared -Iinclude $< -o $@
@@ -204,7 +217,7 @@ tools/microbench/ta_shapes: tools/microbench/ta_shapes.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++20 -Wno-unused-value $< -o $@
 
 clean:
-	rm -f tests/localmap_dropin/harness tools/liblocalmap_host.so tests/newpoints_dropin/harness tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
+	rm -f tools/libcull_host.so tests/cull_dropin/harness tests/localmap_dropin/harness tools/liblocalmap_host.so tests/newpoints_dropin/harness tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
 	rm -rf oracle/_ref oracle/_ref_native build/orbx
 
 .PHONY: all clean oracle_ref

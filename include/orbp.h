@@ -44,6 +44,8 @@
  *                                <- void Tracking::UpdateReferencePoints()                         src/Tracking.cc:738-761
  *                                   and the stamps of Tracking::SearchReferencePointsInFrustum's first loop   src/Tracking.cc:678-694
  *   orbp_rows_purge_device       <- what MapPoint::SetBadFlag / KeyFrame::EraseMapPointMatch do to mvpMapPoints, for the resident columns
+ *   orbp_cull[_batch_device]     <- the decisions of void LocalMapping::KeyFrameCulling()          src/LocalMapping.cc:524-578
+ *                                   with the observations KeyFrame::SetBadFlag erases in between  src/KeyFrame.cc:497-515, src/MapPoint.cc:71-122
  *
  * Map points are named by caller-chosen slots 0 <= slot < capacity.
  *
@@ -611,6 +613,46 @@ int orbp_local_points(orbp_map* map, const int32_t* query, const int32_t* nquery
                       uint8_t* skip, int32_t* overflow, int lcap, void* stream);
 
 int orbp_rows_purge_device(orbp_map* map, const int32_t* slots, int n, int32_t* d_kf_slot, int nkf, int cap, void* stream);
+
+/* ---- Key-frame culling over the columns: the decisions of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:524-578), with what
+ * KeyFrame::SetBadFlag (src/KeyFrame.cc:497-515: the guard and the EraseObservation loop) and MapPoint::EraseObservation / SetBadFlag
+ * (src/MapPoint.cc:71-122) do to the observations in between, so that every candidate is judged on the map its predecessors left.
+ *
+ * Beside the slot column every row has an OCTAVE column, d_kf_oct[k*cap + i] = pKF->GetKeyPointUn(i).octave as a uint8.  A column entry TAKES
+ * PART when i < clamp(d_kf_nt[k], 0, cap), its slot is in range and live in the table, and its octave is below nlevels; any other entry is passed
+ * over in the build, in the count and in the erasure alike, never dereferenced.  DEVIATION: an octave outside [0, nlevels) cannot come from the
+ * extractor; the reference would compare it like any other, here its entry does not exist.
+ * PRECONDITIONS, stated and not checked: a slot occurs at most once per row; every non-bad key frame of the map is a resident row with its
+ * column; bad key frames have no column.  Then H[s][l], the number of rows that hold slot s at a feature of octave l, is the transpose of
+ * mObservations by level, and sum_l H[s][l] == pMP->Observations().
+ *
+ * Candidate c is judged in list order on row r = d_cand[c], with a flag dead[s] per slot (all clear at the start):
+ *   nMPs  = the entries of row r that take part and whose slot is not dead;
+ *   nRed  = those of them with T = sum_l H[s][l] > 3 and (sum_{l <= oct+1} H[s][l]) - 1 >= 3 (the row's own observation lies inside the sum; the
+ *           reference stops counting at three, which changes nothing);
+ *   cull  = (double)nRed > 0.9 * (double)nMPs, one IEEE multiply and one compare as :575 (nMPs == 0 gives 0).
+ * When cull: every entry of row r that takes part, dead or not, loses its observation (H[s][oct] -= 1), a slot whose T is now <= 2 becomes dead,
+ * and the row is erased for the rest of the call.  d_nmps[c], d_nred[c], d_cull[c] are as of the candidate's turn; a candidate whose row is
+ * outside [0, nkf) or was erased earlier in the call writes 0, 0, 0 and reads nothing.  Exactly ncand words of each output are written.
+ * The call leaves no trace: the table's live flags and the columns are not changed (the caller's SetBadFlag calls, orbp_erase and
+ * orbp_rows_purge_device do that).  mbNotErase is the caller's business: a flagged key frame that does not go bad invalidates what follows it.
+ *
+ * The handle owns the scratch, grown on first use and kept: eight words per slot (sixteen 16-bit level counts; a count is at most the number
+ * of rows, <= ORBP_LOCAL_MAX_ROWS, so a field cannot carry) and one dead word per slot.  The kernels put back every word they changed.
+ *
+ * ORBX_ERR_ARG before anything touches the GPU, with nothing changed, for a NULL handle, ncand outside [0, ORBP_CULL_MAX_CANDIDATES], nkf outside
+ * [0, ORBP_LOCAL_MAX_ROWS], cap < 1, nkf * cap >= 2^31, nlevels outside [1, ORBS_MAX_LEVELS], a NULL required array, an int32 array that is not
+ * 4-byte aligned (d_kf_oct needs no alignment).  ncand == 0 or nkf == 0 is ORBX_OK with nothing launched.  Asynchronous on `stream` (NULL: the
+ * map's own), inside the handle's event chain; allocates nothing in the steady state. */
+#define ORBP_CULL_MAX_CANDIDATES 4096
+
+int orbp_cull_batch_device(orbp_map* map, const int32_t* d_cand, int ncand, const int32_t* d_kf_slot, const uint8_t* d_kf_oct,
+                           const int32_t* d_kf_nt, int nkf, int cap, int nlevels, int32_t* d_nmps, int32_t* d_nred, int32_t* d_cull, void* stream);
+
+/* The same with HOST arrays in and out, synchronous: one pinned block up and one down.  cand, nmps, nred and cull (ncand each) are host memory;
+ * the columns (kf_slot, kf_oct, kf_nt) are host memory, or device memory when kf_on_device != 0 (only the candidate list goes up). */
+int orbp_cull(orbp_map* map, const int32_t* cand, int ncand, const int32_t* kf_slot, const uint8_t* kf_oct, const int32_t* kf_nt,
+              int kf_on_device, int nkf, int cap, int nlevels, int32_t* nmps, int32_t* nred, int32_t* cull, void* stream);
 
 #ifdef __cplusplus
 }

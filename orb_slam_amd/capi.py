@@ -60,8 +60,9 @@ EXPORTS_P = ["orbp_create", "orbp_destroy", "orbp_capacity", "orbp_size", "orbp_
              "orbp_track_source_batch_device", "orbp_track_source", "orbp_refresh_batch_device", "orbp_refresh", "orbp_fuse_batch_device",
              "orbp_fuse", "orbp_view_from_sim3", "orbp_loop_project_batch_device", "orbp_loop_search_batch_device", "orbp_loop_search",
              "orbp_sim3_from_pair", "orbp_sim3_search_batch_device", "orbp_sim3_search", "orbp_local_votes_batch_device", "orbp_local_votes",
-             "orbp_local_points_batch_device", "orbp_local_points", "orbp_rows_purge_device"]
+             "orbp_local_points_batch_device", "orbp_local_points", "orbp_rows_purge_device", "orbp_cull_batch_device", "orbp_cull"]
 LOCAL_MAX_PROBLEMS, LOCAL_MAX_ROWS = 64, 65535      # ORBP_LOCAL_MAX_PROBLEMS, ORBP_LOCAL_MAX_ROWS
+CULL_MAX_CANDIDATES = 4096                          # ORBP_CULL_MAX_CANDIDATES
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate", "orbt_new_points_rows_device", "orbt_new_points_rows"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
@@ -354,6 +355,8 @@ def lib():
         L.orbp_local_points_batch_device.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]
         L.orbp_local_points.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp]
         L.orbp_rows_purge_device.argtypes = [vp, vp, ci, vp, ci, ci, vp]
+        L.orbp_cull_batch_device.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]
+        L.orbp_cull.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
         L.orbp_project_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbp_track_source_batch_device.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(Bounds), ctypes.POINTER(SearchParams),
                                                      vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
@@ -1654,6 +1657,30 @@ class MapPointTable:
         rc = lib().orbp_rows_purge_device(self.h, slots.ctypes.data, len(slots), d_kf_slot or None, nkf, cap, stream or None)
         if rc != ORBX_OK:
             raise OrbxError(rc, "orbp_rows_purge_device")
+
+    def cull_batch_device(self, d_cand, ncand, d_kf_slot, d_kf_oct, d_kf_nt, nkf, cap, nlevels, d_nmps, d_nred, d_cull, stream=0):
+        """The decisions of LocalMapping::KeyFrameCulling for the candidate rows d_cand, in list order, over the slot and octave columns of nkf
+        resident rows, asynchronous: d_nmps / d_nred / d_cull[ncand].  Device pointers as ints."""
+        rc = lib().orbp_cull_batch_device(self.h, d_cand or None, ncand, d_kf_slot or None, d_kf_oct or None, d_kf_nt or None, nkf, cap, nlevels,
+                                          d_nmps or None, d_nred or None, d_cull or None, stream or None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_cull_batch_device")
+
+    def cull(self, cand, kf_slot, kf_oct, kf_nt, nlevels=8, nkf=None, cap=None):
+        """The same with host arrays, synchronous -> (nmps, nred, cull), i32[ncand] each.  The columns are host arrays (nkf, cap) / (nkf), or device
+        pointers as ints (nkf and cap must then be given)."""
+        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1)
+        kf_slot, kf_nt, nkf, cap, on_dev = self._columns(kf_slot, kf_nt, nkf, cap)
+        if not on_dev:
+            kf_oct = np.ascontiguousarray(kf_oct, dtype=np.uint8)
+            assert kf_oct.shape == (nkf, cap)
+        nmps, nred, cull = (np.zeros(len(cand), np.int32) for _ in range(3))
+        ptr = lambda a: (a or None) if isinstance(a, int) else a.ctypes.data
+        rc = lib().orbp_cull(self.h, ptr(cand), len(cand), ptr(kf_slot), ptr(kf_oct), ptr(kf_nt), 1 if on_dev else 0, nkf, cap, nlevels, ptr(nmps),
+                             ptr(nred), ptr(cull), None)
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbp_cull")
+        return nmps, nred, cull
 
     def project_batch_device(self, d_views, nviews, factors, d_list, d_nlist, lcap, d_skip, d_rec, d_qxyr, d_qlev, d_qdesc, d_qpos, d_nq,
                              d_overflow, qcap, stream=0):

@@ -43,6 +43,7 @@ LocalMapPoints::~LocalMapPoints() {
     if (d_kf_fv_feat_) orbx_device_free(device_, d_kf_fv_feat_);
     if (d_kf_slot_) orbx_device_free(device_, d_kf_slot_);
     if (d_kf_col_nt_) orbx_device_free(device_, d_kf_col_nt_);
+    if (d_kf_oct_) orbx_device_free(device_, d_kf_oct_);
     if (d_local_) orbx_device_free(device_, d_local_);
 }
 

@@ -197,6 +197,20 @@ public:
     // per ORBP_LOCAL_MAX_PROBLEMS key frames.
     void ConnectionWeights(const std::vector<KeyFrame*>& vpKFs, std::vector<std::map<KeyFrame*, int> >& vKFcounter);
 
+    // void LocalMapping::KeyFrameCulling() (src/LocalMapping.cc:524-578) for mpCurrentKeyFrame = pCurrentKF (LocalMapPointsCull.cc; links only when
+    // that file, LocalMapPointsLocalMap.cc and LocalMapPointsRefresh.cc are built in).  Reads pCurrentKF->GetVectorCovisibleKeyFrames(), leaves out
+    // mnId == 0, key frames never Put and NULL or bad ones, runs ONE orbp_cull over the resident slot and octave columns (include/orbp.h: every
+    // candidate is judged on the map its predecessors' SetBadFlag calls leave), and calls pKF->SetBadFlag() in list order for the candidates
+    // flagged.  After each SetBadFlag() it tests isBad(): a key frame that did not go bad (mbNotErase, which loop closing sets and the host cannot
+    // know beforehand) is not erased, so what the device assumed behind it is wrong; the mirror is then brought up to date as after a complete call
+    // and the call runs again on the candidates behind it.  At the end ForgetKeyFrame for every key frame that went bad and Forget for every
+    // point of those rows that is bad now (the next flush purges them from the resident columns).  *vpCulled (may be NULL): the key frames that
+    // went bad, in order.  The same CONTRACT as above; the octaves are read from GetKeyPointsUn() once per key frame and the number of levels from
+    // GetScaleLevels().
+    void KeyFrameCulling(KeyFrame* pCurrentKF, std::vector<KeyFrame*>* vpCulled = 0);
+    // how many orbp_cull calls the last KeyFrameCulling made (more than one: a flagged key frame was protected)
+    int keyFrameCullingCalls() const { return cull_calls_; }
+
     std::size_t size() const { return slot_.size(); }
     int capacity() const { return capacity_; }
 
@@ -221,6 +235,9 @@ private:
     std::vector<int32_t> kf_col_n_;              // per row: the entries of its column on the device
     void* d_kf_slot_ = nullptr;                  // [col_rows_][col_cap_]
     void* d_kf_col_nt_ = nullptr;                // [col_rows_]
+    void* d_kf_oct_ = nullptr;                   // [col_rows_][col_cap_] bytes: the octave of every feature, beside d_kf_slot_ (orbp_cull)
+    std::vector<uint8_t> kf_oct_up_;             // per row: its octaves are on the device (read from GetKeyPointsUn() once per key frame and store)
+    int cull_calls_ = 0;
     int col_rows_ = 0, col_cap_ = 0;
     void* d_local_ = nullptr;                    // the block of one SearchLocalMap call
     std::size_t local_bytes_ = 0;

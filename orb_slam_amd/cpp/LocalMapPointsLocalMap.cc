@@ -46,13 +46,16 @@ void LocalMapPoints::syncColumns() {
         // a bigger store, zero-initialised (every count 0); every column that was Put is read and uploaded again
         if (d_kf_slot_) orbx_device_free(device_, d_kf_slot_);
         if (d_kf_col_nt_) orbx_device_free(device_, d_kf_col_nt_);
-        d_kf_slot_ = d_kf_col_nt_ = nullptr;
+        if (d_kf_oct_) orbx_device_free(device_, d_kf_oct_);
+        d_kf_slot_ = d_kf_col_nt_ = d_kf_oct_ = nullptr;
         col_rows_ = kf_rows_;
         col_cap_ = need_cap > col_cap_ ? std::max(need_cap, 2 * col_cap_) : col_cap_;       // a longer row doubles the stride
         int rc = orbx_device_alloc(device_, (size_t)col_rows_ * col_cap_ * 4, &d_kf_slot_);
         if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)col_rows_ * 4, &d_kf_col_nt_);
+        if (rc == ORBX_OK) rc = orbx_device_alloc(device_, (size_t)col_rows_ * col_cap_, &d_kf_oct_);
         if (rc != ORBX_OK) fail("orbx_device_alloc (map-point columns)", rc);
         kf_col_n_.assign(col_rows_, 0);
+        kf_oct_up_.assign(col_rows_, 0);
         std::vector<uint8_t> have(col_rows_, 0);
         for (size_t j = 0; j < rows.size(); j++) have[rows[j]] = 1;
         for (int r = 0; r < (int)kf_col_put_.size(); r++) {
@@ -71,6 +74,14 @@ void LocalMapPoints::syncColumns() {
         if (rc == ORBX_OK) rc = orbx_device_upload(device_, static_cast<int32_t*>(d_kf_col_nt_) + r, &n, 4);
         if (rc != ORBX_OK) fail("orbx_device_upload (map-point column)", rc);
         kf_col_n_[r] = n;
+        // the octave column beside it: a key frame's octaves never change, so they are read once, when its column first goes up or the store is rebuilt
+        if (n == 0 || kf_oct_up_[r] || !kf_owner_[r]) continue;
+        const std::vector<cv::KeyPoint> keys = kf_owner_[r]->GetKeyPointsUn();
+        std::vector<uint8_t> oct((size_t)n, 0);
+        for (size_t i = 0; i < oct.size() && i < keys.size(); i++) oct[i] = (uint8_t)std::min(std::max(keys[i].octave, 0), 255);
+        rc = orbx_device_upload(device_, static_cast<uint8_t*>(d_kf_oct_) + (size_t)r * col_cap_, oct.data(), oct.size());
+        if (rc != ORBX_OK) fail("orbx_device_upload (octave column)", rc);
+        kf_oct_up_[r] = 1;
     }
 }
 

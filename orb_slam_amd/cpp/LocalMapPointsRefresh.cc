@@ -59,6 +59,7 @@ void LocalMapPoints::ForgetKeyFrame(KeyFrame* pKF) {
     kf_grid_resident_[it->second] = 0;
     kf_fv_resident_[it->second] = 0;                                  // its FeatureVector goes with it
     kf_nfv_[it->second] = 0;
+    if ((size_t)it->second < kf_oct_up_.size()) kf_oct_up_[it->second] = 0;        // the row's next owner has octaves of its own
     if ((size_t)it->second < kf_col_put_.size() && kf_col_put_[it->second]) {      // its map-point column too (LocalMapPointsLocalMap.cc): the row's count becomes 0
         kf_col_put_[it->second] = 0;
         if (!kf_col_dirty_[it->second]) { kf_col_dirty_[it->second] = 1; col_pending_.push_back(it->second); }

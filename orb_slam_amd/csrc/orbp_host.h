@@ -1,7 +1,7 @@
 // The argument groups of the map-point table's entry points (orbp_project.hip), the clauses their argument checks are composed of, and the
 // layouts the synchronous host forms give the one block an orbp_map keeps (orbx::Staged): OneView, the shared form of the one-view calls
 // (orbp_track, orbp_track_source: TrackBlock; orbp_loop_search: LoopBlock), RefreshBlock and FlatBlock (orbp_fuse: FuseBlock; orbp_sim3_search:
-// Sim3Block), LocalVotesBlock and LocalPointsBlock (orbp_local_votes, orbp_local_points; tests/_probe/local_map_host.cpp).  Each layout's stage() goes through
+// Sim3Block), LocalVotesBlock and LocalPointsBlock (orbp_local_votes, orbp_local_points; tests/_probe/local_map_host.cpp) and CullBlock (orbp_cull; tests/_probe/cull_host.cpp).  Each layout's stage() goes through
 // Layout::put: a host array is copied into its slot and named on the device, an absent one is passed through.  Host C++ only:
 // tests/_probe/host_owners.cpp, tests/_probe/refresh_host.cpp, tests/_probe/fuse_host.cpp, tests/_probe/loop_host.cpp and tests/_probe/sim3_host.cpp hold the checks
 // and the layouts against their sizes without a GPU.
@@ -655,6 +655,59 @@ struct LocalPointsBlock {
             std::memcpy(out.list + e, Layout::at(h, list) + e, k * 4);
             std::memcpy(out.skip + e, Layout::at(h, skip) + e, k);
         }
+    }
+};
+
+// ---- key-frame culling over the slot and octave columns (orbp_cull.hip)
+
+constexpr int CULL_WORDS = 8;                          // words of level counts per slot: sixteen 16-bit fields, level l in word l >> 1 at bit 16 * (l & 1)
+// the candidate rows in list order
+struct CullList { const int32_t* cand; int ncand; };
+// the columns with the octave of every feature beside its slot
+struct CullColumns { Columns K; const uint8_t* oct; int nlevels; };
+struct CullOut { int32_t* nmps; int32_t* nred; int32_t* cull; };
+// The handle's scratch.  hist: CULL_WORDS words per slot; dead: one word per slot; both all 0 between calls, the kernels put back what they changed.
+struct CullScratch { uint32_t* hist; uint32_t* dead; };
+struct Cull { Table T; CullList C; CullColumns K; CullScratch S; CullOut O; };
+hipError_t launch_cull(const Cull& a, hipStream_t st);
+
+// The arguments of orbp_cull* that do not need the handle.  on_device: the candidates and the outputs are device memory (alignment is checked);
+// kf_device: the columns are.  Nothing to do (no candidate or no row) passes before the arrays are looked at.
+inline int check_cull(const CullList& C, const CullColumns& K, const CullOut& O, bool on_device, bool kf_device) {
+    if (C.ncand < 0 || C.ncand > ORBP_CULL_MAX_CANDIDATES || !columns_ok(K.K.nkf, K.K.cap) || K.K.nkf > ORBP_LOCAL_MAX_ROWS) return ORBX_ERR_ARG;
+    if (K.nlevels < 1 || K.nlevels > ORBS_MAX_LEVELS) return ORBX_ERR_ARG;
+    if (C.ncand == 0 || K.K.nkf == 0) return ORBX_OK;
+    if (!C.cand || !K.K.slot || !K.oct || !K.K.nt || !O.nmps || !O.nred || !O.cull) return ORBX_ERR_ARG;
+    if (on_device && !words_aligned(C.cand, O.nmps, O.nred, O.cull)) return ORBX_ERR_ARG;
+    if (kf_device && !words_aligned(K.K.slot, K.K.nt)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// The block of orbp_cull, one pinned copy up and one down:
+//   up    [cand | kf_slot | kf_oct | kf_nt]     (absent: the columns when they are on the device)
+//   down  [nmps | nred | cull]
+struct CullBlock {
+    Layout L;
+    Layout::Slot<int32_t> cand, kf_slot, kf_nt, nmps, nred, cull;
+    Layout::Slot<uint8_t> kf_oct;
+    int ncand, nkf;
+    size_t nfeat;                                      // nkf * cap
+    CullBlock(const CullList& C, const CullColumns& K, bool kf_upload) : ncand(C.ncand), nkf(K.K.nkf), nfeat((size_t)K.K.nkf * K.K.cap) {
+        cand = L.add<int32_t>(ncand);
+        kf_slot = L.add<int32_t>(nfeat, kf_upload); kf_oct = L.add<uint8_t>(nfeat, kf_upload); kf_nt = L.add<int32_t>(nkf, kf_upload);
+        L.end_upload();
+        nmps = L.add<int32_t>(ncand); nred = L.add<int32_t>(ncand); cull = L.add<int32_t>(ncand);
+        L.end_download();
+    }
+    void stage(uint8_t* h, uint8_t* d, const CullList& C, const CullColumns& K, CullList& dc, CullColumns& dk, CullOut& dout) const {
+        dc = {Layout::put(h, d, cand, C.cand, ncand), ncand};
+        dk = {{Layout::put(h, d, kf_slot, K.K.slot, nfeat), Layout::put(h, d, kf_nt, K.K.nt, nkf), K.K.nkf, K.K.cap}, Layout::put(h, d, kf_oct, K.oct, nfeat), K.nlevels};
+        dout = {Layout::at(d, nmps), Layout::at(d, nred), Layout::at(d, cull)};
+    }
+    void unpack(uint8_t* h, const CullOut& out) const {
+        std::memcpy(out.nmps, Layout::at(h, nmps), (size_t)ncand * 4);
+        std::memcpy(out.nred, Layout::at(h, nred), (size_t)ncand * 4);
+        std::memcpy(out.cull, Layout::at(h, cull), (size_t)ncand * 4);
     }
 };
 

@@ -26,7 +26,7 @@
 // list -> live -> geometry load each): its latency grows linearly with the list length.
 //
 // The host side of every orbp_* entry point is here too; the kernels of the other modes are k_refresh (orbp_refresh.hip), k_fuse
-// (orbp_fuse.hip), k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip), k_sim3 / k_sim3_agree (orbp_sim3.hip) and the local map's (orbp_local.hip).  Every search ends in search_tail (window search, then
+// (orbp_fuse.hip), k_loop_test / k_loop_pack / k_loop_gather (orbp_loop.hip), k_sim3 / k_sim3_agree (orbp_sim3.hip), the local map's (orbp_local.hip) and the key-frame culling's (orbp_cull.hip).  Every search ends in search_tail (window search, then
 // k_t2source).  The one-view synchronous forms (orbp_track, orbp_track_source, orbp_loop_search) share one_view over the block orbp::OneView
 // of orbp_host.h, where the argument groups, the checks' clauses and the other forms' blocks are.
 #include <hip/hip_runtime.h>
@@ -220,6 +220,8 @@ struct orbp_map {
     orbx::DevBuf geom, desc, d_live, d_tab, scratch;
     orbx::DevBuf lmult, lfirst, ltiles;               // orbp::LocalScratch of orbp_local_* / orbp_rows_purge_device
     bool local_dirty = true;                          // lmult / lfirst are not (known to be) all 0 / all 0xFF: the next call fills them first
+    orbx::DevBuf chist, cdead;                        // orbp::CullScratch of orbp_cull*
+    bool cull_dirty = true;                           // chist / cdead are not (known to be) all 0: the next call fills them first
     orbx::PinnedBuf h_tab;
     orbx::Block block;                                // of the synchronous host forms (orbx::Staged), one at a time under `mu`
     orbx::Stream own;
@@ -420,6 +422,32 @@ int local_points_locked(orbp_map* m, const orbp::Query& Q, int nproblems, const 
     TRY(local_begin(m, st, S));
     HIPCHK(m, orbp::launch_local_points({table_of(m), Q, R, K, S, O}, nproblems, st));
     local_end(m);
+    return ORBX_OK;
+}
+
+// The culling's scratch holds the table's capacity: grown synchronously on the first call, after the device work that may still use it, and filled
+// by the next cull_locked.
+int fit_cull(orbp_map* m) {
+    const size_t hist = (size_t)m->capacity * orbp::CULL_WORDS * 4, dead = (size_t)m->capacity * 4;
+    if (hist > m->chist.size() || dead > m->cdead.size()) {
+        HIPCHK(m, m->chain.wait());
+        m->cull_dirty = true;
+        HIPCHK(m, m->chist.ensure(hist));
+        HIPCHK(m, m->cdead.ensure(dead));
+    }
+    return ORBX_OK;
+}
+
+// Inside the caller's call: the scratch in its between-calls state (local_begin's mechanism: filled on the stream after a grow or a call whose
+// launches failed half way, and dirty on every way out but the last), then the kernels of orbp_cull.hip.
+int cull_locked(orbp_map* m, const orbp::CullList& C, const orbp::CullColumns& K, const orbp::CullOut& O, hipStream_t st) {
+    if (m->cull_dirty && m->chist.size()) {
+        HIPCHK(m, hipMemsetAsync(m->chist.as(), 0, m->chist.size(), st));
+        HIPCHK(m, hipMemsetAsync(m->cdead.as(), 0, m->cdead.size(), st));
+    }
+    m->cull_dirty = true;
+    HIPCHK(m, orbp::launch_cull({table_of(m), C, K, {m->chist.as<uint32_t>(), m->cdead.as<uint32_t>()}, O}, st));
+    m->cull_dirty = false;
     return ORBX_OK;
 }
 
@@ -1008,6 +1036,43 @@ int orbp_rows_purge_device(orbp_map* m, const int32_t* slots, int n, int32_t* d_
     HIPCHK(m, orbp::launch_rows_purge({n, m->d_tab.as<int32_t>(), m->capacity, S.mult, d_kf_slot, (size_t)nkf * cap}, c.st));
     local_end(m);
     return c.end();
+}
+
+int orbp_cull_batch_device(orbp_map* m, const int32_t* d_cand, int ncand, const int32_t* d_kf_slot, const uint8_t* d_kf_oct, const int32_t* d_kf_nt, int nkf,
+                           int cap, int nlevels, int32_t* d_nmps, int32_t* d_nred, int32_t* d_cull, void* stream) {
+    const orbp::CullList C{d_cand, ncand};
+    const orbp::CullColumns K{{d_kf_slot, d_kf_nt, nkf, cap}, d_kf_oct, nlevels};
+    const orbp::CullOut O{d_nmps, d_nred, d_cull};
+    if (!m || orbp::check_cull(C, K, O, true, true) != ORBX_OK) return ORBX_ERR_ARG;
+    if (ncand == 0 || nkf == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    TRY(fit_cull(m));
+    TRY(c.begin());
+    TRY(cull_locked(m, C, K, O, c.st));
+    return c.end();
+}
+
+int orbp_cull(orbp_map* m, const int32_t* cand, int ncand, const int32_t* kf_slot, const uint8_t* kf_oct, const int32_t* kf_nt, int kf_on_device, int nkf,
+              int cap, int nlevels, int32_t* nmps, int32_t* nred, int32_t* cull, void* stream) {
+    const orbp::CullList C{cand, ncand};
+    const orbp::CullColumns K{{kf_slot, kf_nt, nkf, cap}, kf_oct, nlevels};
+    const orbp::CullOut O{nmps, nred, cull};
+    if (!m || orbp::check_cull(C, K, O, false, kf_on_device != 0) != ORBX_OK) return ORBX_ERR_ARG;
+    if (ncand == 0 || nkf == 0) return ORBX_OK;
+    Call c(m, stream);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    TRY(fit_cull(m));
+    const orbp::CullBlock B(C, K, kf_on_device == 0);
+    Staged s(c, m->block, B.L);
+    TRY(s.fit());
+    orbp::CullList dc;
+    orbp::CullColumns dk;
+    orbp::CullOut dout;
+    B.stage(s.h, s.d, C, K, dc, dk, dout);
+    TRY(s.run([&] { return cull_locked(m, dc, dk, dout, c.st); }));
+    B.unpack(s.h, O);
+    return ORBX_OK;
 }
 
 }  // extern "C"
