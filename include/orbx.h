@@ -333,6 +333,54 @@ int orbx_debug_level_size(const orbx_extractor* h, int level, int* w, int* hgt);
 /* how the last launch group built pyramid level `level` (>= 1): form 0 = k_resize (256-px tile columns), 1 = k_resize_strip (full-width row
  * strips of rows_out output rows), 2 = the fused k_pyramid cones of a small launch group; rows_out is 0 unless form is 1 */
 int orbx_debug_resize_form(const orbx_extractor* h, int level, int* form, int* rows_out);
+/* Which kernel variant (template instantiation) each stage of the extractor launched.  Stages: */
+#define ORBX_VS_COLOR        0   /* colour -> gray conversion in front of the pipeline (k_to_gray) */
+#define ORBX_VS_INGEST       1   /* the one-frame call's fetch of the staged frame (k_ingest) */
+#define ORBX_VS_PYRAMID      2   /* k_pyramid cones | k_resize per level (tiled or strip) */
+#define ORBX_VS_FAST         3   /* k_fast_cells | k_fast_blur */
+#define ORBX_VS_QUOTA        4
+#define ORBX_VS_CELL_SELECT  5   /* k_cell_select, then k_cell_select_long in full launch groups with long lists */
+#define ORBX_VS_LEVEL_SELECT 6
+#define ORBX_VS_BLUR         7   /* the stand-alone blur launch (none when the blur rides in k_fast_blur or runs per keypoint window) */
+#define ORBX_VS_DESCRIBE     8   /* k_describe | k_describe_od */
+#define ORBX_VS_COUNT        9
+/* flags of a stage's launch */
+#define ORBX_VF_LDS_OVER_64K  1u  /* the launch asks for more than 64 KiB of dynamic LDS (hipFuncSetAttribute first) */
+#define ORBX_VF_FUSE_BLUR     2u  /* FAST: the blur's short strips ride in the same launch */
+#define ORBX_VF_OVERLAP       4u  /* blur: forked onto the side stream next to the selection kernels */
+#define ORBX_VF_ON_DEMAND     8u  /* describe: the blur per keypoint window inside the kernel */
+#define ORBX_VF_XCD_AFFINITY 16u  /* the launch renumbers its blocks so that a frame's work items share one XCD */
+/* id: the variant of the stage's first launch, in [0, orbx_debug_variant_count(stage)), or -1 when the stage launched nothing; mask: bit v set
+ * for every variant v the stage launched (the pyramid launches one kernel per cone or level, the cell selection up to two) */
+typedef struct orbx_stage_variant {
+    int32_t id;
+    uint32_t flags;
+    uint64_t mask;
+} orbx_stage_variant;
+/* the variant `stage` of the LAST launch group took, and its name (the kernel with its template arguments, for messages; name may be NULL).
+ * A host-side record made when the group was queued: no launch, no synchronisation, no device read.  The parts of a phased call
+ * (orbx_extract_batch_device_phases) add to one record: after the last part it holds every stage of the batch. */
+int orbx_debug_launch_variant(const orbx_extractor* h, int stage, orbx_stage_variant* out, char* name, int name_cap);
+/* host-only: the number of variants of a stage (-1 for an unknown stage), and the name of one ("?" outside the range) */
+int orbx_debug_variant_count(int stage);
+const char* orbx_debug_variant_name(int stage, int id);
+/* host-only (needs no GPU): the variants a launch group of `nframes` w x h frames would take, out[ORBX_VS_COUNT], decided by the same
+ * functions the launches switch on.  The group is described the way the pipeline sees it: its level-0 rows row_stride bytes apart, frames
+ * frame_stride bytes apart (contiguous form) or named by a table (gather != 0; frame_stride ignored), base_bits = the low bits of the OR of
+ * every frame's base address.  color_fmt >= 0 (ORBX_PIX_*): a conversion launch stands in front (color_gather: from a table; color_bits:
+ * the low bits of the OR of its source and destination bases and strides).  one_frame: the orbx_extract form, whose staged frame of
+ * one_frame_bytes bytes k_ingest fetches.  side_stream: the handle has its side stream (default; ORBX_OVERLAP=0 has none). */
+typedef struct orbx_plan_args {
+    int32_t w, h, nframes;
+    int32_t gather, xcd_affinity, on_demand, od_min_frames, stop_after;
+    int64_t row_stride, frame_stride;
+    uint32_t base_bits;
+    int32_t color_fmt, color_gather;
+    uint32_t color_bits;
+    int32_t one_frame, side_stream;
+    int64_t one_frame_bytes;
+} orbx_plan_args;
+int orbx_debug_plan(const orbx_params* p, const orbx_plan_args* a, orbx_stage_variant* out);
 /* copies stage data of `frame` (index inside the last batch) / `level` into host memory; returns bytes or <0 */
 long orbx_debug_fetch(orbx_extractor* h, int what, int frame, int level, void* host_out, long cap_bytes);
 /* evaluate the device arithmetic on arrays (kind 0: fast_atan2(in0,in1)->out0; kind 1: sincos(in0)->out0,out1) */

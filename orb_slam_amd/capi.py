@@ -31,6 +31,7 @@ EXPORTS = [
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_download",
     "orbx_stream_create", "orbx_stream_create_priority", "orbx_stream_destroy", "orbx_stream_synchronize", "orbx_event_create", "orbx_event_destroy", "orbx_event_record",
     "orbx_stream_wait_event", "orbx_device_copy_async", "orbx_host_alloc", "orbx_host_free", "orbx_device_upload_async", "orbx_device_download_async", "orbx_debug_set_stop_after", "orbx_debug_set_blur_on_demand", "orbx_debug_level_size", "orbx_debug_resize_form", "orbx_debug_fetch",
+    "orbx_debug_launch_variant", "orbx_debug_variant_count", "orbx_debug_variant_name", "orbx_debug_plan",
     "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_eval_blur_window", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
     "orbm_debug_set_match_path",
     "orbm_debug_get_match_path",
@@ -86,6 +87,28 @@ class Params(ctypes.Structure):
     _fields_ = [("nfeatures", ctypes.c_int32), ("scale_factor", ctypes.c_float), ("nlevels", ctypes.c_int32),
                 ("score_type", ctypes.c_int32), ("fast_th", ctypes.c_int32), ("device", ctypes.c_int32),
                 ("max_batch", ctypes.c_int32), ("blur_rounding", ctypes.c_int32), ("fp_contract", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+class StageVariant(ctypes.Structure):
+    """orbx_stage_variant: the variant of a stage's first launch (-1: none), ORBX_VF_* flags, bit mask of every variant launched"""
+    _fields_ = [("id", ctypes.c_int32), ("flags", ctypes.c_uint32), ("mask", ctypes.c_uint64)]
+
+
+class PlanArgs(ctypes.Structure):
+    """orbx_plan_args (include/orbx.h)"""
+    _fields_ = [("w", ctypes.c_int32), ("h", ctypes.c_int32), ("nframes", ctypes.c_int32), ("gather", ctypes.c_int32),
+                ("xcd_affinity", ctypes.c_int32), ("on_demand", ctypes.c_int32), ("od_min_frames", ctypes.c_int32), ("stop_after", ctypes.c_int32),
+                ("row_stride", ctypes.c_int64), ("frame_stride", ctypes.c_int64), ("base_bits", ctypes.c_uint32), ("color_fmt", ctypes.c_int32),
+                ("color_gather", ctypes.c_int32), ("color_bits", ctypes.c_uint32), ("one_frame", ctypes.c_int32), ("side_stream", ctypes.c_int32),
+                ("one_frame_bytes", ctypes.c_int64)]
+
+
+# stages of orbx_debug_launch_variant / orbx_debug_plan (ORBX_VS_*) and the flags of a stage's launch (ORBX_VF_*)
+VS_COLOR, VS_INGEST, VS_PYRAMID, VS_FAST, VS_QUOTA, VS_CELL_SELECT, VS_LEVEL_SELECT, VS_BLUR, VS_DESCRIBE, VS_COUNT = range(10)
+VS_NAMES = ["color", "ingest", "pyramid", "fast", "quota", "cell_select", "level_select", "blur", "describe"]
+VF_LDS_OVER_64K, VF_FUSE_BLUR, VF_OVERLAP, VF_ON_DEMAND, VF_XCD_AFFINITY = 1, 2, 4, 8, 16
+XCD_AFFINITY_MIN_FRAMES = 64      # launch groups of at least this many frames renumber their blocks (orbx_internal.h)
+OD_MIN_FRAMES_DEFAULT = 32        # ... of at least this many may blur per keypoint window (ORBX_OD_MIN_FRAMES_DEFAULT)
 
 
 class Camera(ctypes.Structure):
@@ -269,6 +292,12 @@ def lib():
         L.orbx_debug_level_size.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
         if hasattr(L, "orbx_debug_resize_form"):       # (an older library through ORBX_LIB, for an A/B, lacks it)
             L.orbx_debug_resize_form.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        if hasattr(L, "orbx_debug_launch_variant"):    # (likewise)
+            L.orbx_debug_launch_variant.argtypes = [vp, ci, ctypes.POINTER(StageVariant), ctypes.c_char_p, ci]
+            L.orbx_debug_variant_count.argtypes = [ci]
+            L.orbx_debug_variant_name.argtypes = [ci, ci]
+            L.orbx_debug_variant_name.restype = ctypes.c_char_p
+            L.orbx_debug_plan.argtypes = [ctypes.POINTER(Params), ctypes.POINTER(PlanArgs), ctypes.POINTER(StageVariant)]
         L.orbx_debug_fetch.argtypes = [vp, ci, ci, ci, vp, cl]
         L.orbx_debug_fetch.restype = cl
         L.orbx_debug_eval_math.argtypes = [ci, vp, vp, vp, vp, ci, ci]
@@ -650,6 +679,15 @@ class ORBextractor:
             raise OrbxError(rc, "orbx_debug_resize_form")
         return form.value, rows.value
 
+    def launch_variant(self, stage):
+        """(id, flags, mask, name) of stage VS_* in the last launch group: the variant of its first launch (-1 and "" when the stage launched
+        nothing), VF_* flags, the bit mask of every variant it launched, the kernel's name with its template arguments"""
+        v, name = StageVariant(), ctypes.create_string_buffer(96)
+        rc = self.L.orbx_debug_launch_variant(self.h, stage, ctypes.byref(v), name, len(name))
+        if rc != ORBX_OK:
+            raise OrbxError(rc, "orbx_debug_launch_variant")
+        return v.id, v.flags, v.mask, name.value.decode()
+
     def fetch_plane(self, what, level, frame=0):
         w, hh = self.level_size(level)
         out = np.empty((hh, w), dtype=np.uint8)
@@ -789,6 +827,40 @@ def geometry(w, h, nfeatures=1000, scaleFactor=1.2, nlevels=8, scoreType=FAST_SC
         raise OrbxError(rc, "orbx_debug_geometry")
     keys = ("w", "h", "quota", "grid_cols", "grid_rows", "cell_w", "cell_h", "n_bands")
     return [dict(zip(keys, map(int, out[l]))) for l in range(rc)]
+
+
+def variant_count(stage):
+    """number of kernel variants of stage VS_* (no GPU needed)"""
+    return lib().orbx_debug_variant_count(stage)
+
+
+def variant_name(stage, vid):
+    """the kernel with its template arguments behind variant `vid` of stage VS_*"""
+    return lib().orbx_debug_variant_name(stage, vid).decode()
+
+
+def plan(w, h, nframes, row_stride=None, frame_stride=None, base_bits=0, gather=False, xcd_affinity=None, on_demand=1, od_min_frames=OD_MIN_FRAMES_DEFAULT,
+         stop_after=-1, color_fmt=-1, color_gather=False, color_bits=0, one_frame=False, one_frame_bytes=0, side_stream=True,
+         nfeatures=1000, scaleFactor=1.2, nlevels=8, scoreType=FAST_SCORE, fastTh=20, fp_contract=False):
+    """orbx_debug_plan (no GPU needed): the variants a launch group of nframes w x h frames would take, a list of (id, flags, mask) per stage
+    VS_*, or raises OrbxError.  Defaults: packed rows and frames, an aligned base, the affinity a handle gives a group of that size."""
+    L = lib()
+    p = Params()
+    L.orbx_default_params(ctypes.byref(p))
+    p.nfeatures, p.scale_factor, p.nlevels, p.score_type, p.fast_th, p.fp_contract = nfeatures, scaleFactor, nlevels, scoreType, fastTh, 1 if fp_contract else 0
+    a = PlanArgs()
+    a.w, a.h, a.nframes, a.gather = w, h, nframes, 1 if gather else 0
+    a.xcd_affinity = (1 if nframes >= XCD_AFFINITY_MIN_FRAMES else 0) if xcd_affinity is None else int(xcd_affinity)
+    a.on_demand, a.od_min_frames, a.stop_after = int(on_demand), od_min_frames, stop_after
+    a.row_stride = w if row_stride is None else row_stride
+    a.frame_stride = a.row_stride * h if frame_stride is None else frame_stride
+    a.base_bits, a.color_fmt, a.color_gather, a.color_bits = base_bits, color_fmt, 1 if color_gather else 0, color_bits
+    a.one_frame, a.side_stream, a.one_frame_bytes = 1 if one_frame else 0, 1 if side_stream else 0, one_frame_bytes
+    out = (StageVariant * VS_COUNT)()
+    rc = L.orbx_debug_plan(ctypes.byref(p), ctypes.byref(a), out)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_debug_plan")
+    return [(v.id, v.flags, v.mask) for v in out]
 
 
 def nth_element_perm(resp, nth, device=0):

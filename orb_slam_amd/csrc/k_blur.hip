@@ -339,25 +339,36 @@ __global__ __launch_bounds__(MB_WAVES * 64) void k_blur_mfma(Batch b) {      // 
 }
 
 
-int launch_blur(const Batch& b, const HostGeom& hg, hipStream_t st) {
+// The stand-alone blur launch of a launch group of PYR_FUSED_MAX_FRAMES frames or more (smaller groups blur inside k_fast_blur, with
+// BLUR_ROWS_SMALL-row strips, or per keypoint window: launch_extract never comes here for them).
+StagePlan plan_blur(const Batch& b, const HostGeom& hg) {
     const DevGeom& g = hg.g;
-    const int F = b.nframes;
     const bool aligned = (level0_bits(b) & 3) == 0;
-    if (F < PYR_FUSED_MAX_FRAMES) {   // short strips: 4x the waves, a quarter of the serial row chain each
-        const int nblk = frame_item_blocks(b, (g.nbtiles_total_s + BLUR_WAVES - 1) / BLUR_WAVES);
-        if (aligned) hipLaunchKernelGGL((b.img_tab ? k_blur_gather<true, BLUR_ROWS_SMALL> : k_blur<true, BLUR_ROWS_SMALL>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
-        else hipLaunchKernelGGL((b.img_tab ? k_blur_gather<false, BLUR_ROWS_SMALL> : k_blur<false, BLUR_ROWS_SMALL>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
-    } else if (ORBX_BLUR_MFMA && !b.img_tab && aligned && ((b.img_row_stride | b.img_frame_stride) & 15) == 0 && (g.lv[0].w <= MB_MAX_WIDTH || ORBX_BLUR_MFMA > 1)) {
-        // (gather launch groups take k_blur_gather: same outputs; full groups blur per keypoint window in k_describe_od anyway)
-        // full launch groups whose frames can be staged in whole 16-byte chunks: the filter as int8 matrix products.  Measured
-        // (NOTES.md 9.2): 0.50 against 0.55 ms per 1024 VGA frames and half the VALU instructions, which the lanes next to it pick
-        // up (+1.5 % frames/s); on 1920-byte rows its 96-byte row pieces lose to k_blur's 256-byte ones (0.88 against 0.78 ms per
-        // 256 1080p frames), so wide levels keep k_blur
-        hipLaunchKernelGGL(k_blur_mfma, dim3(frame_item_blocks(b, (g.nmb_total + MB_WAVES - 1) / MB_WAVES)), dim3(MB_WAVES * 64), 0, st, b);
-    } else {
-        const int nblk = frame_item_blocks(b, (g.nbtiles_total + BLUR_WAVES - 1) / BLUR_WAVES);
-        if (aligned) hipLaunchKernelGGL((b.img_tab ? k_blur_gather<true, BLUR_ROWS> : k_blur<true, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
-        else hipLaunchKernelGGL((b.img_tab ? k_blur_gather<false, BLUR_ROWS> : k_blur<false, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b);
+    // full launch groups whose frames can be staged in whole 16-byte chunks: the filter as int8 matrix products.  Measured
+    // (NOTES.md 9.2): 0.50 against 0.55 ms per 1024 VGA frames and half the VALU instructions, which the lanes next to it pick
+    // up (+1.5 % frames/s); on 1920-byte rows its 96-byte row pieces lose to k_blur's 256-byte ones (0.88 against 0.78 ms per
+    // 256 1080p frames), so wide levels keep k_blur
+    // (gather launch groups take k_blur_gather: same outputs; full groups blur per keypoint window in k_describe_od anyway)
+    if (ORBX_BLUR_MFMA && !b.img_tab && aligned && ((b.img_row_stride | b.img_frame_stride) & 15) == 0 && (g.lv[0].w <= MB_MAX_WIDTH || ORBX_BLUR_MFMA > 1))
+        return stage_plan(BV_MFMA);
+    return stage_plan((aligned ? BV_ALIGNED : 0) | (b.img_tab ? BV_GATHER : 0));
+}
+const char* blur_variant_name(int id) {
+    static const char* const names[BV_COUNT] = {"k_blur<false, BLUR_ROWS>", "k_blur<true, BLUR_ROWS>", "k_blur_gather<false, BLUR_ROWS>",
+                                                "k_blur_gather<true, BLUR_ROWS>", "k_blur_mfma"};
+    return id >= 0 && id < BV_COUNT ? names[id] : "?";
+}
+
+int launch_blur(const Batch& b, const HostGeom& hg, hipStream_t st, const StagePlan& plan) {
+    const DevGeom& g = hg.g;
+    const int nblk = frame_item_blocks(b, (g.nbtiles_total + BLUR_WAVES - 1) / BLUR_WAVES);
+    switch (plan.id) {
+        case 0: hipLaunchKernelGGL((k_blur<false, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b); break;
+        case BV_ALIGNED: hipLaunchKernelGGL((k_blur<true, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b); break;
+        case BV_GATHER: hipLaunchKernelGGL((k_blur_gather<false, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b); break;
+        case BV_GATHER | BV_ALIGNED: hipLaunchKernelGGL((k_blur_gather<true, BLUR_ROWS>), dim3(nblk), dim3(BLUR_WAVES * 64), 0, st, b); break;
+        case BV_MFMA: hipLaunchKernelGGL(k_blur_mfma, dim3(frame_item_blocks(b, (g.nmb_total + MB_WAVES - 1) / MB_WAVES)), dim3(MB_WAVES * 64), 0, st, b); break;
+        default: return ORBX_ERR_ARG;
     }
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;

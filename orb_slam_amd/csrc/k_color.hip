@@ -83,41 +83,59 @@ __global__ __launch_bounds__(256) void k_to_gray(ColorArgs a) {
     }
 }
 
-template <int CH, bool BGR, bool GATHER>
-static void launch_to_gray_t(const ColorArgs& a, bool aligned, dim3 grid, hipStream_t stream) {
-    if (aligned) hipLaunchKernelGGL((k_to_gray<CH, BGR, true, GATHER>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((k_to_gray<CH, BGR, false, GATHER>), grid, dim3(256), 0, stream, a);
+// The variant of (format, alignment, source form): orbx_launch.h's ColorVariant numbering, which counts on the formats being 0 .. 4 in
+// the order gray, RGB, BGR, RGBA, BGRA.  Also the case labels of launch_to_gray's switch.
+static_assert(ORBX_PIX_GRAY8 == 0 && ORBX_PIX_RGB8 == 1 && ORBX_PIX_BGR8 == 2 && ORBX_PIX_RGBA8 == 3 && ORBX_PIX_BGRA8 == 4, "ColorVariant numbering");
+constexpr int color_variant(int fmt, bool aligned, bool gather) {
+    return (gather ? CV_GATHER0 + 2 * (fmt - ORBX_PIX_RGB8) : 2 * fmt) + (aligned ? 1 : 0);
+}
+static_assert(color_variant(ORBX_PIX_BGRA8, true, false) + 1 == CV_GATHER0 && color_variant(ORBX_PIX_BGRA8, true, true) + 1 == CV_COUNT, "ColorVariant numbering");
+// fmt: ORBX_PIX_*; a table of gray frames has no conversion (the pipeline reads it itself): id -1
+StagePlan plan_to_gray(const ColorArgs& a, int fmt) {
+    if (pix_channels(fmt) == 0 || (a.tab && fmt == ORBX_PIX_GRAY8)) return StagePlan();
+    const unsigned long long bits = (a.tab ? a.tab_bits : ((uintptr_t)a.src | (unsigned long long)a.src_row_stride | (unsigned long long)a.src_frame_stride)) |
+                                    (uintptr_t)a.dst | (uintptr_t)a.dst2 | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride;
+    return stage_plan(color_variant(fmt, (bits & 15) == 0, a.tab != nullptr));
+}
+const char* color_variant_name(int id) {
+    static const char* const names[CV_COUNT] = {
+        "k_to_gray<1, false, false, false>", "k_to_gray<1, false, true, false>", "k_to_gray<3, false, false, false>", "k_to_gray<3, false, true, false>",
+        "k_to_gray<3, true, false, false>", "k_to_gray<3, true, true, false>", "k_to_gray<4, false, false, false>", "k_to_gray<4, false, true, false>",
+        "k_to_gray<4, true, false, false>", "k_to_gray<4, true, true, false>",
+        "k_to_gray<3, false, false, true>", "k_to_gray<3, false, true, true>", "k_to_gray<3, true, false, true>", "k_to_gray<3, true, true, true>",
+        "k_to_gray<4, false, false, true>", "k_to_gray<4, false, true, true>", "k_to_gray<4, true, false, true>", "k_to_gray<4, true, true, true>"};
+    return id >= 0 && id < CV_COUNT ? names[id] : "?";
 }
 
-template <bool GATHER>
-static void launch_to_gray_fmt(const ColorArgs& a, int fmt, bool aligned, dim3 grid, hipStream_t stream) {
-    switch (fmt) {
-        case ORBX_PIX_GRAY8: launch_to_gray_t<1, false, GATHER>(a, aligned, grid, stream); break;
-        case ORBX_PIX_RGB8: launch_to_gray_t<3, false, GATHER>(a, aligned, grid, stream); break;
-        case ORBX_PIX_BGR8: launch_to_gray_t<3, true, GATHER>(a, aligned, grid, stream); break;
-        case ORBX_PIX_RGBA8: launch_to_gray_t<4, false, GATHER>(a, aligned, grid, stream); break;
-        default: launch_to_gray_t<4, true, GATHER>(a, aligned, grid, stream); break;
-    }
-}
-
-int launch_to_gray(const ColorArgs& args, int nframes, int fmt, hipStream_t stream) {
+int launch_to_gray(const ColorArgs& args, int nframes, int fmt, hipStream_t stream, StagePlan* report) {
+    if (report) *report = StagePlan();
     if (nframes <= 0 || args.w <= 0 || args.h <= 0) return ORBX_OK;
     ColorArgs a = args;
     a.cpr = (a.w + 15) / 16;
     const long long items = (long long)a.cpr * a.h;
     if (items >= (1ll << 31) - 256) return ORBX_ERR_ARG;
     a.items = (int)items;
-    const unsigned long long bits = (a.tab ? a.tab_bits : ((uintptr_t)a.src | (unsigned long long)a.src_row_stride | (unsigned long long)a.src_frame_stride)) |
-                                    (uintptr_t)a.dst | (uintptr_t)a.dst2 | (unsigned long long)a.dst_row_stride | (unsigned long long)a.dst_frame_stride;
-    const bool aligned = (bits & 15) == 0;
+    const StagePlan plan = plan_to_gray(a, fmt);
+    if (plan.id < 0) return ORBX_ERR_ARG;
     constexpr int MAX_Y = 32768;                         // frames per launch (grid.y)
     for (int f0 = 0; f0 < nframes; f0 += MAX_Y) {
         a.f0 = args.f0 + f0;
         const dim3 grid((unsigned)((items + 255) / 256), (unsigned)std::min(MAX_Y, nframes - f0));
-        if (a.tab) launch_to_gray_fmt<true>(a, fmt, aligned, grid, stream);
-        else launch_to_gray_fmt<false>(a, fmt, aligned, grid, stream);
+#define ORBX_TO_GRAY_CASES(FMT, CH, BGR, GA)                                                                                                            \
+    case color_variant(FMT, false, GA): hipLaunchKernelGGL((k_to_gray<CH, BGR, false, GA>), grid, dim3(256), 0, stream, a); break;                \
+    case color_variant(FMT, true, GA): hipLaunchKernelGGL((k_to_gray<CH, BGR, true, GA>), grid, dim3(256), 0, stream, a); break;
+        switch (plan.id) {
+            ORBX_TO_GRAY_CASES(ORBX_PIX_GRAY8, 1, false, false)
+            ORBX_TO_GRAY_CASES(ORBX_PIX_RGB8, 3, false, false) ORBX_TO_GRAY_CASES(ORBX_PIX_BGR8, 3, true, false)
+            ORBX_TO_GRAY_CASES(ORBX_PIX_RGBA8, 4, false, false) ORBX_TO_GRAY_CASES(ORBX_PIX_BGRA8, 4, true, false)
+            ORBX_TO_GRAY_CASES(ORBX_PIX_RGB8, 3, false, true) ORBX_TO_GRAY_CASES(ORBX_PIX_BGR8, 3, true, true)
+            ORBX_TO_GRAY_CASES(ORBX_PIX_RGBA8, 4, false, true) ORBX_TO_GRAY_CASES(ORBX_PIX_BGRA8, 4, true, true)
+            default: return ORBX_ERR_ARG;
+        }
+#undef ORBX_TO_GRAY_CASES
         ORBX_LAUNCH_CHECK();
     }
+    if (report) *report = plan;
     return ORBX_OK;
 }
 

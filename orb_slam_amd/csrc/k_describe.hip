@@ -333,11 +333,27 @@ template <bool FMA>
 __global__ __launch_bounds__(DESC_WAVES * 64) void k_describe_gather(Batch b) { k_describe_body<FMA, true>(b); }
 
 
-int launch_describe(const Batch& b, const HostGeom& hg, hipStream_t stream) {
+// on_demand: the blur per keypoint window inside the kernel (k_describe_od.hip), decided by launch_extract
+StagePlan plan_describe(const Batch& b, const HostGeom& hg, bool on_demand) {
+    return stage_plan((hg.g.fp_contract ? DV_FMA : 0) | (b.img_tab ? DV_GATHER : 0) | (on_demand ? DV_OD : 0), on_demand ? ORBX_VF_ON_DEMAND : 0u);
+}
+const char* describe_variant_name(int id) {
+    static const char* const names[DV_COUNT] = {"k_describe<false>", "k_describe<true>", "k_describe_gather<false>", "k_describe_gather<true>",
+                                                "k_describe_od<false>", "k_describe_od<true>", "k_describe_od_gather<false>", "k_describe_od_gather<true>"};
+    return id >= 0 && id < DV_COUNT ? names[id] : "?";
+}
+
+int launch_describe(const Batch& b, const HostGeom& hg, hipStream_t stream, const StagePlan& plan) {
+    if (plan.id & DV_OD) return launch_describe_od(b, hg, stream, plan.id);
     const DevGeom& g = hg.g;
     const dim3 grid(frame_item_blocks(b, (g.nquads + DESC_WAVES - 1) / DESC_WAVES)), block(DESC_WAVES * 64);
-    if (g.fp_contract) hipLaunchKernelGGL(b.img_tab ? k_describe_gather<true> : k_describe<true>, grid, block, 0, stream, b);
-    else hipLaunchKernelGGL(b.img_tab ? k_describe_gather<false> : k_describe<false>, grid, block, 0, stream, b);
+    switch (plan.id) {
+        case 0: hipLaunchKernelGGL(k_describe<false>, grid, block, 0, stream, b); break;
+        case DV_FMA: hipLaunchKernelGGL(k_describe<true>, grid, block, 0, stream, b); break;
+        case DV_GATHER: hipLaunchKernelGGL(k_describe_gather<false>, grid, block, 0, stream, b); break;
+        case DV_GATHER | DV_FMA: hipLaunchKernelGGL(k_describe_gather<true>, grid, block, 0, stream, b); break;
+        default: return ORBX_ERR_ARG;
+    }
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }

@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "orbx_device.h"
+#include "orbx_launch.h"
 
 namespace orbx {
 
@@ -586,11 +587,17 @@ bool describe_od_supported(const Batch& b, const HostGeom& hg) {
     return wlim0 >= 64 && wlim0 >= g.lv[0].w;
 }
 
-int launch_describe_od(const Batch& b, const HostGeom& hg, hipStream_t stream) {
+// (launch_describe's on-demand half: `variant` is its DV_OD | ... choice)
+int launch_describe_od(const Batch& b, const HostGeom& hg, hipStream_t stream, int variant) {
     const DevGeom& g = hg.g;
     const dim3 grid(frame_item_blocks(b, (g.nquads + OD_WAVES - 1) / OD_WAVES)), block(OD_WAVES * 64);
-    if (g.fp_contract) hipLaunchKernelGGL(b.img_tab ? k_describe_od_gather<true> : k_describe_od<true>, grid, block, 0, stream, b);
-    else hipLaunchKernelGGL(b.img_tab ? k_describe_od_gather<false> : k_describe_od<false>, grid, block, 0, stream, b);
+    switch (variant) {
+        case DV_OD: hipLaunchKernelGGL(k_describe_od<false>, grid, block, 0, stream, b); break;
+        case DV_OD | DV_FMA: hipLaunchKernelGGL(k_describe_od<true>, grid, block, 0, stream, b); break;
+        case DV_OD | DV_GATHER: hipLaunchKernelGGL(k_describe_od_gather<false>, grid, block, 0, stream, b); break;
+        case DV_OD | DV_GATHER | DV_FMA: hipLaunchKernelGGL(k_describe_od_gather<true>, grid, block, 0, stream, b); break;
+        default: return ORBX_ERR_ARG;
+    }
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 

@@ -478,37 +478,61 @@ template <bool ALIGNED, bool SMALL>
 __global__ __launch_bounds__(SMALL ? FAST_SMALL.threads : FAST_LARGE.threads) void k_fast_blur_gather(Batch b) { k_fast_blur_body<ALIGNED, SMALL, true>(b); }
 
 
-// (launch_extract's FAST stage.  fuse_blur: the blur's short strips ride in the same launch)
-int launch_fast(const Batch& b, const HostGeom& hg, hipStream_t stream, bool fuse_blur) {
+// launch_extract's FAST stage: which of the sixteen entry points (orbx_launch.h: FastVariant), then the launch that switches on it.
+// fuse_blur: the blur's short strips ride in the same launch
+StagePlan plan_fast(const Batch& b, const HostGeom& hg, bool fuse_blur) {
+    const DevGeom& g = hg.g;
+    const bool aligned = (level0_bits(b) & 3) == 0;
+    return stage_plan((aligned ? FV_ALIGNED : 0) | (g.fast_small ? FV_SMALL : 0) | (b.img_tab ? FV_GATHER : 0) | (fuse_blur ? FV_BLUR : 0),
+                      (g.fast_lds_bytes > 64 * 1024 ? ORBX_VF_LDS_OVER_64K : 0u) | (fuse_blur ? ORBX_VF_FUSE_BLUR : 0u));
+}
+const char* fast_variant_name(int id) {
+    static const char* const names[FV_COUNT] = {
+        "k_fast_cells<false, FAST_LARGE>", "k_fast_cells<true, FAST_LARGE>", "k_fast_cells<false, FAST_SMALL>", "k_fast_cells<true, FAST_SMALL>",
+        "k_fast_cells_gather<false, FAST_LARGE>", "k_fast_cells_gather<true, FAST_LARGE>", "k_fast_cells_gather<false, FAST_SMALL>", "k_fast_cells_gather<true, FAST_SMALL>",
+        "k_fast_blur<false, false>", "k_fast_blur<true, false>", "k_fast_blur<false, true>", "k_fast_blur<true, true>",
+        "k_fast_blur_gather<false, false>", "k_fast_blur_gather<true, false>", "k_fast_blur_gather<false, true>", "k_fast_blur_gather<true, true>"};
+    return id >= 0 && id < FV_COUNT ? names[id] : "?";
+}
+
+int launch_fast(const Batch& b, const HostGeom& hg, hipStream_t stream, const StagePlan& plan) {
     const DevGeom& g = hg.g;
     const int F = b.nframes;
-    const bool aligned = (level0_bits(b) & 3) == 0;
     const size_t lds = (size_t)g.fast_lds_bytes;
+    const bool big_lds = (plan.flags & ORBX_VF_LDS_OVER_64K) != 0;
     auto launch = [&](auto kern, int threads) -> bool {
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        if (big_lds && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
         hipLaunchKernelGGL(kern, dim3(frame_item_blocks(b, g.nbands_total)), dim3(threads), lds, stream, b);
         return true;
     };
     constexpr FastShape A = FAST_SMALL, B = FAST_LARGE;
+    const int threads = (plan.id & FV_SMALL) ? A.threads : B.threads;
+    const int per_frame = (g.nbtiles_total_s + threads / 64 - 1) / (threads / 64) + g.nbands_total;
+    auto launch2 = [&](auto kern) -> bool {       // the blur's short strips ride in front of every frame's bands
+        if (big_lds && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        hipLaunchKernelGGL(kern, dim3(F * per_frame), dim3(threads), lds, stream, b);
+        return true;
+    };
     bool ok;
-    if (fuse_blur) {
-        const int threads = g.fast_small ? A.threads : B.threads;
-        const int per_frame = (g.nbtiles_total_s + threads / 64 - 1) / (threads / 64) + g.nbands_total;
-        auto launch2 = [&](auto kern) -> bool {
-            if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-            hipLaunchKernelGGL(kern, dim3(F * per_frame), dim3(threads), lds, stream, b);
-            return true;
-        };
-        if (b.img_tab) {
-            if (g.fast_small) ok = aligned ? launch2(k_fast_blur_gather<true, true>) : launch2(k_fast_blur_gather<false, true>);
-            else ok = aligned ? launch2(k_fast_blur_gather<true, false>) : launch2(k_fast_blur_gather<false, false>);
-        } else if (g.fast_small) ok = aligned ? launch2(k_fast_blur<true, true>) : launch2(k_fast_blur<false, true>);
-        else ok = aligned ? launch2(k_fast_blur<true, false>) : launch2(k_fast_blur<false, false>);
-    } else if (b.img_tab) {
-        if (g.fast_small) ok = aligned ? launch(k_fast_cells_gather<true, A.threads, A.ppt>, A.threads) : launch(k_fast_cells_gather<false, A.threads, A.ppt>, A.threads);
-        else ok = aligned ? launch(k_fast_cells_gather<true, B.threads, B.ppt>, B.threads) : launch(k_fast_cells_gather<false, B.threads, B.ppt>, B.threads);
-    } else if (g.fast_small) ok = aligned ? launch(k_fast_cells<true, A.threads, A.ppt>, A.threads) : launch(k_fast_cells<false, A.threads, A.ppt>, A.threads);
-    else ok = aligned ? launch(k_fast_cells<true, B.threads, B.ppt>, B.threads) : launch(k_fast_cells<false, B.threads, B.ppt>, B.threads);
+    switch (plan.id) {
+        case 0: ok = launch(k_fast_cells<false, B.threads, B.ppt>, B.threads); break;
+        case FV_ALIGNED: ok = launch(k_fast_cells<true, B.threads, B.ppt>, B.threads); break;
+        case FV_SMALL: ok = launch(k_fast_cells<false, A.threads, A.ppt>, A.threads); break;
+        case FV_SMALL | FV_ALIGNED: ok = launch(k_fast_cells<true, A.threads, A.ppt>, A.threads); break;
+        case FV_GATHER: ok = launch(k_fast_cells_gather<false, B.threads, B.ppt>, B.threads); break;
+        case FV_GATHER | FV_ALIGNED: ok = launch(k_fast_cells_gather<true, B.threads, B.ppt>, B.threads); break;
+        case FV_GATHER | FV_SMALL: ok = launch(k_fast_cells_gather<false, A.threads, A.ppt>, A.threads); break;
+        case FV_GATHER | FV_SMALL | FV_ALIGNED: ok = launch(k_fast_cells_gather<true, A.threads, A.ppt>, A.threads); break;
+        case FV_BLUR: ok = launch2(k_fast_blur<false, false>); break;
+        case FV_BLUR | FV_ALIGNED: ok = launch2(k_fast_blur<true, false>); break;
+        case FV_BLUR | FV_SMALL: ok = launch2(k_fast_blur<false, true>); break;
+        case FV_BLUR | FV_SMALL | FV_ALIGNED: ok = launch2(k_fast_blur<true, true>); break;
+        case FV_BLUR | FV_GATHER: ok = launch2(k_fast_blur_gather<false, false>); break;
+        case FV_BLUR | FV_GATHER | FV_ALIGNED: ok = launch2(k_fast_blur_gather<true, false>); break;
+        case FV_BLUR | FV_GATHER | FV_SMALL: ok = launch2(k_fast_blur_gather<false, true>); break;
+        case FV_BLUR | FV_GATHER | FV_SMALL | FV_ALIGNED: ok = launch2(k_fast_blur_gather<true, true>); break;
+        default: return ORBX_ERR_ARG;
+    }
     if (!ok) return ORBX_ERR_DEVICE;
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;

@@ -441,71 +441,92 @@ int resize_form(const Batch& b, const HostGeom& hg, int level, StripChoice& sc) 
 }
 
 template <int NG>
-static void launch_resize_strip(const Batch& b, int l, const StripChoice& sc, hipStream_t stream) {
+static void launch_resize_strip(const Batch& b, int l, const StripChoice& sc, bool gather, hipStream_t stream) {
     const LevelGeom& L = b.g.lv[l];
     const int nstrips = rzs_strips(L.h, sc.rows_out);
     const unsigned magic = frame_item_magic_of(nstrips);
     dim3 grid(frame_item_blocks(b, nstrips));
-    const resize_strip_fn fn = b.img_tab && l == 1 ? static_cast<resize_strip_fn>(&k_resize_gather<NG>) : static_cast<resize_strip_fn>(&k_resize<NG>);
+    const resize_strip_fn fn = gather ? static_cast<resize_strip_fn>(&k_resize_gather<NG>) : static_cast<resize_strip_fn>(&k_resize<NG>);
     hipLaunchKernelGGL(fn, grid, dim3(256), (size_t)sc.lds_bytes, stream, b, l, sc.rows_out, nstrips, magic);
 }
 
-// (launch_extract's pyramid stage; the per-frame status fill that rides on it stays with the caller)
-int launch_pyramid(const Batch& b, const HostGeom& hg, hipStream_t stream) {
+// The launches of the pyramid stage, in order (orbx_launch.h).  Fused cones when the batch is too small to fill the chip (the drop-in call: one
+// frame): there the chain of dependent launches is the cost (189 vs 236 us per VGA frame); a full batch prefers the leaner per-level kernels
+// (0.72 vs 0.81 ms per 1024 frames: the cones recompute their overlap and synchronise per level).
+PyramidPlan plan_pyramid(const Batch& b, const HostGeom& hg) {
     const DevGeom& g = hg.g;
-    const int F = b.nframes;
-    const bool fused_pyramid = g.npyr_groups > 0 && F < PYR_FUSED_MAX_FRAMES;
     const bool al0 = (level0_bits(b) & 3) == 0;
-    // Fused launches when the batch is too small to fill the chip (the drop-in call: one frame): there the chain of dependent
-    // launches is the cost (189 vs 236 us per VGA frame); a full batch prefers the leaner per-level kernels (0.72 vs 0.81 ms per 1024
-    // frames: the cones recompute their overlap and synchronise per level).
-    if (fused_pyramid) {
+    PyramidPlan p;
+    StripChoice sc;
+    if (g.nlevels > 1 && resize_form(b, hg, 1, sc) == RZ_FORM_FUSED) {
         for (int gi = 0; gi < g.npyr_groups; gi++) {
-            const PyrGroup& pg = g.pyr[gi];
-            const bool al = pg.l0 > 0 || al0;
-            dim3 grid(pg.ntx, pg.nty, F);
-            if (b.img_tab && pg.l0 == 0) {     // (gather form: only the cone that starts at level 0 reads the caller's frames)
-                if (al) hipLaunchKernelGGL((k_pyramid<true, true>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
-                else hipLaunchKernelGGL((k_pyramid<false, true>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
-            } else if (al) hipLaunchKernelGGL((k_pyramid<true, false>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
-            else hipLaunchKernelGGL((k_pyramid<false, false>), grid, dim3(256), (size_t)pg.lds_bytes, stream, b, gi);
-            ORBX_LAUNCH_CHECK();
+            const bool first = g.pyr[gi].l0 == 0;       // (gather form: only the cone that starts at level 0 reads the caller's frames)
+            p.launch[p.n++] = PyramidLaunch{PV_PYRAMID0 + ((!first || al0) ? 1 : 0) + ((b.img_tab && first) ? 2 : 0), gi, StripChoice{0, 0}};
         }
-    } else {
-        for (int l = 1; l < g.nlevels; l++) {
+        return p;
+    }
+    for (int l = 1; l < g.nlevels; l++) {
+        const LevelGeom& L = g.lv[l];
+        const bool gather = b.img_tab && l == 1;        // (gather form: level 1 is the one resized from the caller's frames)
+        if (resize_form(b, hg, l, sc) == RZ_FORM_STRIP) {
+            const int ng = rzs_groups(L.w);             // groups of 64 dword columns: up to four keep their column constants in registers
+            p.launch[p.n++] = PyramidLaunch{(gather ? PV_STRIP_GATHER0 : PV_STRIP0) + (ng <= 4 ? ng : 0), l, sc};
+        } else
+            p.launch[p.n++] = PyramidLaunch{PV_TILED0 + ((l > 1 || al0) ? 1 : 0) + (L.rz_window ? 2 : 0) + (gather ? 4 : 0), l, StripChoice{0, 0}};
+    }
+    return p;
+}
+const char* pyramid_variant_name(int id) {
+    static const char* const names[PV_COUNT] = {
+        "k_pyramid<false, false>", "k_pyramid<true, false>", "k_pyramid<false, true>", "k_pyramid<true, true>",
+        "k_resize<false, false>", "k_resize<true, false>", "k_resize<false, true>", "k_resize<true, true>",
+        "k_resize_gather<false, false>", "k_resize_gather<true, false>", "k_resize_gather<false, true>", "k_resize_gather<true, true>",
+        "k_resize<0>", "k_resize<1>", "k_resize<2>", "k_resize<3>", "k_resize<4>",
+        "k_resize_gather<0>", "k_resize_gather<1>", "k_resize_gather<2>", "k_resize_gather<3>", "k_resize_gather<4>"};
+    return id >= 0 && id < PV_COUNT ? names[id] : "?";
+}
+
+// (launch_extract's pyramid stage; the per-frame status fill that rides on it stays with the caller)
+int launch_pyramid(const Batch& b, const PyramidPlan& plan, hipStream_t stream) {
+    const DevGeom& g = b.g;
+    for (int i = 0; i < plan.n; i++) {
+        const PyramidLaunch& pl = plan.launch[i];
+        if (pl.variant < PV_TILED0) {
+            const PyrGroup& pg = g.pyr[pl.index];
+            const dim3 grid(pg.ntx, pg.nty, b.nframes);
+            const size_t lds = (size_t)pg.lds_bytes;
+            switch (pl.variant - PV_PYRAMID0) {
+                case 0: hipLaunchKernelGGL((k_pyramid<false, false>), grid, dim3(256), lds, stream, b, pl.index); break;
+                case 1: hipLaunchKernelGGL((k_pyramid<true, false>), grid, dim3(256), lds, stream, b, pl.index); break;
+                case 2: hipLaunchKernelGGL((k_pyramid<false, true>), grid, dim3(256), lds, stream, b, pl.index); break;
+                default: hipLaunchKernelGGL((k_pyramid<true, true>), grid, dim3(256), lds, stream, b, pl.index); break;
+            }
+        } else if (pl.variant < PV_STRIP0) {
+            const int l = pl.index;
             const LevelGeom& L = g.lv[l];
-            StripChoice sc;
-            if (resize_form(b, hg, l, sc) == RZ_FORM_STRIP) {
-                switch (rzs_groups(L.w)) {      // groups of 64 dword columns: up to four keep their column constants in registers
-                    case 1: launch_resize_strip<1>(b, l, sc, stream); break;
-                    case 2: launch_resize_strip<2>(b, l, sc, stream); break;
-                    case 3: launch_resize_strip<3>(b, l, sc, stream); break;
-                    case 4: launch_resize_strip<4>(b, l, sc, stream); break;
-                    default: launch_resize_strip<0>(b, l, sc, stream); break;
-                }
-                ORBX_LAUNCH_CHECK();
-                continue;
-            }
-            dim3 grid(frame_item_blocks(b, ((L.w + 255) / 256) * ((L.h + RZ_ROWS - 1) / RZ_ROWS)));
-            const bool al = l > 1 || al0;
+            const dim3 grid(frame_item_blocks(b, ((L.w + 255) / 256) * ((L.h + RZ_ROWS - 1) / RZ_ROWS)));
             const size_t lds = (size_t)L.rz_pitch * L.rz_rows;
-            if (b.img_tab && l == 1) {        // (gather form: level 1 is the one resized from the caller's frames)
-                if (L.rz_window) {
-                    if (al) hipLaunchKernelGGL((k_resize_gather<true, true>), grid, dim3(256), lds, stream, b, l);
-                    else hipLaunchKernelGGL((k_resize_gather<false, true>), grid, dim3(256), lds, stream, b, l);
-                } else {
-                    if (al) hipLaunchKernelGGL((k_resize_gather<true, false>), grid, dim3(256), lds, stream, b, l);
-                    else hipLaunchKernelGGL((k_resize_gather<false, false>), grid, dim3(256), lds, stream, b, l);
-                }
-            } else if (L.rz_window) {
-                if (al) hipLaunchKernelGGL((k_resize<true, true>), grid, dim3(256), lds, stream, b, l);
-                else hipLaunchKernelGGL((k_resize<false, true>), grid, dim3(256), lds, stream, b, l);
-            } else {
-                if (al) hipLaunchKernelGGL((k_resize<true, false>), grid, dim3(256), lds, stream, b, l);
-                else hipLaunchKernelGGL((k_resize<false, false>), grid, dim3(256), lds, stream, b, l);
+            switch (pl.variant - PV_TILED0) {
+                case 0: hipLaunchKernelGGL((k_resize<false, false>), grid, dim3(256), lds, stream, b, l); break;
+                case 1: hipLaunchKernelGGL((k_resize<true, false>), grid, dim3(256), lds, stream, b, l); break;
+                case 2: hipLaunchKernelGGL((k_resize<false, true>), grid, dim3(256), lds, stream, b, l); break;
+                case 3: hipLaunchKernelGGL((k_resize<true, true>), grid, dim3(256), lds, stream, b, l); break;
+                case 4: hipLaunchKernelGGL((k_resize_gather<false, false>), grid, dim3(256), lds, stream, b, l); break;
+                case 5: hipLaunchKernelGGL((k_resize_gather<true, false>), grid, dim3(256), lds, stream, b, l); break;
+                case 6: hipLaunchKernelGGL((k_resize_gather<false, true>), grid, dim3(256), lds, stream, b, l); break;
+                default: hipLaunchKernelGGL((k_resize_gather<true, true>), grid, dim3(256), lds, stream, b, l); break;
             }
-            ORBX_LAUNCH_CHECK();
+        } else {
+            const bool gather = pl.variant >= PV_STRIP_GATHER0;
+            switch (pl.variant - (gather ? PV_STRIP_GATHER0 : PV_STRIP0)) {
+                case 1: launch_resize_strip<1>(b, pl.index, pl.sc, gather, stream); break;
+                case 2: launch_resize_strip<2>(b, pl.index, pl.sc, gather, stream); break;
+                case 3: launch_resize_strip<3>(b, pl.index, pl.sc, gather, stream); break;
+                case 4: launch_resize_strip<4>(b, pl.index, pl.sc, gather, stream); break;
+                default: launch_resize_strip<0>(b, pl.index, pl.sc, gather, stream); break;
+            }
         }
+        ORBX_LAUNCH_CHECK();
     }
     return ORBX_OK;
 }

@@ -590,31 +590,50 @@ int launch_debug_nth(const float* d_resp, int n, int nth, int* d_out) {
 }
 
 
-int launch_quota(const Batch& b, const HostGeom& hg, hipStream_t stream) {
+StagePlan plan_quota(const HostGeom& hg) {
+    return stage_plan(QV_QUOTA, (size_t)hg.g.quota_cells * QUOTA_LDS_PER_CELL > 64 * 1024 ? ORBX_VF_LDS_OVER_64K : 0u);
+}
+
+int launch_quota(const Batch& b, const HostGeom& hg, hipStream_t stream, const StagePlan& plan) {
     const DevGeom& g = hg.g;
     const size_t lds = (size_t)g.quota_cells * QUOTA_LDS_PER_CELL;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quota), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
+    if ((plan.flags & ORBX_VF_LDS_OVER_64K) && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quota), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
     hipLaunchKernelGGL(k_quota, dim3(frame_item_blocks(b, g.nlevels)), dim3(64), lds, stream, b, frame_item_magic_of(g.nlevels));
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;
 }
 
-int launch_cell_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
+// a launch group too small to fill the chip takes ONE launch with the full staging area per wave (a dependent launch costs
+// more than the occupancy gains); otherwise short lists first, then the (usually empty) list of long cells
+static int cell_select_entries(const Batch& b, const DevGeom& g) {
+    return b.nframes < PYR_FUSED_MAX_FRAMES ? g.sel_lds_entries : std::min(SEL_SMALL, g.sel_lds_entries);
+}
+// (the lists never exceed SEL_LDS_MAX_ENTRIES: the shared areas of k_cell_select_long and of the level kernels stay far below 64 KiB)
+static_assert(sel_long_bytes(SEL_LDS_MAX_ENTRIES) <= 64 * 1024 && sel_wave_bytes(SEL_LDS_MAX_ENTRIES) <= 64 * 1024, "no opt-in for large LDS needed");
+StagePlan plan_cell_select(const Batch& b, const HostGeom& hg) {
     const DevGeom& g = hg.g;
-    const int F = b.nframes;
-    // a launch group too small to fill the chip takes ONE launch with the full staging area per wave (a dependent launch costs
-    // more than the occupancy gains); otherwise short lists first, then the (usually empty) list of long cells
-    const int small = F < PYR_FUSED_MAX_FRAMES ? g.sel_lds_entries : std::min(SEL_SMALL, g.sel_lds_entries);
+    const int small = cell_select_entries(b, g);
+    StagePlan p = stage_plan(b.img_tab ? CS_SELECT_GATHER : CS_SELECT, (size_t)4 * sel_wave_bytes(small) > 64 * 1024 ? ORBX_VF_LDS_OVER_64K : 0u);     // (gather form: Harris reads the caller's frames)
+    if (small < g.sel_lds_entries) p.mask |= 1ull << (b.img_tab ? CS_LONG_GATHER : CS_LONG);
+    return p;
+}
+const char* cell_select_variant_name(int id) {
+    static const char* const names[CS_COUNT] = {"k_cell_select", "k_cell_select_gather", "k_cell_select_long", "k_cell_select_long_gather"};
+    return id >= 0 && id < CS_COUNT ? names[id] : "?";
+}
+
+int launch_cell_select(const Batch& b, const HostGeom& hg, hipStream_t stream, const StagePlan& plan) {
+    const DevGeom& g = hg.g;
+    const int small = cell_select_entries(b, g);
     const size_t lds = (size_t)4 * sel_wave_bytes(small);
-    auto* const ksel = b.img_tab ? k_cell_select_gather : k_cell_select;      // (gather form: Harris reads the caller's frames)
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ksel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
+    auto* const ksel = plan.id == CS_SELECT_GATHER ? k_cell_select_gather : k_cell_select;
+    if ((plan.flags & ORBX_VF_LDS_OVER_64K) && hipFuncSetAttribute(reinterpret_cast<const void*>(ksel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
     const int per4 = (g.ncells_total + 3) / 4;
     hipLaunchKernelGGL(ksel, dim3(frame_item_blocks(b, per4)), dim3(256), lds, stream, b, small, frame_item_magic_of(per4));
     ORBX_LAUNCH_CHECK();
-    if (small < g.sel_lds_entries) {
+    if (plan.mask & (1ull << CS_LONG | 1ull << CS_LONG_GATHER)) {
         const size_t ldsl = (size_t)sel_long_bytes(g.sel_lds_entries);
-        auto* const klong = b.img_tab ? k_cell_select_long_gather : k_cell_select_long;
-        if (ldsl > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(klong), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl) != hipSuccess) return ORBX_ERR_DEVICE;
+        auto* const klong = (plan.mask & (1ull << CS_LONG_GATHER)) ? k_cell_select_long_gather : k_cell_select_long;
         const int perl = (g.ncells_total + SEL_LONG_CHUNK - 1) / SEL_LONG_CHUNK;
         hipLaunchKernelGGL(klong, dim3(frame_item_blocks(b, perl)), dim3(SEL_LONG_WAVES * 64), ldsl, stream, b, frame_item_magic_of(perl));
         ORBX_LAUNCH_CHECK();
@@ -622,17 +641,16 @@ int launch_cell_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
     return ORBX_OK;
 }
 
-int launch_level_select(const Batch& b, const HostGeom& hg, hipStream_t stream) {
+StagePlan plan_level_select(const Batch& b, const HostGeom&) { return stage_plan(b.nframes < PYR_FUSED_MAX_FRAMES ? LS_ONE : LS_CHUNKED); }
+const char* level_select_variant_name(int id) { return id == LS_ONE ? "k_level_select_one" : id == LS_CHUNKED ? "k_level_select" : "?"; }
+
+int launch_level_select(const Batch& b, const HostGeom& hg, hipStream_t stream, const StagePlan& plan) {
     const DevGeom& g = hg.g;
-    if (b.nframes < PYR_FUSED_MAX_FRAMES) {
-        const size_t lds = (size_t)g.sel_lds_level;
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level_select_one), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
-        hipLaunchKernelGGL(k_level_select_one, dim3(b.nframes * g.nlevels), dim3(64), lds, stream, b);
+    if (plan.id == LS_ONE) {
+        hipLaunchKernelGGL(k_level_select_one, dim3(b.nframes * g.nlevels), dim3(64), (size_t)g.sel_lds_level, stream, b);
     } else {
-        const size_t lds = (size_t)sel_long_bytes(g.sel_lds_entries);
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ORBX_ERR_DEVICE;
         const int per = (g.nlevels + LSEL_CHUNK - 1) / LSEL_CHUNK;
-        hipLaunchKernelGGL(k_level_select, dim3(frame_item_blocks(b, per)), dim3(LSEL_WAVES * 64), lds, stream, b, frame_item_magic_of(per));
+        hipLaunchKernelGGL(k_level_select, dim3(frame_item_blocks(b, per)), dim3(LSEL_WAVES * 64), (size_t)sel_long_bytes(g.sel_lds_entries), stream, b, frame_item_magic_of(per));
     }
     ORBX_LAUNCH_CHECK();
     return ORBX_OK;

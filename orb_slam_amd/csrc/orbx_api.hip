@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "orbx_internal.h"
+#include "orbx_launch.h"
 
 namespace orbx {
 int launch_eval_math(int kind, const float* in0, const float* in1, float* out0, float* out1, int n);
@@ -46,6 +47,8 @@ struct orbx_extractor {
     SideStream side;
     Batch last;
     bool have_last = false;
+    LaunchPlan last_plan;             // what the last launch group launched (orbx_debug_launch_variant) ...
+    StagePlan pend_color, pend_ingest;   // ... and what its entry point queued in front of it; cleared when the group takes them over
     // phased calls (orbx_extract_batch_device_phases): the parts already queued for the batch described by ph_key
     int ph_done = 0;
     struct PhaseKey {
@@ -170,9 +173,18 @@ static hipMemoryType host_memory_type(const void* p) {
 
 // queues one launch group; it becomes the group the diagnostics read
 static int launch_group(orbx_extractor* h, const Batch& b, hipStream_t stream, int phases = ORBX_PHASE_ALL) {
-    const int rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side, phases);
+    LaunchPlan plan;
+    const int rc = launch_extract(b, h->hg, stream, h->stop_after, &h->timer, &h->side, phases, &plan);
+    plan.st[VS_COLOR] = h->pend_color;
+    plan.st[VS_INGEST] = h->pend_ingest;
+    h->pend_color = h->pend_ingest = StagePlan();
+    // a later part of a phased call (one launch group, the same batch: checked by the caller): the parts queued before keep their record
+    if (!(phases & ORBX_PHASE_PYRAMID) && h->have_last)
+        for (int s = 0; s < VS_COUNT; s++)
+            if (plan.st[s].id < 0) plan.st[s] = h->last_plan.st[s];
     if (rc != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; }
     h->last = b;
+    h->last_plan = plan;
     h->have_last = true;
     return ORBX_OK;
 }
@@ -255,7 +267,7 @@ static int convert(orbx_extractor* h, const uint8_t* src, ptrdiff_t srs, ptrdiff
     memset(&a, 0, sizeof(a));
     a.src = src; a.src_row_stride = srs; a.src_frame_stride = sfs; a.tab = tab; a.tab_bits = tab_bits;
     a.dst = dst; a.dst2 = dst2; a.dst_row_stride = drs; a.dst_frame_stride = dfs; a.w = w; a.h = hgt;
-    const int rc = launch_to_gray(a, n, fmt, stream);
+    const int rc = launch_to_gray(a, n, fmt, stream, &h->pend_color);
     if (rc != ORBX_OK) h->err = rc == ORBX_ERR_ARG ? "frame too large for the conversion kernel" : "kernel launch failed (no gfx950 code object for this device?)";
     return rc;
 }
@@ -514,9 +526,11 @@ int orbx_extract(orbx_extractor* h, const uint8_t* img, int w, int hgt, ptrdiff_
     // the first pyramid launch); large ones go through the runtime's pipelined copy.  Out: k_describe, the only writer of the results,
     // stores n / status / keypoints / descriptors straight into the pinned, device-mapped block (posted PCIe writes, visible to the
     // host once the stream has drained) - the D2H copy and the kernel -> copy dependency in front of it (~15 us) are gone.
-    if (bytes <= (size_t)512 << 10) {
+    h->pend_color = StagePlan();
+    h->pend_ingest = plan_ingest(bytes, h->zero_copy);
+    if (bytes <= INGEST_MAX_BYTES) {
         for (int y = 0; y < hgt; y++) memcpy(h->h_img1.as() + (size_t)y * dstride, img + (ptrdiff_t)y * stride, (size_t)w);
-        if (h->zero_copy) { if ((rc = launch_ingest(h->d_img1.as(), h->h_img1.mapped(), bytes, h->s1)) != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; } }
+        if (h->pend_ingest.id >= 0) { if ((rc = launch_ingest(h->d_img1.as(), h->h_img1.mapped(), bytes, h->s1)) != ORBX_OK) { h->err = "kernel launch failed (no gfx950 code object for this device?)"; return rc; } }
         else HIPCHK(h, hipMemcpyAsync(h->d_img1, h->h_img1, bytes, hipMemcpyHostToDevice, h->s1));
     } else {
         HIPCHK(h, hipMemcpy2DAsync(h->d_img1, dstride, img, stride, w, hgt, hipMemcpyHostToDevice, h->s1));
@@ -725,6 +739,55 @@ int orbx_debug_resize_form(const orbx_extractor* h, int level, int* form, int* r
     StripChoice sc;
     *form = resize_form(h->last, h->hg, level, sc);
     *rows_out = sc.rows_out;
+    return ORBX_OK;
+}
+
+int orbx_debug_launch_variant(const orbx_extractor* h, int stage, orbx_stage_variant* out, char* name, int name_cap) {
+    if (!h || !h->have_last || !out || stage < 0 || stage >= VS_COUNT) return ORBX_ERR_ARG;
+    const StagePlan& s = h->last_plan.st[stage];
+    out->id = s.id; out->flags = s.flags; out->mask = s.mask;
+    if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s", s.id < 0 ? "" : variant_name(stage, s.id));
+    return ORBX_OK;
+}
+
+int orbx_debug_variant_count(int stage) { return variant_count(stage); }
+const char* orbx_debug_variant_name(int stage, int id) { return variant_name(stage, id); }
+
+int orbx_debug_plan(const orbx_params* p, const orbx_plan_args* a, orbx_stage_variant* out) {
+    if (!p || !a || !out || a->nframes < 1 || a->row_stride < a->w) return ORBX_ERR_ARG;
+    HostGeom hg;
+    std::string err;
+    const int rc = build_geometry(*p, a->w, a->h, hg, err);
+    if (rc != ORBX_OK) return rc;
+    // the group as launch_group sees it: only the fields the decisions read (no pointer is followed)
+    Batch b;
+    memset(&b, 0, sizeof(b));
+    b.g = hg.g;
+    b.nframes = a->nframes;
+    b.xcd_affinity = a->xcd_affinity ? 1 : 0;
+    b.blur_on_demand = a->on_demand ? 1 : 0;
+    b.od_min_frames = a->od_min_frames;
+    b.img_row_stride = a->row_stride;
+    ImgSrc none = {nullptr, 0};
+    if (a->gather) {
+        b.img_tab = &none;
+        b.img_tab_bits = (unsigned long long)a->base_bits | (unsigned long long)a->row_stride;
+        b.img_tab_min_stride = b.img_tab_max_stride = a->row_stride;
+    } else {
+        b.img = reinterpret_cast<const uint8_t*>((uintptr_t)a->base_bits);
+        b.img_frame_stride = a->frame_stride;
+    }
+    LaunchPlan plan = plan_extract(b, hg, a->stop_after, a->side_stream != 0, ORBX_PHASE_ALL);
+    if (a->color_fmt >= 0) {
+        ColorArgs c;
+        memset(&c, 0, sizeof(c));
+        ImgSrc cnone = {nullptr, 0};
+        if (a->color_gather) { c.tab = &cnone; c.tab_bits = a->color_bits; }
+        else c.src = reinterpret_cast<const uint8_t*>((uintptr_t)a->color_bits);
+        plan.st[VS_COLOR] = plan_to_gray(c, a->color_fmt);
+    }
+    if (a->one_frame) plan.st[VS_INGEST] = plan_ingest((size_t)a->one_frame_bytes, true);
+    for (int s = 0; s < VS_COUNT; s++) { out[s].id = plan.st[s].id; out[s].flags = plan.st[s].flags; out[s].mask = plan.st[s].mask; }
     return ORBX_OK;
 }
 

@@ -402,7 +402,7 @@ static int build_geometry_band(const orbx_params& p, int w, int h, HostGeom& out
         for (int l = 0; l < nl; l++) max_level = std::max(max_level, g.lv[l].sel_cap);
         // lists are staged in LDS up to 2048 entries (8 B + two uint16 scratch words each); longer ones (possible only in
         // pathological images) take a sequential global-memory path
-        g.sel_lds_entries = std::min(std::max(max_cell, max_level), 2048);
+        g.sel_lds_entries = std::min(std::max(max_cell, max_level), SEL_LDS_MAX_ENTRIES);
         g.sel_lds_cell = align_up(g.sel_lds_entries * ((int)sizeof(Cand) + 4), 16);
         g.sel_lds_level = g.sel_lds_cell;
         if (g.sel_lds_cell > 160 * 1024 || g.sel_lds_level > 160 * 1024) { err = "keypoint list does not fit the 160 KiB LDS"; return ORBX_ERR_CAPACITY; }

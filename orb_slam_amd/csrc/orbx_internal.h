@@ -173,6 +173,7 @@ struct PyrGroup {
 #define ORBX_PYR_TILE 16, 16
 #endif
 
+constexpr int SEL_LDS_MAX_ENTRIES = 2048;                            // list entries the selection kernels stage in LDS at most (DevGeom::sel_lds_entries)
 constexpr int QUOTA_LDS_PER_CELL = 10;                              // k_quota: two ints + two bytes of LDS per cell of a level
 constexpr int QUOTA_MAX_CELLS = 160 * 1024 / QUOTA_LDS_PER_CELL / 64 * 64;   // 16384: what one workgroup's LDS holds
 // Per FAST work item (row band of a grid cell).  `thr` is the threshold the band's list and counters were made at: fastTh when the
@@ -312,7 +313,8 @@ static inline int pix_channels(int fmt) {
     }
 }
 // k_color.hip: queue the conversion of nframes frames on `stream` (ORBX_ERR_ARG for a frame of 2^31 chunks or more)
-int launch_to_gray(const ColorArgs& a, int nframes, int fmt, hipStream_t stream);
+struct StagePlan;
+int launch_to_gray(const ColorArgs& a, int nframes, int fmt, hipStream_t stream, StagePlan* report = nullptr);      // report (optional): the variant launched (orbx_launch.h)
 
 // Host-side geometry builder result.
 struct HostGeom {
@@ -358,10 +360,11 @@ struct SideStream {
     Event fork, join;
 };
 // `phases`: ORBX_PHASE_* bits of include/orbx.h (which parts of the sequence to queue; ORBX_PHASE_ALL = everything)
+// `report` (optional): what the launch group launched, stage by stage (orbx_launch.h)
+struct LaunchPlan;
 int launch_extract(const Batch& b, const HostGeom& hg, hipStream_t stream, int stop_after, StageTimer* timer, const SideStream* side,
-                   int phases = ORBX_PHASE_ALL);
+                   int phases = ORBX_PHASE_ALL, LaunchPlan* report = nullptr);
 // k_describe_od.hip: the description stage with the Gaussian blur computed per keypoint window (no blurred plane)
 bool describe_od_supported(const Batch& b, const HostGeom& hg);
-int launch_describe_od(const Batch& b, const HostGeom& hg, hipStream_t stream);
 
 }  // namespace orbx
