@@ -67,6 +67,10 @@ CULL_MAX_CANDIDATES = 4096                          # ORBP_CULL_MAX_CANDIDATES
 # include/orbt.h (triangulation of new map points)
 EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate", "orbt_new_points_rows_device", "orbt_new_points_rows"]
 (T_NONE, T_ACCEPTED, T_PARALLAX, T_W_ZERO, T_DEPTH1, T_DEPTH2, T_REPROJ1, T_REPROJ2, T_ZERO_DIST, T_SCALE, T_SKIP_INDEX, T_SKIP_OCTAVE) = range(12)
+# include/orbi.h (monocular initialisation)
+EXPORTS_I = ["orbi_normalize", "orbi_pose_from_rt", "orbi_models_batch_device", "orbi_models", "orbi_check_rt_batch_device", "orbi_check_rt"]
+INIT_MAX_PROBLEMS, INIT_MAX_MATCHES, INIT_MAX_ITERS, INIT_MAX_HYP = 32, 16384, 1024, 8      # ORBI_MAX_*
+(RT_NONE, RT_GOOD, RT_COUNTED, RT_NONFINITE, RT_DEPTH1, RT_DEPTH2, RT_REPROJ1, RT_REPROJ2, RT_SKIP_INDEX) = range(9)
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
 # orbp_fused.status
@@ -205,6 +209,12 @@ TRI_CAMERA_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("O
 # orbt_pair as a numpy record (arrays of pairs are uploaded as they are)
 TRI_PAIR_DTYPE = np.dtype([("kf1", TRI_CAMERA_DTYPE), ("kf2", TRI_CAMERA_DTYPE), ("scale_factor", np.float32), ("reserved", np.int32)])
 assert TRI_PAIR_DTYPE.itemsize == ctypes.sizeof(TriPair) == 160
+
+# orbi_problem / orbi_pose as numpy records (include/orbi.h)
+INIT_PROBLEM_DTYPE = np.dtype([("norm1", np.float32, 4), ("norm2", np.float32, 4), ("sigma", np.float32), ("n1", np.int32), ("n2", np.int32),
+                               ("nmatches", np.int32), ("iters", np.int32), ("reserved", np.int32)])
+INIT_POSE_DTYPE = np.dtype([("R", np.float32, 9), ("t", np.float32, 3), ("P2", np.float32, 12), ("O2", np.float32, 3)])
+assert INIT_PROBLEM_DTYPE.itemsize == 56 and INIT_POSE_DTYPE.itemsize == 108
 
 # orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
 VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
@@ -398,6 +408,12 @@ def lib():
                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbt_new_points_rows.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.orbi_normalize.argtypes = [vp, ci, vp]
+        L.orbi_pose_from_rt.argtypes = [cf, cf, cf, cf, vp, vp, vp]
+        L.orbi_models_batch_device.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbi_models.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
+        L.orbi_check_rt_batch_device.argtypes = [cf, cf, cf, cf, vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, vp, cf, vp, vp, vp, vp, vp, vp, vp]
+        L.orbi_check_rt.argtypes = [cf, cf, cf, cf, vp, ci, vp, ci, vp, ci, vp, ci, vp, cf, vp, vp, vp, vp, vp, vp, vp, ci]
         _LIB = L
     return _LIB
 
@@ -1142,6 +1158,100 @@ def triangulate(pair, factors1, sigma2_1, factors2, sigma2_2, kps1, kps2, match1
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbt_triangulate (accepted: %d)" % count.value)
     return status[:n1], x3d[:n1], (v[:n1] if want_v else None), acc_idx[:count.value], acc_x3d[:count.value]
+
+
+def init_normalize(kps):
+    """Initializer::Normalize over all key points of one frame -> float32 {sX, sY, meanX, meanY} (include/orbi.h; needs no GPU)"""
+    k = np.ascontiguousarray(kps, dtype=KP_DTYPE)
+    out = np.zeros(4, np.float32)
+    rc = lib().orbi_normalize(k.ctypes.data if len(k) else None, len(k), out.ctypes.data)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbi_normalize")
+    return out
+
+
+def init_pose_from_rt(fx, fy, cx, cy, R, t):
+    """an INIT_POSE_DTYPE record {R, t, P2 = K*[R|t], O2 = -R.t()*t} in the cv::Mat evaluation order of DESIGN.md §2 (needs no GPU)"""
+    R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+    pose = np.zeros(1, INIT_POSE_DTYPE)
+    rc = lib().orbi_pose_from_rt(float(fx), float(fy), float(cx), float(cy), R.ctypes.data, t.ctypes.data, pose.ctypes.data)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbi_pose_from_rt")
+    return pose[0]
+
+
+def init_problem(kps1, kps2, nmatches, iters, sigma=1.0):
+    """an INIT_PROBLEM_DTYPE record for one frame pair (Normalize of both frames included)"""
+    q = np.zeros(1, INIT_PROBLEM_DTYPE)
+    q["norm1"][0] = init_normalize(kps1); q["norm2"][0] = init_normalize(kps2)
+    q["sigma"] = sigma; q["n1"] = len(kps1); q["n2"] = len(kps2); q["nmatches"] = nmatches; q["iters"] = iters
+    return q[0]
+
+
+def init_models_batch_device(problems, d_kps1, kcap1, d_kps2, kcap2, d_matches, mcap, d_sets, icap, d_scoreH, d_scoreF, d_H21, d_H12, d_F21, d_hn,
+                             d_fpre, d_best, d_S, d_inlH, d_inlF, stream=0):
+    """the H / F RANSAC of Initializer::Initialize for len(problems) frame pairs (include/orbi.h); problems: host INIT_PROBLEM_DTYPE records,
+    the rest device pointers as ints (0 = NULL)"""
+    pr = np.ascontiguousarray(problems, dtype=INIT_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbi_models_batch_device(pr.ctypes.data, len(pr), d_kps1, kcap1, d_kps2, kcap2, d_matches, mcap, d_sets, icap, d_scoreH, d_scoreF, d_H21,
+                                        d_H12, d_F21, d_hn or None, d_fpre or None, d_best, d_S, d_inlH, d_inlF, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbi_models_batch_device")
+
+
+def init_models(problem, kps1, kps2, matches, sets, device=0):
+    """one frame pair, host arrays, synchronous -> dict(scoreH, scoreF, H21, H12, F21, hn, fpre, bestH, bestF, SH, SF, inlH, inlF)"""
+    pr = np.ascontiguousarray(problem, dtype=INIT_PROBLEM_DTYPE).reshape(1)
+    k1 = np.ascontiguousarray(kps1, dtype=KP_DTYPE); k2 = np.ascontiguousarray(kps2, dtype=KP_DTYPE)
+    mt = np.ascontiguousarray(matches, dtype=np.int32).reshape(-1, 2); st = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 8)
+    N, I = int(pr["nmatches"][0]), int(pr["iters"][0])
+    if len(mt) != N or len(st) != I or len(k1) != pr["n1"][0] or len(k2) != pr["n2"][0]:
+        raise ValueError("the arrays do not have the problem's counts")
+    o = dict(scoreH=np.zeros(I, np.float32), scoreF=np.zeros(I, np.float32), H21=np.zeros((I, 9), np.float32), H12=np.zeros((I, 9), np.float32),
+             F21=np.zeros((I, 9), np.float32), hn=np.zeros((I, 9), np.float32), fpre=np.zeros((I, 9), np.float32), inlH=np.zeros(N, np.uint8),
+             inlF=np.zeros(N, np.uint8))
+    best = np.zeros(2, np.int32); S = np.zeros(2, np.float32)
+    rc = lib().orbi_models(pr.ctypes.data, k1.ctypes.data, k2.ctypes.data, mt.ctypes.data, st.ctypes.data, o["scoreH"].ctypes.data, o["scoreF"].ctypes.data,
+                           o["H21"].ctypes.data, o["H12"].ctypes.data, o["F21"].ctypes.data, o["hn"].ctypes.data, o["fpre"].ctypes.data, best.ctypes.data,
+                           S.ctypes.data, o["inlH"].ctypes.data, o["inlF"].ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbi_models")
+    o.update(bestH=int(best[0]), bestF=int(best[1]), SH=S[0], SF=S[1])
+    return o
+
+
+def init_check_rt_batch_device(fx, fy, cx, cy, d_poses, nhyp, n1, n2, nmatches, d_kps1, kcap1, d_kps2, kcap2, d_matches, mcap, d_flags, th2, d_status,
+                               d_x3d, d_cos, d_good, d_v, d_ngood, stream=0):
+    """Initializer::CheckRT for nhyp poses of len(nmatches) frame pairs (include/orbi.h); n1, n2, nmatches host int arrays, the rest device
+    pointers as ints (0 = NULL)"""
+    a, b, c = (np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for x in (n1, n2, nmatches))
+    if not len(a) == len(b) == len(c):
+        raise ValueError("n1, n2 and nmatches must have one length")
+    rc = lib().orbi_check_rt_batch_device(float(fx), float(fy), float(cx), float(cy), d_poses, nhyp, len(c), a.ctypes.data, b.ctypes.data, c.ctypes.data,
+                                          d_kps1, kcap1, d_kps2, kcap2, d_matches, mcap, d_flags, float(th2), d_status, d_x3d, d_cos, d_good, d_v or None,
+                                          d_ngood, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbi_check_rt_batch_device")
+
+
+def init_check_rt(fx, fy, cx, cy, poses, kps1, kps2, matches, flags, th2, device=0):
+    """one frame pair, host arrays, synchronous -> dict(status[nhyp, N], x3d[nhyp, N, 3], cos[nhyp, N], good[nhyp, N], v[nhyp, N, 4], ngood[nhyp],
+    parallax[nhyp])"""
+    ps = np.ascontiguousarray(poses, dtype=INIT_POSE_DTYPE).reshape(-1)
+    k1 = np.ascontiguousarray(kps1, dtype=KP_DTYPE); k2 = np.ascontiguousarray(kps2, dtype=KP_DTYPE)
+    mt = np.ascontiguousarray(matches, dtype=np.int32).reshape(-1, 2); fl = np.ascontiguousarray(flags, dtype=np.uint8)
+    H, N = len(ps), len(mt)
+    if len(fl) != N:
+        raise ValueError("one flag per match entry")
+    o = dict(status=np.zeros((H, N), np.uint8), x3d=np.zeros((H, N, 3), np.float32), cos=np.zeros((H, N), np.float32), good=np.zeros((H, N), np.uint8),
+             v=np.zeros((H, N, 4), np.float32), ngood=np.zeros(H, np.int32), parallax=np.zeros(H, np.float32))
+    rc = lib().orbi_check_rt(float(fx), float(fy), float(cx), float(cy), ps.ctypes.data, H, k1.ctypes.data, len(k1), k2.ctypes.data, len(k2), mt.ctypes.data, N,
+                             fl.ctypes.data, float(th2), o["status"].ctypes.data, o["x3d"].ctypes.data, o["cos"].ctypes.data, o["good"].ctypes.data,
+                             o["v"].ctypes.data, o["ngood"].ctypes.data, o["parallax"].ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbi_check_rt")
+    return o
 
 
 def epipolar_bound(sigma2):

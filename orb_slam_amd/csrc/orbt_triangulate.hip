@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "orb_jacobi.h"
 #include "orbp_device.h"
 #include "orbt.h"
 #include "orbx_host.h"
@@ -24,66 +25,13 @@ namespace orbt {
 
 constexpr int TPB = 512;              // one workgroup: eight waves, two per SIMD
 constexpr int WAVES = TPB / 64;
-constexpr int MAX_SWEEPS = 12;        // a 4 x 4 symmetric matrix converges in 5-7; the bound ends a NaN matrix
 
 struct Levels {
     float f1[ORBS_MAX_LEVELS], s1[ORBS_MAX_LEVELS], f2[ORBS_MAX_LEVELS], s2[ORBS_MAX_LEVELS];
     int n;
 };
 
-// one Jacobi rotation of the symmetric S (both halves kept) in the (P, Q) plane, accumulated into V
-template <int P, int Q>
-__device__ __forceinline__ void rotate(double (&S)[4][4], double (&V)[4][4]) {
-    const double apq = S[P][Q];
-    if (!(apq != 0.0) || apq != apq) return;
-    const double theta = (S[Q][Q] - S[P][P]) / (2.0 * apq);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (k != P && k != Q) {
-            const double skp = S[k][P], skq = S[k][Q];
-            S[k][P] = S[P][k] = c * skp - s * skq;
-            S[k][Q] = S[Q][k] = s * skp + c * skq;
-        }
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - s * vkq;
-        V[k][Q] = s * vkp + c * vkq;
-    }
-    S[P][P] = S[P][P] - t * apq;
-    S[Q][Q] = S[Q][Q] + t * apq;
-    S[P][Q] = S[Q][P] = 0.0;
-}
-
-// the right singular vector of the float A (row major) for its smallest singular value: the eigenvector of A'A for its smallest
-// eigenvalue, in double, rounded to float
-__device__ __forceinline__ void null_vector(const float (&A)[4][4], float (&v)[4]) {
-    double S[4][4], V[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double s = 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; r++) s = s + (double)A[r][i] * (double)A[r][j];
-            S[i][j] = s;
-            V[i][j] = i == j ? 1.0 : 0.0;
-        }
-    for (int sweep = 0; sweep < MAX_SWEEPS; sweep++) {
-        const double off = S[0][1] * S[0][1] + S[0][2] * S[0][2] + S[0][3] * S[0][3] + S[1][2] * S[1][2] + S[1][3] * S[1][3] + S[2][3] * S[2][3];
-        const double diag = S[0][0] * S[0][0] + S[1][1] * S[1][1] + S[2][2] * S[2][2] + S[3][3] * S[3][3];
-        if (!(off > 1e-36 * diag)) break;                    // converged, a zero matrix, or NaN
-        rotate<0, 1>(S, V); rotate<0, 2>(S, V); rotate<0, 3>(S, V);
-        rotate<1, 2>(S, V); rotate<1, 3>(S, V); rotate<2, 3>(S, V);
-    }
-    int k = 0;
-    double best = S[0][0];
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        if (S[i][i] < best) { best = S[i][i]; k = i; }
-#pragma unroll
-    for (int i = 0; i < 4; i++) v[i] = (float)(k == 0 ? V[i][0] : k == 1 ? V[i][1] : k == 2 ? V[i][2] : V[i][3]);
-}
+using orbj::null_vector;              // the 4 x 4 Jacobi iteration, shared with the monocular initialisation (orb_jacobi.h)
 
 // (float)(row r of Rcw . x3D + tcw[r]): the dot as a double sum from 0.0 (cv::Mat::dot), the translation added in double
 __device__ __forceinline__ float cam_coord(const orbt_camera& C, int r, const float (&X)[3]) {
