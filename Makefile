@@ -9,7 +9,7 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -ffp-contract=off -mll
 ORBX_SRCS  := $(wildcard orb_slam_amd/csrc/*.hip)
 ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*.h)
 
-all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tests/newpoints_dropin/harness tests/localmap_dropin/harness tests/cull_dropin/harness tests/init_dropin/harness tests/init_dropin/harness_host tools/libmappoints_host.so tools/liblocalmap_host.so tools/libcull_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/libinit_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
+all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tests/newpoints_dropin/harness tests/localmap_dropin/harness tests/cull_dropin/harness tests/init_dropin/harness tests/init_dropin/harness_host tests/pnp_dropin/harness tests/pnp_dropin/harness_host tools/libmappoints_host.so tools/liblocalmap_host.so tools/libcull_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/libinit_host.so tools/libpnp_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
 
 # the hash of the kernel sources travels inside the library (orbx_build_id): counters replayed by bench.py must come from THIS build
 SRC_HASH   := $(shell cat $(sort $(ORBX_SRCS) $(ORBX_HDRS)) | sha256sum | cut -c1-16)
@@ -164,6 +164,17 @@ tests/init_dropin/harness_host: tests/init_dropin/harness.cpp $(INIT_DROPIN) too
 	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -Itests/init_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp -Iorb_slam_amd/csrc $< orb_slam_amd/cpp/Initializer.cc -o $@ \
 	    -Ltools -linit_host -Wl,-rpath,'$$ORIGIN/../../tools'
 
+# the PnPsolver drop-in (orb_slam_amd/cpp/PnPsolver.cc over include/orbe.h) over a stand-in Frame.h, driven by scenes (tests/test_gpu_pnp_dropin.py); MapPoint.h
+# and cvmini.h are those of tests/mappoints_dropin.  harness_host is the same class linked against the host route (tools/libpnp_host.so):
+# tests/test_pnp_dropin_host.py
+PNP_DROPIN := orb_slam_amd/cpp/PnPsolver.cc orb_slam_amd/cpp/PnPsolver.h tests/pnp_dropin/Frame.h tests/mappoints_dropin/MapPoint.h tests/mappoints_dropin/cvmini.h include/orbe.h
+tests/pnp_dropin/harness: tests/pnp_dropin/harness.cpp $(PNP_DROPIN) include/orbx.h orb_slam_amd/liborbx.so
+	$(CXX) -O2 -std=c++14 -Wall -Itests/pnp_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/PnPsolver.cc -o $@ \
+	    -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+tests/pnp_dropin/harness_host: tests/pnp_dropin/harness.cpp $(PNP_DROPIN) tools/libpnp_host.so
+	$(CXX) -O2 -std=c++14 -Wall -Itests/pnp_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/PnPsolver.cc -o $@ \
+	    -Ltools -lpnp_host -Wl,-rpath,'$$ORIGIN/../../tools'
+
 # the NewMapPoints drop-in (orb_slam_amd/cpp/NewMapPoints.cc) over a stand-in KeyFrame.h, driven by scripts
 # (tests/test_gpu_triangulate_dropin.py); cvmini.h is that of tests/mappoints_dropin
 TRI_DROPIN := orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h tests/triangulate_dropin/KeyFrame.h tests/mappoints_dropin/cvmini.h
@@ -196,6 +207,11 @@ tools/libsim3_host.so: tools/sim3_host_route.cpp include/orbp.h
 # double Jacobi iteration on one host core; tests/test_init_host.py holds it against the numpy restatement
 tools/libinit_host.so: tools/init_host_route.cpp include/orbi.h orb_slam_amd/csrc/orbi_math.h orb_slam_amd/csrc/orb_jacobi.h
 	$(CXX) -O2 -std=c++14 -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
+
+# the host route tools/bench_pnp.py measures the EPnP RANSAC of the relocalisation (orbe_hypotheses, orbe_refine, orbe_select, orbe_iterate) against:
+# the C ABI of include/orbe.h on one host core over the same arithmetic text; tests/test_pnp_host.py holds it against the numpy restatement
+tools/libpnp_host.so: tools/pnp_host_route.cpp include/orbe.h orb_slam_amd/csrc/orbe_math.h orb_slam_amd/csrc/orbe_host.h orb_slam_amd/csrc/orb_jacobi.h
+	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
 
 # the host route tools/bench_local_map.py measures the local-map chain against: the three object-graph walks over flat stand-in arrays on one host core
 tools/liblocalmap_host.so: tools/local_map_host_route.cpp
@@ -233,7 +249,7 @@ tools/microbench/ta_shapes: tools/microbench/ta_shapes.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++20 -Wno-unused-value $< -o $@
 
 clean:
-	rm -f tests/init_dropin/harness tests/init_dropin/harness_host tools/libinit_host.so tools/libcull_host.so tests/cull_dropin/harness tests/localmap_dropin/harness tools/liblocalmap_host.so tests/newpoints_dropin/harness tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
+	rm -f tools/libpnp_host.so tests/pnp_dropin/harness tests/pnp_dropin/harness_host tests/init_dropin/harness tests/init_dropin/harness_host tools/libinit_host.so tools/libcull_host.so tests/cull_dropin/harness tests/localmap_dropin/harness tools/liblocalmap_host.so tests/newpoints_dropin/harness tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
 	rm -rf oracle/_ref oracle/_ref_native build/orbx
 
 .PHONY: all clean oracle_ref

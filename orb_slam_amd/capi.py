@@ -71,6 +71,9 @@ EXPORTS_T = ["orbt_triangulate_batch_device", "orbt_triangulate", "orbt_new_poin
 EXPORTS_I = ["orbi_normalize", "orbi_pose_from_rt", "orbi_models_batch_device", "orbi_models", "orbi_check_rt_batch_device", "orbi_check_rt"]
 INIT_MAX_PROBLEMS, INIT_MAX_MATCHES, INIT_MAX_ITERS, INIT_MAX_HYP = 32, 16384, 1024, 8      # ORBI_MAX_*
 (RT_NONE, RT_GOOD, RT_COUNTED, RT_NONFINITE, RT_DEPTH1, RT_DEPTH2, RT_REPROJ1, RT_REPROJ2, RT_SKIP_INDEX) = range(9)
+# include/orbe.h (the EPnP RANSAC of the relocalisation)
+EXPORTS_E = ["orbe_ransac_parameters", "orbe_hypotheses_batch_device", "orbe_hypotheses", "orbe_refine_batch_device", "orbe_refine",
+             "orbe_refit_batch_device", "orbe_refit", "orbe_select_batch_device", "orbe_select", "orbe_iterate", "orbe_iterate_batch"]
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
 # orbp_fused.status
@@ -215,6 +218,15 @@ INIT_PROBLEM_DTYPE = np.dtype([("norm1", np.float32, 4), ("norm2", np.float32, 4
                                ("nmatches", np.int32), ("iters", np.int32), ("reserved", np.int32)])
 INIT_POSE_DTYPE = np.dtype([("R", np.float32, 9), ("t", np.float32, 3), ("P2", np.float32, 12), ("O2", np.float32, 3)])
 assert INIT_PROBLEM_DTYPE.itemsize == 56 and INIT_POSE_DTYPE.itemsize == 108
+# orbe_problem / orbe_state / orbe_result as numpy records (include/orbe.h)
+PNP_PROBLEM_DTYPE = np.dtype([("fu", np.float32), ("fv", np.float32), ("uc", np.float32), ("vc", np.float32), ("n", np.int32), ("iters", np.int32),
+                              ("min_inliers", np.int32), ("max_its", np.int32)])
+PNP_STATE_DTYPE = np.dtype([("iterations", np.int32), ("best_inliers", np.int32), ("refine_ok", np.int32), ("refined_inliers", np.int32),
+                            ("best_tcw", np.float32, 12), ("refined_tcw", np.float32, 12)])
+PNP_RESULT_DTYPE = np.dtype([("kind", np.int32), ("stop", np.int32), ("no_more", np.int32), ("ninliers", np.int32), ("tcw", np.float32, 12)])
+assert PNP_PROBLEM_DTYPE.itemsize == 32 and PNP_STATE_DTYPE.itemsize == 112 and PNP_RESULT_DTYPE.itemsize == 64
+PNP_KIND_NONE, PNP_KIND_BEST, PNP_KIND_REFINED = 0, 1, 2
+PNP_MAX_PROBLEMS, PNP_MAX_POINTS, PNP_MAX_ITERS = 32, 8192, 1024
 
 # orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
 VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
@@ -408,6 +420,7 @@ def lib():
                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.orbt_new_points_rows.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        pnp_bind(L)
         L.orbi_normalize.argtypes = [vp, ci, vp]
         L.orbi_pose_from_rt.argtypes = [cf, cf, cf, cf, vp, vp, vp]
         L.orbi_models_batch_device.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1158,6 +1171,215 @@ def triangulate(pair, factors1, sigma2_1, factors2, sigma2_2, kps1, kps2, match1
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbt_triangulate (accepted: %d)" % count.value)
     return status[:n1], x3d[:n1], (v[:n1] if want_v else None), acc_idx[:count.value], acc_x3d[:count.value]
+
+
+def pnp_bind(L):
+    """the argument types of the orbe_* entry points (include/orbe.h); tools/libpnp_host.so exports the host forms with the same types"""
+    vp, ci, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
+    L.orbe_ransac_parameters.argtypes = [ci, cd, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp]
+    L.orbe_hypotheses.argtypes = [vp] * 12 + [ci]
+    L.orbe_refine.argtypes = [vp] * 6 + [ci] + [vp] * 5 + [ci]
+    L.orbe_refit.argtypes = [vp] * 11 + [ci]
+    L.orbe_select.argtypes = [vp] * 15 + [ci]
+    L.orbe_iterate.argtypes = [vp] * 10 + [ci]
+    L.orbe_iterate_batch.argtypes = [vp, ci] + [vp] * 9 + [ci]
+    if hasattr(L, "orbe_hypotheses_batch_device"):
+        L.orbe_hypotheses_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbe_refine_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbe_refit_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbe_select_batch_device.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    return L
+
+
+def pnp_ransac_parameters(sigma2, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991, L=None):
+    """PnPsolver::SetRansacParameters (include/orbe.h; needs no GPU; the defaults are the reference's) -> (min_inliers, max_its, epsilon, maxerr[N])"""
+    s2 = np.ascontiguousarray(sigma2, dtype=np.float32).reshape(-1)
+    mi, mx = ctypes.c_int32(0), ctypes.c_int32(0)
+    eps = ctypes.c_float(0)
+    maxerr = np.zeros(max(len(s2), 1), np.float32)
+    rc = (L or lib()).orbe_ransac_parameters(len(s2), float(probability), int(min_inliers), int(max_iterations), int(min_set), float(epsilon), float(th2),
+                                             s2.ctypes.data if len(s2) else None, ctypes.addressof(mi), ctypes.addressof(mx), ctypes.addressof(eps),
+                                             maxerr.ctypes.data)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_ransac_parameters")
+    return mi.value, mx.value, np.float32(eps.value), maxerr[:len(s2)]
+
+
+def pnp_problem(fu, fv, uc, vc, n, iters, min_inliers, max_its):
+    """a PNP_PROBLEM_DTYPE record"""
+    q = np.zeros(1, PNP_PROBLEM_DTYPE)
+    q["fu"] = fu; q["fv"] = fv; q["uc"] = uc; q["vc"] = vc
+    q["n"] = n; q["iters"] = iters; q["min_inliers"] = min_inliers; q["max_its"] = max_its
+    return q[0]
+
+
+def pnp_state(n):
+    """a fresh solver state -> (PNP_STATE_DTYPE[1], best_flags[n], refined_flags[n])"""
+    return np.zeros(1, PNP_STATE_DTYPE), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+
+
+def _pnp_points(pr, p3d, p2d, maxerr):
+    N = int(pr["n"][0])
+    a3 = np.ascontiguousarray(p3d, dtype=np.float32).reshape(-1, 3); a2 = np.ascontiguousarray(p2d, dtype=np.float32).reshape(-1, 2)
+    am = np.ascontiguousarray(maxerr, dtype=np.float32).reshape(-1)
+    if not len(a3) == len(a2) == len(am) == N:
+        raise ValueError("the arrays do not have the problem's count")
+    return N, a3, a2, am
+
+
+def pnp_hypotheses(problem, p3d, p2d, maxerr, sets, want_vecs=True, device=0, L=None):
+    """every hypothesis of one call, host arrays, synchronous -> dict(R[I, 9], t[I, 3], err[I, 3], branch[I], vecs[I, 4, 12] or None, count[I],
+    flags[I, N]) (include/orbe.h).  L: another library with the same ABI (tools/libpnp_host.so)"""
+    pr = np.ascontiguousarray(problem, dtype=PNP_PROBLEM_DTYPE).reshape(1)
+    N, a3, a2, am = _pnp_points(pr, p3d, p2d, maxerr)
+    st = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 4)
+    I = int(pr["iters"][0])
+    if len(st) != I:
+        raise ValueError("one set per iteration")
+    o = dict(R=np.zeros((I, 9)), t=np.zeros((I, 3)), err=np.zeros((I, 3)), branch=np.zeros(I, np.int32), vecs=np.zeros((I, 4, 12)) if want_vecs else None,
+             count=np.zeros(I, np.int32), flags=np.zeros((I, N), np.uint8))
+    rc = (L or lib()).orbe_hypotheses(pr.ctypes.data, a3.ctypes.data, a2.ctypes.data, am.ctypes.data, st.ctypes.data, o["R"].ctypes.data, o["t"].ctypes.data,
+                                      o["err"].ctypes.data, o["branch"].ctypes.data, o["vecs"].ctypes.data if want_vecs else None, o["count"].ctypes.data,
+                                      o["flags"].ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_hypotheses")
+    return o
+
+
+def pnp_refine(problem, p3d, p2d, maxerr, count, flags, best_in=0, poison=None, device=0, L=None):
+    """Refine of every record of one call, host arrays, synchronous -> dict(R[I, 9], t[I, 3], count[I], flags[I, N], ok[I]); what is not a record keeps
+    the value `poison` = (double, int32, uint8) the arrays start with (default NaN, -1, 255)"""
+    pr = np.ascontiguousarray(problem, dtype=PNP_PROBLEM_DTYPE).reshape(1)
+    N, a3, a2, am = _pnp_points(pr, p3d, p2d, maxerr)
+    I = int(pr["iters"][0])
+    cn = np.ascontiguousarray(count, dtype=np.int32).reshape(-1); fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1, N)
+    if len(cn) != I or len(fl) != I:
+        raise ValueError("one count and one flag array per iteration")
+    pd, pi, pb = poison or (np.nan, -1, 255)
+    o = dict(R=np.full((I, 9), pd), t=np.full((I, 3), pd), count=np.full(I, pi, np.int32), flags=np.full((I, N), pb, np.uint8), ok=np.full(I, pi, np.int32))
+    rc = (L or lib()).orbe_refine(pr.ctypes.data, a3.ctypes.data, a2.ctypes.data, am.ctypes.data, cn.ctypes.data, fl.ctypes.data, int(best_in),
+                                  o["R"].ctypes.data, o["t"].ctypes.data, o["count"].ctypes.data, o["flags"].ctypes.data, o["ok"].ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_refine")
+    return o
+
+
+def pnp_refit(problem, p3d, p2d, maxerr, flags_in, want_vecs=True, device=0, L=None):
+    """the n-point fit over planted flag arrays (problem.iters of them), host arrays, synchronous -> dict(R, t, vecs or None, count, flags, ok)"""
+    pr = np.ascontiguousarray(problem, dtype=PNP_PROBLEM_DTYPE).reshape(1)
+    N, a3, a2, am = _pnp_points(pr, p3d, p2d, maxerr)
+    I = int(pr["iters"][0])
+    fi = np.ascontiguousarray(flags_in, dtype=np.uint8).reshape(-1, N)
+    if len(fi) != I:
+        raise ValueError("one flag array per slot")
+    o = dict(R=np.zeros((I, 9)), t=np.zeros((I, 3)), vecs=np.zeros((I, 4, 12)) if want_vecs else None, count=np.zeros(I, np.int32),
+             flags=np.zeros((I, N), np.uint8), ok=np.zeros(I, np.int32))
+    rc = (L or lib()).orbe_refit(pr.ctypes.data, a3.ctypes.data, a2.ctypes.data, am.ctypes.data, fi.ctypes.data, o["R"].ctypes.data, o["t"].ctypes.data,
+                                 o["vecs"].ctypes.data if want_vecs else None, o["count"].ctypes.data, o["flags"].ctypes.data, o["ok"].ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_refit")
+    return o
+
+
+def pnp_select(problem, hyp, ref, state, best_flags, refined_flags, device=0, L=None):
+    """the walk of PnPsolver::iterate over hyp (of pnp_hypotheses) and ref (of pnp_refine); state (PNP_STATE_DTYPE[1]), best_flags and refined_flags are
+    updated in place -> (PNP_RESULT_DTYPE record, result_flags[N])"""
+    pr = np.ascontiguousarray(problem, dtype=PNP_PROBLEM_DTYPE).reshape(1)
+    N = int(pr["n"][0])
+    if state.dtype != PNP_STATE_DTYPE or not state.flags.c_contiguous or best_flags.dtype != np.uint8 or refined_flags.dtype != np.uint8 or \
+            len(best_flags) != N or len(refined_flags) != N:
+        raise ValueError("state: PNP_STATE_DTYPE[1]; best_flags, refined_flags: uint8[N]")
+    res = np.zeros(1, PNP_RESULT_DTYPE); rfl = np.zeros(N, np.uint8)
+    a = [np.ascontiguousarray(hyp["R"], np.float64), np.ascontiguousarray(hyp["t"], np.float64), np.ascontiguousarray(hyp["count"], np.int32),
+         np.ascontiguousarray(hyp["flags"], np.uint8), np.ascontiguousarray(ref["R"], np.float64), np.ascontiguousarray(ref["t"], np.float64),
+         np.ascontiguousarray(ref["count"], np.int32), np.ascontiguousarray(ref["flags"], np.uint8), np.ascontiguousarray(ref["ok"], np.int32)]
+    rc = (L or lib()).orbe_select(pr.ctypes.data, *[x.ctypes.data for x in a], state.ctypes.data, best_flags.ctypes.data, refined_flags.ctypes.data,
+                                  res.ctypes.data, rfl.ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_select")
+    return res[0], rfl
+
+
+def pnp_iterate(problem, p3d, p2d, maxerr, sets, state, best_flags, refined_flags, device=0, L=None):
+    """one call of PnPsolver::iterate after its draw, host arrays, synchronous; state, best_flags, refined_flags are updated in place
+    -> (PNP_RESULT_DTYPE record, result_flags[N])"""
+    pr = np.ascontiguousarray(problem, dtype=PNP_PROBLEM_DTYPE).reshape(1)
+    N, a3, a2, am = _pnp_points(pr, p3d, p2d, maxerr)
+    st = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 4)
+    if len(st) != int(pr["iters"][0]):
+        raise ValueError("one set per iteration")
+    if state.dtype != PNP_STATE_DTYPE or not state.flags.c_contiguous or best_flags.dtype != np.uint8 or refined_flags.dtype != np.uint8 or \
+            len(best_flags) != N or len(refined_flags) != N:
+        raise ValueError("state: PNP_STATE_DTYPE[1]; best_flags, refined_flags: uint8[N]")
+    res = np.zeros(1, PNP_RESULT_DTYPE); rfl = np.zeros(N, np.uint8)
+    rc = (L or lib()).orbe_iterate(pr.ctypes.data, a3.ctypes.data, a2.ctypes.data, am.ctypes.data, st.ctypes.data, state.ctypes.data, best_flags.ctypes.data,
+                                   refined_flags.ctypes.data, res.ctypes.data, rfl.ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_iterate")
+    return res[0], rfl
+
+
+def pnp_iterate_batch(problems, p3d, p2d, maxerr, sets, states, best_flags, refined_flags, device=0, L=None):
+    """the next iterate() of several solvers as ONE chain with one synchronisation (what the drop-in PnPsolver::Prefetch calls): lists of per-solver
+    host arrays; states (PNP_STATE_DTYPE[P]) and the flag arrays are updated in place -> (PNP_RESULT_DTYPE[P], [result_flags])"""
+    pr = np.ascontiguousarray(problems, dtype=PNP_PROBLEM_DTYPE).reshape(-1)
+    P = len(pr)
+    a3 = [np.ascontiguousarray(x, np.float32) for x in p3d]; a2 = [np.ascontiguousarray(x, np.float32) for x in p2d]
+    am = [np.ascontiguousarray(x, np.float32) for x in maxerr]; st = [np.ascontiguousarray(x, np.int32) for x in sets]
+    if not (len(a3) == len(a2) == len(am) == len(st) == len(best_flags) == len(refined_flags) == P) or states.dtype != PNP_STATE_DTYPE or len(states) != P:
+        raise ValueError("one entry per solver")
+    for p in range(P):
+        n, it = int(pr["n"][p]), int(pr["iters"][p])
+        if a3[p].size != n * 3 or a2[p].size != n * 2 or am[p].size != n or st[p].size != it * 4 or best_flags[p].dtype != np.uint8 or \
+                refined_flags[p].dtype != np.uint8 or len(best_flags[p]) != n or len(refined_flags[p]) != n:
+            raise ValueError("the arrays of solver %d do not have its counts" % p)
+    res = np.zeros(P, PNP_RESULT_DTYPE)
+    out = [np.zeros(int(n), np.uint8) for n in pr["n"]]
+    ptrs = lambda arrs: (ctypes.c_void_p * P)(*[x.ctypes.data for x in arrs])
+    keep = [ptrs(a3), ptrs(a2), ptrs(am), ptrs(st), ptrs(best_flags), ptrs(refined_flags), ptrs(out)]
+    rc = (L or lib()).orbe_iterate_batch(pr.ctypes.data, P, ctypes.addressof(keep[0]), ctypes.addressof(keep[1]), ctypes.addressof(keep[2]),
+                                         ctypes.addressof(keep[3]), states.ctypes.data, ctypes.addressof(keep[4]), ctypes.addressof(keep[5]), res.ctypes.data,
+                                         ctypes.addressof(keep[6]), device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_iterate_batch")
+    return res, out
+
+
+def pnp_hypotheses_batch_device(problems, d_p3d, d_p2d, d_maxerr, ncap, d_sets, icap, d_R, d_t, d_err, d_branch, d_vecs, d_count, d_flags, stream=0):
+    """the hypotheses of len(problems) calls (include/orbe.h); problems: host PNP_PROBLEM_DTYPE records, the rest device pointers as ints (0 = NULL)"""
+    pr = np.ascontiguousarray(problems, dtype=PNP_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbe_hypotheses_batch_device(pr.ctypes.data, len(pr), d_p3d, d_p2d, d_maxerr, ncap, d_sets, icap, d_R, d_t, d_err, d_branch, d_vecs or None,
+                                            d_count, d_flags, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_hypotheses_batch_device")
+
+
+def pnp_refine_batch_device(problems, d_p3d, d_p2d, d_maxerr, ncap, icap, d_count, d_flags, d_state, d_rR, d_rt, d_rcount, d_rflags, d_rok, stream=0):
+    """Refine of every record of len(problems) calls (include/orbe.h)"""
+    pr = np.ascontiguousarray(problems, dtype=PNP_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbe_refine_batch_device(pr.ctypes.data, len(pr), d_p3d, d_p2d, d_maxerr, ncap, icap, d_count, d_flags, d_state, d_rR, d_rt, d_rcount, d_rflags,
+                                        d_rok, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_refine_batch_device")
+
+
+def pnp_refit_batch_device(problems, d_p3d, d_p2d, d_maxerr, ncap, icap, d_flags_in, d_rR, d_rt, d_rvecs, d_rcount, d_rflags, d_rok, stream=0):
+    """the n-point fit over planted flag arrays of len(problems) problems (include/orbe.h)"""
+    pr = np.ascontiguousarray(problems, dtype=PNP_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbe_refit_batch_device(pr.ctypes.data, len(pr), d_p3d, d_p2d, d_maxerr, ncap, icap, d_flags_in, d_rR, d_rt, d_rvecs or None, d_rcount, d_rflags,
+                                       d_rok, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_refit_batch_device")
+
+
+def pnp_select_batch_device(problems, ncap, icap, d_R, d_t, d_count, d_flags, d_rR, d_rt, d_rcount, d_rflags, d_rok, d_state, d_best_flags, d_refined_flags,
+                            d_result, d_result_flags, stream=0):
+    """the walk of PnPsolver::iterate for len(problems) solvers; their states and flag arrays are updated on the device (include/orbe.h)"""
+    pr = np.ascontiguousarray(problems, dtype=PNP_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbe_select_batch_device(pr.ctypes.data, len(pr), ncap, icap, d_R, d_t, d_count, d_flags, d_rR, d_rt, d_rcount, d_rflags, d_rok, d_state,
+                                        d_best_flags, d_refined_flags, d_result, d_result_flags, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbe_select_batch_device")
 
 
 def init_normalize(kps):

@@ -203,8 +203,10 @@ ORB_HD void svd3(const double* A, double* U, double* w, double* Vt) {
 }
 
 #if defined(__HIPCC__)
-// The same by ONE WAVE that is a whole workgroup (so that __syncthreads orders its LDS traffic): S and V in LDS, lane k < N owns row k.
-// Every lane reads the same three entries for the angle, so the decision to skip is uniform.
+// The same by a whole workgroup (every thread calls it, so that the uniform __syncthreads order its LDS traffic): S and V in LDS, thread k < N owns
+// row k, thread N the 2 x 2 block; threads above N only read.  k_init_models and k_pnp_hypotheses call it with ONE wave, k_pnp_refine with four (the
+// initialising stores of V by threads 64 and above repeat the same values).  Every thread reads the same three entries for the angle, so the decision
+// to skip is uniform.
 template <int N>
 __device__ __forceinline__ void sym_eig_wave(double* S, double* V, int lane) {
     for (int e = lane; e < N * N; e += 64) V[e] = e / N == e % N ? 1.0 : 0.0;

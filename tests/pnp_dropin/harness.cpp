@@ -1,0 +1,96 @@
+// Drives ORB_SLAM::PnPsolver (orb_slam_amd/cpp/PnPsolver.cc) over the stand-in Frame.h of this directory and MapPoint.h of tests/mappoints_dropin:
+// harness IN OUT.
+// IN (binary, little endian): float fx, fy, cx, cy; int32 nsolvers, ncalls, nIterations, mode (0: the solvers one by one, 1: Prefetch before every
+// round, 2: Prefetch with nIterations + 1 and then iterate(nIterations): the cache must be dropped), nlevels; float sigma2[nlevels]; per solver:
+// int32 nkeys, nsets; float minInliers-as-parameters {probability, minInliers, maxIterations, minSet, epsilon, th2}; per key: float x, y, int32 octave,
+// int32 kind (0 no map point, 1 a map point, 2 a bad map point), float X, Y, Z; int32 sets[nsets * 4] (nsets = 0: the class draws with rand() after
+// srand(0), made once at the start).
+// OUT: per call round and solver: int32 empty, noMore, nInliers, kind, stop, range, iterations, prefetched; float Tcw[16]; uint8 vbInliers[nkeys].
+// Linked against liborbx.so (harness) it runs on the GPU, against tools/libpnp_host.so (harness_host) the same class runs on the host.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <vector>
+
+#include "PnPsolver.h"
+
+template <class T> static void rd(std::FILE* f, T* p, size_t n) {
+    if (n && std::fread(p, sizeof(T), n, f) != n) { std::fprintf(stderr, "short read\n"); std::exit(2); }
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) { std::fprintf(stderr, "usage: harness IN OUT\n"); return 2; }
+    std::FILE* f = std::fopen(argv[1], "rb");
+    if (!f) { std::fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
+    float cam[4];
+    int32_t hdr[5];
+    rd(f, cam, 4);
+    rd(f, hdr, 5);
+    const int nsolvers = hdr[0], ncalls = hdr[1], nIterations = hdr[2], mode = hdr[3], nlevels = hdr[4];
+    std::vector<float> sigma2(nlevels);
+    rd(f, sigma2.data(), nlevels);
+    std::srand(0);
+    std::vector<std::unique_ptr<ORB_SLAM::Frame> > frames;
+    std::vector<std::vector<std::unique_ptr<ORB_SLAM::MapPoint> > > points(nsolvers);
+    std::vector<std::unique_ptr<ORB_SLAM::PnPsolver> > solvers;
+    std::vector<int> nkeys(nsolvers);
+    for (int s = 0; s < nsolvers; s++) {
+        int32_t h[2];
+        float par[6];
+        rd(f, h, 2);
+        rd(f, par, 6);
+        nkeys[s] = h[0];
+        frames.emplace_back(new ORB_SLAM::Frame);
+        ORB_SLAM::Frame& F = *frames.back();
+        F.fx = cam[0]; F.fy = cam[1]; F.cx = cam[2]; F.cy = cam[3];
+        F.mvLevelSigma2 = sigma2;
+        F.mvKeysUn.resize(h[0]);
+        std::vector<ORB_SLAM::MapPoint*> matches(h[0], nullptr);
+        for (int i = 0; i < h[0]; i++) {
+            float xy[2], X[3];
+            int32_t ok[2];
+            rd(f, xy, 2); rd(f, ok, 2); rd(f, X, 3);
+            F.mvKeysUn[i].pt.x = xy[0]; F.mvKeysUn[i].pt.y = xy[1]; F.mvKeysUn[i].octave = ok[0];
+            if (ok[1]) {
+                points[s].emplace_back(new ORB_SLAM::MapPoint);
+                ORB_SLAM::MapPoint* mp = points[s].back().get();
+                for (int j = 0; j < 3; j++) mp->mWorldPos.at<float>(j) = X[j];
+                mp->mbBad = ok[1] == 2;
+                matches[i] = mp;
+            }
+        }
+        std::vector<int32_t> sets((size_t)h[1] * 4);
+        rd(f, sets.data(), sets.size());
+        solvers.emplace_back(new ORB_SLAM::PnPsolver(F, matches));
+        solvers.back()->SetRansacParameters(par[0], (int)par[1], (int)par[2], (int)par[3], par[4], par[5]);
+        if (h[1]) solvers.back()->UseSets(sets);
+    }
+    std::fclose(f);
+    std::FILE* o = std::fopen(argv[2], "wb");
+    if (!o) { std::fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+    std::vector<ORB_SLAM::PnPsolver*> list;
+    for (auto& s : solvers) list.push_back(s.get());
+    list.push_back(nullptr);                                   // Relocalisation's list has NULL entries
+    for (int call = 0; call < ncalls; call++) {
+        if (mode == 1) ORB_SLAM::PnPsolver::Prefetch(list, nIterations);
+        if (mode == 2) ORB_SLAM::PnPsolver::Prefetch(list, nIterations + 1);
+        for (int s = 0; s < nsolvers; s++) {
+            bool noMore = false;
+            std::vector<bool> inl;
+            int nInliers = -1;
+            cv::Mat T = nIterations > 0 ? solvers[s]->iterate(nIterations, noMore, inl, nInliers) : solvers[s]->find(inl, nInliers);
+            const ORB_SLAM::PnPsolver::Report& r = solvers[s]->LastReport();
+            int32_t head[8] = {T.empty(), noMore, nInliers, r.kind, r.stop, r.range, r.iterations, r.prefetched};
+            float tcw[16] = {0};
+            if (!T.empty()) for (int i = 0; i < 16; i++) tcw[i] = T.at<float>(i);
+            std::vector<uint8_t> fl(nkeys[s], 0);
+            for (size_t i = 0; i < inl.size(); i++) fl[i] = inl[i];
+            std::fwrite(head, 4, 8, o);
+            std::fwrite(tcw, 4, 16, o);
+            std::fwrite(fl.data(), 1, fl.size(), o);
+        }
+    }
+    std::fclose(o);
+    return 0;
+}
