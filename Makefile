@@ -9,7 +9,15 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -ffp-contract=off -mll
 ORBX_SRCS  := $(wildcard orb_slam_amd/csrc/*.hip)
 ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*.h)
 
-all: orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so oracle_ref orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tests/refresh_dropin/harness tests/fuse_dropin/harness tests/loop_dropin/harness tests/sim3_dropin/harness tests/bow_dropin/harness tests/newpoints_dropin/harness tests/localmap_dropin/harness tests/cull_dropin/harness tests/init_dropin/harness tests/init_dropin/harness_host tests/pnp_dropin/harness tests/pnp_dropin/harness_host tools/libmappoints_host.so tools/liblocalmap_host.so tools/libcull_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/libfuse_host.so tools/libloop_host.so tools/libsim3_host.so tools/libinit_host.so tools/libpnp_host.so tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_layout_fp4 tools/microbench/mfma_valu_mix tools/microbench/fetch_calib tools/microbench/valu_exec_mask tools/microbench/ta_shapes
+# what `all` builds and `clean` removes, named once
+LIBS             := orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
+EXAMPLES         := $(addprefix orb_slam_amd/cpp/,example_frame example_batch example_color example_pipeline example_lanes bench_single_frame)
+DROPIN_HARNESSES := $(patsubst %,tests/%_dropin/harness,kfdb mappoints source triangulate refresh fuse loop sim3 bow newpoints localmap cull init pnp) \
+    tests/init_dropin/harness_host tests/pnp_dropin/harness_host
+HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp)
+MICROBENCH       := $(addprefix tools/microbench/,valu_rate valu_rate2 mfma_layout mfma_layout_fp4 mfma_valu_mix fetch_calib valu_exec_mask ta_shapes)
+
+all: $(LIBS) oracle_ref $(EXAMPLES) $(DROPIN_HARNESSES) build/dropin/tracking_only.ok $(HOST_ROUTE_LIBS) $(MICROBENCH)
 
 # the hash of the kernel sources travels inside the library (orbx_build_id): counters replayed by bench.py must come from THIS build
 SRC_HASH   := $(shell cat $(sort $(ORBX_SRCS) $(ORBX_HDRS)) | sha256sum | cut -c1-16)
@@ -61,126 +69,42 @@ orb_slam_amd/cpp/example_lanes: orb_slam_amd/cpp/example_lanes.cpp orb_slam_amd/
 orb_slam_amd/cpp/bench_single_frame: orb_slam_amd/cpp/bench_single_frame.cpp include/orbx.h orb_slam_amd/liborbx.so
 	$(CXX) -O2 -std=c++14 -Iinclude $< -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
-# the KeyFrameDatabase drop-in (orb_slam_amd/cpp/KeyFrameDatabase.cc) over stand-in KeyFrame.h / Frame.h, driven by scripts
-# (tests/test_gpu_kfdb_dropin.py)
+# the KeyFrameDatabase drop-in (orb_slam_amd/cpp/KeyFrameDatabase.cc) over its own stand-in KeyFrame.h / Frame.h (they sit on cvcompat.h), driven by
+# scripts (tests/test_gpu_kfdb_dropin.py)
 KFDB_DROPIN := orb_slam_amd/cpp/KeyFrameDatabase.cc orb_slam_amd/cpp/KeyFrameDatabase.h orb_slam_amd/cpp/ORBVocabulary.h tests/kfdb_dropin/KeyFrame.h tests/kfdb_dropin/Frame.h
 tests/kfdb_dropin/harness: tests/kfdb_dropin/harness.cpp $(KFDB_DROPIN) include/orbd.h include/orbv.h include/orbx.h orb_slam_amd/liborbx.so
 	$(CXX) -O2 -std=c++14 -pthread -Itests/kfdb_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/KeyFrameDatabase.cc -o $@ -Lorb_slam_amd -lorbx \
 	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
 
-# the LocalMapPoints drop-in (orb_slam_amd/cpp/LocalMapPoints.cc) over stand-in Frame.h / MapPoint.h, driven by scripts
-# (tests/test_gpu_mappoints_dropin.py)
-MP_DROPIN := orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPoints.h orb_slam_amd/cpp/ORBmatcherAccess.h $(wildcard tests/mappoints_dropin/*.h)
-tests/mappoints_dropin/harness: tests/mappoints_dropin/harness.cpp $(MP_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc -o $@ -Lorb_slam_amd -lorbx \
-	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# the last-frame / key-frame searches of the drop-in (orb_slam_amd/cpp/LocalMapPointsSource.cc) over stand-in Frame.h / KeyFrame.h, driven by
-# scripts (tests/test_gpu_source_dropin.py); MapPoint.h and cvmini.h are those of tests/mappoints_dropin
-SRC_DROPIN := orb_slam_amd/cpp/LocalMapPointsSource.cc $(MP_DROPIN) $(wildcard tests/source_dropin/*.h)
-tests/source_dropin/harness: tests/source_dropin/harness.cpp $(SRC_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/source_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsSource.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::Refresh (orb_slam_amd/cpp/LocalMapPointsRefresh.cc) over stand-in MapPoint.h / KeyFrame.h, driven by scripts
-# (tests/test_gpu_refresh_dropin.py); Frame.h and cvmini.h are those of tests/mappoints_dropin
-RF_DROPIN := orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPoints.h orb_slam_amd/cpp/ORBmatcherAccess.h \
-    $(wildcard tests/refresh_dropin/*.h) tests/mappoints_dropin/Frame.h tests/mappoints_dropin/cvmini.h
-tests/refresh_dropin/harness: tests/refresh_dropin/harness.cpp $(RF_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/refresh_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::Fuse / FuseInNeighbors (orb_slam_amd/cpp/LocalMapPointsFuse.cc, over the key-frame store of LocalMapPointsRefresh.cc) over stand-in
-# MapPoint.h / KeyFrame.h, driven by scripts (tests/test_gpu_fuse_dropin.py); Frame.h and cvmini.h are those of tests/mappoints_dropin
-FU_DROPIN := orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPoints.h \
-    orb_slam_amd/cpp/ORBmatcherAccess.h $(wildcard tests/fuse_dropin/*.h) tests/mappoints_dropin/Frame.h tests/mappoints_dropin/cvmini.h
-tests/fuse_dropin/harness: tests/fuse_dropin/harness.cpp $(FU_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/fuse_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::SearchByProjection(pKF, Scw, ...) / SearchAndFuse (orb_slam_amd/cpp/LocalMapPointsLoop.cc, over searchFuse of LocalMapPointsFuse.cc and the
-# key-frame store of LocalMapPointsRefresh.cc) over a stand-in KeyFrame.h, driven by scripts (tests/test_gpu_loop_dropin.py); MapPoint.h is that of
-# tests/fuse_dropin, Frame.h and cvmini.h those of tests/mappoints_dropin
-LP_DROPIN := orb_slam_amd/cpp/LocalMapPointsLoop.cc $(FU_DROPIN) $(wildcard tests/loop_dropin/*.h)
-tests/loop_dropin/harness: tests/loop_dropin/harness.cpp $(LP_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/loop_dropin -Itests/fuse_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsLoop.cc -o $@ -Lorb_slam_amd -lorbx \
-	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::SearchBySim3 (orb_slam_amd/cpp/LocalMapPointsSim3.cc, over residentForFuse of LocalMapPointsFuse.cc and the key-frame store of
-# LocalMapPointsRefresh.cc), driven by scripts (tests/test_gpu_sim3_dropin.py); MapPoint.h is this directory's (it adds GetIndexInKeyFrame), KeyFrame.h
-# that of tests/loop_dropin, Frame.h and cvmini.h those of tests/mappoints_dropin
-S3_DROPIN := orb_slam_amd/cpp/LocalMapPointsSim3.cc $(FU_DROPIN) $(wildcard tests/sim3_dropin/*.h) tests/loop_dropin/KeyFrame.h
-tests/sim3_dropin/harness: tests/sim3_dropin/harness.cpp $(S3_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/sim3_dropin -Itests/loop_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsSim3.cc -o $@ -Lorb_slam_amd -lorbx \
-	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::SearchByBoW (orb_slam_amd/cpp/LocalMapPointsBoW.cc, over residentForFuse of LocalMapPointsFuse.cc and the key-frame store of
-# LocalMapPointsRefresh.cc), driven by scripts (tests/test_gpu_bow_dropin.py); KeyFrame.h and Frame.h are this directory's (they add the FeatureVector),
-# MapPoint.h that of tests/fuse_dropin, cvmini.h that of tests/mappoints_dropin
-BW_DROPIN := orb_slam_amd/cpp/LocalMapPointsBoW.cc orb_slam_amd/cpp/FeatureVectorCSR.h $(FU_DROPIN) $(wildcard tests/bow_dropin/*.h)
-tests/bow_dropin/harness: tests/bow_dropin/harness.cpp $(BW_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/bow_dropin -Itests/fuse_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsBoW.cc -o $@ -Lorb_slam_amd -lorbx \
-	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::CreateNewMapPoints (orb_slam_amd/cpp/LocalMapPointsNewPoints.cc, over residentForBoW of LocalMapPointsBoW.cc) next to the loop over
-# TriangulateNewMapPoints (orb_slam_amd/cpp/NewMapPoints.cc), driven by scripts (tests/test_gpu_newpoints_dropin.py); KeyFrame.h is this directory's (it
-# adds the level tables), Frame.h that of tests/bow_dropin, MapPoint.h that of tests/fuse_dropin, cvmini.h that of tests/mappoints_dropin
-NP_DROPIN := orb_slam_amd/cpp/LocalMapPointsNewPoints.cc orb_slam_amd/cpp/NewPointsPacking.h orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h \
-    orb_slam_amd/cpp/LocalMapPointsBoW.cc orb_slam_amd/cpp/FeatureVectorCSR.h $(FU_DROPIN) tests/bow_dropin/Frame.h $(wildcard tests/newpoints_dropin/*.h)
-tests/newpoints_dropin/harness: tests/newpoints_dropin/harness.cpp $(NP_DROPIN) include/orbt.h include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/newpoints_dropin -Itests/bow_dropin -Itests/fuse_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< \
-	    orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsFuse.cc orb_slam_amd/cpp/LocalMapPointsBoW.cc \
-	    orb_slam_amd/cpp/LocalMapPointsNewPoints.cc orb_slam_amd/cpp/NewMapPoints.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::PutKeyFrame / UpdateReferenceKeyFrames / SearchLocalMap / ConnectionWeights (orb_slam_amd/cpp/LocalMapPointsLocalMap.cc, over the rows of the
-# key-frame store of LocalMapPointsRefresh.cc), driven by scenes (tests/test_gpu_local_map_dropin.py); Frame.h, KeyFrame.h and MapPoint.h are this
-# directory's (they add mnTrackReferenceForFrame and the covisibility list), cvmini.h that of tests/mappoints_dropin
-LM_DROPIN := orb_slam_amd/cpp/LocalMapPointsLocalMap.cc orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPoints.h \
-    orb_slam_amd/cpp/ORBmatcherAccess.h $(wildcard tests/localmap_dropin/*.h) tests/mappoints_dropin/cvmini.h
-tests/localmap_dropin/harness: tests/localmap_dropin/harness.cpp $(LM_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/localmap_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsLocalMap.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# LocalMapPoints::KeyFrameCulling (orb_slam_amd/cpp/LocalMapPointsCull.cc, over the columns of LocalMapPointsLocalMap.cc and the rows of
-# LocalMapPointsRefresh.cc), driven by scenes (tests/test_gpu_cull_dropin.py); Frame.h, KeyFrame.h and MapPoint.h are this directory's (they add
-# SetBadFlag, EraseObservation, SetNotErase and the covisibility list), cvmini.h that of tests/mappoints_dropin
-CULL_DROPIN := orb_slam_amd/cpp/LocalMapPointsCull.cc orb_slam_amd/cpp/LocalMapPointsLocalMap.cc orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPoints.cc \
-    orb_slam_amd/cpp/LocalMapPoints.h orb_slam_amd/cpp/ORBmatcherAccess.h $(wildcard tests/cull_dropin/*.h) tests/mappoints_dropin/cvmini.h
-tests/cull_dropin/harness: tests/cull_dropin/harness.cpp $(CULL_DROPIN) include/orbp.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/cull_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/LocalMapPoints.cc \
-	    orb_slam_amd/cpp/LocalMapPointsRefresh.cc orb_slam_amd/cpp/LocalMapPointsLocalMap.cc orb_slam_amd/cpp/LocalMapPointsCull.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-
-# the Initializer drop-in (orb_slam_amd/cpp/Initializer.cc over include/orbi.h) over a stand-in Frame.h, driven by scenes (tests/test_gpu_init_dropin.py);
-# cvmini.h is that of tests/mappoints_dropin.  harness_host is the same class linked against the host route (tools/libinit_host.so exports the C ABI of
-# orbi.h on one host core): tests/test_init_dropin_host.py and tools/bench_init.py
-INIT_DROPIN := orb_slam_amd/cpp/Initializer.cc orb_slam_amd/cpp/Initializer.h tests/init_dropin/Frame.h tests/mappoints_dropin/cvmini.h orb_slam_amd/csrc/orb_jacobi.h include/orbi.h
-tests/init_dropin/harness: tests/init_dropin/harness.cpp $(INIT_DROPIN) include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -Itests/init_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp -Iorb_slam_amd/csrc $< orb_slam_amd/cpp/Initializer.cc -o $@ \
-	    -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-tests/init_dropin/harness_host: tests/init_dropin/harness.cpp $(INIT_DROPIN) tools/libinit_host.so
-	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -Itests/init_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp -Iorb_slam_amd/csrc $< orb_slam_amd/cpp/Initializer.cc -o $@ \
-	    -Ltools -linit_host -Wl,-rpath,'$$ORIGIN/../../tools'
-
-# the PnPsolver drop-in (orb_slam_amd/cpp/PnPsolver.cc over include/orbe.h) over a stand-in Frame.h, driven by scenes (tests/test_gpu_pnp_dropin.py); MapPoint.h
-# and cvmini.h are those of tests/mappoints_dropin.  harness_host is the same class linked against the host route (tools/libpnp_host.so):
-# tests/test_pnp_dropin_host.py
-PNP_DROPIN := orb_slam_amd/cpp/PnPsolver.cc orb_slam_amd/cpp/PnPsolver.h tests/pnp_dropin/Frame.h tests/mappoints_dropin/MapPoint.h tests/mappoints_dropin/cvmini.h include/orbe.h
-tests/pnp_dropin/harness: tests/pnp_dropin/harness.cpp $(PNP_DROPIN) include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/pnp_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/PnPsolver.cc -o $@ \
-	    -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
-tests/pnp_dropin/harness_host: tests/pnp_dropin/harness.cpp $(PNP_DROPIN) tools/libpnp_host.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/pnp_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/PnPsolver.cc -o $@ \
-	    -Ltools -lpnp_host -Wl,-rpath,'$$ORIGIN/../../tools'
-
-# the NewMapPoints drop-in (orb_slam_amd/cpp/NewMapPoints.cc) over a stand-in KeyFrame.h, driven by scripts
-# (tests/test_gpu_triangulate_dropin.py); cvmini.h is that of tests/mappoints_dropin
-TRI_DROPIN := orb_slam_amd/cpp/NewMapPoints.cc orb_slam_amd/cpp/NewMapPoints.h tests/triangulate_dropin/KeyFrame.h tests/mappoints_dropin/cvmini.h
-tests/triangulate_dropin/harness: tests/triangulate_dropin/harness.cpp $(TRI_DROPIN) include/orbt.h include/orbs.h include/orbf.h include/orbx.h orb_slam_amd/liborbx.so
-	$(CXX) -O2 -std=c++14 -Wall -Itests/triangulate_dropin -Itests/mappoints_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/NewMapPoints.cc -o $@ \
-	    -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+# The other drop-in classes (orb_slam_amd/cpp/LocalMapPoints*.cc, NewMapPoints.cc, Initializer.cc, PnPsolver.cc) are compiled once, against the one set
+# of stand-in ORB_SLAM classes in tests/standin, into one archive.  tests/NAME_dropin/harness.cpp drives them through scripts or scenes
+# (tests/test_gpu_NAME_dropin.py); the linker takes the members a harness needs.  harness_host is the same harness and class linked against the host
+# route of the C ABI (tools/libNAME_host.so) in liborbx's place: tests/test_init_dropin_host.py, tests/test_pnp_dropin_host.py, tools/bench_init.py.
+DROPIN_CXXFLAGS := -O2 -std=c++14 -Wall -Itests/standin -Iinclude -Iorb_slam_amd/cpp
+DROPIN_HDRS := $(wildcard tests/standin/*.h orb_slam_amd/cpp/*.h include/*.h)
+DROPIN_OBJS := $(patsubst orb_slam_amd/cpp/%.cc,build/dropin/%.o,$(wildcard orb_slam_amd/cpp/LocalMapPoints*.cc) $(addprefix orb_slam_amd/cpp/,NewMapPoints.cc Initializer.cc PnPsolver.cc))
+DROPIN_LIB  := build/dropin/libdropin.a
+# Initializer.cc shares orb_jacobi.h with the kernels and must round as they do (private: what these targets cause to be built does not inherit it)
+build/dropin/Initializer.o tests/init_dropin/harness tests/init_dropin/harness_host: private DROPIN_CXXFLAGS += -ffp-contract=off -Iorb_slam_amd/csrc
+build/dropin/Initializer.o: orb_slam_amd/csrc/orb_jacobi.h
+build/dropin/%.o: orb_slam_amd/cpp/%.cc $(DROPIN_HDRS)
+	@mkdir -p build/dropin
+	$(CXX) $(DROPIN_CXXFLAGS) -c $< -o $@
+$(DROPIN_LIB): $(DROPIN_OBJS)
+	rm -f $@ && ar rcs $@ $^
+tests/%_dropin/harness: tests/%_dropin/harness.cpp $(DROPIN_LIB) $(DROPIN_HDRS) orb_slam_amd/liborbx.so
+	$(CXX) $(DROPIN_CXXFLAGS) $< $(DROPIN_LIB) -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+tests/init_dropin/harness_host: tests/init_dropin/harness.cpp $(DROPIN_LIB) $(DROPIN_HDRS) tools/libinit_host.so
+	$(CXX) $(DROPIN_CXXFLAGS) $< $(DROPIN_LIB) -o $@ -Ltools -linit_host -Wl,-rpath,'$$ORIGIN/../../tools'
+tests/pnp_dropin/harness_host: tests/pnp_dropin/harness.cpp $(DROPIN_LIB) $(DROPIN_HDRS) tools/libpnp_host.so
+	$(CXX) $(DROPIN_CXXFLAGS) $< $(DROPIN_LIB) -o $@ -Ltools -lpnp_host -Wl,-rpath,'$$ORIGIN/../../tools'
+# LocalMapPoints.cc and LocalMapPointsSource.cc promise to name nothing of MapPoint and KeyFrame beyond what the tracking searches need: they compile
+# against the stand-ins with everything else taken away
+build/dropin/tracking_only.ok: orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPointsSource.cc $(DROPIN_HDRS)
+	@mkdir -p build/dropin
+	$(CXX) $(DROPIN_CXXFLAGS) -DSTANDIN_TRACKING_ONLY -fsyntax-only orb_slam_amd/cpp/LocalMapPoints.cc
+	$(CXX) $(DROPIN_CXXFLAGS) -DSTANDIN_TRACKING_ONLY -fsyntax-only orb_slam_amd/cpp/LocalMapPointsSource.cc
+	@touch $@
 
 # the host route tools/bench_triangulate.py measures the device triangulation against (one host core); tests/test_triangulate_host.py
 # holds it against the numpy restatement
@@ -249,7 +173,7 @@ tools/microbench/ta_shapes: tools/microbench/ta_shapes.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++20 -Wno-unused-value $< -o $@
 
 clean:
-	rm -f tools/libpnp_host.so tests/pnp_dropin/harness tests/pnp_dropin/harness_host tests/init_dropin/harness tests/init_dropin/harness_host tools/libinit_host.so tools/libcull_host.so tests/cull_dropin/harness tests/localmap_dropin/harness tools/liblocalmap_host.so tests/newpoints_dropin/harness tests/bow_dropin/harness tests/sim3_dropin/harness tools/libsim3_host.so tests/loop_dropin/harness tests/fuse_dropin/harness tools/libfuse_host.so tools/libloop_host.so tests/refresh_dropin/harness tests/mappoints_dropin/harness tests/source_dropin/harness tests/triangulate_dropin/harness tools/libmappoints_host.so tools/libsource_host.so tools/libtriangulate_host.so tools/librefresh_host.so tools/microbench/mfma_layout_fp4 tools/microbench/valu_exec_mask tools/microbench/ta_shapes tools/microbench/valu_rate tools/microbench/valu_rate2 tools/microbench/mfma_layout tools/microbench/mfma_valu_mix tools/microbench/fetch_calib orb_slam_amd/cpp/bench_single_frame tests/kfdb_dropin/harness orb_slam_amd/cpp/example_lanes orb_slam_amd/cpp/example_frame orb_slam_amd/cpp/example_batch orb_slam_amd/cpp/example_color orb_slam_amd/cpp/example_pipeline orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
-	rm -rf oracle/_ref oracle/_ref_native build/orbx
+	rm -f $(LIBS) $(EXAMPLES) $(DROPIN_HARNESSES) $(HOST_ROUTE_LIBS) $(MICROBENCH)
+	rm -rf oracle/_ref oracle/_ref_native build/orbx build/dropin
 
 .PHONY: all clean oracle_ref

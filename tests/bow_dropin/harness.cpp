@@ -1,5 +1,5 @@
-// Drives ORB_SLAM::LocalMapPoints::SearchByBoW (orb_slam_amd/cpp/LocalMapPointsBoW.cc, over the stand-in KeyFrame.h / Frame.h of this directory,
-// which carry a FeatureVector member, and the MapPoint.h of tests/fuse_dropin) through a script.  Next to the product's calls stand the loops that
+// Drives ORB_SLAM::LocalMapPoints::SearchByBoW (orb_slam_amd/cpp/LocalMapPointsBoW.cc, over the stand-in KeyFrame.h / Frame.h of tests/standin,
+// which carry a FeatureVector member, and its MapPoint.h) through a script.  Next to the product's calls stand the loops that
 // call ORBmatcher::SearchByBoW in the reference (src/Tracking.cc:880-901, src/LoopClosing.cc:246-274) with, in the function's place, its own
 // assignment lines (src/ORBmatcher.cc:159 + :227, :727 + :795) over a match table the script supplies; tests/test_gpu_bow_dropin.py runs both over
 // one object graph and compares every candidate's vector and count.  Floats travel as the hex of their bit pattern.
@@ -35,30 +35,12 @@
 #include "KeyFrame.h"
 #include "LocalMapPoints.h"
 #include "MapPoint.h"
+#include "harness_io.h"
 
-namespace ORB_SLAM {
-float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
-int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
-float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
-int MapPoint::nReplaced = 0;
-}
 using namespace ORB_SLAM;
 
 namespace {
 
-float rdf(std::istringstream& in) {
-    std::string h;
-    in >> h;
-    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-void rddesc(std::istringstream& in, unsigned char* d) {
-    std::string h;
-    in >> h;
-    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
-}
 void report(int ret, const std::vector<MapPoint*>& matches) {
     printf("S %d\nM", ret);
     for (MapPoint* p : matches) printf(" %ld", p ? (long)p->mnId : -1L);
@@ -199,7 +181,7 @@ int main(int argc, char** argv) {
             const int n = lmp().SearchByBoW(&kfs.at(k1), &kfs.at(k2), v);
             report(n, v);
         } else if (op == "forget") { int k; in >> k; lmp().ForgetKeyFrame(&kfs.at(k));
-        } else if (op == "fetched") { int k; in >> k; printf("F %d\n", kfs.at(k).getFeatVec);
+        } else if (op == "fetched") { int k; in >> k; printf("F %d\n", kfs.at(k).nGetFeatureVector);
         } else {
             fprintf(stderr, "unknown script line: %s\n", line.c_str());
             return 2;

@@ -1,5 +1,5 @@
-// Drives ORB_SLAM::LocalMapPoints::KeyFrameCulling (orb_slam_amd/cpp/LocalMapPointsCull.cc, over the stand-in Frame.h / KeyFrame.h / MapPoint.h of this
-// directory) through scenes; tests/test_gpu_cull_dropin.py writes the scenes of tests/golden/cull_ref_*.npz and compares what comes out with what the
+// Drives ORB_SLAM::LocalMapPoints::KeyFrameCulling (orb_slam_amd/cpp/LocalMapPointsCull.cc, over the stand-in Frame.h / KeyFrame.h / MapPoint.h of
+// tests/standin) through scenes; tests/test_gpu_cull_dropin.py writes the scenes of tests/golden/cull_ref_*.npz and compares what comes out with what the
 // reference's own text left behind.
 //
 //   harness SCENES
@@ -24,12 +24,8 @@
 #include "KeyFrame.h"
 #include "LocalMapPoints.h"
 #include "MapPoint.h"
+#include "harness_io.h"
 
-namespace ORB_SLAM {
-float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
-int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
-float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
-}
 using namespace ORB_SLAM;
 
 int main(int argc, char** argv) {
@@ -45,6 +41,7 @@ int main(int argc, char** argv) {
         std::vector<KeyFrame*> kf(nkf);
         for (int p = 0; p < npts; p++) {
             mps[p].mnId = p;
+            mps[p].mfMinDistance = 1.f; mps[p].mfMaxDistance = 4.f;
             for (int k = 0; k < 3; k++) { mps[p].mWorldPos.at<float>(k) = (float)(p % 5 + k); mps[p].mNormalVector.at<float>(k) = k == 2 ? 1.f : 0.f; }
             for (int b = 0; b < 32; b++) mps[p].mDescriptor.ptr<unsigned char>(0)[b] = (unsigned char)(p + b);
         }
@@ -105,7 +102,7 @@ int main(int argc, char** argv) {
         for (KeyFrame* k : local) printf(" %d", kidx[k]);
         printf("\nref %d\n", ref ? kidx[ref] : -1);
         int extra = 0;
-        for (int k = 0; k < nkf; k++) extra += kf[k]->keysRead > 1 ? kf[k]->keysRead - 1 : 0;
+        for (int k = 0; k < nkf; k++) extra += kf[k]->nGetKeyPointsUn > 1 ? kf[k]->nGetKeyPointsUn - 1 : 0;
         printf("keys %d\n", extra);
     }
     return 0;

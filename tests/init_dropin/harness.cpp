@@ -1,4 +1,4 @@
-// Drives ORB_SLAM::Initializer (orb_slam_amd/cpp/Initializer.cc) over the stand-in Frame.h of this directory: harness IN OUT [REPS].
+// Drives ORB_SLAM::Initializer (orb_slam_amd/cpp/Initializer.cc) over the stand-in Frame.h of tests/standin: harness IN OUT [REPS].
 // IN (binary, little endian): float fx, fy, cx, cy, sigma; int32 iters, n1, n2, given; n1 + n2 key points (28 bytes each); int32 vMatches12[n1];
 // int32 sets[iters * 8] when given != 0 (otherwise the class draws them with rand() after srand(0)).
 // OUT: int32 ok, model ('H', 'F' or 0), bestH, bestF, nInliers, chosen, nhyp; float SH, SF, RH; int32 nGood[8]; float parallax[8], R21[9], t21[3];
@@ -28,6 +28,7 @@ int main(int argc, char** argv) {
     const int iters = hdr[0], n1 = hdr[1], n2 = hdr[2], given = hdr[3];
     ORB_SLAM::Frame F1, F2;
     for (ORB_SLAM::Frame* F : {&F1, &F2}) {
+        F->mK = cv::Mat(3, 3, CV_32F);
         for (int i = 0; i < 9; i++) F->mK.at<float>(i) = i % 4 == 0 ? 1.0f : 0.0f;
         F->mK.at<float>(0, 0) = par[0]; F->mK.at<float>(1, 1) = par[1]; F->mK.at<float>(0, 2) = par[2]; F->mK.at<float>(1, 2) = par[3];
     }

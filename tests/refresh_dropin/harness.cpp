@@ -1,5 +1,5 @@
-// Drives ORB_SLAM::LocalMapPoints::Refresh (orb_slam_amd/cpp/LocalMapPointsRefresh.cc, over the stand-in MapPoint.h / KeyFrame.h of this
-// directory and the Frame.h of tests/mappoints_dropin) through a script; tests/test_gpu_refresh_dropin.py builds the script and compares
+// Drives ORB_SLAM::LocalMapPoints::Refresh (orb_slam_amd/cpp/LocalMapPointsRefresh.cc, over the stand-in MapPoint.h / KeyFrame.h /
+// Frame.h of tests/standin) through a script; tests/test_gpu_refresh_dropin.py builds the script and compares
 // with tests/refresh_ref.py.  Floats travel as the hex of their bit pattern.
 //
 //   harness SCRIPT
@@ -26,30 +26,13 @@
 #include "KeyFrame.h"
 #include "LocalMapPoints.h"
 #include "MapPoint.h"
+#include "harness_io.h"
 
-namespace ORB_SLAM {
-float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
-int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
-float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
-}
 using namespace ORB_SLAM;
 
 namespace {
 
-float rdf(std::istringstream& in) {
-    std::string h;
-    in >> h;
-    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 unsigned bitsof(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-void rddesc(std::istringstream& in, unsigned char* d) {
-    std::string h;
-    in >> h;
-    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
-}
 std::vector<MapPoint*> rdlist(std::istringstream& in, std::map<long, std::unique_ptr<MapPoint> >& mps) {
     int k = 0;
     in >> k;
@@ -104,7 +87,7 @@ int main(int argc, char** argv) {
             for (int c = 0; c < 3; c++) K.Ow.at<float>(c) = rdf(in);
             in >> bad >> n;
             K.mbBad = bad != 0;
-            K.mvScaleFactors = factors;
+            K.mvScaleFactors = factors; K.mnScaleLevels = (int)factors.size();
             K.mvKeysUn.assign(n, cv::KeyPoint());
             K.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);
             for (int i = 0; i < n; i++) {
@@ -127,7 +110,7 @@ int main(int argc, char** argv) {
             const std::vector<MapPoint*> v = rdlist(in, mps);
             const std::vector<orbp_refreshed> r = L->Refresh(v, descriptors != 0);
             int fetched = 0;
-            for (const KeyFrame& K : kfs) fetched += K.getKeys;
+            for (const KeyFrame& K : kfs) fetched += K.nGetKeyPointsUn;
             printf("F %zu %d %d\n", L->size(), L->capacity(), fetched);
             for (size_t i = 0; i < v.size(); i++)
                 printf("R %ld %d %08x %08x %08x %08x %08x %d %d\n", v[i] ? (long)v[i]->mnId : -1L, r[i].status, bitsof(r[i].normal[0]), bitsof(r[i].normal[1]),

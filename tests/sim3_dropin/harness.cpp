@@ -1,5 +1,5 @@
-// Drives ORB_SLAM::LocalMapPoints::SearchBySim3 (orb_slam_amd/cpp/LocalMapPointsSim3.cc, over the stand-in MapPoint.h of this directory, the
-// KeyFrame.h of tests/loop_dropin and the Frame.h of tests/mappoints_dropin) through a script, and on request runs the reference's last step
+// Drives ORB_SLAM::LocalMapPoints::SearchBySim3 (orb_slam_amd/cpp/LocalMapPointsSim3.cc, over the stand-in MapPoint.h / KeyFrame.h /
+// Frame.h of tests/standin) through a script, and on request runs the reference's last step
 // (src/ORBmatcher.cc:1489-1502: vpMatches12[i1] = vpMapPoints2[idx2], nFound++) over an agreement table the script supplies instead of the two
 // searches; tests/test_gpu_sim3_dropin.py builds two identical object graphs that way and compares what is left of vpMatches12.
 // Floats travel as the hex of their bit pattern.
@@ -24,30 +24,11 @@
 #include "KeyFrame.h"
 #include "LocalMapPoints.h"
 #include "MapPoint.h"
+#include "harness_io.h"
 
-namespace ORB_SLAM {
-float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
-int Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
-float Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv;
-int MapPoint::nReplaced = 0;
-}
 using namespace ORB_SLAM;
 
 namespace {
-
-float rdf(std::istringstream& in) {
-    std::string h;
-    in >> h;
-    const uint32_t u = (uint32_t)strtoul(h.c_str(), nullptr, 16);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-void rddesc(std::istringstream& in, unsigned char* d) {
-    std::string h;
-    in >> h;
-    for (int i = 0; i < 32; i++) d[i] = (unsigned char)strtoul(h.substr(i * 2, 2).c_str(), nullptr, 16);
-}
 
 typedef std::map<long, std::unique_ptr<MapPoint> > Points;
 
@@ -121,7 +102,7 @@ int main(int argc, char** argv) {
             for (int r = 0; r < 3; r++) K.tcw.at<float>(r) = rdf(in);
             for (int r = 0; r < 3; r++) K.Ow.at<float>(r) = 0.0f;          // the camera centre is not read by this search
             in >> n;
-            K.mvScaleFactors = factors;
+            K.mvScaleFactors = factors; K.mnScaleLevels = (int)factors.size();
             K.mvKeysUn.assign(n, cv::KeyPoint());
             K.mvpMapPoints.assign(n, nullptr);
             K.mDescriptors = cv::Mat(n > 0 ? n : 1, 32, CV_8U);

@@ -1,5 +1,7 @@
-// The little of OpenCV that ORB_SLAM's Frame.h / MapPoint.h expose to LocalMapPoints.cc, for the stand-in headers of this directory:
-// a matrix of floats or bytes with at<T>() / ptr<T>(), and cv::KeyPoint.
+// The little of OpenCV that ORB_SLAM's Frame.h / KeyFrame.h / MapPoint.h expose to the drop-in classes of orb_slam_amd/cpp, for the stand-in
+// headers of this directory: a matrix of floats or bytes with at<T>() / ptr<T>(), cv::KeyPoint and cv::Point3f.  A copy of a Mat shares its
+// store, as OpenCV's does.
+// tests/kfdb_dropin keeps its own Frame.h / KeyFrame.h: they sit on orb_slam_amd/cpp/cvcompat.h, whose cv::Mat is another type than this one.
 #pragma once
 #include <cstddef>
 #include <memory>
@@ -11,6 +13,12 @@
 namespace cv {
 
 struct Point2f { float x = 0, y = 0; };
+
+struct Point3f {
+    float x, y, z;
+    Point3f() : x(0), y(0), z(0) {}
+    Point3f(float a, float b, float c) : x(a), y(b), z(c) {}
+};
 
 struct KeyPoint {
     Point2f pt;
