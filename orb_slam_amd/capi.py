@@ -74,6 +74,9 @@ INIT_MAX_PROBLEMS, INIT_MAX_MATCHES, INIT_MAX_ITERS, INIT_MAX_HYP = 32, 16384, 1
 # include/orbe.h (the EPnP RANSAC of the relocalisation)
 EXPORTS_E = ["orbe_ransac_parameters", "orbe_hypotheses_batch_device", "orbe_hypotheses", "orbe_refine_batch_device", "orbe_refine",
              "orbe_refit_batch_device", "orbe_refit", "orbe_select_batch_device", "orbe_select", "orbe_iterate", "orbe_iterate_batch"]
+# include/orbh.h (the Sim3 RANSAC of loop closing)
+EXPORTS_H = ["orbh_ransac_parameters", "orbh_max_errors", "orbh_hypotheses_batch_device", "orbh_hypotheses", "orbh_select_batch_device", "orbh_select",
+             "orbh_iterate", "orbh_iterate_batch"]
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
 # orbp_fused.status
@@ -227,6 +230,18 @@ PNP_RESULT_DTYPE = np.dtype([("kind", np.int32), ("stop", np.int32), ("no_more",
 assert PNP_PROBLEM_DTYPE.itemsize == 32 and PNP_STATE_DTYPE.itemsize == 112 and PNP_RESULT_DTYPE.itemsize == 64
 PNP_KIND_NONE, PNP_KIND_BEST, PNP_KIND_REFINED = 0, 1, 2
 PNP_MAX_PROBLEMS, PNP_MAX_POINTS, PNP_MAX_ITERS = 32, 8192, 1024
+# orbh_problem / orbh_hyp / orbh_state / orbh_result as numpy records (include/orbh.h)
+SIM3SOLVER_PROBLEM_DTYPE = np.dtype([("fx1", np.float32), ("fy1", np.float32), ("cx1", np.float32), ("cy1", np.float32), ("fx2", np.float32),
+                                     ("fy2", np.float32), ("cx2", np.float32), ("cy2", np.float32), ("n", np.int32), ("iters", np.int32),
+                                     ("min_inliers", np.int32), ("max_its", np.int32)])
+SIM3SOLVER_HYP_DTYPE = np.dtype([("q", np.float64, 4), ("R", np.float32, 9), ("t", np.float32, 3), ("s", np.float32), ("T12", np.float32, 16),
+                                 ("T21", np.float32, 16), ("count", np.int32)])
+SIM3SOLVER_STATE_DTYPE = np.dtype([("iterations", np.int32), ("best_inliers", np.int32), ("best_T12", np.float32, 16), ("best_R", np.float32, 9),
+                                   ("best_t", np.float32, 3), ("best_s", np.float32)])
+SIM3SOLVER_RESULT_DTYPE = np.dtype([("found", np.int32), ("stop", np.int32), ("no_more", np.int32), ("ninliers", np.int32), ("T12", np.float32, 16)])
+assert SIM3SOLVER_PROBLEM_DTYPE.itemsize == 48 and SIM3SOLVER_HYP_DTYPE.itemsize == 216 and SIM3SOLVER_STATE_DTYPE.itemsize == 124 and \
+    SIM3SOLVER_RESULT_DTYPE.itemsize == 80
+SIM3SOLVER_MAX_PROBLEMS, SIM3SOLVER_MAX_POINTS, SIM3SOLVER_MAX_ITERS, SIM3SOLVER_POINT_ROWS = 32, 8192, 1024, 12
 
 # orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
 VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
@@ -421,6 +436,7 @@ def lib():
         L.orbt_new_points_rows.argtypes = [ctypes.POINTER(SearchParams), vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         pnp_bind(L)
+        sim3solver_bind(L)
         L.orbi_normalize.argtypes = [vp, ci, vp]
         L.orbi_pose_from_rt.argtypes = [cf, cf, cf, cf, vp, vp, vp]
         L.orbi_models_batch_device.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1171,6 +1187,188 @@ def triangulate(pair, factors1, sigma2_1, factors2, sigma2_2, kps1, kps2, match1
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbt_triangulate (accepted: %d)" % count.value)
     return status[:n1], x3d[:n1], (v[:n1] if want_v else None), acc_idx[:count.value], acc_x3d[:count.value]
+
+
+def sim3solver_bind(L):
+    """the argument types of the orbh_* entry points (include/orbh.h); tools/libsim3solver_host.so exports the host forms with the same types"""
+    vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    L.orbh_ransac_parameters.argtypes = [ci, cd, ci, ci, vp]
+    L.orbh_max_errors.argtypes = [ci, vp, vp]
+    L.orbh_hypotheses.argtypes = [vp] * 10 + [ci]
+    L.orbh_select.argtypes = [vp] * 7 + [ci]
+    L.orbh_iterate.argtypes = [vp] * 14 + [ci]
+    L.orbh_iterate_batch.argtypes = [vp, ci] + [vp] * 13 + [ci]
+    if hasattr(L, "orbh_hypotheses_batch_device"):
+        L.orbh_hypotheses_batch_device.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, vp]
+        L.orbh_select_batch_device.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    return L
+
+
+def sim3solver_words(n):
+    """flag words of n correspondences (ORBH_WORDS)"""
+    return (int(n) + 63) // 64
+
+
+def sim3solver_unpack(words, n):
+    """packed flag words [..., W] -> uint8 flags [..., n] (bit i % 64 of word i // 64)"""
+    w = np.ascontiguousarray(words, dtype="<u8")
+    bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[:-1] + (-1,)), axis=-1, bitorder="little")
+    return bits[..., :n]
+
+
+def sim3solver_ransac_parameters(n, probability=0.99, min_inliers=6, max_iterations=300, L=None):
+    """Sim3Solver::SetRansacParameters (include/orbh.h; needs no GPU; the defaults are the reference's) -> mRansacMaxIts"""
+    mx = ctypes.c_int32(0)
+    rc = (L or lib()).orbh_ransac_parameters(int(n), float(probability), int(min_inliers), int(max_iterations), ctypes.addressof(mx))
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_ransac_parameters")
+    return mx.value
+
+
+def sim3solver_max_errors(sigma2, L=None):
+    """mvnMaxError1/2 as the comparisons see them: (float)(size_t)(9.210*sigma2) (include/orbh.h; needs no GPU)"""
+    s2 = np.ascontiguousarray(sigma2, dtype=np.float32).reshape(-1)
+    out = np.zeros(len(s2), np.float32)
+    rc = (L or lib()).orbh_max_errors(len(s2), s2.ctypes.data if len(s2) else None, out.ctypes.data if len(s2) else None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_max_errors")
+    return out
+
+
+def sim3solver_problem(cam1, cam2, n, iters, min_inliers, max_its):
+    """a SIM3SOLVER_PROBLEM_DTYPE record; cam = (fx, fy, cx, cy)"""
+    q = np.zeros(1, SIM3SOLVER_PROBLEM_DTYPE)
+    q["fx1"], q["fy1"], q["cx1"], q["cy1"] = cam1
+    q["fx2"], q["fy2"], q["cx2"], q["cy2"] = cam2
+    q["n"] = n; q["iters"] = iters; q["min_inliers"] = min_inliers; q["max_its"] = max_its
+    return q[0]
+
+
+def sim3solver_state(n):
+    """a fresh solver state -> (SIM3SOLVER_STATE_DTYPE[1], best_flags[W])"""
+    return np.zeros(1, SIM3SOLVER_STATE_DTYPE), np.zeros(sim3solver_words(n), np.uint64)
+
+
+def _sim3solver_points(n, pts):
+    """pts = (x3dc1[n, 3], x3dc2[n, 3], p1im1[n, 2], p2im2[n, 2], maxerr1[n], maxerr2[n]) as contiguous float arrays"""
+    a = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in pts]
+    if len(a) != 6 or [x.size for x in a] != [n * 3, n * 3, n * 2, n * 2, n, n]:
+        raise ValueError("the arrays do not have the problem's count")
+    return a
+
+
+def sim3solver_point_table(pts, ncap=None):
+    """the struct-of-arrays point table of one problem (include/orbh.h): float32[12, ncap]"""
+    n = len(np.asarray(pts[4]).reshape(-1))
+    a = _sim3solver_points(n, pts)
+    t = np.zeros((SIM3SOLVER_POINT_ROWS, ncap or n), np.float32)
+    t[0:3, :n] = a[0].reshape(n, 3).T; t[3:6, :n] = a[1].reshape(n, 3).T
+    t[6:8, :n] = a[2].reshape(n, 2).T; t[8:10, :n] = a[3].reshape(n, 2).T
+    t[10, :n] = a[4]; t[11, :n] = a[5]
+    return t
+
+
+def sim3solver_hypotheses(problem, pts, sets, device=0, L=None):
+    """every hypothesis of one call, host arrays, synchronous -> (SIM3SOLVER_HYP_DTYPE[I], flag words uint64[I, W]) (include/orbh.h).
+    L: another library with the same ABI (tools/libsim3solver_host.so)"""
+    pr = np.ascontiguousarray(problem, dtype=SIM3SOLVER_PROBLEM_DTYPE).reshape(1)
+    N, I = int(pr["n"][0]), int(pr["iters"][0])
+    a = _sim3solver_points(N, pts)
+    st = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 3)
+    if len(st) != I:
+        raise ValueError("one set per iteration")
+    hyp = np.zeros(max(I, 1), SIM3SOLVER_HYP_DTYPE); fl = np.zeros((max(I, 1), sim3solver_words(max(N, 1))), np.uint64)
+    rc = (L or lib()).orbh_hypotheses(pr.ctypes.data, *[x.ctypes.data for x in a], st.ctypes.data, hyp.ctypes.data, fl.ctypes.data, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_hypotheses")
+    return hyp[:I], fl[:I]
+
+
+def _sim3solver_check_state(N, state, best_flags):
+    if state.dtype != SIM3SOLVER_STATE_DTYPE or not state.flags.c_contiguous or best_flags.dtype != np.uint64 or len(best_flags) != sim3solver_words(N):
+        raise ValueError("state: SIM3SOLVER_STATE_DTYPE[1]; best_flags: uint64[W]")
+
+
+def sim3solver_select(problem, hyp, flags, state, best_flags, device=0, L=None):
+    """the walk of Sim3Solver::iterate over the hypotheses; state (SIM3SOLVER_STATE_DTYPE[1]) and best_flags are updated in place
+    -> (SIM3SOLVER_RESULT_DTYPE record, result flag words[W])"""
+    pr = np.ascontiguousarray(problem, dtype=SIM3SOLVER_PROBLEM_DTYPE).reshape(1)
+    N, I = int(pr["n"][0]), int(pr["iters"][0])
+    _sim3solver_check_state(N, state, best_flags)
+    h = np.ascontiguousarray(hyp, dtype=SIM3SOLVER_HYP_DTYPE).reshape(-1); f = np.ascontiguousarray(flags, dtype=np.uint64).reshape(-1)
+    if len(h) != I or len(f) != I * sim3solver_words(N):
+        raise ValueError("one hypothesis and one flag row per iteration")
+    res = np.zeros(1, SIM3SOLVER_RESULT_DTYPE); rfl = np.zeros(sim3solver_words(N), np.uint64)
+    rc = (L or lib()).orbh_select(pr.ctypes.data, h.ctypes.data, f.ctypes.data, state.ctypes.data, best_flags.ctypes.data, res.ctypes.data, rfl.ctypes.data,
+                                  device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_select")
+    return res[0], rfl
+
+
+def sim3solver_iterate(problem, pts, sets, state, best_flags, want_hyp=True, device=0, L=None):
+    """calls of Sim3Solver::iterate after their draw, host arrays, synchronous; state and best_flags are updated in place
+    -> (SIM3SOLVER_RESULT_DTYPE record, result flag words[W], hyp[I] or None, flag words[I, W] or None)"""
+    pr = np.ascontiguousarray(problem, dtype=SIM3SOLVER_PROBLEM_DTYPE).reshape(1)
+    N, I = int(pr["n"][0]), int(pr["iters"][0])
+    a = _sim3solver_points(N, pts)
+    st = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 3)
+    if len(st) != I:
+        raise ValueError("one set per iteration")
+    _sim3solver_check_state(N, state, best_flags)
+    W = sim3solver_words(max(N, 1))
+    res = np.zeros(1, SIM3SOLVER_RESULT_DTYPE); rfl = np.zeros(W, np.uint64)
+    hyp = np.zeros(max(I, 1), SIM3SOLVER_HYP_DTYPE) if want_hyp else None; fl = np.zeros((max(I, 1), W), np.uint64) if want_hyp else None
+    rc = (L or lib()).orbh_iterate(pr.ctypes.data, *[x.ctypes.data for x in a], st.ctypes.data, state.ctypes.data, best_flags.ctypes.data, res.ctypes.data,
+                                   rfl.ctypes.data, hyp.ctypes.data if want_hyp else None, fl.ctypes.data if want_hyp else None, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_iterate")
+    return res[0], rfl, (hyp[:I] if want_hyp else None), (fl[:I] if want_hyp else None)
+
+
+def sim3solver_iterate_batch(problems, pts, sets, states, best_flags, want_hyp=True, device=0, L=None):
+    """the same for several solvers as ONE chain with one synchronisation (what the drop-in Sim3Solver::Prefetch calls): pts and sets are lists of
+    per-solver host arrays; states (SIM3SOLVER_STATE_DTYPE[P]) and the best flag words are updated in place
+    -> (SIM3SOLVER_RESULT_DTYPE[P], [result flag words], [hyp] or None, [flag words] or None)"""
+    pr = np.ascontiguousarray(problems, dtype=SIM3SOLVER_PROBLEM_DTYPE).reshape(-1)
+    P = len(pr)
+    if not (len(pts) == len(sets) == len(best_flags) == P) or states.dtype != SIM3SOLVER_STATE_DTYPE or len(states) != P or P < 1:
+        raise ValueError("one entry per solver")
+    arrs = [_sim3solver_points(int(pr["n"][p]), pts[p]) for p in range(P)]
+    st = [np.ascontiguousarray(x, np.int32).reshape(-1, 3) for x in sets]
+    for p in range(P):
+        if len(st[p]) != int(pr["iters"][p]) or best_flags[p].dtype != np.uint64 or len(best_flags[p]) != sim3solver_words(pr["n"][p]):
+            raise ValueError("the arrays of solver %d do not have its counts" % p)
+    res = np.zeros(P, SIM3SOLVER_RESULT_DTYPE)
+    out = [np.zeros(sim3solver_words(n), np.uint64) for n in pr["n"]]
+    hyp = [np.zeros(int(i), SIM3SOLVER_HYP_DTYPE) for i in pr["iters"]]
+    fl = [np.zeros((int(i), sim3solver_words(n)), np.uint64) for i, n in zip(pr["iters"], pr["n"])]
+    ptrs = lambda xs: (ctypes.c_void_p * P)(*[x.ctypes.data for x in xs])
+    keep = [ptrs([a[k] for a in arrs]) for k in range(6)] + [ptrs(st), ptrs(best_flags), ptrs(out), ptrs(hyp), ptrs(fl)]
+    ad = [ctypes.addressof(k) for k in keep]
+    rc = (L or lib()).orbh_iterate_batch(pr.ctypes.data, P, ad[0], ad[1], ad[2], ad[3], ad[4], ad[5], ad[6], states.ctypes.data, ad[7], res.ctypes.data, ad[8],
+                                         ad[9] if want_hyp else None, ad[10] if want_hyp else None, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_iterate_batch")
+    return res, out, (hyp if want_hyp else None), (fl if want_hyp else None)
+
+
+def sim3solver_hypotheses_batch_device(problems, d_points, ncap, d_sets, icap, d_hyp, d_flags, stream=0):
+    """the hypotheses of len(problems) calls (include/orbh.h); problems: host SIM3SOLVER_PROBLEM_DTYPE records, the rest device pointers as ints"""
+    pr = np.ascontiguousarray(problems, dtype=SIM3SOLVER_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbh_hypotheses_batch_device(pr.ctypes.data, len(pr), d_points or None, ncap, d_sets or None, icap, d_hyp or None, d_flags or None,
+                                            stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_hypotheses_batch_device")
+
+
+def sim3solver_select_batch_device(problems, ncap, icap, d_hyp, d_flags, d_state, d_best_flags, d_result, d_result_flags, stream=0):
+    """the walk of Sim3Solver::iterate for len(problems) solvers; their states and best flags are updated on the device (include/orbh.h)"""
+    pr = np.ascontiguousarray(problems, dtype=SIM3SOLVER_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbh_select_batch_device(pr.ctypes.data, len(pr), ncap, icap, d_hyp or None, d_flags or None, d_state or None, d_best_flags or None,
+                                        d_result or None, d_result_flags or None, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbh_select_batch_device")
 
 
 def pnp_bind(L):
