@@ -394,6 +394,10 @@ int orbx_debug_eval_math(int kind, const float* in0, const float* in1, float* ou
 /* evaluate the device's FAST compass pre-test (k_fast_cells phase A1) on n dword quintuples at threshold t: c = four centre pixels,
  * e / w = the pixels 3 to their right / left, nn / ss = 3 rows above / below; out: the flag of pixel j in bit 8 j + 7 */
 int orbx_debug_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t, int device);
+/* evaluate the FAST kernels' exact score (phase B, packed halves) and opposite-pair pre-test (phase A2) on n caller-supplied rings at threshold
+ * tmin: centre[i] the pixel, ring16[16 i + k] ring pixel k (k = 0 at (0, +3), then through (+3, 0), (0, -3), (-3, 0)).  score[i] = the
+ * cv::FAST corner score, or 0 where it is below tmin; pair[i] = 1 where the pair test passes the pixel on */
+int orbx_debug_eval_score(const uint8_t* centre, const uint8_t* ring16, uint8_t* score, uint8_t* pair, int n, int tmin, int device);
 /* run k_describe_od's per-key-point blur (its row pass, float column pass and rounding epilogue, four windows per wave as in the kernel) on n
  * caller-supplied windows of 43 rows x 48 bytes: out = the n blurred regions of 37 rows x 40 bytes the descriptor taps read (window rows 3 .. 39,
  * columns 4 .. 43).  rounding: ORBX_BLUR_* for every column; general != 0: through the per-lane epilogue of edge windows instead of the fast one */

@@ -32,7 +32,7 @@ EXPORTS = [
     "orbx_stream_create", "orbx_stream_create_priority", "orbx_stream_destroy", "orbx_stream_synchronize", "orbx_event_create", "orbx_event_destroy", "orbx_event_record",
     "orbx_stream_wait_event", "orbx_device_copy_async", "orbx_host_alloc", "orbx_host_free", "orbx_device_upload_async", "orbx_device_download_async", "orbx_debug_set_stop_after", "orbx_debug_set_blur_on_demand", "orbx_debug_level_size", "orbx_debug_resize_form", "orbx_debug_fetch",
     "orbx_debug_launch_variant", "orbx_debug_variant_count", "orbx_debug_variant_name", "orbx_debug_plan",
-    "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_eval_blur_window", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
+    "orbx_debug_eval_math", "orbx_debug_eval_compass", "orbx_debug_eval_score", "orbx_debug_eval_blur_window", "orbx_debug_stage_timing", "orbx_debug_stage_time", "orbx_debug_nth_element", "orbx_debug_geometry",
     "orbm_debug_set_match_path",
     "orbm_debug_get_match_path",
 ]
@@ -339,6 +339,8 @@ def lib():
         L.orbx_debug_fetch.restype = cl
         L.orbx_debug_eval_math.argtypes = [ci, vp, vp, vp, vp, ci, ci]
         L.orbx_debug_eval_compass.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci]
+        if hasattr(L, "orbx_debug_eval_score"):        # (likewise)
+            L.orbx_debug_eval_score.argtypes = [vp, vp, vp, vp, ci, ci, ci]
         L.orbx_debug_eval_blur_window.argtypes = [vp, vp, ci, ci, ci, ci]
         L.orbx_debug_nth_element.argtypes = [vp, ci, ci, vp, ci]
         L.orbx_debug_geometry.argtypes = [ctypes.POINTER(Params), ci, ci, vp, ci]
@@ -938,6 +940,20 @@ def eval_compass(c, e, w, n, s, t, device=0):
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbx_debug_eval_compass")
     return out
+
+
+def eval_score(centre, ring16, tmin, device=0):
+    """the FAST kernels' exact score (phase B, packed halves) and opposite-pair pre-test (phase A2) on rings: centre (n,) uint8, ring16 (n, 16)
+    uint8 in ring order from (0, +3) -> (score, pair): the corner score or 0 below tmin, and 1 where the pair test passes the pixel on"""
+    centre = np.ascontiguousarray(centre, dtype=np.uint8)
+    ring16 = np.ascontiguousarray(ring16, dtype=np.uint8)
+    assert centre.ndim == 1 and ring16.shape == (centre.size, 16)
+    score = np.empty_like(centre)
+    pair = np.empty_like(centre)
+    rc = lib().orbx_debug_eval_score(centre.ctypes.data, ring16.ctypes.data, score.ctypes.data, pair.ctypes.data, centre.size, int(tmin), device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_debug_eval_score")
+    return score, pair
 
 
 def eval_blur_window(windows, blur_rounding=BLUR_X86_SSE2, general=False, device=0):

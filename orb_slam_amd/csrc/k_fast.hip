@@ -20,29 +20,45 @@ __device__ __forceinline__ int fast_pair_test(const uint8_t* c, int S, int v, in
     return (int)(v - a > t) | (int)(bq - v > t);
 }
 
-__device__ __forceinline__ int fast_score_raw(const uint8_t* c, int S, int v, int tmin) {
-    int x[16];
-    x[0] = c[3 * S]; x[1] = c[3 * S + 1]; x[2] = c[2 * S + 2]; x[3] = c[S + 3]; x[4] = c[3]; x[5] = c[-S + 3]; x[6] = c[-2 * S + 2]; x[7] = c[-3 * S + 1];
-    x[8] = c[-3 * S]; x[9] = c[-3 * S - 1]; x[10] = c[-2 * S - 2]; x[11] = c[-S - 3]; x[12] = c[-3]; x[13] = c[S - 3]; x[14] = c[2 * S - 2]; x[15] = c[3 * S - 1];
-    int hi3[16], lo3[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        hi3[k] = imax3(x[k], x[(k + 1) & 15], x[(k + 2) & 15]);
-        lo3[k] = imin3(x[k], x[(k + 1) & 15], x[(k + 2) & 15]);
+// B's arithmetic: the exact score on packed halves (orb_math.h: fast9_score_pk_with, which fixes the pairing and the swap pattern of every
+// step).  Word j holds ring pixels j and j + 8 in its 16-bit halves; a byte in a half is the f16 denormal 0x00XX, positive f16 order is integer
+// order and the kernels keep f16 denormals, so one v_pk_maximum3_f16 / v_pk_minimum3_f16 is the integer max3 / min3 of two ring positions
+// at once, and op_sel supplies the swapped halves the circular indexing needs: 42 three-input instructions per pass where the unpacked
+// form (rounds 1-7: v_max3_u32 / v_min3_u32 on one position each) took 80.  tools/microbench/valu_rate2.hip checks that the two opcodes return
+// byte-valued halves bit for bit (all 2^24 triples per half and swap pattern) and prices them; tests/test_gpu_fast_score_pk.py holds this
+// against fast9_score through orbx_debug_eval_score.
+struct PkHalvesF16 {
+#define ORBX_PK3(OPC, SEL) asm(OPC " %0, %1, %2, %3" SEL : "=v"(o) : "v"(a), "v"(b), "v"(c))
+    static __device__ __forceinline__ uint32_t max3(uint32_t a, uint32_t b, uint32_t c, int form) {
+        uint32_t o;
+        if (form == PK_SWAP_BC) ORBX_PK3("v_pk_maximum3_f16", " op_sel:[0,1,1] op_sel_hi:[1,0,0]");
+        else if (form == PK_SWAP_C) ORBX_PK3("v_pk_maximum3_f16", " op_sel:[0,0,1] op_sel_hi:[1,1,0]");
+        else ORBX_PK3("v_pk_maximum3_f16", "");
+        return o;
     }
-    int hi9[16], lo9[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        hi9[k] = imax3(hi3[k], hi3[(k + 3) & 15], hi3[(k + 6) & 15]);
-        lo9[k] = imin3(lo3[k], lo3[(k + 3) & 15], lo3[(k + 6) & 15]);
+    static __device__ __forceinline__ uint32_t min3(uint32_t a, uint32_t b, uint32_t c, int form) {
+        uint32_t o;
+        if (form == PK_SWAP_BC) ORBX_PK3("v_pk_minimum3_f16", " op_sel:[0,1,1] op_sel_hi:[1,0,0]");
+        else if (form == PK_SWAP_C) ORBX_PK3("v_pk_minimum3_f16", " op_sel:[0,0,1] op_sel_hi:[1,1,0]");
+        else ORBX_PK3("v_pk_minimum3_f16", "");
+        return o;
     }
-    // 16 -> 1 with three-input ops (8 instead of 16 two-input ones)
-    const int min_hi9 = imin3(imin3(imin3(hi9[0], hi9[1], hi9[2]), imin3(hi9[3], hi9[4], hi9[5]), imin3(hi9[6], hi9[7], hi9[8])),
-                              imin3(imin3(hi9[9], hi9[10], hi9[11]), imin3(hi9[12], hi9[13], hi9[14]), hi9[15]), 255);
-    const int max_lo9 = imax3(imax3(imax3(lo9[0], lo9[1], lo9[2]), imax3(lo9[3], lo9[4], lo9[5]), imax3(lo9[6], lo9[7], lo9[8])),
-                              imax3(imax3(lo9[9], lo9[10], lo9[11]), imax3(lo9[12], lo9[13], lo9[14]), lo9[15]), 0);
-    const int s = imax(v - min_hi9, max_lo9 - v) - 1;   // == OpenCV cornerScore for every corner
-    return s >= tmin ? s : 0;
+#undef ORBX_PK3
+};
+// the ring of the pixel at c as packed words: X[j] = ring j | ring (j + 8) << 16 (ring offsets: fast_pair_test above)
+__device__ __forceinline__ void fast_ring_pk(const uint8_t* c, int S, uint32_t X[8]) {
+    // all sixteen reads first, in the order the words are put together, then the words: left to itself the scheduler puts the first word
+    // together after four reads, behind a full wait, and the pass pays two LDS round trips (the barrier pins the order, not the waits)
+    const uint32_t x0 = c[3 * S], x8 = c[-3 * S], x1 = c[3 * S + 1], x9 = c[-3 * S - 1], x2 = c[2 * S + 2], x10 = c[-2 * S - 2], x3 = c[S + 3], x11 = c[-S - 3];
+    const uint32_t x4 = c[3], x12 = c[-3], x5 = c[-S + 3], x13 = c[S - 3], x6 = c[-2 * S + 2], x14 = c[2 * S - 2], x7 = c[-3 * S + 1], x15 = c[3 * S - 1];
+    __builtin_amdgcn_sched_barrier(0);
+    X[0] = x0 | x8 << 16; X[1] = x1 | x9 << 16; X[2] = x2 | x10 << 16; X[3] = x3 | x11 << 16;
+    X[4] = x4 | x12 << 16; X[5] = x5 | x13 << 16; X[6] = x6 | x14 << 16; X[7] = x7 | x15 << 16;
+}
+__device__ __forceinline__ int fast_score_pk(const uint8_t* c, int S, int v, int tmin) {
+    uint32_t X[8];
+    fast_ring_pk(c, S, X);
+    return fast9_score_pk_with<PkHalvesF16>(X, v, tmin);   // == OpenCV cornerScore for every corner
 }
 
 // ------------------------------------------------------------------------------------ FAST + NMS + cell lists
@@ -74,6 +90,11 @@ __device__ __forceinline__ int fast_score_raw(const uint8_t* c, int S, int v, in
 // invariants allow (7 workgroups per CU on VGA grids), the staging moves 16 bytes per lane, the drain scores both remainders in
 // one pass without the pair test, the list output scans with DPP adds instead of ds_bpermute and counts by ballot.  (NOTES.md 8.2b;
 // what did NOT help: pooling the waves' remainders behind extra barriers, an L2 prefetch of a later band, smaller bands.)
+// The exact score (phase B) runs on packed halves: two ring positions per word, one v_pk_maximum3_f16 / v_pk_minimum3_f16 per step, 42 steps
+// plus 8 v_lshl_or_b32 where the unpacked form took 80 (fast_score_pk above; NOTES.md 8.2e).  Every wave runs it at least once, in the
+// drain.  What it gains depends on how close to its issue limit the kernel runs on the box at hand: -5.8 % of the kernel where the parent
+// took 0.786 ms per 1024 VGA frames, nothing where it took 0.726.  (What did NOT help: assembling the halves by ds_read_u8_d16 / _d16_hi,
+// which do not keep the other half on this device; seven reads at byte addresses in place of the sixteen byte reads, +29 %.)
 struct FastHdr { int n_hi, n_lo, overflow, pad1; int wsum[8]; int pad2[4]; };
 static_assert(sizeof(FastHdr) == 64, "LDS carve");
 
@@ -111,6 +132,26 @@ __global__ void k_eval_compass(const uint32_t* c, const uint32_t* e, const uint3
 }
 int launch_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t) {
     hipLaunchKernelGGL(k_eval_compass, dim3((n + 255) / 256), dim3(256), 0, 0, c, e, w, nn, ss, out, n, t);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+// (diagnostics: the kernels' exact score and pair test on caller-supplied rings.  Every lane lays its ring out as a 7 x 7 patch of pitch 8 in
+// LDS and calls fast_score_pk / fast_pair_test on it as phases B and A2 do on the staged band, ring reads included.)
+__global__ __launch_bounds__(256) void k_eval_score(const uint8_t* centre, const uint8_t* ring16, uint8_t* score, uint8_t* pair, int n, int tmin) {
+    constexpr int PS = 8, PATCH = 7 * PS;
+    constexpr int RDX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1}, RDY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
+    __shared__ uint8_t s_patch[256 * PATCH];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint8_t* c = s_patch + threadIdx.x * PATCH + 3 * PS + 3;
+    c[0] = centre[i];
+#pragma unroll
+    for (int k = 0; k < 16; k++) c[RDY[k] * PS + RDX[k]] = ring16[16ll * i + k];
+    score[i] = (uint8_t)fast_score_pk(c, PS, c[0], tmin);      // (a lane reads its own patch only: no barrier)
+    pair[i] = (uint8_t)fast_pair_test(c, PS, c[0], tmin);
+}
+int launch_eval_score(const uint8_t* centre, const uint8_t* ring16, uint8_t* score, uint8_t* pair, int n, int tmin) {
+    hipLaunchKernelGGL(k_eval_score, dim3((n + 255) / 256), dim3(256), 0, 0, centre, ring16, score, pair, n, tmin);
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
@@ -239,7 +280,7 @@ __device__ __forceinline__ void fast_band_task(const Batch& b, int frame, int it
         int sc = 0;
         if (on) {
             const uint8_t* c = s_img + p;
-            sc = fast_score_raw(c, S, c[0], tmin);
+            sc = fast_score_pk(c, S, c[0], tmin);
             s_sc[p] = (uint8_t)sc;
         }
         const unsigned long long mk = __ballot(sc != 0);

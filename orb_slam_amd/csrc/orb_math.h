@@ -138,6 +138,67 @@ ORBX_HD int fast9_score(const int d[16], int tmin) {
     return s >= tmin ? s : 0;
 }
 
+// ---- the same score on packed halves (k_fast.hip phase B: fast_score_pk) ------------------------
+// Two ring positions per 32-bit word: X[j] = x[j] | x[j + 8] << 16, j = 0..7, x the ring PIXELS (not differences).  Ring position i of any of
+// the three levels (pixels, windows of 3, windows of 9) is R(i) = word i for i < 8 and word i - 8 WITH ITS HALVES SWAPPED for 8 <= i < 16, so
+// that step j works on positions j (low half) and j + 8 (high half) at once:
+//   hi3[j] = max3(R(j), R(j + 1), R(j + 2))       8 steps, halves (hi3[j], hi3[j + 8])
+//   hi9[j] = max3(H3(j), H3(j + 3), H3(j + 6))    8 steps, halves (hi9[j], hi9[j + 8])
+//   min over the 16 hi9: 8 words -> 3 -> 1 by min3 (4 steps), then the word against itself with swapped halves (1 step)
+// and the same with min and max exchanged: 42 three-input steps where fast9_score takes 80.  The sources of a step are in rising position, so
+// only three swap patterns occur: none, the third source, the second and third (PK_PLAIN / PK_SWAP_C / PK_SWAP_BC).
+// OPS supplies max3 / min3 of three words per half with those patterns.  PkHalvesInt below does it with integer compares on the halves (the
+// definition; tests/test_fast_score_pk_host.py holds fast9_score_pk against fast9_score); the kernel's PkHalvesF16 does each in one
+// v_pk_maximum3_f16 / v_pk_minimum3_f16, the swaps by op_sel: a half 0x00XX is a positive f16 denormal, positive f16 order is integer order,
+// and the kernels keep denormals (float_denorm_mode_16_64 = 3), so the instruction returns one of its inputs unchanged.
+// d = v - x turns a max over pixels into a min over differences: in fast9_score's terms dark = max_k lo9(d) = v - min_k hi9(x) and
+// bright = min_k hi9(d) = v - max_k lo9(x), so the score max(dark, -bright) - 1 is max(v - min_k hi9(x), max_k lo9(x) - v) - 1.
+enum { PK_PLAIN = 0, PK_SWAP_C = 1, PK_SWAP_BC = 2 };
+ORBX_HD uint32_t pk_swap(uint32_t a) { return a >> 16 | a << 16; }
+struct PkHalvesInt {
+    static ORBX_HD uint32_t each(uint32_t a, uint32_t b, uint32_t c, int form, bool want_max) {
+        if (form >= PK_SWAP_C) c = pk_swap(c);
+        if (form == PK_SWAP_BC) b = pk_swap(b);
+        uint32_t o = 0;
+        for (int h = 0; h < 32; h += 16) {
+            const int x = (int)((a >> h) & 0xFFFFu), y = (int)((b >> h) & 0xFFFFu), z = (int)((c >> h) & 0xFFFFu);
+            o |= (uint32_t)(want_max ? imax3(x, y, z) : imin3(x, y, z)) << h;
+        }
+        return o;
+    }
+    static ORBX_HD uint32_t max3(uint32_t a, uint32_t b, uint32_t c, int form) { return each(a, b, c, form, true); }
+    static ORBX_HD uint32_t min3(uint32_t a, uint32_t b, uint32_t c, int form) { return each(a, b, c, form, false); }
+};
+// swap pattern of a step whose second / third source sit at ring positions ib <= ic (the first is always below 8)
+ORBX_HD constexpr int pk_form(int ib, int ic) { return ib >= 8 ? PK_SWAP_BC : ic >= 8 ? PK_SWAP_C : PK_PLAIN; }
+// min over k of hi9[k] (low half of the result) from the pixel words; MAXW = false: max over k of lo9[k]
+template <class OPS, bool MAXW>
+ORBX_HD uint32_t fast9_window_pk(const uint32_t X[8]) {
+    uint32_t W3[8], W9[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int f = pk_form(j + 1, j + 2);
+        W3[j] = MAXW ? OPS::max3(X[j], X[(j + 1) & 7], X[(j + 2) & 7], f) : OPS::min3(X[j], X[(j + 1) & 7], X[(j + 2) & 7], f);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int f = pk_form(j + 3, j + 6);
+        W9[j] = MAXW ? OPS::max3(W3[j], W3[(j + 3) & 7], W3[(j + 6) & 7], f) : OPS::min3(W3[j], W3[(j + 3) & 7], W3[(j + 6) & 7], f);
+    }
+    // the other way round: the min of the window maxima
+    auto red = [](uint32_t a, uint32_t b, uint32_t c, int f) { return MAXW ? OPS::min3(a, b, c, f) : OPS::max3(a, b, c, f); };
+    const uint32_t m = red(red(W9[0], W9[1], W9[2], PK_PLAIN), red(W9[3], W9[4], W9[5], PK_PLAIN), red(W9[6], W9[7], W9[7], PK_PLAIN), PK_PLAIN);
+    return red(m, m, m, PK_SWAP_BC) & 0xFFFFu;      // each half against the other
+}
+template <class OPS>
+ORBX_HD int fast9_score_pk_with(const uint32_t X[8], int v, int tmin) {
+    const int min_hi9 = (int)fast9_window_pk<OPS, true>(X), max_lo9 = (int)fast9_window_pk<OPS, false>(X);
+    const int s = imax(v - min_hi9, max_lo9 - v) - 1;
+    return s >= tmin ? s : 0;
+}
+// X[j] = ring[j] | ring[j + 8] << 16 (pixels 0..255), v the centre: == fast9_score of d[k] = v - ring[k]
+ORBX_HD int fast9_score_pk(const uint32_t X[8], int v, int tmin) { return fast9_score_pk_with<PkHalvesInt>(X, v, tmin); }
+
 // ---- FAST compass pre-test by byte averages (k_fast.hip phase A1) ------------------------------
 // avg_u8 is one byte of v_lerp_u8: (a + b + (c & 1)) >> 1, the sum nine bits wide.  With x a ring pixel, v the centre, d = x - v,
 // t the threshold and r = t & 1 (so that t + r is even):
@@ -147,7 +208,7 @@ ORBX_HD int fast9_score(const int d[16], int tmin) {
 // The dark side admits the one extra difference d == -t (253 + r - t is always odd, so no constant cuts h between -t and -t - 1: h
 // was rounded with the bright side's r).  The test is a filter in front of the exact score, so a superset changes no result.
 // Valid for 0 <= t <= 254; a larger t is clamped to 254: the filter then passes d = 255 and d <= -254 although nothing is a corner
-// at such a threshold, and the exact score (fast_score_raw: s >= tmin) rejects those pixels as it rejects every other false flag.
+// at such a threshold, and the exact score (fast_score_pk: s >= tmin) rejects those pixels as it rejects every other false flag.
 // tests/test_fast_compass_host.py runs every (x, v, t).
 ORBX_HD int avg_u8(int a, int b, int c) { return (a + b + (c & 1)) >> 1; }
 ORBX_HD int compass_t(int t) { return t < 0 ? 0 : t > 254 ? 254 : t; }

@@ -11,6 +11,7 @@
 namespace orbx {
 int launch_eval_math(int kind, const float* in0, const float* in1, float* out0, float* out1, int n);
 int launch_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t* w, const uint32_t* nn, const uint32_t* ss, uint32_t* out, int n, int t);
+int launch_eval_score(const uint8_t* centre, const uint8_t* ring16, uint8_t* score, uint8_t* pair, int n, int tmin);
 int launch_eval_blur_window(const uint8_t* win, uint8_t* out, int n, int ties_even, int general);
 void stage_timer_collect(StageTimer& t);
 int launch_debug_nth(const float* d_resp, int n, int nth, int* d_out);
@@ -937,6 +938,21 @@ int orbx_debug_eval_compass(const uint32_t* c, const uint32_t* e, const uint32_t
     const int rc = launch_eval_compass(s[ic], s[ie], s[iw], s[in_], s[is], s[o], n, t);
     if (rc != ORBX_OK) return rc;
     HIPTRY(s.get(out, o, n));
+    return ORBX_OK;
+}
+
+int orbx_debug_eval_score(const uint8_t* centre, const uint8_t* ring16, uint8_t* score, uint8_t* pair, int n, int tmin, int device) {
+    if (n <= 0) return ORBX_OK;
+    if (!centre || !ring16 || !score || !pair || tmin < 0 || n > (1 << 26)) return ORBX_ERR_ARG;
+    HIPTRY(hipSetDevice(device));
+    Staging s;
+    const auto ic = s.in(centre, n), ir = s.in(ring16, (size_t)n * 16);
+    const auto os = s.out<uint8_t>(n), op = s.out<uint8_t>(n);
+    HIPTRY(s.alloc());
+    const int rc = launch_eval_score(s[ic], s[ir], s[os], s[op], n, tmin);
+    if (rc != ORBX_OK) return rc;
+    HIPTRY(s.get(score, os, n));
+    HIPTRY(s.get(pair, op, n));
     return ORBX_OK;
 }
 
