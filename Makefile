@@ -12,9 +12,9 @@ ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*
 # what `all` builds and `clean` removes, named once
 LIBS             := orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
 EXAMPLES         := $(addprefix orb_slam_amd/cpp/,example_frame example_batch example_color example_pipeline example_lanes bench_single_frame)
-DROPIN_HARNESSES := $(patsubst %,tests/%_dropin/harness,kfdb mappoints source triangulate refresh fuse loop sim3 bow newpoints localmap cull init pnp sim3solver) \
-    tests/init_dropin/harness_host tests/pnp_dropin/harness_host tests/sim3solver_dropin/harness_host
-HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp sim3solver)
+DROPIN_HARNESSES := $(patsubst %,tests/%_dropin/harness,kfdb mappoints source triangulate refresh fuse loop sim3 bow newpoints localmap cull init pnp sim3solver poseopt) \
+    tests/init_dropin/harness_host tests/pnp_dropin/harness_host tests/sim3solver_dropin/harness_host tests/poseopt_dropin/harness_host
+HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp sim3solver poseopt)
 MICROBENCH       := $(addprefix tools/microbench/,valu_rate valu_rate2 mfma_layout mfma_layout_fp4 mfma_valu_mix fetch_calib valu_exec_mask ta_shapes)
 
 all: $(LIBS) oracle_ref $(EXAMPLES) $(DROPIN_HARNESSES) build/dropin/tracking_only.ok $(HOST_ROUTE_LIBS) $(MICROBENCH)
@@ -76,13 +76,13 @@ tests/kfdb_dropin/harness: tests/kfdb_dropin/harness.cpp $(KFDB_DROPIN) include/
 	$(CXX) -O2 -std=c++14 -pthread -Itests/kfdb_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/KeyFrameDatabase.cc -o $@ -Lorb_slam_amd -lorbx \
 	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
 
-# The other drop-in classes (orb_slam_amd/cpp/LocalMapPoints*.cc, NewMapPoints.cc, Initializer.cc, PnPsolver.cc, Sim3Solver.cc) are compiled once, against the one set
+# The other drop-in classes (orb_slam_amd/cpp/LocalMapPoints*.cc, NewMapPoints.cc, Initializer.cc, PnPsolver.cc, Sim3Solver.cc, PoseOptimizer.cc) are compiled once, against the one set
 # of stand-in ORB_SLAM classes in tests/standin, into one archive.  tests/NAME_dropin/harness.cpp drives them through scripts or scenes
 # (tests/test_gpu_NAME_dropin.py); the linker takes the members a harness needs.  harness_host is the same harness and class linked against the host
-# route of the C ABI (tools/libNAME_host.so) in liborbx's place: tests/test_init_dropin_host.py, tests/test_pnp_dropin_host.py, tests/test_sim3solver_dropin_host.py, tools/bench_init.py.
+# route of the C ABI (tools/libNAME_host.so) in liborbx's place: tests/test_init_dropin_host.py, tests/test_pnp_dropin_host.py, tests/test_sim3solver_dropin_host.py, tests/test_poseopt_dropin_host.py, tools/bench_init.py.
 DROPIN_CXXFLAGS := -O2 -std=c++14 -Wall -Itests/standin -Iinclude -Iorb_slam_amd/cpp
 DROPIN_HDRS := $(wildcard tests/standin/*.h orb_slam_amd/cpp/*.h include/*.h)
-DROPIN_OBJS := $(patsubst orb_slam_amd/cpp/%.cc,build/dropin/%.o,$(wildcard orb_slam_amd/cpp/LocalMapPoints*.cc) $(addprefix orb_slam_amd/cpp/,NewMapPoints.cc Initializer.cc PnPsolver.cc Sim3Solver.cc))
+DROPIN_OBJS := $(patsubst orb_slam_amd/cpp/%.cc,build/dropin/%.o,$(wildcard orb_slam_amd/cpp/LocalMapPoints*.cc) $(addprefix orb_slam_amd/cpp/,NewMapPoints.cc Initializer.cc PnPsolver.cc Sim3Solver.cc PoseOptimizer.cc))
 DROPIN_LIB  := build/dropin/libdropin.a
 # Initializer.cc shares orb_jacobi.h with the kernels and must round as they do (private: what these targets cause to be built does not inherit it)
 build/dropin/Initializer.o tests/init_dropin/harness tests/init_dropin/harness_host: private DROPIN_CXXFLAGS += -ffp-contract=off -Iorb_slam_amd/csrc
@@ -102,6 +102,8 @@ tests/pnp_dropin/harness_host: tests/pnp_dropin/harness.cpp $(DROPIN_LIB) $(DROP
 	$(CXX) $(DROPIN_CXXFLAGS) $< $(DROPIN_LIB) -o $@ -Ltools -lpnp_host -Wl,-rpath,'$$ORIGIN/../../tools'
 tests/sim3solver_dropin/harness_host: tests/sim3solver_dropin/harness.cpp $(DROPIN_LIB) $(DROPIN_HDRS) tools/libsim3solver_host.so
 	$(CXX) $(DROPIN_CXXFLAGS) $< $(DROPIN_LIB) -o $@ -Ltools -lsim3solver_host -Wl,-rpath,'$$ORIGIN/../../tools'
+tests/poseopt_dropin/harness_host: tests/poseopt_dropin/harness.cpp $(DROPIN_LIB) $(DROPIN_HDRS) tools/libposeopt_host.so
+	$(CXX) $(DROPIN_CXXFLAGS) $< $(DROPIN_LIB) -o $@ -Ltools -lposeopt_host -Wl,-rpath,'$$ORIGIN/../../tools'
 # LocalMapPoints.cc and LocalMapPointsSource.cc promise to name nothing of MapPoint and KeyFrame beyond what the tracking searches need: they compile
 # against the stand-ins with everything else taken away
 build/dropin/tracking_only.ok: orb_slam_amd/cpp/LocalMapPoints.cc orb_slam_amd/cpp/LocalMapPointsSource.cc $(DROPIN_HDRS)
@@ -144,6 +146,11 @@ tools/libpnp_host.so: tools/pnp_host_route.cpp include/orbe.h orb_slam_amd/csrc/
 # the host route tools/bench_sim3solver.py measures the Sim3 RANSAC of loop closing (orbh_hypotheses, orbh_select, orbh_iterate) against: the C ABI of
 # include/orbh.h on one host core over the same arithmetic text; tests/test_sim3solver_host.py holds it against the numpy restatement
 tools/libsim3solver_host.so: tools/sim3solver_host_route.cpp include/orbh.h orb_slam_amd/csrc/orbh_math.h orb_slam_amd/csrc/orbh_host.h orb_slam_amd/csrc/orb_jacobi.h
+	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
+
+# the host route tools/bench_poseopt.py measures the pose optimisation of tracking (orbo_pose, orbo_pose_batch) against: the host forms of
+# include/orbo.h on one host core over the same arithmetic text and summation order; tests/test_poseopt_host.py holds it against the numpy restatement
+tools/libposeopt_host.so: tools/poseopt_host_route.cpp include/orbo.h orb_slam_amd/csrc/orbo_math.h orb_slam_amd/csrc/orbo_host.h orb_slam_amd/csrc/orb_jacobi.h
 	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
 
 # the host route tools/bench_local_map.py measures the local-map chain against: the three object-graph walks over flat stand-in arrays on one host core

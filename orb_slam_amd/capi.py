@@ -77,6 +77,8 @@ EXPORTS_E = ["orbe_ransac_parameters", "orbe_hypotheses_batch_device", "orbe_hyp
 # include/orbh.h (the Sim3 RANSAC of loop closing)
 EXPORTS_H = ["orbh_ransac_parameters", "orbh_max_errors", "orbh_hypotheses_batch_device", "orbh_hypotheses", "orbh_select_batch_device", "orbh_select",
              "orbh_iterate", "orbh_iterate_batch"]
+# include/orbo.h (tracking's motion-only pose optimisation)
+EXPORTS_O = ["orbo_pose_batch_device", "orbo_pose", "orbo_pose_batch"]
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
 # orbp_fused.status
@@ -242,6 +244,15 @@ SIM3SOLVER_RESULT_DTYPE = np.dtype([("found", np.int32), ("stop", np.int32), ("n
 assert SIM3SOLVER_PROBLEM_DTYPE.itemsize == 48 and SIM3SOLVER_HYP_DTYPE.itemsize == 216 and SIM3SOLVER_STATE_DTYPE.itemsize == 124 and \
     SIM3SOLVER_RESULT_DTYPE.itemsize == 80
 SIM3SOLVER_MAX_PROBLEMS, SIM3SOLVER_MAX_POINTS, SIM3SOLVER_MAX_ITERS, SIM3SOLVER_POINT_ROWS = 32, 8192, 1024, 12
+# orbo_problem / orbo_result / orbo_step as numpy records (include/orbo.h)
+POSEOPT_PROBLEM_DTYPE = np.dtype([("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("n", np.int32)])
+POSEOPT_RESULT_DTYPE = np.dtype([("Tcw", np.float32, 16), ("q", np.float64, 4), ("t", np.float64, 3), ("ninitial", np.int32), ("nbad", np.int32),
+                                 ("rounds", np.int32), ("iters", np.int32, 4), ("noutlier", np.int32)])
+POSEOPT_STEP_DTYPE = np.dtype([("chi_in", np.float64), ("chi_out", np.float64), ("lambda", np.float64), ("trials", np.int32), ("status", np.int32)])
+assert POSEOPT_PROBLEM_DTYPE.itemsize == 20 and POSEOPT_RESULT_DTYPE.itemsize == 152 and POSEOPT_STEP_DTYPE.itemsize == 32
+POSEOPT_MAX_PROBLEMS, POSEOPT_MAX_EDGES, POSEOPT_EDGE_ROWS, POSEOPT_ROUNDS, POSEOPT_MAX_ITERS = 64, 8192, 6, 4, 32
+POSEOPT_ROUND_SLOT = (0, 10, 20, 27)        # a round's first record of the trace
+POSEOPT_OK, POSEOPT_TERMINATE, POSEOPT_NOT_RUN = 0, 1, 2
 
 # orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
 VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
@@ -439,6 +450,7 @@ def lib():
                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         pnp_bind(L)
         sim3solver_bind(L)
+        poseopt_bind(L)
         L.orbi_normalize.argtypes = [vp, ci, vp]
         L.orbi_pose_from_rt.argtypes = [cf, cf, cf, cf, vp, vp, vp]
         L.orbi_models_batch_device.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1385,6 +1397,90 @@ def sim3solver_select_batch_device(problems, ncap, icap, d_hyp, d_flags, d_state
                                         d_result or None, d_result_flags or None, stream or None)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbh_select_batch_device")
+
+
+def poseopt_bind(L):
+    """the argument types of the orbo_* entry points (include/orbo.h); tools/libposeopt_host.so exports the host forms with the same types"""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.orbo_pose.argtypes = [vp] * 8 + [ci]
+    L.orbo_pose_batch.argtypes = [vp, ci] + [vp] * 7 + [ci]
+    if hasattr(L, "orbo_pose_batch_device"):
+        L.orbo_pose_batch_device.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    return L
+
+
+def poseopt_problem(cam, n):
+    """one orbo_problem record: cam = (fx, fy, cx, cy), n edges"""
+    q = np.zeros((), POSEOPT_PROBLEM_DTYPE)
+    q["fx"], q["fy"], q["cx"], q["cy"] = cam
+    q["n"] = n
+    return q
+
+
+def poseopt_edge_table(xyz, uv, inv_sigma2, ncap=None):
+    """a frame's edges as the device table: ORBO_EDGE_ROWS rows of ncap floats (include/orbo.h)"""
+    n = len(inv_sigma2)
+    ncap = max(n, 1) if ncap is None else ncap
+    t = np.zeros((POSEOPT_EDGE_ROWS, ncap), np.float32)
+    if n:
+        t[0:3, :n] = np.asarray(xyz, np.float32).reshape(n, 3).T
+        t[3:5, :n] = np.asarray(uv, np.float32).reshape(n, 2).T
+        t[5, :n] = inv_sigma2
+    return t
+
+
+def _poseopt_arrays(n, xyz, uv, inv_sigma2, Tcw):
+    a = (np.ascontiguousarray(xyz, np.float32).reshape(-1, 3), np.ascontiguousarray(uv, np.float32).reshape(-1, 2),
+         np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1))
+    if not all(len(x) == n for x in a):
+        raise ValueError("the edge arrays do not have the problem's n")
+    T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(-1)[:12] if np.size(Tcw) == 16 else Tcw, np.float32).reshape(12)
+    return a, T
+
+
+def poseopt_pose(problem, xyz, uv, inv_sigma2, Tcw, want_trace=False, device=0, L=None):
+    """Optimizer::PoseOptimization for one frame, host arrays, synchronous (include/orbo.h): Tcw is the 3 x 4 [R | t] (or the 4 x 4 matrix)
+    -> (POSEOPT_RESULT_DTYPE record, outlier flags uint8[n], POSEOPT_STEP_DTYPE[32] or None)"""
+    pr = np.ascontiguousarray(problem, dtype=POSEOPT_PROBLEM_DTYPE).reshape(1)
+    n = int(pr["n"][0])
+    a, T = _poseopt_arrays(n, xyz, uv, inv_sigma2, Tcw)
+    res = np.zeros(1, POSEOPT_RESULT_DTYPE); words = np.zeros(max(sim3solver_words(n), 1), np.uint64)
+    tr = np.zeros(POSEOPT_MAX_ITERS, POSEOPT_STEP_DTYPE) if want_trace else None
+    rc = (L or lib()).orbo_pose(pr.ctypes.data, *[x.ctypes.data if n else None for x in a], T.ctypes.data, res.ctypes.data, words.ctypes.data if n else None,
+                                tr.ctypes.data if want_trace else None, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbo_pose")
+    return res[0], sim3solver_unpack(words, n), tr
+
+
+def poseopt_pose_batch(problems, xyz, uv, inv_sigma2, Tcw, want_trace=False, device=0, L=None):
+    """the same for several frames as ONE launch with one synchronisation (the relocaliser's candidates): xyz, uv, inv_sigma2 are lists of per-frame
+    host arrays, Tcw is [P, 12] -> (POSEOPT_RESULT_DTYPE[P], [outlier flags uint8[n]], [POSEOPT_STEP_DTYPE[32]] or None)"""
+    pr = np.ascontiguousarray(problems, dtype=POSEOPT_PROBLEM_DTYPE).reshape(-1)
+    P = len(pr)
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(P, 12)
+    if not (len(xyz) == len(uv) == len(inv_sigma2) == P) or P < 1:
+        raise ValueError("one entry per frame")
+    arrs = [_poseopt_arrays(int(pr["n"][p]), xyz[p], uv[p], inv_sigma2[p], T[p])[0] for p in range(P)]
+    res = np.zeros(P, POSEOPT_RESULT_DTYPE)
+    words = [np.zeros(max(sim3solver_words(n), 1), np.uint64) for n in pr["n"]]
+    tr = [np.zeros(POSEOPT_MAX_ITERS, POSEOPT_STEP_DTYPE) for _ in range(P)]
+    ptrs = lambda xs, ns: (ctypes.c_void_p * P)(*[x.ctypes.data if n else None for x, n in zip(xs, ns)])
+    keep = [ptrs([a[k] for a in arrs], pr["n"]) for k in range(3)] + [ptrs(words, pr["n"]), ptrs(tr, [1] * P)]
+    ad = [ctypes.addressof(k) for k in keep]
+    rc = (L or lib()).orbo_pose_batch(pr.ctypes.data, P, ad[0], ad[1], ad[2], T.ctypes.data, res.ctypes.data, ad[3], ad[4] if want_trace else None, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbo_pose_batch")
+    return res, [sim3solver_unpack(w, int(n)) for w, n in zip(words, pr["n"])], (tr if want_trace else None)
+
+
+def poseopt_pose_batch_device(problems, d_edges, ncap, d_Tcw, d_result, d_outlier, d_trace=0, stream=0):
+    """the poses of len(problems) frames (include/orbo.h); problems: host POSEOPT_PROBLEM_DTYPE records, the rest device pointers as ints"""
+    pr = np.ascontiguousarray(problems, dtype=POSEOPT_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbo_pose_batch_device(pr.ctypes.data, len(pr), d_edges or None, ncap, d_Tcw or None, d_result or None, d_outlier or None, d_trace or None,
+                                      stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbo_pose_batch_device")
 
 
 def pnp_bind(L):
