@@ -13,8 +13,9 @@ ORBX_HDRS  := $(wildcard orb_slam_amd/csrc/*.h orb_slam_amd/csrc/*.inc include/*
 LIBS             := orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracle/liborb_oracle.so
 EXAMPLES         := $(addprefix orb_slam_amd/cpp/,example_frame example_batch example_color example_pipeline example_lanes bench_single_frame)
 DROPIN_HARNESSES := $(patsubst %,tests/%_dropin/harness,kfdb mappoints source triangulate refresh fuse loop sim3 bow newpoints localmap cull init pnp sim3solver poseopt) \
-    tests/init_dropin/harness_host tests/pnp_dropin/harness_host tests/sim3solver_dropin/harness_host tests/poseopt_dropin/harness_host
-HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp sim3solver poseopt)
+    tests/init_dropin/harness_host tests/pnp_dropin/harness_host tests/sim3solver_dropin/harness_host tests/poseopt_dropin/harness_host \
+    tests/localba_dropin/harness tests/localba_dropin/harness_host
+HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp sim3solver poseopt localba)
 MICROBENCH       := $(addprefix tools/microbench/,valu_rate valu_rate2 mfma_layout mfma_layout_fp4 mfma_valu_mix fetch_calib valu_exec_mask ta_shapes)
 
 all: $(LIBS) oracle_ref $(EXAMPLES) $(DROPIN_HARNESSES) build/dropin/tracking_only.ok $(HOST_ROUTE_LIBS) $(MICROBENCH)
@@ -75,6 +76,17 @@ KFDB_DROPIN := orb_slam_amd/cpp/KeyFrameDatabase.cc orb_slam_amd/cpp/KeyFrameDat
 tests/kfdb_dropin/harness: tests/kfdb_dropin/harness.cpp $(KFDB_DROPIN) include/orbd.h include/orbv.h include/orbx.h orb_slam_amd/liborbx.so
 	$(CXX) -O2 -std=c++14 -pthread -Itests/kfdb_dropin -Iinclude -Iorb_slam_amd/cpp $< orb_slam_amd/cpp/KeyFrameDatabase.cc -o $@ -Lorb_slam_amd -lorbx \
 	    -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+
+# the BundleAdjuster drop-in (orb_slam_amd/cpp/BundleAdjuster.cc) over its own stand-in KeyFrame.h / MapPoint.h / Map.h (tests/standin lacks SetPose, GetInvSigma2,
+# the mnBA* marks and EraseObservation's bad rule; they sit on its cvmini.h), driven by scenes (tests/test_gpu_localba_dropin.py); harness_host is the same
+# class linked against the host route (tests/test_localba_dropin_host.py)
+LOCALBA_DROPIN := orb_slam_amd/cpp/BundleAdjuster.cc orb_slam_amd/cpp/BundleAdjuster.h $(addprefix tests/localba_dropin/,KeyFrame.h MapPoint.h Map.h) tests/standin/cvmini.h \
+    include/orbb.h include/orbo.h include/orbx.h
+LOCALBA_CXXFLAGS := -O2 -std=c++14 -Wall -Itests/localba_dropin -Itests/standin -Iinclude -Iorb_slam_amd/cpp
+tests/localba_dropin/harness: tests/localba_dropin/harness.cpp $(LOCALBA_DROPIN) orb_slam_amd/liborbx.so
+	$(CXX) $(LOCALBA_CXXFLAGS) $< orb_slam_amd/cpp/BundleAdjuster.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+tests/localba_dropin/harness_host: tests/localba_dropin/harness.cpp $(LOCALBA_DROPIN) tools/liblocalba_host.so
+	$(CXX) $(LOCALBA_CXXFLAGS) $< orb_slam_amd/cpp/BundleAdjuster.cc -o $@ -Ltools -llocalba_host -Wl,-rpath,'$$ORIGIN/../../tools'
 
 # The other drop-in classes (orb_slam_amd/cpp/LocalMapPoints*.cc, NewMapPoints.cc, Initializer.cc, PnPsolver.cc, Sim3Solver.cc, PoseOptimizer.cc) are compiled once, against the one set
 # of stand-in ORB_SLAM classes in tests/standin, into one archive.  tests/NAME_dropin/harness.cpp drives them through scripts or scenes
@@ -151,6 +163,11 @@ tools/libsim3solver_host.so: tools/sim3solver_host_route.cpp include/orbh.h orb_
 # the host route tools/bench_poseopt.py measures the pose optimisation of tracking (orbo_pose, orbo_pose_batch) against: the host forms of
 # include/orbo.h on one host core over the same arithmetic text and summation order; tests/test_poseopt_host.py holds it against the numpy restatement
 tools/libposeopt_host.so: tools/poseopt_host_route.cpp include/orbo.h orb_slam_amd/csrc/orbo_math.h orb_slam_amd/csrc/orbo_host.h orb_slam_amd/csrc/orb_jacobi.h
+	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
+
+# the host route tools/bench_localba.py measures the bundle adjustment of the mapping thread (orbb_optimize) against: the host forms of
+# include/orbb.h on one host core over the same arithmetic text and summation orders; tests/test_localba_host.py holds it against the numpy restatement
+tools/liblocalba_host.so: tools/localba_host_route.cpp include/orbb.h include/orbo.h orb_slam_amd/csrc/orbb_math.h orb_slam_amd/csrc/orbb_host.h orb_slam_amd/csrc/orbo_math.h orb_slam_amd/csrc/orbo_host.h orb_slam_amd/csrc/orb_jacobi.h
 	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
 
 # the host route tools/bench_local_map.py measures the local-map chain against: the three object-graph walks over flat stand-in arrays on one host core

@@ -79,6 +79,8 @@ EXPORTS_H = ["orbh_ransac_parameters", "orbh_max_errors", "orbh_hypotheses_batch
              "orbh_iterate", "orbh_iterate_batch"]
 # include/orbo.h (tracking's motion-only pose optimisation)
 EXPORTS_O = ["orbo_pose_batch_device", "orbo_pose", "orbo_pose_batch"]
+# include/orbb.h (the bundle adjustment of the mapping thread)
+EXPORTS_B = ["orbb_state_from_float", "orbb_state_to_float", "orbb_work_bytes", "orbb_optimize_device", "orbb_optimize"]
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
 # orbp_fused.status
@@ -253,6 +255,14 @@ assert POSEOPT_PROBLEM_DTYPE.itemsize == 20 and POSEOPT_RESULT_DTYPE.itemsize ==
 POSEOPT_MAX_PROBLEMS, POSEOPT_MAX_EDGES, POSEOPT_EDGE_ROWS, POSEOPT_ROUNDS, POSEOPT_MAX_ITERS = 64, 8192, 6, 4, 32
 POSEOPT_ROUND_SLOT = (0, 10, 20, 27)        # a round's first record of the trace
 POSEOPT_OK, POSEOPT_TERMINATE, POSEOPT_NOT_RUN = 0, 1, 2
+# orbb_problem / orbb_result as numpy records (include/orbb.h); the trace is POSEOPT_STEP_DTYPE[LOCALBA_MAX_ITERS]
+LOCALBA_PROBLEM_DTYPE = np.dtype([("nfree", np.int32), ("nfixed", np.int32), ("npoints", np.int32), ("nedges", np.int32)])
+LOCALBA_RESULT_DTYPE = np.dtype([("chi_first", np.float64), ("chi_last", np.float64), ("lambda", np.float64), ("iters", np.int32), ("status", np.int32),
+                                 ("launches", np.int32), ("syncs", np.int32)])
+assert LOCALBA_PROBLEM_DTYPE.itemsize == 16 and LOCALBA_RESULT_DTYPE.itemsize == 40
+LOCALBA_MAX_FREE, LOCALBA_MAX_POSES, LOCALBA_MAX_POINTS, LOCALBA_MAX_EDGES, LOCALBA_MAX_ITERS = 128, 4096, 1 << 20, 1 << 22, 64
+LOCALBA_REDUCE_LANES, LOCALBA_CTL = 1024, 8
+LOCALBA_RUN_OK, LOCALBA_RUN_TERMINATE, LOCALBA_RUN_NOTHING = 0, 1, 2
 
 # orbp_view / orbp_record as numpy records (arrays of views are uploaded as they are)
 VIEW_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
@@ -451,6 +461,7 @@ def lib():
         pnp_bind(L)
         sim3solver_bind(L)
         poseopt_bind(L)
+        localba_bind(L)
         L.orbi_normalize.argtypes = [vp, ci, vp]
         L.orbi_pose_from_rt.argtypes = [cf, cf, cf, cf, vp, vp, vp]
         L.orbi_models_batch_device.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1481,6 +1492,123 @@ def poseopt_pose_batch_device(problems, d_edges, ncap, d_Tcw, d_result, d_outlie
                                       stream or None)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbo_pose_batch_device")
+
+
+def localba_bind(L):
+    """the argument types of the orbb_* entry points (include/orbb.h); tools/liblocalba_host.so exports the host forms with the same types"""
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    L.orbb_state_from_float.argtypes = [vp] * 5
+    L.orbb_state_to_float.argtypes = [vp] * 5
+    L.orbb_work_bytes.argtypes = [vp]
+    L.orbb_work_bytes.restype = ctypes.c_size_t
+    L.orbb_optimize.argtypes = [vp] * 6 + [cf] + [vp] * 4 + [ci] + [vp] * 4 + [ci]
+    if hasattr(L, "orbb_optimize_device"):
+        L.orbb_optimize_device.argtypes = [vp] * 6 + [cf] + [vp] * 4 + [ci, vp, ctypes.c_size_t] + [vp] * 5
+    return L
+
+
+LOCALBA_HUBER_DELTA = float(np.float32(np.sqrt(5.991)))        # `const float thHuber = sqrt(5.991)` of both callers
+
+
+def ba_problem(nfree, nfixed, npoints, nedges):
+    """one orbb_problem record"""
+    q = np.zeros((), LOCALBA_PROBLEM_DTYPE)
+    q["nfree"], q["nfixed"], q["npoints"], q["nedges"] = nfree, nfixed, npoints, nedges
+    return q
+
+
+def ba_dump_fields(nfree, npoints):
+    """the arrays of the first-build dump in order: (name, shape)"""
+    n = 6 * nfree
+    return [("Hpp", (nfree, 28)), ("Hll", (npoints, 6)), ("bl", (npoints, 3)), ("S", (n, n)), ("bs", (n,)), ("xp", (n,)), ("xl", (npoints, 3))]
+
+
+def ba_work_bytes(problem, L=None):
+    pr = np.ascontiguousarray(problem, dtype=LOCALBA_PROBLEM_DTYPE).reshape(1)
+    return int((L or lib()).orbb_work_bytes(pr.ctypes.data))
+
+
+def ba_state_from_float(problem, Tcw, world, L=None):
+    """Converter::toSE3Quat of every pose ([np, 3 x 4] or [np, 4 x 4] float rows of [R | t]) and the float world positions widened
+    -> (pose_qt float64[np, 7], point_xyz float64[npoints, 3])"""
+    pr = np.ascontiguousarray(problem, dtype=LOCALBA_PROBLEM_DTYPE).reshape(1)
+    npo, P = int(pr["nfree"][0] + pr["nfixed"][0]), int(pr["npoints"][0])
+    T = np.asarray(Tcw, np.float32).reshape(npo, -1)
+    T = np.ascontiguousarray(T[:, :12])
+    X = np.ascontiguousarray(world, np.float32).reshape(P, 3)
+    q, x = np.zeros((npo, 7)), np.zeros((P, 3))
+    rc = (L or lib()).orbb_state_from_float(pr.ctypes.data, T.ctypes.data, X.ctypes.data if P else None, q.ctypes.data, x.ctypes.data if P else None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbb_state_from_float")
+    return q, x
+
+
+def ba_state_to_float(problem, pose_qt, point_xyz, L=None):
+    """what SetPose(Converter::toCvMat(SE3quat)) and SetWorldPos store -> (Tcw float32[np, 4, 4], world float32[npoints, 3])"""
+    pr = np.ascontiguousarray(problem, dtype=LOCALBA_PROBLEM_DTYPE).reshape(1)
+    npo, P = int(pr["nfree"][0] + pr["nfixed"][0]), int(pr["npoints"][0])
+    q = np.ascontiguousarray(pose_qt, np.float64).reshape(npo, 7)
+    x = np.ascontiguousarray(point_xyz, np.float64).reshape(P, 3)
+    T, X = np.zeros((npo, 4, 4), np.float32), np.zeros((P, 3), np.float32)
+    rc = (L or lib()).orbb_state_to_float(pr.ctypes.data, q.ctypes.data, x.ctypes.data if P else None, T.ctypes.data, X.ctypes.data if P else None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbb_state_to_float")
+    return T, X
+
+
+def ba_pack_bits(bits):
+    """edge bits (bool[nedges]) as the words of include/orbb.h: bit e % 64 of word e / 64"""
+    b = np.asarray(bits, bool).reshape(-1)
+    pad = np.zeros(max(sim3solver_words(len(b)), 1) * 64, np.uint8)
+    pad[:len(b)] = b
+    return np.packbits(pad, bitorder="little").view("<u8").astype(np.uint64)
+
+
+def ba_optimize(problem, cam, point_first, edge_pose, edge_uv, edge_inv_sigma2, pose_qt, point_xyz, active, chi2, iters, huber_delta=LOCALBA_HUBER_DELTA,
+                want_trace=False, want_dump=False, device=0, L=None):
+    """g2o's optimize(iters) over host arrays, synchronous (include/orbb.h).  active: bool[nedges]; chi2: float64[nedges] or None (zeros).  The state
+    arrays are not modified -> dict(result, pose_qt, point_xyz, chi2, flags uint8[nedges], trace POSEOPT_STEP_DTYPE[64] or None, dump dict or None)"""
+    pr = np.ascontiguousarray(problem, dtype=LOCALBA_PROBLEM_DTYPE).reshape(1)
+    nf, npo, P, E = int(pr["nfree"][0]), int(pr["nfree"][0] + pr["nfixed"][0]), int(pr["npoints"][0]), int(pr["nedges"][0])
+    cam = np.ascontiguousarray(cam, np.float32).reshape(npo, 4)
+    first = np.ascontiguousarray(point_first, np.int32).reshape(P + 1)
+    ep = np.ascontiguousarray(edge_pose, np.int32).reshape(E)
+    uv = np.ascontiguousarray(edge_uv, np.float32).reshape(E, 2)
+    w = np.ascontiguousarray(edge_inv_sigma2, np.float32).reshape(E)
+    q = np.array(pose_qt, np.float64).reshape(npo, 7).copy()
+    x = np.array(point_xyz, np.float64).reshape(P, 3).copy()
+    act = ba_pack_bits(np.asarray(active, bool).reshape(E))
+    c2 = np.zeros(E) if chi2 is None else np.array(chi2, np.float64).reshape(E).copy()
+    res = np.zeros(1, LOCALBA_RESULT_DTYPE)
+    fl = np.zeros(max(sim3solver_words(E), 1), np.uint64)
+    tr = np.zeros(LOCALBA_MAX_ITERS, POSEOPT_STEP_DTYPE) if want_trace else None
+    dump = np.zeros(nf * 28 + P * 12 + 36 * nf * nf + 12 * nf) if want_dump else None
+    ptr = lambda a, n=1: a.ctypes.data if (a is not None and n) else None
+    rc = (L or lib()).orbb_optimize(pr.ctypes.data, cam.ctypes.data, first.ctypes.data, ptr(ep, E), ptr(uv, E), ptr(w, E), huber_delta, q.ctypes.data, ptr(x, P),
+                                    ptr(act, E), ptr(c2, E), iters, res.ctypes.data, ptr(fl, E), ptr(tr), ptr(dump), device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbb_optimize")
+    d = None
+    if want_dump:
+        d, at = {}, 0
+        for name, shape in ba_dump_fields(nf, P):
+            k = int(np.prod(shape))
+            d[name] = dump[at:at + k].reshape(shape)
+            at += k
+    return dict(result=res[0], pose_qt=q, point_xyz=x, chi2=c2, flags=sim3solver_unpack(fl, E), trace=tr, dump=d)
+
+
+def ba_optimize_device(problem, d_cam, d_point_first, d_edge_pose, d_edge_uv, d_edge_inv_sigma2, d_pose_qt, d_point_xyz, d_active, d_chi2, iters, d_work,
+                       work_bytes, d_flags, d_trace=0, d_dump=0, huber_delta=LOCALBA_HUBER_DELTA, stream=0):
+    """the same over device pointers (ints); allocates nothing and returns, synchronised, the LOCALBA_RESULT_DTYPE record"""
+    pr = np.ascontiguousarray(problem, dtype=LOCALBA_PROBLEM_DTYPE).reshape(1)
+    res = np.zeros(1, LOCALBA_RESULT_DTYPE)
+    rc = lib().orbb_optimize_device(pr.ctypes.data, d_cam or None, d_point_first or None, d_edge_pose or None, d_edge_uv or None, d_edge_inv_sigma2 or None,
+                                    huber_delta, d_pose_qt or None, d_point_xyz or None, d_active or None, d_chi2 or None, iters, d_work or None, work_bytes,
+                                    res.ctypes.data, d_flags or None, d_trace or None, d_dump or None, stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbb_optimize_device")
+    return res[0]
 
 
 def pnp_bind(L):

@@ -121,20 +121,30 @@ ORB_HD void rotate(const double (&q)[4], double X, double Y, double Z, double (&
     o[2] = (Z + q[3] * u2) + (q[0] * u1 - q[1] * u0);
 }
 
-// to_homogeneous_matrix (se3quat.h:270-278) narrowed to float
-ORB_HD void pose_to_Tcw(const Pose& P, float (&T)[16]) {
-    const double x = P.q[0], y = P.q[1], z = P.q[2], w = P.q[3];
+// toRotationMatrix (orbo.h, output)
+ORB_HD void rotation_matrix(const double (&q)[4], double (&R)[3][3]) {
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
     const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
     const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    T[0] = (float)(1.0 - (tyy + tzz));
-    T[1] = (float)(txy - twz);
-    T[2] = (float)(txz + twy);
-    T[4] = (float)(txy + twz);
-    T[5] = (float)(1.0 - (txx + tzz));
-    T[6] = (float)(tyz - twx);
-    T[8] = (float)(txz - twy);
-    T[9] = (float)(tyz + twx);
-    T[10] = (float)(1.0 - (txx + tyy));
+    R[0][0] = 1.0 - (tyy + tzz);
+    R[0][1] = txy - twz;
+    R[0][2] = txz + twy;
+    R[1][0] = txy + twz;
+    R[1][1] = 1.0 - (txx + tzz);
+    R[1][2] = tyz - twx;
+    R[2][0] = txz - twy;
+    R[2][1] = tyz + twx;
+    R[2][2] = 1.0 - (txx + tyy);
+}
+
+// to_homogeneous_matrix (se3quat.h:270-278) narrowed to float
+ORB_HD void pose_to_Tcw(const Pose& P, float (&T)[16]) {
+    double R[3][3];
+    rotation_matrix(P.q, R);
+ORB_UNROLL
+    for (int r = 0; r < 3; r++)
+ORB_UNROLL
+        for (int c = 0; c < 3; c++) T[r * 4 + c] = (float)R[r][c];
     T[3] = (float)P.t[0];
     T[7] = (float)P.t[1];
     T[11] = (float)P.t[2];
@@ -157,8 +167,8 @@ ORB_HD double edge_chi2(const Cam& c, const Pose& P, const Edge& E) {
 }
 
 // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho[0], rho[1]
-ORB_HD void huber(double chi2, double& rho0, double& rho1) {
-    const double delta = huber_delta(), dsqr = huber_dsqr();
+// (delta and dsqr as arguments: the bundle adjustment of orbb_math.h takes its delta from the caller)
+ORB_HD void huber(double chi2, double delta, double dsqr, double& rho0, double& rho1) {
     if (chi2 <= dsqr) {
         rho0 = chi2;
         rho1 = 1.0;
@@ -168,15 +178,11 @@ ORB_HD void huber(double chi2, double& rho0, double& rho1) {
         rho1 = delta / s;
     }
 }
+ORB_HD void huber(double chi2, double& rho0, double& rho1) { huber(chi2, huber_delta(), huber_dsqr(), rho0, rho1); }
 
-// one edge into a lane's sums: linearizeOplus (.cpp:97-134) and constructQuadraticForm (base_binary_edge.hpp:91-113)
-ORB_HD void add_edge(const Cam& c, const Pose& P, const Edge& E, double (&acc)[NACC]) {
-    double p[3], e[2];
-    const double chi2 = edge_error(c, P, E, p, e);
-    double rho0, rho1;
-    huber(chi2, rho0, rho1);
+// the Jacobian of the error by the pose (linearizeOplus, .cpp:121-133) at the camera point p
+ORB_HD void pose_jacobian(const Cam& c, const double (&p)[3], double (&J)[2][6]) {
     const double x = p[0], y = p[1], z = p[2], z2 = z * z;
-    double J[2][6];
     J[0][0] = ((x * y) / z2) * c.fx;
     J[0][1] = (-(1.0 + (x * x) / z2)) * c.fx;
     J[0][2] = (y / z) * c.fx;
@@ -189,6 +195,16 @@ ORB_HD void add_edge(const Cam& c, const Pose& P, const Edge& E, double (&acc)[N
     J[1][3] = 0.0;
     J[1][4] = (-1.0 / z) * c.fy;
     J[1][5] = (y / z2) * c.fy;
+}
+
+// one edge into a lane's sums: linearizeOplus (.cpp:97-134) and constructQuadraticForm (base_binary_edge.hpp:91-113)
+ORB_HD void add_edge(const Cam& c, const Pose& P, const Edge& E, double delta, double dsqr, double (&acc)[NACC]) {
+    double p[3], e[2];
+    const double chi2 = edge_error(c, P, E, p, e);
+    double rho0, rho1;
+    huber(chi2, delta, dsqr, rho0, rho1);
+    double J[2][6];
+    pose_jacobian(c, p, J);
     const double wr = E.w * rho1;
     const double r0 = ((-E.w) * e[0]) * rho1, r1 = ((-E.w) * e[1]) * rho1;
     int a = 0;
@@ -200,6 +216,7 @@ ORB_UNROLL
     for (int i = 0; i < 6; i++) acc[21 + i] = acc[21 + i] + (J[0][i] * r0 + J[1][i] * r1);
     acc[27] = acc[27] + rho0;
 }
+ORB_HD void add_edge(const Cam& c, const Pose& P, const Edge& E, double (&acc)[NACC]) { add_edge(c, P, E, huber_delta(), huber_dsqr(), acc); }
 
 // what a lane sums: its active edges lane, lane + 64, ... in index order.  load(i) is edge i.
 template <class Load>
