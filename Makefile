@@ -14,8 +14,8 @@ LIBS             := orb_slam_amd/liborbx.so orb_slam_amd/libsynthframes.so oracl
 EXAMPLES         := $(addprefix orb_slam_amd/cpp/,example_frame example_batch example_color example_pipeline example_lanes bench_single_frame)
 DROPIN_HARNESSES := $(patsubst %,tests/%_dropin/harness,kfdb mappoints source triangulate refresh fuse loop sim3 bow newpoints localmap cull init pnp sim3solver poseopt) \
     tests/init_dropin/harness_host tests/pnp_dropin/harness_host tests/sim3solver_dropin/harness_host tests/poseopt_dropin/harness_host \
-    tests/localba_dropin/harness tests/localba_dropin/harness_host
-HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp sim3solver poseopt localba)
+    tests/localba_dropin/harness tests/localba_dropin/harness_host tests/sim3opt_dropin/harness tests/sim3opt_dropin/harness_host
+HOST_ROUTE_LIBS  := $(patsubst %,tools/lib%_host.so,mappoints localmap cull source triangulate refresh fuse loop sim3 init pnp sim3solver poseopt localba sim3opt)
 MICROBENCH       := $(addprefix tools/microbench/,valu_rate valu_rate2 mfma_layout mfma_layout_fp4 mfma_valu_mix fetch_calib valu_exec_mask ta_shapes)
 
 all: $(LIBS) oracle_ref $(EXAMPLES) $(DROPIN_HARNESSES) build/dropin/tracking_only.ok $(HOST_ROUTE_LIBS) $(MICROBENCH)
@@ -87,6 +87,17 @@ tests/localba_dropin/harness: tests/localba_dropin/harness.cpp $(LOCALBA_DROPIN)
 	$(CXX) $(LOCALBA_CXXFLAGS) $< orb_slam_amd/cpp/BundleAdjuster.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
 tests/localba_dropin/harness_host: tests/localba_dropin/harness.cpp $(LOCALBA_DROPIN) tools/liblocalba_host.so
 	$(CXX) $(LOCALBA_CXXFLAGS) $< orb_slam_amd/cpp/BundleAdjuster.cc -o $@ -Ltools -llocalba_host -Wl,-rpath,'$$ORIGIN/../../tools'
+
+# the Sim3Optimizer drop-in (orb_slam_amd/cpp/Sim3Optimizer.cc) over its own stand-in KeyFrame.h / MapPoint.h / Sim3.h (tests/standin lacks GetInvSigma2 and
+# GetCalibrationMatrix; Sim3.h has g2o's accessor names, so the template overload runs), driven by scenes (tests/test_gpu_sim3opt_dropin.py); harness_host is
+# the same class linked against the host route (tests/test_sim3opt_dropin_host.py).  Sim3Optimizer.cc shares orbg_math.h with the kernel and rounds as it does.
+SIM3OPT_DROPIN := orb_slam_amd/cpp/Sim3Optimizer.cc orb_slam_amd/cpp/Sim3Optimizer.h $(addprefix tests/sim3opt_dropin/,KeyFrame.h MapPoint.h Sim3.h) tests/standin/cvmini.h \
+    include/orbg.h include/orbo.h include/orbx.h orb_slam_amd/csrc/orbg_math.h orb_slam_amd/csrc/orbo_math.h orb_slam_amd/csrc/orb_jacobi.h
+SIM3OPT_CXXFLAGS := -O2 -std=c++14 -Wall -ffp-contract=off -Itests/sim3opt_dropin -Itests/standin -Iinclude -Iorb_slam_amd/cpp -Iorb_slam_amd/csrc
+tests/sim3opt_dropin/harness: tests/sim3opt_dropin/harness.cpp $(SIM3OPT_DROPIN) orb_slam_amd/liborbx.so
+	$(CXX) $(SIM3OPT_CXXFLAGS) $< orb_slam_amd/cpp/Sim3Optimizer.cc -o $@ -Lorb_slam_amd -lorbx -Wl,-rpath,'$$ORIGIN/../../orb_slam_amd' -Wl,-rpath,/opt/rocm/lib
+tests/sim3opt_dropin/harness_host: tests/sim3opt_dropin/harness.cpp $(SIM3OPT_DROPIN) tools/libsim3opt_host.so
+	$(CXX) $(SIM3OPT_CXXFLAGS) $< orb_slam_amd/cpp/Sim3Optimizer.cc -o $@ -Ltools -lsim3opt_host -Wl,-rpath,'$$ORIGIN/../../tools'
 
 # The other drop-in classes (orb_slam_amd/cpp/LocalMapPoints*.cc, NewMapPoints.cc, Initializer.cc, PnPsolver.cc, Sim3Solver.cc, PoseOptimizer.cc) are compiled once, against the one set
 # of stand-in ORB_SLAM classes in tests/standin, into one archive.  tests/NAME_dropin/harness.cpp drives them through scripts or scenes
@@ -168,6 +179,11 @@ tools/libposeopt_host.so: tools/poseopt_host_route.cpp include/orbo.h orb_slam_a
 # the host route tools/bench_localba.py measures the bundle adjustment of the mapping thread (orbb_optimize) against: the host forms of
 # include/orbb.h on one host core over the same arithmetic text and summation orders; tests/test_localba_host.py holds it against the numpy restatement
 tools/liblocalba_host.so: tools/localba_host_route.cpp include/orbb.h include/orbo.h orb_slam_amd/csrc/orbb_math.h orb_slam_amd/csrc/orbb_host.h orb_slam_amd/csrc/orbo_math.h orb_slam_amd/csrc/orbo_host.h orb_slam_amd/csrc/orb_jacobi.h
+	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
+
+# the host route tools/bench_sim3opt.py measures the Sim3 refinement of loop closing (orbg_sim3, orbg_sim3_batch) against: the host forms of
+# include/orbg.h on one host core over the same arithmetic text and summation order; tests/test_sim3opt_host.py holds it against the numpy restatement
+tools/libsim3opt_host.so: tools/sim3opt_host_route.cpp include/orbg.h include/orbo.h orb_slam_amd/csrc/orbg_math.h orb_slam_amd/csrc/orbg_host.h orb_slam_amd/csrc/orbo_math.h orb_slam_amd/csrc/orbo_host.h orb_slam_amd/csrc/orb_jacobi.h
 	$(CXX) -O2 -std=c++14 -Wall -ffp-contract=off -fPIC -shared -Iinclude -Iorb_slam_amd/csrc $< -o $@
 
 # the host route tools/bench_local_map.py measures the local-map chain against: the three object-graph walks over flat stand-in arrays on one host core

@@ -80,6 +80,8 @@ EXPORTS_H = ["orbh_ransac_parameters", "orbh_max_errors", "orbh_hypotheses_batch
 # include/orbo.h (tracking's motion-only pose optimisation)
 EXPORTS_O = ["orbo_pose_batch_device", "orbo_pose", "orbo_pose_batch"]
 # include/orbb.h (the bundle adjustment of the mapping thread)
+# include/orbg.h (loop closing's Sim3 refinement)
+EXPORTS_G = ["orbg_sim3_batch_device", "orbg_sim3", "orbg_sim3_batch"]
 EXPORTS_B = ["orbb_state_from_float", "orbb_state_to_float", "orbb_work_bytes", "orbb_optimize_device", "orbb_optimize"]
 # orbp_view.mode; MODE_SIM3: orbp_sim3_dir.mode
 MODE_FRAME, MODE_LAST_FRAME, MODE_KEYFRAME, MODE_FUSE, MODE_LOOP, MODE_SIM3 = 0, 1, 2, 3, 4, 5
@@ -255,6 +257,14 @@ assert POSEOPT_PROBLEM_DTYPE.itemsize == 20 and POSEOPT_RESULT_DTYPE.itemsize ==
 POSEOPT_MAX_PROBLEMS, POSEOPT_MAX_EDGES, POSEOPT_EDGE_ROWS, POSEOPT_ROUNDS, POSEOPT_MAX_ITERS = 64, 8192, 6, 4, 32
 POSEOPT_ROUND_SLOT = (0, 10, 20, 27)        # a round's first record of the trace
 POSEOPT_OK, POSEOPT_TERMINATE, POSEOPT_NOT_RUN = 0, 1, 2
+# orbg_problem / orbg_result as numpy records (include/orbg.h); the trace is POSEOPT_STEP_DTYPE[SIM3OPT_MAX_ITERS]
+SIM3OPT_PROBLEM_DTYPE = np.dtype([("fx1", np.float32), ("fy1", np.float32), ("cx1", np.float32), ("cy1", np.float32), ("fx2", np.float32),
+                                  ("fy2", np.float32), ("cx2", np.float32), ("cy2", np.float32), ("th2", np.float32), ("n", np.int32)])
+SIM3OPT_RESULT_DTYPE = np.dtype([("q", np.float64, 4), ("t", np.float64, 3), ("s", np.float64), ("S12", np.float32, 16), ("ncorr", np.int32),
+                                 ("nbad", np.int32), ("nin", np.int32), ("ret0", np.int32), ("iters", np.int32, 2)])
+assert SIM3OPT_PROBLEM_DTYPE.itemsize == 40 and SIM3OPT_RESULT_DTYPE.itemsize == 152
+SIM3OPT_MAX_PROBLEMS, SIM3OPT_MAX_PAIRS, SIM3OPT_PAIR_ROWS, SIM3OPT_MAX_ITERS = 64, 8192, 12, 15
+SIM3OPT_PHASE_SLOT = (0, 5)                 # a phase's first record of the trace
 # orbb_problem / orbb_result as numpy records (include/orbb.h); the trace is POSEOPT_STEP_DTYPE[LOCALBA_MAX_ITERS]
 LOCALBA_PROBLEM_DTYPE = np.dtype([("nfree", np.int32), ("nfixed", np.int32), ("npoints", np.int32), ("nedges", np.int32)])
 LOCALBA_RESULT_DTYPE = np.dtype([("chi_first", np.float64), ("chi_last", np.float64), ("lambda", np.float64), ("iters", np.int32), ("status", np.int32),
@@ -461,6 +471,7 @@ def lib():
         pnp_bind(L)
         sim3solver_bind(L)
         poseopt_bind(L)
+        sim3opt_bind(L)
         localba_bind(L)
         L.orbi_normalize.argtypes = [vp, ci, vp]
         L.orbi_pose_from_rt.argtypes = [cf, cf, cf, cf, vp, vp, vp]
@@ -1492,6 +1503,97 @@ def poseopt_pose_batch_device(problems, d_edges, ncap, d_Tcw, d_result, d_outlie
                                       stream or None)
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbo_pose_batch_device")
+
+
+def sim3opt_bind(L):
+    """the argument types of the orbg_* entry points (include/orbg.h); tools/libsim3opt_host.so exports the host forms with the same types"""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.orbg_sim3.argtypes = [vp] * 9 + [ci]
+    L.orbg_sim3_batch.argtypes = [vp, ci] + [vp] * 8 + [ci]
+    if hasattr(L, "orbg_sim3_batch_device"):
+        L.orbg_sim3_batch_device.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    return L
+
+
+def sim3opt_problem(cam1, cam2, th2, n):
+    """one orbg_problem record: cam1, cam2 = (fx, fy, cx, cy) of K1 and K2, the argument th2, n pairs"""
+    q = np.zeros((), SIM3OPT_PROBLEM_DTYPE)
+    q["fx1"], q["fy1"], q["cx1"], q["cy1"] = cam1
+    q["fx2"], q["fy2"], q["cx2"], q["cy2"] = cam2
+    q["th2"] = th2
+    q["n"] = n
+    return q
+
+
+def sim3opt_start(R, t, s):
+    """the thirteen floats of a start similarity: R row major, t, s (the arguments of g2o::Sim3(R, t, s), LoopClosing.cc:320)"""
+    return np.concatenate([np.asarray(R, np.float32).reshape(9), np.asarray(t, np.float32).reshape(3), np.asarray([s], np.float32)])
+
+
+def sim3opt_pair_table(P1c, P2c, obs1, obs2, ncap=None):
+    """a candidate's pairs as the device table: ORBG_PAIR_ROWS rows of ncap floats (include/orbg.h)"""
+    a = _sim3opt_arrays(None, P1c, P2c, obs1, obs2)
+    n = len(a[0])
+    ncap = max(n, 1) if ncap is None else ncap
+    t = np.zeros((SIM3OPT_PAIR_ROWS, ncap), np.float32)
+    for k in range(4):
+        t[3 * k:3 * k + 3, :n] = a[k].T
+    return t
+
+
+def _sim3opt_arrays(n, P1c, P2c, obs1, obs2):
+    a = tuple(np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (P1c, P2c, obs1, obs2))
+    if not all(len(x) == (len(a[0]) if n is None else n) for x in a):
+        raise ValueError("the pair arrays do not have the problem's n")
+    return a
+
+
+def sim3opt_sim3(problem, P1c, P2c, obs1, obs2, S12, want_trace=False, device=0, L=None):
+    """Optimizer::OptimizeSim3 for one loop candidate, host arrays, synchronous (include/orbg.h): P1c, P2c are [n, 3], obs1 = (u1, v1, w1) and
+    obs2 = (u2, v2, w2) are [n, 3], S12 the thirteen floats of sim3opt_start
+    -> (SIM3OPT_RESULT_DTYPE record, removed flags uint8[n], POSEOPT_STEP_DTYPE[15] or None)"""
+    pr = np.ascontiguousarray(problem, dtype=SIM3OPT_PROBLEM_DTYPE).reshape(1)
+    n = int(pr["n"][0])
+    a = _sim3opt_arrays(n, P1c, P2c, obs1, obs2)
+    S = np.ascontiguousarray(S12, np.float32).reshape(13)
+    res = np.zeros(1, SIM3OPT_RESULT_DTYPE); words = np.zeros(max(sim3solver_words(n), 1), np.uint64)
+    tr = np.zeros(SIM3OPT_MAX_ITERS, POSEOPT_STEP_DTYPE) if want_trace else None
+    rc = (L or lib()).orbg_sim3(pr.ctypes.data, *[x.ctypes.data if n else None for x in a], S.ctypes.data, res.ctypes.data,
+                                words.ctypes.data if n else None, tr.ctypes.data if want_trace else None, device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbg_sim3")
+    return res[0], sim3solver_unpack(words, n), tr
+
+
+def sim3opt_sim3_batch(problems, P1c, P2c, obs1, obs2, S12, want_trace=False, device=0, L=None):
+    """the same for several candidates as ONE launch with one synchronisation: P1c, P2c, obs1, obs2 are lists of per-candidate host arrays, S12 is
+    [P, 13] -> (SIM3OPT_RESULT_DTYPE[P], [removed flags uint8[n]], [POSEOPT_STEP_DTYPE[15]] or None)"""
+    pr = np.ascontiguousarray(problems, dtype=SIM3OPT_PROBLEM_DTYPE).reshape(-1)
+    P = len(pr)
+    S = np.ascontiguousarray(S12, np.float32).reshape(P, 13)
+    if not (len(P1c) == len(P2c) == len(obs1) == len(obs2) == P) or P < 1:
+        raise ValueError("one entry per candidate")
+    arrs = [_sim3opt_arrays(int(pr["n"][p]), P1c[p], P2c[p], obs1[p], obs2[p]) for p in range(P)]
+    res = np.zeros(P, SIM3OPT_RESULT_DTYPE)
+    words = [np.zeros(max(sim3solver_words(n), 1), np.uint64) for n in pr["n"]]
+    tr = [np.zeros(SIM3OPT_MAX_ITERS, POSEOPT_STEP_DTYPE) for _ in range(P)]
+    ptrs = lambda xs, ns: (ctypes.c_void_p * P)(*[x.ctypes.data if n else None for x, n in zip(xs, ns)])
+    keep = [ptrs([a[k] for a in arrs], pr["n"]) for k in range(4)] + [ptrs(words, pr["n"]), ptrs(tr, [1] * P)]
+    ad = [ctypes.addressof(k) for k in keep]
+    rc = (L or lib()).orbg_sim3_batch(pr.ctypes.data, P, ad[0], ad[1], ad[2], ad[3], S.ctypes.data, res.ctypes.data, ad[4], ad[5] if want_trace else None,
+                                      device)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbg_sim3_batch")
+    return res, [sim3solver_unpack(w, int(n)) for w, n in zip(words, pr["n"])], (tr if want_trace else None)
+
+
+def sim3opt_sim3_batch_device(problems, d_pairs, ncap, d_S12, d_result, d_removed, d_trace=0, stream=0):
+    """the similarities of len(problems) candidates (include/orbg.h); problems: host SIM3OPT_PROBLEM_DTYPE records, the rest device pointers as ints"""
+    pr = np.ascontiguousarray(problems, dtype=SIM3OPT_PROBLEM_DTYPE).reshape(-1)
+    rc = lib().orbg_sim3_batch_device(pr.ctypes.data, len(pr), d_pairs or None, ncap, d_S12 or None, d_result or None, d_removed or None, d_trace or None,
+                                      stream or None)
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbg_sim3_batch_device")
 
 
 def localba_bind(L):

@@ -252,23 +252,26 @@ ORB_HD void classify_edge(const Load& load, const Cam& c, const Pose& est, const
 }
 
 // LinearSolverDense on (H + lambda*I) x = b: NOT pinned to Eigen (orbo.h, step 2).  x is written only when the solve succeeds.
-ORB_HD bool ldlt_solve(const double (&acc)[NACC], double lambda, double (&x)[6]) {
-    double A[6][6], L[6][6], d[6];
+// Dimension N: acc holds the N*(N + 1)/2 upper entries of H row by row, then the N of b (6 here, 7 for the similarity of orbg_math.h).
+template <int N, int NA>
+ORB_HD bool ldlt_solve_n(const double (&acc)[NA], double lambda, double (&x)[N]) {
+    constexpr int NB = N * (N + 1) / 2;
+    double A[N][N], L[N][N], d[N];
     int a = 0;
 ORB_UNROLL
-    for (int i = 0; i < 6; i++)
+    for (int i = 0; i < N; i++)
 ORB_UNROLL
-        for (int j = i; j < 6; j++, a++) A[j][i] = (i == j) ? acc[a] + lambda : acc[a];      // the lower triangle
+        for (int j = i; j < N; j++, a++) A[j][i] = (i == j) ? acc[a] + lambda : acc[a];      // the lower triangle
     bool ok = true;
 ORB_UNROLL
-    for (int j = 0; j < 6; j++) {
+    for (int j = 0; j < N; j++) {
         double s = A[j][j];
 ORB_UNROLL
         for (int k = 0; k < j; k++) s = s - (L[j][k] * L[j][k]) * d[k];
         d[j] = s;
         if (s < 0 || !__builtin_isfinite(s)) ok = false;
 ORB_UNROLL
-        for (int i = j + 1; i < 6; i++) {
+        for (int i = j + 1; i < N; i++) {
             double t = A[i][j];
 ORB_UNROLL
             for (int k = 0; k < j; k++) t = t - (L[i][k] * L[j][k]) * d[k];
@@ -276,25 +279,26 @@ ORB_UNROLL
         }
     }
     if (!ok) return false;
-    double y[6];
+    double y[N];
 ORB_UNROLL
-    for (int i = 0; i < 6; i++) {
-        double s = acc[21 + i];
+    for (int i = 0; i < N; i++) {
+        double s = acc[NB + i];
 ORB_UNROLL
         for (int k = 0; k < i; k++) s = s - L[i][k] * y[k];
         y[i] = s;
     }
 ORB_UNROLL
-    for (int i = 0; i < 6; i++) y[i] = y[i] / d[i];
+    for (int i = 0; i < N; i++) y[i] = y[i] / d[i];
 ORB_UNROLL
-    for (int i = 5; i >= 0; i--) {
+    for (int i = N - 1; i >= 0; i--) {
         double s = y[i];
 ORB_UNROLL
-        for (int k = i + 1; k < 6; k++) s = s - L[k][i] * x[k];
+        for (int k = i + 1; k < N; k++) s = s - L[k][i] * x[k];
         x[i] = s;
     }
     return true;
 }
+ORB_HD bool ldlt_solve(const double (&acc)[NACC], double lambda, double (&x)[6]) { return ldlt_solve_n<6, NACC>(acc, lambda, x); }
 
 ORB_HD double dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 
